@@ -12,6 +12,11 @@ GPU, checks that N devices exist, starts N fresh rank processes of this script (
 set, the fan-out of Self_Play.py:346-363), forwards rank 0's JSON line and fails if any rank fails.  Under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` the ranks already exist and each runs the bench body.
 Games shard by global slot (rank r owns slots [r G, (r + 1) G)); the only collective is the all-reduce of the counters.
+
+A plain run measures the headline figure only: set-up, burn-in, warm-up, the K timed steps, the result line.  `--full` adds
+everything else the line can carry, each from runs of its own: the per-kernel and roofline segments, the extra legs (evaluation
+cache, the reference's simulation convention), the Gumbel and Gomoku configurations and the CPU baseline.
+`--dump-outputs DIR` writes what the timed path computed, as of the end of its last step, to DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -48,7 +53,7 @@ def parse(argv=None):
     ap.add_argument("--eval-cache", type=int, default=0, help="log2 entries of the on-device evaluation cache (SURVEY 8f rank 3); 0 = off (the headline number is measured with it off: every request goes through the evaluator)")
     ap.add_argument("--ref-convention-leg", type=int, default=-1, help="1: extra leg at int(1.5 * sims) simulations per move, what Self_Play passes for MCTS_iteration_limit = sims (Self_Play.py:99); default on for the connect4 config at N = 1")
     ap.add_argument("--other-configs", type=int, default=-1, help="1: also measure BASELINE configs[4] (Gumbel) and configs[3] (Gomoku) and append them to the line as "
-                                                                  "'gumbel' / 'gomoku' objects (default: on for the plain headline command at N = 1)")
+                                                                  "'gumbel' / 'gomoku' objects (--full only; default: on for the headline command at N = 1)")
     ap.add_argument("--game-groups", type=int, default=0, help="gaz_engine_config::game_groups of the measured engines: 0 = the library's choice (2 for the headline config), "
                                                                "1 = one batch, K = K batches with their launches in flight together")
     ap.add_argument("--burn-in-waves", type=int, default=-1, help="untimed waves before the warm-up steps (default: about two game lengths for the Connect4 configs — 8000 PUCT / "
@@ -60,6 +65,10 @@ def parse(argv=None):
     ap.add_argument("--cpu-baseline-seconds", type=float, default=20.0)
     ap.add_argument("--cpu-baseline-cores", type=int, default=0, help="worker threads = torch threads of the CPU baseline (0 = the cores this "
                                                                       "process may use: affinity, cut to the cgroup CPU quota)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: per-kernel / roofline segments, the extra "
+                                                        "legs, the other configurations and the CPU baseline (the flags above tune them)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the timed path computed (the position, last "
+                                                                      "move and phase of every game, the engine's counters) to DIR/<name>.npy")
     ap.add_argument("--emu-lib", default="", help="TEST HOOK (tests/test_bench_launcher.py): run the bench body on the one-lane CPU emulation build of the "
                                                   "device code over gloo; never a measurement")
     return ap.parse_args(argv)
@@ -265,6 +274,39 @@ def random_histories(game, n, rng, max_ply):
     return out
 
 
+DUMP_BYTES = 64 << 20        # --dump-outputs: at most this much in all (ranks included)
+
+
+def dump_outputs(eng, out_dir, rank=0, world=1):
+    """What a caller of the timed path receives after its last step, written as DIR/<name>.npy (rank r > 0: <name>_rank<r>.npy), float32
+    or float64 (integers as float64: exact).  Per game: the position the search and the network have led it to (ply = moves played,
+    history = their action indices, -1 padded), the move last chosen and the phase of the search (SelfPlayEngine.read_positions /
+    root_stats; the root rows of root_stats are only filled when a move completes, so mid-move they carry nothing); per engine: the
+    counters (game_stats[0:6], evals, sims, plies, cache_hits).  Larger than the budget: a fixed, seeded sample of the games (games.npy
+    holds their slots).  Read-only: the engine runs on unchanged afterwards."""
+    rs = eng.root_stats()
+    hist = eng.read_positions()
+    G = len(hist)
+    T = max([len(h) for h in hist] + [1])
+    history = np.full((G, T), -1.0, np.float32)
+    for g, h in enumerate(hist):
+        history[g, :len(h)] = h
+    per_game = dict(ply=np.array([len(h) for h in hist], np.float64), history=history, chosen=rs["chosen"].astype(np.float64),
+                    phase=rs["phase"].astype(np.float64))
+    row_bytes = sum(a.nbytes // G for a in per_game.values()) + 8
+    keep = min(G, (DUMP_BYTES // max(world, 1) - 4096) // row_bytes)
+    games = np.arange(G) if keep == G else np.sort(np.random.default_rng(2024).choice(G, keep, replace=False))
+    s = eng.stats()
+    arrays = {k: np.ascontiguousarray(a[games]) for k, a in per_game.items()}
+    arrays["games"] = games.astype(np.float64)
+    arrays["counters"] = np.array([int(x) for x in s["game_stats"]] + [s["evals"], s["sims"], s["plies"], s["cache_hits"]], np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), a)
+    return arrays
+
+
 def main():
     argv = sys.argv[1:]
     args = parse(argv)
@@ -294,13 +336,15 @@ def main():
         if rank == 0:
             print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
-    def measure(config, G, sims_arg, blocks_arg, steps, warmup, legs):
-        """One configuration, start to finish -> (the result dict on rank 0 / None elsewhere, the network)."""
+    def measure(config, G, sims_arg, blocks_arg, steps, warmup, legs, dump_dir=""):
+        """One configuration, start to finish -> (the result dict on rank 0 / None elsewhere, the network).  Without --full: the headline
+        segment only (no per-kernel timing, no extra segments or legs)."""
+        full = args.full
         game, dG, dS, dB, max_actions, ef, es, cpuct, alpha, search, gm = CONFIGS[config]
         G = G or dG; sims = sims_arg or dS; blocks = blocks_arg or dB
         gumbel = search == "gumbel"
         use_net = args.evaluator == "resnet"
-        net = NETS[game](blocks, seed=0, policy_head="linear" if gumbel else "softmax").eval() if (use_net or not args.no_cpu_baseline) else None
+        net = NETS[game](blocks, seed=0, policy_head="linear" if gumbel else "softmax").eval() if (use_net or (full and not args.no_cpu_baseline)) else None
         weights = net.export_engine_weights() if use_net else None
         cache_leg = args.cache_leg if args.cache_leg >= 0 else (0 if config == "gomoku" else 24)
         # steady state (SURVEY 8d; VERDICT r2 weak 8).  The ply mix decides how many simulations of a move need the evaluator (openings ~190 of
@@ -364,15 +408,21 @@ def main():
 
         eng = make_engine(sims, args.eval_cache)
         log(f"[{config}] engine ready: {world} rank(s) x {G} games, {sims} sims/move, evaluator={args.evaluator}")
-        dt, delta = timed_run(eng, True)
+        dt, delta = timed_run(eng, full)
         log(f"[{config}] timed region done: {dt:.3f}s for {steps} steps")
-        tm = eng.timing()
-        kname, kflops = eng.dominant_kernel()
+        if dump_dir:
+            dump_outputs(eng, dump_dir, rank, world)
+            log(f"[{config}] outputs of the last step written to {dump_dir}")
         fused = bool(eng.stats().get("fused_wave"))
         groups = int(eng.stats().get("game_groups", 1))
         tm_fused, kname_fused, tm_groups = None, None, None
         keng = eng                                              # the engine the per-kernel segments run on
-        if groups > 1 and use_net:
+        if full:
+            tm = eng.timing()
+            kname, kflops = eng.dominant_kernel()
+        else:                                                   # plain run: no kernel timing, hence no roofline
+            tm, kname, kflops = dict(ms_tree=0.0, ms_eval=0.0, ms_dominant=0.0, n_dominant=0, n_waves=0), "", 0.0
+        if full and groups > 1 and use_net:
             # The headline segment ran the games as `groups` batches with their launches in flight TOGETHER (gaz_engine_config::game_groups): the
             # durations of overlapping kernels price nothing.  The per-kernel numbers (roofline, roofline_tree, the fused launch) are therefore
             # taken on ONE batch of all the games — the launch shape the rocprofv3 summaries under profiles/ show — on a second engine brought to
@@ -387,7 +437,7 @@ def main():
             tm = keng.timing()
             kname, kflops = keng.dominant_kernel()
             log(f"[{config}] one-batch engine for the per-kernel segments ready")
-        if fused and use_net:
+        if full and fused and use_net:
             # The headline segment ran the tree step and the trunk kernel as ONE launch (k_wave_trunk): its duration includes the part of
             # the tree step it could not hide, so it does not price the MFMA kernel.  Time the trunk kernel on its own in a second
             # segment of this run: same engine, same games, tree step and trunk launched separately (results are bit-identical).
@@ -398,7 +448,8 @@ def main():
             tm = keng.timing()
             kname, kflops = keng.dominant_kernel()
             keng.set_fused_wave(True)
-        keng.timing_reset(False)
+        if full:
+            keng.timing_reset(False)
         if keng is not eng:
             keng.close()
         t_red = time.perf_counter()
@@ -508,15 +559,16 @@ def main():
                                    evals_per_position=evals / max(positions, 1), evals_per_s=evals / dt, sims_per_s=n_sims / dt,
                                    eval_cache_log2=args.eval_cache, eval_cache_hits=hits,
                                    eval_tflops=(evals - hits) * fl["total"] / dt / 1e12,
-                                   fused_tree_and_trunk_launch=fused, fused_launch_faults=faults, game_groups=groups,
-                                   ms_tree_kernel_per_wave=tm["ms_tree"] / tw,
-                                   ms_evaluator_per_wave=tm["ms_eval"] / tw,
-                                   per_wave_note=(("tree / evaluator ms per wave come from the unfused timing segment" + (" on one batch of all the games" if tm_groups else "")) if tm_fused is not None else None)),
-                       roofline=roof, roofline_tree=roof_tree)
+                                   fused_tree_and_trunk_launch=fused, fused_launch_faults=faults, game_groups=groups))
+            if full:                                            # per-kernel figures: timing events in the timed region + segments of their own
+                out["detail"].update(ms_tree_kernel_per_wave=tm["ms_tree"] / tw, ms_evaluator_per_wave=tm["ms_eval"] / tw,
+                                     per_wave_note=(("tree / evaluator ms per wave come from the unfused timing segment" + (" on one batch of all the games" if tm_groups else "")) if tm_fused is not None else None))
+                out.update(roofline=roof, roofline_tree=roof_tree)
 
-        # ---- extra legs (never the headline value) -------------------------------------------------------------------------
+        # ---- extra legs (never the headline value; --full only) ------------------------------------------------------------
         # (1) the same workload with the on-device evaluation cache (the reference's Connect4 config runs its
         #     Session_Cache too).  Search results are bit-identical; repeated states are answered from HBM inside the tree kernel.
+        legs = legs and full
         if legs and cache_leg and args.eval_cache == 0 and use_net:
             e2 = make_engine(sims, cache_leg)
             dt2, d2 = timed_run(e2, False)
@@ -542,11 +594,11 @@ def main():
                                                         "move (Self_Play.py:99); NOT the headline value")
         return out, net
 
-    out, net = measure(args.config, args.games, args.sims, args.blocks, args.steps, args.warmup, legs=True)
-    # ---- BASELINE configs[3] and configs[4] in the same command: their own workloads, their own rooflines (priced per launch)
-    # and evaluations per position; shorter timed regions (a Gomoku wave is six times a Connect4 wave).  Never the headline value.
+    out, net = measure(args.config, args.games, args.sims, args.blocks, args.steps, args.warmup, legs=True, dump_dir=args.dump_outputs)
+    # ---- BASELINE configs[3] and configs[4] in the same command (--full only): their own workloads, their own rooflines (priced
+    # per launch) and evaluations per position; shorter timed regions (a Gomoku wave is six times a Connect4 wave).  Never the headline value.
     other = args.other_configs if args.other_configs >= 0 else int(args.config == "connect4" and world == 1 and not emu and args.games == 0 and args.sims == 0 and args.blocks == 0)
-    if other:
+    if other and args.full:
         for name, steps, warm in (("gumbel", max(2, args.steps // 2), max(1, args.warmup // 2)), ("gomoku", max(2, args.steps // 4), 1)):
             o2, _ = measure(name, 0, 0, 0, steps, warm, legs=False)
             if rank == 0:
@@ -557,7 +609,7 @@ def main():
                 out[name]["ms_tree_kernel_per_wave"] = o2["detail"]["ms_tree_kernel_per_wave"]
                 out[name]["ms_evaluator_per_wave"] = o2["detail"]["ms_evaluator_per_wave"]
                 out[name]["note"] = f"BASELINE.json configs[{4 if name == 'gumbel' else 3}] measured by the same command; NOT the headline value"
-    if rank == 0 and not args.no_cpu_baseline and world == 1 and args.config == "connect4" and not emu:
+    if rank == 0 and args.full and not args.no_cpu_baseline and world == 1 and args.config == "connect4" and not emu:
         args.sims = args.sims or CONFIGS["connect4"][2]
         out["cpu_baseline"] = cpu_baseline(args, net)
     if rank == 0:

@@ -76,6 +76,31 @@ def test_launcher_propagates_a_failing_rank(tmp_path):
     assert p.returncode != 0 and b'"metric"' not in p.stdout
 
 
+def test_dump_outputs_are_the_same_from_run_to_run_and_with_full(emu_lib, tmp_path):
+    """--dump-outputs DIR: what the timed path computed after its last step, float32 / float64 .npy files within 64 MB, identical for two
+    runs with the same arguments and for a --full run (its extra timing changes no result).  A plain line carries no per-kernel figures."""
+    lines = {}
+    for tag, extra in (("a", []), ("b", []), ("full", ["--full"])):
+        p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--emu-lib", emu_lib, "--dump-outputs", str(tmp_path / tag)] + SMALL + extra,
+                           env=_clean_env(), capture_output=True, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        lines[tag] = json.loads([ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")][-1])
+    assert lines["a"]["steps"] == 2 and lines["a"]["ms_per_step"] > 0 and "roofline" not in lines["a"]
+    assert "roofline" in lines["full"] and "ms_tree_kernel_per_wave" in lines["full"]["detail"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert {"ply.npy", "history.npy", "chosen.npy", "counters.npy"} <= set(names)
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        a = np.load(tmp_path / "a" / n)
+        assert a.dtype in (np.float32, np.float64), n
+        for tag in ("b", "full"):
+            np.testing.assert_array_equal(a, np.load(tmp_path / tag / n), err_msg=f"{tag}: {n}")
+    ply, hist = np.load(tmp_path / "a" / "ply.npy"), np.load(tmp_path / "a" / "history.npy")
+    assert ply.shape == (6,) and ply.sum() > 0 and hist.shape[0] == 6 and (hist[0, :int(ply[0])] >= 0).all()
+    counters = np.load(tmp_path / "a" / "counters.npy")             # game_stats[0:6], evals, sims, plies, cache_hits: since the start
+    assert counters.shape == (10,) and counters[8] >= lines["a"]["detail"]["positions"] > 0
+
+
 def test_cpu_baseline_runs_workers_against_one_batching_server(oracle):
     """The bench's cpu_baseline leg: one oracle game per host core, every leaf a request to ONE batching PyTorch server
     (Client_Server.py:162-217) — here a short window with a one-block network."""

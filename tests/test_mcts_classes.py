@@ -87,12 +87,16 @@ def test_mcts_run_with_time_limit(emu_lib, oracle):
     from grok_alpha_zero_amd.mcts import MCTS
     game = GAMES["Connect4"]()
     mcts = MCTS(game, None, c_puct_init=2.5, dirichlet_alpha=0.5, tau=0.0, seed=3, hash_salt=1, lib_path=emu_lib)
+    # a time-only run is also capped by the node arena (MCTS._MAX_TIMED_ITERATIONS): the limit is kept short enough that the clock, not
+    # the cap, ends the search even on a fast host (a fast host reaches the cap in about 0.1 s)
+    limit = 0.04
     t0 = time.time()
-    move, rows = mcts.run(iteration_limit=None, time_limit=0.2, use_bar=False)
+    move, rows = mcts.run(iteration_limit=None, time_limit=limit, use_bar=False)
     dt = time.time() - t0
-    assert 0.15 <= dt < 5.0
+    assert 0.75 * limit <= dt < 5.0
     visits = sum(int(r[4]) for r in rows)
-    assert visits >= 7 and rows == sorted(rows, key=lambda r: r[4], reverse=True)
+    assert 7 <= visits < MCTS._MAX_TIMED_ITERATIONS                            # the clock ended it
+    assert rows == sorted(rows, key=lambda r: r[4], reverse=True)
     assert int(move) == int(rows[0][0])                                       # tau = 0: the most visited move
     game.do_action(move); mcts.prune_tree(move)
     move2, rows2 = mcts.run(iteration_limit=40, time_limit=60.0, use_bar=False)   # the iteration limit ends it long before the clock

@@ -3,7 +3,7 @@
 # stamp timeline of one launch (tools/fused_timeline.py).  usage: tools/ab_fused.sh <tag> [extra bench args]
 out=gpurun_out/${1:-ab}; mkdir -p $out; shift
 run() {  # name, queue
-  GAZ_FUSE_QUEUE=$2 GAZ_FUSED_STAMPS=$out/$1.stamps:2500 timeout -k 10 200 python bench.py --steps 8 --warmup 3 --other-configs 0 --no-cpu-baseline --cache-leg 0 --ref-convention-leg 0 "${@:3}" > $out/$1.json 2> $out/$1.err || { tail -5 $out/$1.err; return 1; }
+  GAZ_FUSE_QUEUE=$2 GAZ_FUSED_STAMPS=$out/$1.stamps:2500 timeout -k 10 200 python bench.py --full --steps 8 --warmup 3 --other-configs 0 --no-cpu-baseline --cache-leg 0 --ref-convention-leg 0 "${@:3}" > $out/$1.json 2> $out/$1.err || { tail -5 $out/$1.err; return 1; }
   python - <<PY
 import json
 d=json.loads(open("$out/$1.json").read().strip().splitlines()[-1])

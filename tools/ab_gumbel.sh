@@ -2,7 +2,7 @@
 # Gumbel config (BASELINE configs[4]) on one box: fused launch with four games per wavefront / one game per wavefront / separate launches
 out=gpurun_out/${1:-abg}; mkdir -p $out
 run() {  # name, env...
-  env "${@:2}" timeout -k 10 200 python bench.py --config gumbel --steps 8 --warmup 3 --no-cpu-baseline --cache-leg 0 > $out/$1.json 2> $out/$1.err || { tail -5 $out/$1.err; return 1; }
+  env "${@:2}" timeout -k 10 200 python bench.py --full --config gumbel --steps 8 --warmup 3 --no-cpu-baseline --cache-leg 0 > $out/$1.json 2> $out/$1.err || { tail -5 $out/$1.err; return 1; }
   python - <<PY
 import json
 d=json.loads(open("$out/$1.json").read().strip().splitlines()[-1])

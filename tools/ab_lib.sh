@@ -2,7 +2,7 @@
 # A/B of two builds of the library on one box: tools/ab_lib.sh <tag> <libA> <libB> [config ...]
 out=gpurun_out/$1; mkdir -p $out; A=$2; B=$3; shift 3
 run() {  # name, lib, config
-  GAZ_ENGINE_LIB=$2 timeout -k 10 250 python bench.py --config $3 --steps 8 --warmup 2 --other-configs 0 --no-cpu-baseline --cache-leg 0 --ref-convention-leg 0 > $out/$1.json 2> $out/$1.err || { tail -5 $out/$1.err; return 1; }
+  GAZ_ENGINE_LIB=$2 timeout -k 10 250 python bench.py --full --config $3 --steps 8 --warmup 2 --other-configs 0 --no-cpu-baseline --cache-leg 0 --ref-convention-leg 0 > $out/$1.json 2> $out/$1.err || { tail -5 $out/$1.err; return 1; }
   python - <<PY
 import json
 d=json.loads(open("$out/$1.json").read().strip().splitlines()[-1])

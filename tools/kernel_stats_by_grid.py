@@ -1,5 +1,5 @@
 """rocprofv3 --kernel-trace CSV -> launches grouped by (kernel, workgroups): calls, average / min / max duration.
-rocprofv3 --stats averages a kernel over ALL its launches; bench.py runs three configurations in one command, and the same trunk kernel serves a
+rocprofv3 --stats averages a kernel over ALL its launches; bench.py --full runs three configurations in one command, and the same trunk kernel serves a
 4096-board (Connect4) and an 8192-board (Gumbel) batch — this table keeps them apart so that a launch shape's average can be held against the
 bench line's avg_launch_us.  usage: python tools/kernel_stats_by_grid.py <run_kernel_trace.csv> [min_total_ms] > out.csv"""
 import csv

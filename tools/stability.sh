@@ -11,7 +11,7 @@ print("steps $k: %.0f pos/s  %.2fM evals/s  evals/pos %.1f  games finished %d" %
 PY
 done
 for f in 1 0; do
-  GAZ_FUSE_GOMOKU=$f timeout -k 10 300 python bench.py --config gomoku --steps 3 --warmup 1 --no-cpu-baseline --cache-leg 0 > $out/gmk_f$f.json 2> $out/gmk_f$f.err || { tail -3 $out/gmk_f$f.err; exit 1; }
+  GAZ_FUSE_GOMOKU=$f timeout -k 10 300 python bench.py --full --config gomoku --steps 3 --warmup 1 --no-cpu-baseline --cache-leg 0 > $out/gmk_f$f.json 2> $out/gmk_f$f.err || { tail -3 $out/gmk_f$f.err; exit 1; }
   python - <<PY
 import json
 d=json.loads(open("$out/gmk_f$f.json").read().strip().splitlines()[-1]); t=d["detail"]; r=d["roofline"]

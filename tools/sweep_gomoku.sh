@@ -1,7 +1,7 @@
 #!/bin/bash
 out=gpurun_out/${1:-gmk}; mkdir -p $out
 run() {  # name, args...
-  timeout -k 10 250 python bench.py --config gomoku --steps 3 --warmup 1 --no-cpu-baseline --cache-leg 0 "${@:2}" > $out/$1.json 2> $out/$1.err || { tail -5 $out/$1.err; return 1; }
+  timeout -k 10 250 python bench.py --full --config gomoku --steps 3 --warmup 1 --no-cpu-baseline --cache-leg 0 "${@:2}" > $out/$1.json 2> $out/$1.err || { tail -5 $out/$1.err; return 1; }
   python - <<PY
 import json
 d=json.loads(open("$out/$1.json").read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # evaluation-free simulations per game and launch (--max-tree-sims), current fused launches, one box: headline, Gumbel, Gomoku
 out=gpurun_out/${1:-mts}; mkdir -p $out
 run() {  # name, config, args...
-  timeout -k 10 250 python bench.py --config $2 --other-configs 0 --no-cpu-baseline --cache-leg 0 --ref-convention-leg 0 "${@:3}" > $out/$1.json 2> $out/$1.err || { tail -5 $out/$1.err; return 1; }
+  timeout -k 10 250 python bench.py --full --config $2 --other-configs 0 --no-cpu-baseline --cache-leg 0 --ref-convention-leg 0 "${@:3}" > $out/$1.json 2> $out/$1.err || { tail -5 $out/$1.err; return 1; }
   python - <<PY
 import json
 d=json.loads(open("$out/$1.json").read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # games per tree block of the fused launch (GAZ_FUSE_TREE_ROUNDS x 16), headline and Gumbel configs, one box
 out=gpurun_out/${1:-rounds}; mkdir -p $out
 run() {  # name, config, env...
-  env "${@:3}" timeout -k 10 200 python bench.py --config $2 --steps 8 --warmup 3 --other-configs 0 --no-cpu-baseline --cache-leg 0 --ref-convention-leg 0 > $out/$1.json 2> $out/$1.err || { tail -5 $out/$1.err; return 1; }
+  env "${@:3}" timeout -k 10 200 python bench.py --full --config $2 --steps 8 --warmup 3 --other-configs 0 --no-cpu-baseline --cache-leg 0 --ref-convention-leg 0 > $out/$1.json 2> $out/$1.err || { tail -5 $out/$1.err; return 1; }
   python - <<PY
 import json
 d=json.loads(open("$out/$1.json").read().strip().splitlines()[-1])

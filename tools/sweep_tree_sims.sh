@@ -3,7 +3,7 @@
 out=gpurun_out/${1:-sweep}; mkdir -p $out
 for st in 1 0; do
 for m in 1 2 3 4 6; do
-  timeout -k 10 200 python bench.py --steps 8 --warmup 3 --stagger $st --max-tree-sims $m --other-configs 0 --no-cpu-baseline --cache-leg 0 --ref-convention-leg 0 > $out/s${st}_m$m.json 2> $out/s${st}_m$m.err || exit 1
+  timeout -k 10 200 python bench.py --full --steps 8 --warmup 3 --stagger $st --max-tree-sims $m --other-configs 0 --no-cpu-baseline --cache-leg 0 --ref-convention-leg 0 > $out/s${st}_m$m.json 2> $out/s${st}_m$m.err || exit 1
   python - <<PY
 import json
 d=json.loads(open("$out/s${st}_m$m.json").read().strip().splitlines()[-1])
