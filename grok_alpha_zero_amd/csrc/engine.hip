@@ -81,9 +81,22 @@ template <class G> GAZ_KERNEL k_reset_games(DevParams<G> E, const int32_t* slots
 }
 
 // put one slot at an arbitrary position (MCTS attaches to a live game object, MCTS.py:296-313): replay `n` actions on an empty
-// board, then let the state machine build the root(s) there.
+// board, then let the state machine build the root(s) there.  The record's prefix rows [0, n) hold the prefix as their actions and
+// zeros in every per-move field (no search ran there): the record of the slot's previous game would otherwise show through.
 template <class G> GAZ_KERNEL k_set_position(DevParams<G> E, int g, const int32_t* actions, int n) {
-    if (block_id() != 0 || lane_id() != 0 || g < 0 || g >= E.n_games) return;
+    using RL = RecLayout<G>;
+    if (block_id() != 0 || g < 0 || g >= E.n_games) return;
+    {
+        uint8_t* rec = E.recs + (size_t)g * RL::SIZE;
+        const int m = n < G::MAXT ? n : G::MAXT;
+        uint32_t* q = reinterpret_cast<uint32_t*>(rec + RL::OFF_Q); uint32_t* rv = reinterpret_cast<uint32_t*>(rec + RL::OFF_RV);
+        uint32_t* ev = reinterpret_cast<uint32_t*>(rec + RL::OFF_EV);
+        for (int i = lane_id(); i < m; i += WAVE) { q[i] = 0u; rv[i] = 0u; ev[i] = 0u; }
+        uint32_t* pol = reinterpret_cast<uint32_t*>(rec + RL::OFF_POL); uint32_t* nn = reinterpret_cast<uint32_t*>(rec + RL::OFF_N);
+        uint32_t* w = reinterpret_cast<uint32_t*>(rec + RL::OFF_W); uint32_t* p = reinterpret_cast<uint32_t*>(rec + RL::OFF_P);
+        for (int i = lane_id(); i < m * G::A; i += WAVE) { pol[i] = 0u; nn[i] = 0u; w[i] = 0u; p[i] = 0u; }
+    }
+    if (lane_id() != 0) return;
     GameState<G>& gs = E.games[g];
     const uint32_t seq = gs.game_seq, sid = gs.slot_id; const uint64_t ne = gs.n_evals, ns = gs.n_sims, np = gs.n_plies;
     memset(&gs, 0, sizeof(gs));
@@ -93,7 +106,7 @@ template <class G> GAZ_KERNEL k_set_position(DevParams<G> E, int g, const int32_
         const int a = actions[i];
         gs.board[landing_cell<G>(gs.board, a)] = (int8_t)player;
         gs.hist[i] = (uint8_t)a; player = -player;
-        E.recs[(size_t)g * RecLayout<G>::SIZE + RecLayout<G>::OFF_ACT + i] = (uint8_t)a;
+        E.recs[(size_t)g * RL::SIZE + RL::OFF_ACT + i] = (uint8_t)a;
     }
     gs.n_hist = n < G::MAXT ? n : G::MAXT; gs.next_player = player;
     gs.roots_todo = (E.single_tree || E.gstate) ? 1 : 3; gs.phase = (E.sync_moves && E.single_tree) ? PH_IDLE : PH_ROOT; gs.pend_kind = PEND_NONE;
@@ -942,21 +955,35 @@ template <class G> struct EngineT : gaz_engine {
     int set_position(int slot, const int32_t* actions, int n) override {
         if (n_eff != E.n_games) return fail("set_position: not after gaz_engine_repack (a physical slot no longer identifies a game)");
         if (slot < 0 || slot >= E.n_games || n < 0 || n > G::MAXT) return fail("set_position: bad slot / history length");
+        // the game ends at ply max_actions (absolute plies, Self_Play.py:155-157): a longer history would never reach that cap and play on past
+        // what the record and the tree arena were sized for
+        if (n >= E.max_actions) return fail("set_position: a history of " + std::to_string(n) + " actions leaves no move below max_actions = " + std::to_string(E.max_actions));
         if (n > 0) HIP_OK(hipMemcpyAsync(dMoves, actions, sizeof(int32_t) * n, hipMemcpyHostToDevice, stream));   // dMoves holds >= MAXT? n_games ints
         GAZ_LAUNCH(k_set_position<G>, 1, WAVE, stream, E, slot, (const int32_t*)dMoves, n);
         HIP_OK(hipGetLastError());
         return 0;
     }
-    uint8_t* dHist = nullptr;
+    uint8_t* dHist = nullptr; std::vector<uint8_t> hHist;
     int read_positions(int32_t* n_hist, uint8_t* hist, int stride) override {
         if (!n_hist || !hist || stride < G::MAXT) return fail("read_positions: hist must hold at least max_T actions per slot");
-        if (stride > G::TPAD) stride = G::TPAD;
         if (!dHist && dalloc(&dHist, (size_t)E.n_games * G::TPAD)) return 1;
-        GAZ_LAUNCH(k_read_positions<G>, E.n_games, WAVE, stream, E, dPhase, dHist, stride);
+        // the device rows are TPAD apart; the caller's rows `stride` apart (bytes past TPAD are zero: no history is longer than MAXT)
+        GAZ_LAUNCH(k_read_positions<G>, E.n_games, WAVE, stream, E, dPhase, dHist, G::TPAD);
         HIP_OK(hipGetLastError());
         HIP_OK(hipMemcpyAsync(n_hist, dPhase, (size_t)E.n_games * 4, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipMemcpyAsync(hist, dHist, (size_t)E.n_games * stride, hipMemcpyDeviceToHost, stream));
+        if (stride == G::TPAD) HIP_OK(hipMemcpyAsync(hist, dHist, (size_t)E.n_games * stride, hipMemcpyDeviceToHost, stream));
+        else {
+            hHist.resize((size_t)E.n_games * G::TPAD);
+            HIP_OK(hipMemcpyAsync(hHist.data(), dHist, hHist.size(), hipMemcpyDeviceToHost, stream));
+        }
         HIP_OK(hipStreamSynchronize(stream));
+        if (stride != G::TPAD) {
+            const int row = stride < G::TPAD ? stride : G::TPAD;
+            for (int g = 0; g < E.n_games; ++g) {
+                memcpy(hist + (size_t)g * stride, hHist.data() + (size_t)g * G::TPAD, row);
+                memset(hist + (size_t)g * stride + row, 0, (size_t)(stride - row));
+            }
+        }
         return 0;
     }
     int start_search() override { GAZ_LAUNCH(k_start_search<G>, E.n_games, WAVE, stream, E); HIP_OK(hipGetLastError()); return 0; }
@@ -1199,7 +1226,8 @@ struct GroupEngine : gaz_engine {
         for (int c = 0; c < K(); ++c) {
             uint64_t s[16];
             if (up(kid[c], kid[c]->get_stats(s))) return 1;
-            for (int i = 0; i < 9; ++i) out[i] += s[i];
+            if (s[0] > out[0]) out[0] = s[0];        // game_stats[0] = the LONGEST game (atomic_max on the device), as parallel.reduce_stats
+            for (int i = 1; i < 9; ++i) out[i] += s[i];
             out[10] += s[10]; out[13] += s[13];
             if (s[9] > out[9]) out[9] = s[9];        // waves: every group has run the same number
             if (!s[12]) out[12] = 0;                 // one launch per wave: only if every group runs it
@@ -1244,8 +1272,7 @@ struct GroupEngine : gaz_engine {
     int debug_fused_fault(int mod) override { return each([&](gaz_engine* k, int) { return k->debug_fused_fault(mod); }); }
     int read_positions(int32_t* n_hist, uint8_t* hist, int stride) override {
         if (!n_hist || !hist || stride < lay.max_T) return fail("read_positions: hist must hold at least max_T actions per slot");
-        const int st = stride > lay.t_pad ? lay.t_pad : stride;      // the row stride the groups write with
-        return each([&](gaz_engine* k, int c) { return k->read_positions(n_hist + first[c], hist + (size_t)first[c] * st, stride); });
+        return each([&](gaz_engine* k, int c) { return k->read_positions(n_hist + first[c], hist + (size_t)first[c] * stride, stride); });
     }
     int repack(int32_t* n_active, int32_t* n_launch) override {      // every group packs its own live games; the sums are reported
         int32_t a = 0, l = 0;

@@ -166,7 +166,12 @@ int gaz_engine_batch_ptrs(gaz_engine* h, void** d_inputs_i8, void** d_policy_f32
 int gaz_engine_read_batch(gaz_engine* h, int8_t* inputs, int32_t* pending);    /* host copies: [n_games][H*W*C], [n_games] */
 int gaz_engine_write_outputs(gaz_engine* h, const float* policy, const float* value);   /* host -> device rows */
 
-/* place one slot at the position reached by `n` actions from the empty board (new roots are built there) */
+/* place one slot at the position reached by `n` actions from the empty board (new roots are built there).  The game keeps its
+ * game_seq, the next player follows from the parity of n, both trees start fresh (event counter 0), and the tau schedule, the
+ * last-moves input planes and the max_actions cap count the prefix: the game ends by the cap at ply max_actions, so n must be
+ * below max_actions (refused otherwise).  No opening override for n > 0.  The drained record of that game spans all plies from
+ * the empty board: T counts the prefix, actions[0, n) are the prefix and every per-move field of rows [0, n) (policy, q, root
+ * N / W / P, root visits, evaluator calls) is 0 — no search ran there. */
 int gaz_engine_set_position(gaz_engine* h, int32_t slot, const int32_t* actions, int32_t n);
 /* iteration_limit of the following MCTS.run calls (<= 0: unchanged); tau_mode -1 = Self_Play schedule, 0 / 1 = fixed tau */
 int gaz_engine_set_search_params(gaz_engine* h, int32_t run_iterations, int32_t tau_mode);
@@ -207,8 +212,9 @@ int gaz_engine_get_stats(gaz_engine* h, uint64_t out[16]);  /* [0..5] game_stats
                                                                [13] trunk workgroups of fused launches that gave up waiting for their games (see
                                                                     gaz_engine_debug_fused_fault); non-zero = the engine has fallen back to separate launches ([12] says whether it still is: the
                                                                     one-launch form is tried again after 20000 waves, at most twice),
-                                                               [14] game groups (gaz_engine_config::game_groups as resolved; 0 = one batch): with groups, [0..8], [10], [13]
-                                                                    are sums over the groups and [12] says that every group runs the one-launch form */
+                                                               [14] game groups (gaz_engine_config::game_groups as resolved; 0 = one batch): with groups, [0] (the longest
+                                                                    game) is the maximum over the groups, [1..8], [10], [13] are sums over the groups and [12] says that every
+                                                                    group runs the one-launch form */
 int gaz_engine_synchronize(gaz_engine* h);
 
 /* Connect4 PUCT with the ResNet evaluator runs the tree step and the trunk kernel of a wave as ONE launch (k_wave_trunk: the trunk
@@ -237,7 +243,7 @@ int gaz_engine_repack(gaz_engine* h, int32_t* n_active, int32_t* n_launch);
 
 /* The action history of every slot's game in progress — game.action_history of the reference's Game objects, as action indices; what
  * gaz_engine_set_position takes.  n_hist int32 [n_games] (0 for a halted slot), hist uint8 [n_games][stride] with stride >= the game's
- * max_T (gaz_record_layout.max_T).  Synchronises the engine's stream.  bench.py draws its staggered start from it. */
+ * max_T (gaz_record_layout.max_T): row g starts at hist + g * stride, and its bytes past the history are 0.  Synchronises the engine's stream.  bench.py draws its staggered start from it. */
 int gaz_engine_read_positions(gaz_engine* h, int32_t* n_hist, uint8_t* hist, int32_t stride);
 
 /* measurement hooks (bench.py): HIP-event timing of the kernels launched on the engine's stream */

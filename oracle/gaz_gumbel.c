@@ -336,10 +336,18 @@ static int g_run(ggumbel* t, int iteration_limit, gaz_move_row* rows, int* n_row
 int gaz_selfplay_game_gumbel(const gaz_sp_config* cfg, int m, double c_visit, double c_scale, int iteration_limit,
                              gaz_eval_fn eval, void* ctx, uint64_t seed, uint32_t slot, uint32_t game_seq, int use_libm,
                              gaz_sp_record* rec) {
+    return gaz_selfplay_game_gumbel_from(cfg, m, c_visit, c_scale, iteration_limit, eval, ctx, seed, slot, game_seq, use_libm, NULL, 0, rec);
+}
+
+int gaz_selfplay_game_gumbel_from(const gaz_sp_config* cfg, int m, double c_visit, double c_scale, int iteration_limit,
+                                  gaz_eval_fn eval, void* ctx, uint64_t seed, uint32_t slot, uint32_t game_seq, int use_libm,
+                                  const int* start_history, int n_start, gaz_sp_record* rec) {
     gaz_game_desc g = gaz_game(cfg->game_id);
     int HW = g.H * g.W, SZ = HW * g.C, A = g.A;
     int8_t board[225]; int history[256]; int n_history = 0, next_player = -1;
     memset(board, 0, sizeof(board));
+    rec->T = 0; rec->winner = GAZ_RUNNING; rec->total_evals = 0;
+    if (gaz_replay_history(&g, cfg->max_actions, start_history, n_start, board, history, &n_history, &next_player)) return -1;
     g_libm = use_libm & 1;                           /* bit 1 of use_libm: activation_fn = "stablemax" (Self_Play.py:69) */
     gaz_event ev; ev.key[0] = (uint32_t)seed; ev.key[1] = (uint32_t)(seed >> 32); ev.slot = slot; ev.game_seq = game_seq;
     ev.event = 0; ev.tree = 0; ev.purpose = 0;
@@ -348,7 +356,7 @@ int gaz_selfplay_game_gumbel(const gaz_sp_config* cfg, int m, double c_visit, do
     t.eval = eval; t.eval_ctx = ctx; t.m = m; t.c_visit = c_visit; t.c_scale = c_scale; t.use_gumbel_noise = (use_libm & 4) ? 0 : 1;   /* bit 2: MCTS_Gumbel(use_gumbel_noise=False), MCTS_Gumbel.py:157,592 */
     t.use_softmax = (use_libm & 2) ? 0 : 1;
     t.ev = &ev;
-    int winner = GAZ_RUNNING, T = 0, actions_count = 0; gaz_move_row rows[225]; int n_rows;
+    int winner = GAZ_RUNNING, T = 0, actions_count = n_start; gaz_move_row rows[225]; int n_rows;
     g_create_root(&t);
     while (winner == GAZ_RUNNING && actions_count < cfg->max_actions) {
         gaz_input_state(&g, board, -next_player, history, n_history, rec->states + (size_t)T * SZ);

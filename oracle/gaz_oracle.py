@@ -74,10 +74,16 @@ def lib():
         L.gaz_hash_eval.argtypes = [C.c_void_p, C.POINTER(C.c_int8), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.gaz_selfplay_game.argtypes = [C.POINTER(SPConfig), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(SPRecord)]
         L.gaz_selfplay_game.restype = C.c_int
+        L.gaz_selfplay_game_from.argtypes = [C.POINTER(SPConfig), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                             C.POINTER(C.c_int), C.c_int, C.POINTER(SPRecord)]
+        L.gaz_selfplay_game_from.restype = C.c_int
         L.gaz_oracle_set_libm.argtypes = [C.c_int]
         L.gaz_selfplay_game_gumbel.argtypes = [C.POINTER(SPConfig), C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(SPRecord)]
         L.gaz_selfplay_game_gumbel.restype = C.c_int
+        L.gaz_selfplay_game_gumbel_from.argtypes = [C.POINTER(SPConfig), C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(SPRecord)]
+        L.gaz_selfplay_game_gumbel_from.restype = C.c_int
         L.gaz_puct_best_index.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int,
                                           C.c_uint64, C.c_double, C.c_double, C.c_int]
         L.gaz_puct_best_index.restype = C.c_int
@@ -157,18 +163,22 @@ def hash_eval(state_i8, A, salt):
 
 # ---------------------------------------------------------------- self-play of one game
 def selfplay_game_gumbel(game, iteration_limit, max_actions, m, c_visit, c_scale, seed, slot=0, game_seq=0, evaluator=None,
-                         hash_salt=0, use_libm=False, opening_actions=None, stablemax=False, gumbel_noise=True):
+                         hash_salt=0, use_libm=False, opening_actions=None, stablemax=False, gumbel_noise=True, start_history=None):
     """One Gumbel self-play game (MCTS_Gumbel.run(iteration_limit) per move, gumbel noise on).  stablemax=True: activation_fn =
-    "stablemax" in the deterministic selection (build_config["use_stablemax"], Self_Play.py:69)."""
+    "stablemax" in the deterministic selection (build_config["use_stablemax"], Self_Play.py:69).  start_history: see selfplay_game."""
     return selfplay_game(game, iteration_limit, max_actions, 0, 0, 0.0, 0.0, seed, slot, game_seq, evaluator, hash_salt,
-                         use_libm=use_libm, gumbel=(m, c_visit, c_scale, bool(stablemax), bool(gumbel_noise)), opening_actions=opening_actions)
+                         use_libm=use_libm, gumbel=(m, c_visit, c_scale, bool(stablemax), bool(gumbel_noise)), opening_actions=opening_actions,
+                         start_history=start_history)
 
 
 def selfplay_game(game, run_iterations, max_actions, explore_first, explore_second, c_puct_init, dirichlet_alpha,
                   seed, slot=0, game_seq=0, evaluator=None, hash_salt=0, c_puct_base=19652.0, create_new_root=False,
-                  use_libm=False, gumbel=None, opening_actions=None, live=None):
+                  use_libm=False, gumbel=None, opening_actions=None, live=None, start_history=None):
     """Play one PUCT self-play game with the oracle.  evaluator(state_i8[H,W,C]) -> (policy f32[A], value f32),
-    or None for the built-in hash evaluator.  Returns a dict of numpy arrays (see gaz_sp_record)."""
+    or None for the built-in hash evaluator.  Returns a dict of numpy arrays (see gaz_sp_record).
+    start_history: action indices played from the empty board before the first search, as gaz_engine_set_position puts a slot there
+    (next player from the parity, fresh trees, the tau schedule and the cap counting absolute plies); the arrays then hold the searched
+    plies only, "T" counts those and "n_start" the prefix."""
     L = lib()
     gid = GAME_IDS[game] if isinstance(game, str) else int(game)
     H, W, Cc, A = GAME_DIMS[gid]
@@ -190,17 +200,19 @@ def selfplay_game(game, run_iterations, max_actions, explore_first, explore_seco
     for i, (a, w) in enumerate(opening_actions or []):     # [(action index, weight)], train_config["opening_actions"]
         cfg.opening_actions[i] = int(a); cfg.opening_weights[i] = float(w); cfg.n_opening = i + 1
     L.gaz_oracle_set_libm(int(use_libm))
+    start = np.ascontiguousarray(start_history if start_history is not None else [], np.int32).reshape(-1)
+    startp = _p(start, C.c_int)
 
     def play(fn, ctxp):
         if gumbel is None:
-            L.gaz_selfplay_game(C.byref(cfg), fn, ctxp, seed, slot, game_seq, C.byref(rec))
+            return L.gaz_selfplay_game_from(C.byref(cfg), fn, ctxp, seed, slot, game_seq, startp, start.size, C.byref(rec))
         else:
-            L.gaz_selfplay_game_gumbel(C.byref(cfg), int(gumbel[0]), float(gumbel[1]), float(gumbel[2]), run_iterations, fn, ctxp,
-                                       seed, slot, game_seq, int(bool(use_libm)) | (2 if (len(gumbel) > 3 and gumbel[3]) else 0) | (4 if (len(gumbel) > 4 and not gumbel[4]) else 0),
-                                       C.byref(rec))
+            return L.gaz_selfplay_game_gumbel_from(C.byref(cfg), int(gumbel[0]), float(gumbel[1]), float(gumbel[2]), run_iterations, fn, ctxp,
+                                                   seed, slot, game_seq, int(bool(use_libm)) | (2 if (len(gumbel) > 3 and gumbel[3]) else 0) | (4 if (len(gumbel) > 4 and not gumbel[4]) else 0),
+                                                   startp, start.size, C.byref(rec))
     if evaluator is None:
         ctx = HashEvalCtx(hash_salt, A)
-        play(C.cast(L.gaz_hash_eval, C.c_void_p), C.cast(C.byref(ctx), C.c_void_p))
+        rc = play(C.cast(L.gaz_hash_eval, C.c_void_p), C.cast(C.byref(ctx), C.c_void_p))
     else:
         def cb(_ctx, state, n, pol, val):
             s = np.ctypeslib.as_array(state, shape=(n,)).reshape(H, W, Cc)
@@ -208,9 +220,11 @@ def selfplay_game(game, run_iterations, max_actions, explore_first, explore_seco
             np.ctypeslib.as_array(pol, shape=(A,))[:] = np.asarray(p, np.float32).reshape(-1)
             val[0] = float(v)
         fn = EVAL_FN(cb)
-        play(C.cast(fn, C.c_void_p), None)
+        rc = play(C.cast(fn, C.c_void_p), None)
     L.gaz_oracle_set_libm(0)
+    if rc < 0:
+        raise ValueError(f"start_history of {start.size} actions is not a legal unfinished game shorter than max_actions = {max_actions}")
     T = rec.T
     out = {k: v[:T].copy() for k, v in arrs.items()}
-    out["winner"] = rec.winner; out["T"] = T; out["total_evals"] = int(rec.total_evals)
+    out["winner"] = rec.winner; out["T"] = T; out["total_evals"] = int(rec.total_evals); out["n_start"] = int(start.size)
     return out

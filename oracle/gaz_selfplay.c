@@ -45,13 +45,39 @@ int gaz_opening_override(const gaz_sp_config* cfg, int mcts_action, uint64_t see
     return acts[n - 1];
 }
 
-/* Self_Play.play (Self_Play.py:71-175), use_gumbel = False. */
+/* A game attached to a position (MCTS.py:296-313, the engine's gaz_engine_set_position): the n_start actions are played from the
+ * empty board, first mover -1, into board / history; the next player follows from the parity.  -1 when the history is not a
+ * legal unfinished game shorter than max_actions (the cap counts absolute plies, so no move would be left to search). */
+int gaz_replay_history(const gaz_game_desc* g, int max_actions, const int* start_history, int n_start,
+                       int8_t* board, int* history, int* n_history, int* next_player) {
+    if (n_start < 0 || n_start >= max_actions || (n_start > 0 && !start_history)) return -1;
+    for (int i = 0; i < n_start; ++i) {
+        int legal[225], n_legal = gaz_legal_actions(g, board, legal), ok = 0;
+        for (int k = 0; k < n_legal; ++k) if (legal[k] == start_history[i]) ok = 1;
+        if (!ok) return -1;
+        gaz_do_action(g, board, start_history[i], *next_player);
+        history[(*n_history)++] = start_history[i]; *next_player = -*next_player;
+        if (gaz_check_win(g, board, -*next_player, start_history[i]) != GAZ_RUNNING) return -1;
+    }
+    return 0;
+}
+
+/* Self_Play.play (Self_Play.py:71-175), use_gumbel = False, from the empty board */
 int gaz_selfplay_game(const gaz_sp_config* cfg, gaz_eval_fn eval, void* ctx, uint64_t seed, uint32_t slot,
                       uint32_t game_seq, gaz_sp_record* rec) {
+    return gaz_selfplay_game_from(cfg, eval, ctx, seed, slot, game_seq, NULL, 0, rec);
+}
+
+/* the same from a position.  start_history / n_start: see gaz_replay_history; the record then holds the searched plies only
+ * (row 0 = ply n_start).  Returns T, or -1 for a start history that gaz_replay_history refuses. */
+int gaz_selfplay_game_from(const gaz_sp_config* cfg, gaz_eval_fn eval, void* ctx, uint64_t seed, uint32_t slot,
+                           uint32_t game_seq, const int* start_history, int n_start, gaz_sp_record* rec) {
     gaz_game_desc g = gaz_game(cfg->game_id);
     int HW = g.H * g.W, SZ = HW * g.C, A = g.A;
     int8_t board[225]; int history[256]; int n_history = 0; int next_player = -1;
     memset(board, 0, sizeof(board));
+    rec->T = 0; rec->winner = GAZ_RUNNING; rec->total_evals = 0;
+    if (gaz_replay_history(&g, cfg->max_actions, start_history, n_start, board, history, &n_history, &next_player)) return -1;
 
     /* Self_Play.__init__ (Self_Play.py:37-57): two trees on ONE game object; mcts1 first */
     gaz_puct* mcts[2];
@@ -59,7 +85,7 @@ int gaz_selfplay_game(const gaz_sp_config* cfg, gaz_eval_fn eval, void* ctx, uin
         mcts[k] = gaz_puct_create(cfg->game_id, board, history, &n_history, &next_player, eval, ctx,
                                   cfg->c_puct_init, cfg->c_puct_base, 1, cfg->dirichlet_alpha, 0.25, 1.0,
                                   seed, slot, game_seq, (uint32_t)k);
-    int actions_count = 0, winner = GAZ_RUNNING, T = 0;
+    int actions_count = n_start, winner = GAZ_RUNNING, T = 0;                        /* the cap counts absolute plies */
     gaz_move_row rows[225]; int n_rows;
     while (winner == GAZ_RUNNING && actions_count < cfg->max_actions) {
         if (T >= rec->cap_T) { fprintf(stderr, "oracle: record capacity\n"); abort(); }

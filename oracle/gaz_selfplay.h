@@ -40,11 +40,22 @@ typedef struct {
 
 int gaz_selfplay_game(const gaz_sp_config* cfg, gaz_eval_fn eval, void* ctx, uint64_t seed, uint32_t slot,
                       uint32_t game_seq, gaz_sp_record* rec);
+/* *_from: the game starts at the position start_history[n_start] (gaz_engine_set_position's semantics: next player from the parity,
+ * fresh trees, tau schedule and input encoding count the prefix, no opening override after ply 0, the max_actions cap counts
+ * absolute plies); the record holds the searched plies only.  Returns T, or -1 for a history that is illegal, finished or
+ * not shorter than max_actions.  The entry points without _from keep their signature: they start from the empty board. */
+int gaz_replay_history(const gaz_game_desc* g, int max_actions, const int* start_history, int n_start,
+                       int8_t* board, int* history, int* n_history, int* next_player);
+int gaz_selfplay_game_from(const gaz_sp_config* cfg, gaz_eval_fn eval, void* ctx, uint64_t seed, uint32_t slot,
+                           uint32_t game_seq, const int* start_history, int n_start, gaz_sp_record* rec);
 void gaz_oracle_set_libm(int on);
 /* Self_Play.play with use_gumbel = True: MCTS_Gumbel.run(iteration_limit) per move, fresh tree every move */
 int gaz_selfplay_game_gumbel(const gaz_sp_config* cfg, int m, double c_visit, double c_scale, int iteration_limit,
                              gaz_eval_fn eval, void* ctx, uint64_t seed, uint32_t slot, uint32_t game_seq, int use_libm,
                              gaz_sp_record* rec);
+int gaz_selfplay_game_gumbel_from(const gaz_sp_config* cfg, int m, double c_visit, double c_scale, int iteration_limit,
+                                  gaz_eval_fn eval, void* ctx, uint64_t seed, uint32_t slot, uint32_t game_seq, int use_libm,
+                                  const int* start_history, int n_start, gaz_sp_record* rec);
 #ifdef __cplusplus
 }
 #endif

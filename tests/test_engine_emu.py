@@ -334,6 +334,7 @@ def test_emu_game_groups_play_exactly_the_games_of_one_batch(emu_lib, oracle, se
         st = eng.stats()
         assert st["game_groups"] == k and len(recs) == budget
         assert st["game_stats"][2] == budget and st["plies"] == sum(r["T"] for r in recs)
+        assert st["game_stats"][0] == max(r["T"] for r in recs) and st["game_stats"][1] == sum(r["T"] for r in recs)   # [0]: the longest game
         out[k] = ({(r["slot"], r["game_seq"]): r for r in recs}, st)
         eng.close()
     one, many = out[1][0], out[groups][0]
@@ -342,6 +343,7 @@ def test_emu_game_groups_play_exactly_the_games_of_one_batch(emu_lib, oracle, se
         for f in ("actions", "root_N", "root_W", "root_P", "policies", "q", "evals", "root_visits", "winner", "T", "values"):
             np.testing.assert_array_equal(np.asarray(one[key][f]), np.asarray(many[key][f]), err_msg=f"{key} {f}")
     assert out[1][1]["evals"] == out[groups][1]["evals"] and out[1][1]["sims"] == out[groups][1]["sims"]
+    np.testing.assert_array_equal(out[1][1]["game_stats"], out[groups][1]["game_stats"])
     for (slot, seq) in list(one)[:4]:
         o = (oracle.selfplay_game_gumbel("Connect4", iters, 42, 4, 50.0, 1.0, 21, slot, seq, hash_salt=5) if search == "gumbel"
              else oracle.selfplay_game("Connect4", iters, 42, 4, 3, 2.5, 0.5, 21, slot, seq, hash_salt=5))
@@ -379,3 +381,174 @@ def test_emu_game_groups_route_per_slot_calls_and_refuse_what_they_cannot_serve(
         mk(8)
     with pytest.raises(RuntimeError, match="games_budget"):
         mk(2, games_budget=5)
+
+
+# ---------------------------------------------------------------- set_position against the oracle's start_history game
+def _legal_prefix(game, n, rng):
+    """a random legal history of exactly n plies that has not ended (engine action indices)"""
+    from grok_alpha_zero_amd.games import GAMES
+    cls = GAMES[game]
+    while True:
+        g, hist = cls(), []
+        for _ in range(n):
+            legal = g.get_legal_actions()
+            a = legal[int(rng.integers(0, len(legal)))]
+            g.do_action(a); hist.append(int(cls.action_to_index(a)))
+            if g.check_win() != -2:
+                break
+        else:
+            return hist
+
+
+def _drain_until(eng, want, rounds=4000, waves=16):
+    """run waves until a record of every (slot, game_seq) in `want` has been drained -> {(slot, game_seq): record}"""
+    got = {}
+    for _ in range(rounds):
+        eng.run_waves(waves)
+        for r in eng.drain_finished():
+            got[(r["slot"], r["game_seq"])] = r
+        if all(k in got for k in want):
+            return got
+    raise AssertionError(f"games {sorted(set(want) - set(got))} did not finish")
+
+
+def _check_from_position(r, o, prefix, what):
+    """engine record of a game placed by set_position vs the oracle's game from start_history = prefix: the record spans every ply
+    from the empty board — rows [0, n) are the prefix with zero per-move fields, rows [n, T) equal the oracle's rows bit for bit"""
+    n = len(prefix)
+    assert o["n_start"] == n and r["T"] == n + o["T"] and r["winner"] == o["winner"], (what, r["T"], n, o["T"], r["winner"], o["winner"])
+    np.testing.assert_array_equal(r["actions"][:n], prefix, err_msg=f"{what}: prefix actions")
+    for k in ("policies", "root_N", "root_W", "root_P", "root_visits", "q", "evals"):
+        assert not np.asarray(r[k][:n]).any(), f"{what}: {k} of the prefix rows is not 0"
+    for k in ("actions", "root_N", "root_visits", "root_W", "root_P", "policies", "values", "q", "evals"):
+        np.testing.assert_array_equal(np.asarray(r[k][n:]), np.asarray(o[k]), err_msg=f"{what}: {k}")
+
+
+# explore_first = 5 / explore_second = 4: tau = 1 for the first mover at plies 0, 2, .., 8 and for the second at 1, 3, 5 — the prefixes of 3 and 6
+# plies end inside those windows (odd: the second player moves next; even: the first), the game leaves them later
+SETPOS_CASES = [
+    ("Connect4", "puct", 42, 5, 4, [3, 6, 0, 9]),
+    ("Connect4", "gumbel", 42, 0, 0, [3, 6, 11]),
+    ("TicTacToe", "puct", 9, 2, 1, [1, 2, 4]),
+]
+
+
+@pytest.mark.parametrize("game,search,max_actions,ef,es,lengths", SETPOS_CASES)
+def test_emu_set_position_matches_oracle_start_history(emu_lib, oracle, game, search, max_actions, ef, es, lengths):
+    """gaz_engine_set_position + continuous self-play (one game per slot) vs the oracle's game from the same history
+    (oracle start_history: next player from the parity, fresh trees, tau schedule / input planes / max_actions cap counting the prefix)."""
+    from grok_alpha_zero_amd.engine import SelfPlayEngine, SEARCH_GUMBEL, SEARCH_PUCT
+    iters, G = 20, len(lengths)
+    kw = dict(search=SEARCH_GUMBEL, gumbel_m=4, c_visit=50.0, c_scale=1.0) if search == "gumbel" else dict(search=SEARCH_PUCT)
+    rng = np.random.default_rng(31)
+    prefixes = [_legal_prefix(game, n, rng) for n in lengths]
+    eng = SelfPlayEngine(game, G, iters, max_actions, ef, es, 2.5, 0.5, seed=17, hash_salt=4, slot_offset=40, ring_capacity=4 * G,
+                         games_budget=G, lib_path=emu_lib, **kw)
+    for g, h in enumerate(prefixes):
+        eng.set_position(g, h)
+    recs = _drain_until(eng, [(40 + g, 0) for g in range(G)])
+    eng.close()
+    for g, h in enumerate(prefixes):
+        if search == "gumbel":
+            o = oracle.selfplay_game_gumbel(game, iters, max_actions, 4, 50.0, 1.0, 17, 40 + g, 0, hash_salt=4, start_history=h)
+        else:
+            o = oracle.selfplay_game(game, iters, max_actions, ef, es, 2.5, 0.5, 17, 40 + g, 0, hash_salt=4, start_history=h)
+        _check_from_position(recs[(40 + g, 0)], o, h, f"{game} {search} prefix of {len(h)}")
+
+
+def _gomoku_history(mine, theirs):
+    """a Gomoku history from the empty board in which the first mover (-1) places `mine` and the second (+1) `theirs`, interleaved"""
+    assert len(mine) in (len(theirs), len(theirs) + 1)
+    h = []
+    for i in range(len(mine)):
+        h.append(mine[i][0] * 15 + mine[i][1])
+        if i < len(theirs):
+            h.append(theirs[i][0] * 15 + theirs[i][1])
+    return h
+
+
+def test_emu_set_position_gomoku_terminal_move(emu_lib, oracle):
+    """A Gomoku position (10 plies, first mover to move) with the mover's open four on row 7: the winning moves are terminal actions of
+    the root (MCTS.py:247-294) and the game ends by five in a row on the first searched ply — engine and oracle alike."""
+    from grok_alpha_zero_amd.engine import SelfPlayEngine
+    h = _gomoku_history([(7, 5), (7, 6), (7, 7), (7, 8), (2, 2)], [(3, 10), (11, 4), (12, 12), (1, 13), (10, 1)])
+    eng = SelfPlayEngine("Gomoku", 1, 24, 40, 6, 4, 4.5, 0.05, seed=8, hash_salt=2, ring_capacity=4, games_budget=1, lib_path=emu_lib)
+    eng.set_position(0, h)
+    r = _drain_until(eng, [(0, 0)], rounds=400)[(0, 0)]
+    eng.close()
+    o = oracle.selfplay_game("Gomoku", 24, 40, 6, 4, 4.5, 0.05, 8, 0, 0, hash_salt=2, start_history=h)
+    _check_from_position(r, o, h, "Gomoku open four")
+    assert r["winner"] == -1 and r["T"] == len(h) + 1 and r["actions"][-1] in (7 * 15 + 4, 7 * 15 + 9)
+
+
+def test_emu_set_position_prefix_rows_after_an_earlier_game(emu_lib, oracle):
+    """set_position in a slot that has already played a game and is in the middle of the next one: the game keeps its game_seq, its
+    record's prefix rows carry the prefix and zeros (not the earlier games' search data), the rest equals the oracle's game."""
+    from grok_alpha_zero_amd.engine import SelfPlayEngine
+    eng = SelfPlayEngine("Connect4", 2, 16, 42, 8, 7, 2.5, 0.5, seed=5, hash_salt=3, ring_capacity=16, lib_path=emu_lib)
+    done = _drain_until(eng, [(0, 0), (1, 0)], waves=8)
+    eng.run_waves(40)                                      # both slots are in the middle of a later game now
+    done.update({(r["slot"], r["game_seq"]): r for r in eng.drain_finished()})
+    s1 = 1 + max(q for (s, q) in done if s == 1)           # the game in progress in slot 1
+    h = _legal_prefix("Connect4", 7, np.random.default_rng(2))
+    eng.set_position(1, h)
+    r = _drain_until(eng, [(1, s1)], waves=8)[(1, s1)]
+    eng.close()
+    o = oracle.selfplay_game("Connect4", 16, 42, 8, 7, 2.5, 0.5, 5, 1, s1, hash_salt=3, start_history=h)
+    _check_from_position(r, o, h, f"Connect4 slot 1 game {s1}")
+
+
+@pytest.mark.parametrize("groups", [1, 2])
+def test_emu_set_position_at_the_max_actions_cap(emu_lib, oracle, groups):
+    """The cap (ply + 1 == max_actions, Self_Play.py:155-157) counts absolute plies: n = max_actions - 1 plays one move and is a draw by the
+    cap; n >= max_actions would never be capped and is refused — by the single engine and through the game groups."""
+    from grok_alpha_zero_amd.engine import SelfPlayEngine, EngineError
+    M, G = 12, 4
+    rng = np.random.default_rng(44)
+    eng = SelfPlayEngine("Connect4", G, 16, M, 8, 7, 2.5, 0.5, seed=9, hash_salt=1, ring_capacity=4 * G, games_budget=G, game_groups=groups,
+                         lib_path=emu_lib)
+    assert eng.stats()["game_groups"] == groups
+    h = _legal_prefix("Connect4", M - 1, rng)
+    slot = G - 1                                           # the last group's last slot
+    for n in (M, M + 3):
+        with pytest.raises(EngineError, match="max_actions"):
+            eng.set_position(slot, _legal_prefix("Connect4", n, rng))
+    eng.set_position(slot, h)
+    recs = _drain_until(eng, [(g, 0) for g in range(G)])
+    eng.close()
+    r = recs[(slot, 0)]
+    o = oracle.selfplay_game("Connect4", 16, M, 8, 7, 2.5, 0.5, 9, slot, 0, hash_salt=1, start_history=h)
+    assert o["T"] == 1 and o["winner"] == 0
+    _check_from_position(r, o, h, f"Connect4 prefix of {M - 1}, max_actions {M}")
+    for n in (M, M + 3):
+        with pytest.raises(ValueError):
+            oracle.selfplay_game("Connect4", 16, M, 8, 7, 2.5, 0.5, 9, slot, 0, hash_salt=1, start_history=_legal_prefix("Connect4", n, rng))
+
+
+@pytest.mark.parametrize("groups", [1, 3])
+def test_emu_read_positions_honours_the_row_stride(emu_lib, groups):
+    """gaz_engine_read_positions with a row pitch wider than the engine's own (t_pad + 16), called through the C entry point: row g starts at
+    g * stride, the bytes past each history are 0, nothing is written past n_games * stride."""
+    import ctypes as C
+    from grok_alpha_zero_amd.engine import SelfPlayEngine
+    G = 7
+    eng = SelfPlayEngine("Connect4", G, 16, 42, 8, 7, 2.5, 0.5, seed=3, hash_salt=1, game_groups=groups, lib_path=emu_lib)
+    rng = np.random.default_rng(6)
+    hs = [_legal_prefix("Connect4", n, rng) for n in (5, 0, 9, 2, 13, 1, 7)]
+    for g, h in enumerate(hs):
+        if h:
+            eng.set_position(g, h)
+    eng.run_waves(12)
+    want = eng.read_positions()                            # stride = t_pad
+    assert sum(len(w) > 0 for w in want) >= 5
+    stride = int(eng.layout.t_pad) + 16
+    n = np.full(G + 1, -7, np.int32)
+    buf = np.full((G + 1) * stride, 0xAB, np.uint8)
+    assert eng.L.gaz_engine_read_positions(eng.h, n.ctypes.data, buf.ctypes.data, C.c_int32(stride)) == 0
+    assert eng.stats()["game_groups"] == groups
+    eng.close()
+    rows = buf[:G * stride].reshape(G, stride)
+    for g in range(G):
+        assert n[g] == len(want[g]) and rows[g, :n[g]].tolist() == want[g], (g, rows[g, :n[g]].tolist(), want[g])
+        assert not rows[g, n[g]:].any(), f"slot {g}: bytes past the history are not 0"
+    assert n[G] == -7 and (buf[G * stride:] == 0xAB).all()
