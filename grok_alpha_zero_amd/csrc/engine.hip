@@ -1284,20 +1284,20 @@ struct GroupEngine : gaz_engine {
                     const float* pin, float* pout) override { return up(kid[0], kid[0]->probe_rules(actions, n_actions, n_pos, stride, b, l, w, in, t, pin, pout)); }
 };
 
-// auto (game_groups = 0): two groups where that was measured to pay (see above); GAZ_GAME_GROUPS overrides the automatic choice only
+// auto (game_groups = 0): two groups where that was measured to pay (see above; measured at num_filters = 128 only, so other widths run one group); GAZ_GAME_GROUPS overrides the automatic choice only
 static int choose_game_groups(const gaz_engine_config& c) {
     if (c.game_groups != 0) return c.game_groups;
     static const int env = getenv("GAZ_GAME_GROUPS") ? atoi(getenv("GAZ_GAME_GROUPS")) : 0;
     const bool able = !c.sync_moves && c.evaluator != GAZ_EVAL_EXTERNAL && !(c.games_budget > 0 && c.games_budget < c.n_games);
     if (env > 0) return (able && env <= c.n_games) ? env : 1;
     // (with the evaluation cache every group has a table of its own — nothing is shared between groups: 108.2 k -> 110.2 k positions/s)
-    const bool pays = c.game == GAZ_GAME_CONNECT4 && c.search == GAZ_SEARCH_PUCT && c.evaluator == GAZ_EVAL_RESNET && c.net_blocks > 0 && c.n_games >= 3072;
+    const bool pays = c.game == GAZ_GAME_CONNECT4 && c.search == GAZ_SEARCH_PUCT && c.evaluator == GAZ_EVAL_RESNET && c.net_blocks > 0 && c.net_filters == 128 && c.n_games >= 3072;
     // Gomoku (2048 games, 10 blocks; the one-launch wave needs the cache off): 2195 -> 2330 positions/s, 2384 with four tree rounds per block
     // (EngineT::one_wave); from empty boards 1706 -> 1855.  Three groups 2225.  Its heads are a chain of small kernels (~300 us of a 3000-us wave)
     // that one batch runs on an idle chip
-    const bool pays_gmk = c.game == GAZ_GAME_GOMOKU && c.search == GAZ_SEARCH_PUCT && c.evaluator == GAZ_EVAL_RESNET && c.net_blocks > 0 && c.eval_cache_log2 == 0 && c.n_games >= 2048;
+    const bool pays_gmk = c.game == GAZ_GAME_GOMOKU && c.search == GAZ_SEARCH_PUCT && c.evaluator == GAZ_EVAL_RESNET && c.net_blocks > 0 && c.net_filters == 128 && c.eval_cache_log2 == 0 && c.n_games >= 2048;
     // Gumbel (8192 games -> 2 x 4096, two tree rounds per block instead of four): 323.9 k -> 344.1 k positions/s same box (with four rounds: -1 %)
-    const bool pays_gumbel = c.game == GAZ_GAME_CONNECT4 && c.search == GAZ_SEARCH_GUMBEL && c.evaluator == GAZ_EVAL_RESNET && c.net_blocks > 0 && c.eval_cache_log2 == 0 && c.n_games >= 6144;
+    const bool pays_gumbel = c.game == GAZ_GAME_CONNECT4 && c.search == GAZ_SEARCH_GUMBEL && c.evaluator == GAZ_EVAL_RESNET && c.net_blocks > 0 && c.net_filters == 128 && c.eval_cache_log2 == 0 && c.n_games >= 6144;
     return able && (pays || pays_gmk || pays_gumbel) ? 2 : 1;
 }
 

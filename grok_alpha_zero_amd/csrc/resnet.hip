@@ -21,6 +21,7 @@
 #include <algorithm>
 #include "evaluator.hpp"
 #include "conv3x3.hpp"
+#include "conv_wide.hpp"
 #include "netops.hpp"
 #include "resblock.hpp"
 #include "trunk.hpp"
@@ -475,6 +476,13 @@ __global__ __launch_bounds__(128) void k_tail(TailArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ host
+// residual widths (build_config["num_filters"]) of the Connect4 and Gomoku networks: 128 runs the fused trunk kernels, the others
+// k_conv_wide (conv_wide.hpp) one convolution per launch
+static bool net_width_supported(int f) { return f == 64 || f == 128 || f == 192 || f == 256; }
+static std::string net_width_error(int f) {
+    return "num_filters (net_filters) = " + std::to_string(f) + " is not supported: the Connect4 and Gomoku networks run num_filters in {64, 128, 192, 256}";
+}
+
 struct ResNetEvaluator : Evaluator {
     int H, W, C, A, HW, blocks, filters, nmax, logits;
     std::map<std::string, float*> f32;              // device fp32 tensors by name
@@ -526,6 +534,21 @@ struct ResNetEvaluator : Evaluator {
             pair_next = pair_first ? d + numel : nullptr; pair_first = false;
             hipMemcpy(d, h.data(), numel * 2, hipMemcpyHostToDevice); b16[name] = d; return true;
         };
+        auto up_wide = [&](const std::string& name, int cout, int cin, int ntaps) -> bool {   // [ntaps][cout][cin] -> arrange_wide_weights order
+            const int64_t numel = (int64_t)ntaps * cout * cin;
+            const gaz_tensor* g = need(name, numel); if (!g) return false;
+            std::vector<bf16_t> h(numel);
+            arrange_wide_weights(g->data, cout, cin, ntaps, h.data(), f2bf_host);
+            bf16_t* d = dalloc<bf16_t>(numel); if (!d) { *err = "hipMalloc"; return false; }
+            hipMemcpy(d, h.data(), numel * 2, hipMemcpyHostToDevice); b16[name] = d; return true;
+        };
+        auto up_bias2p = [&](int Fc) -> bool {      // block 0: conv2 and the projection share one accumulator and one fp32 bias b2 + bp
+            std::vector<float> h(Fc);
+            const float* b2 = by["block0.conv2.bias"]->data; const float* bp = by["block0.proj.bias"]->data;
+            for (int c = 0; c < Fc; ++c) h[c] = b2[c] + bp[c];
+            float* d = dalloc<float>(Fc); if (!d) { *err = "hipMalloc"; return false; }
+            hipMemcpy(d, h.data(), Fc * 4, hipMemcpyHostToDevice); f32["block0.bias2p"] = d; return true;
+        };
         const int Fc = filters, F = HW * 8;
         if (!up_f32("stem.w", 9 * 128 * C) || !up_f32("stem.scale", 128) || !up_f32("stem.shift", 128)) return 1;
         {   // MFMA stem operand, BN scale folded into the weights
@@ -534,14 +557,23 @@ struct ResNetEvaluator : Evaluator {
             stem_frag = dalloc<bf16_t>(h.size()); if (!stem_frag) { *err = "hipMalloc"; return 1; }
             hipMemcpy(stem_frag, h.data(), h.size() * 2, hipMemcpyHostToDevice);
         }
-        for (int i = 0; i < blocks; ++i) {
+        if (Fc != 128) {                            // k_conv_wide operands (conv_wide.hpp); block 0 projects the 128-channel stem
+            for (int i = 0; i < blocks; ++i) {
+                const std::string b = "block" + std::to_string(i); const int cin = i == 0 ? 128 : Fc;
+                if (!up_f32(b + ".bn1.scale", cin) || !up_f32(b + ".bn1.shift", cin) || !up_wide(b + ".conv1.w", Fc, cin, 9) ||
+                    !up_f32(b + ".conv1.scale", Fc) || !up_f32(b + ".conv1.shift", Fc) || !up_wide(b + ".conv2.w", Fc, Fc, 9) ||
+                    !up_f32(b + ".conv2.bias", Fc)) return 1;
+            }
+            if (blocks > 0 && (!up_wide("block0.proj.w", Fc, 128, 1) || !up_f32("block0.proj.bias", Fc) || !up_bias2p(Fc))) return 1;
+        }
+        for (int i = 0; Fc == 128 && i < blocks; ++i) {
             const std::string b = "block" + std::to_string(i);
             pair_first = true;
             if (!up_f32(b + ".bn1.scale", Fc) || !up_f32(b + ".bn1.shift", Fc) || !up_b16(b + ".conv1.w", 9LL * Fc * Fc) ||
                 !up_f32(b + ".conv1.scale", Fc) || !up_f32(b + ".conv1.shift", Fc) || !up_b16(b + ".conv2.w", 9LL * Fc * Fc) ||
                 !up_f32(b + ".conv2.bias", Fc)) return 1;
         }
-        if (blocks > 0) {   // k_trunk operands: the slices of all blocks as one array, the per-block parameters as [block][5][128]
+        if (blocks > 0 && Fc == 128) {   // k_trunk operands: the slices of all blocks as one array, the per-block parameters as [block][5][128]
             const size_t WB = 18 * (size_t)Fc * Fc;
             trunk_w = dalloc<bf16_t>(blocks * WB); trunk_prm = dalloc<float>((size_t)blocks * TR_PRM);
             if (!trunk_w || !trunk_prm) { *err = "hipMalloc"; return 1; }
@@ -552,7 +584,7 @@ struct ResNetEvaluator : Evaluator {
                 for (int k = 0; k < 5; ++k) hipMemcpy(trunk_prm + ((size_t)i * 5 + k) * 128, f32[b + names[k]], 128 * 4, hipMemcpyDeviceToDevice);
             }
         }
-        if (!(getenv("GAZ_TILE_PERM") && atoi(getenv("GAZ_TILE_PERM")) == 0) && !perm_big && 96 / HW >= 1) {
+        if (!(getenv("GAZ_TILE_PERM") && atoi(getenv("GAZ_TILE_PERM")) == 0) && !perm_big && 96 / HW >= 1 && Fc == 128) {
             // the kernels' static sit-out masks (trunk.hpp conv9): 128-row tile = two wave rows (y = 0 | x = 0) and (y = H - 1 | x = W - 1); 96-row
             // tile = one wave row (y = 0 | y = H - 1 | x = 0).  Both permutations must deliver exactly that, or neither is used.
             unsigned want_big[8] = {0x007u, 0x049u, 0, 0, 0x1C0u, 0x124u, 0, 0}, want_small[6] = {0x007u, 0x1C0u, 0x049u, 0, 0, 0};
@@ -566,7 +598,7 @@ struct ResNetEvaluator : Evaluator {
                 perm_clashes = lb.clashes + ls.clashes;
             } else { perm_big = perm_small = nullptr; }
         }
-        if (!up_b16("heads.conv.w", 9LL * 32 * Fc) || !up_f32("heads.conv.bias", 32)) return 1;
+        if (!(Fc == 128 ? up_b16("heads.conv.w", 9LL * 32 * Fc) : up_wide("heads.conv.w", 32, Fc, 9)) || !up_f32("heads.conv.bias", 32)) return 1;
         for (const char* pre : {"p", "v"}) {
             const std::string p = pre; const int nout = p == "p" ? A : 1;
             if (!up_f32(p + ".bn0.scale", F) || !up_f32(p + ".bn0.shift", F) || !up_f32(p + ".d1.w", (int64_t)F * 128) ||
@@ -596,7 +628,7 @@ struct ResNetEvaluator : Evaluator {
 
     bool supports_row_base() const override { return true; }
     bool head_features(const float** p, const float** v, int* pr, int* vr) override { *p = pfeat; *v = vfeat; *pr = HW * 8; *vr = HW * 8; return true; }
-    bool supports_split() const override { return fused && trunk && trunk_whole && blocks > 0 && HW <= 128; }
+    bool supports_split() const override { return filters == 128 && fused && trunk && trunk_whole && blocks > 0 && HW <= 128; }
     // kernel arguments + grid of the whole-trunk launch for rows [p0, p0 + n) (k_trunk_mix / k_trunk with stem and heads inside)
     bool make_trunk_plan(const int8_t* in, int n, int p0, TrunkLaunchPlan& P) {
         if (!loaded || !supports_split()) return false;
@@ -641,6 +673,7 @@ struct ResNetEvaluator : Evaluator {
     // stem + every residual block (+ the heads' first convolution): planes of rows [p0, p0 + n) -> pfeat / vfeat rows [p0, p0 + n)
     void forward_trunk(hipStream_t s, const int8_t* in, int n, bool timing, int p0) override {
         if (!loaded) return;                        // engine_create without weights: outputs stay as they are
+        if (filters != 128) { forward_trunk_wide(s, in, n, timing, p0); return; }
         const int M = n * HW;
         // activation / feature buffers of rows [p0, p0 + n)
         bf16_t* const X = this->X + (size_t)p0 * HW * 128; bf16_t* const X2 = this->X2 + (size_t)p0 * HW * 128;
@@ -737,6 +770,59 @@ struct ResNetEvaluator : Evaluator {
             hipLaunchKernelGGL(k_conv_heads, dim3((M + HC_ROWS - 1) / HC_ROWS), dim3(RB3_THREADS), hc_lds_bytes(), s, hc);
         }
     }
+    // F != 128 (conv_wide.hpp): stem -> X (128 channels), a0 = relu(bn1_0(x0)) -> X2; block 0: conv1 128 -> F (X2 -> Hh), conv2 + the
+    // 128 -> F projection of x0 in one accumulator (Hh, X -> X2); blocks 1..: conv1 (Aa -> Hh), conv2 + residual (Hh, X2 -> X2); every
+    // conv2 also writes the next block's operand relu(bn1(bf16 x)) -> Aa; heads' first convolution F -> 32 -> pfeat / vfeat.  Separate
+    // launches only (no fused tree + trunk launch at these widths: supports_split() is false).
+    void forward_trunk_wide(hipStream_t s, const int8_t* in, int n, bool timing, int p0) {
+        const int M = n * HW, CW = std::max(filters, 128);
+        bf16_t* const X = this->X + (size_t)p0 * HW * CW; bf16_t* const X2 = this->X2 + (size_t)p0 * HW * CW;
+        bf16_t* const Aa = this->Aa + (size_t)p0 * HW * CW; bf16_t* const Hh = this->Hh + (size_t)p0 * HW * CW;
+        float* const pfeat = this->pfeat + (size_t)p0 * HW * 8; float* const vfeat = this->vfeat + (size_t)p0 * HW * 8;
+        {
+            StemMArgs sm; memset(&sm, 0, sizeof(sm)); sm.in = in; sm.wfrag = reinterpret_cast<const uint4*>(stem_frag); sm.shift = f32["stem.shift"]; sm.out = X;
+            sm.M = M; sm.H = H; sm.W = W;
+            const int tiles = (M + 31) / 32;
+            sm.tiles_per_wave = std::max(1, (tiles + 1343) / 2688);
+            hipLaunchKernelGGL((k_stem_mfma<4, 128, true, false>), dim3((tiles + 4 * sm.tiles_per_wave - 1) / (4 * sm.tiles_per_wave)), dim3(256), 0, s, sm);
+            const long n8 = (long)M * 128 / 8;
+            hipLaunchKernelGGL(k_affine_relu, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, X, f32["block0.bn1.scale"], f32["block0.bn1.shift"], X2, n8, 128);
+        }
+        hipEvent_t e0 = 0, e1 = 0;
+        if (timing) { hipEventCreate(&e0); hipEventCreate(&e1); tev.push_back(e0); tev.push_back(e1); hipEventRecord(e0, s); }
+        for (int i = 0; i < blocks; ++i) {
+            const std::string b = "block" + std::to_string(i), nb = "block" + std::to_string(i + 1);
+            const bool last = i + 1 == blocks;
+            WideConvArgs c1; memset(&c1, 0, sizeof(c1));
+            c1.in = i == 0 ? X2 : Aa; c1.wgt = b16[b + ".conv1.w"]; c1.scaleA = f32[b + ".conv1.scale"]; c1.shiftA = f32[b + ".conv1.shift"];
+            c1.out1 = Hh; c1.act1 = ACT_RELU; c1.M = M; c1.H = H; c1.W = W;
+            WideConvArgs c2; memset(&c2, 0, sizeof(c2));
+            c2.in = Hh; c2.wgt = b16[b + ".conv2.w"]; c2.out1 = X2; c2.act1 = ACT_NONE; c2.M = M; c2.H = H; c2.W = W;
+            if (!last) { c2.scaleB = f32[nb + ".bn1.scale"]; c2.shiftB = f32[nb + ".bn1.shift"]; c2.out2 = Aa; }
+            if (i == 0) { c2.in2 = X; c2.wgt2 = b16["block0.proj.w"]; c2.shiftA = f32["block0.bias2p"]; }
+            else { c2.shiftA = f32[b + ".conv2.bias"]; c2.res = X2; }
+            switch (filters) {
+            case 64:
+                if (i == 0) { conv_wide_launch<128, 64, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<64, 64, 9, 128, CW_EPI_BF16>(s, c2); }
+                else { conv_wide_launch<64, 64, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<64, 64, 9, 0, CW_EPI_BF16>(s, c2); }
+                break;
+            case 192:
+                if (i == 0) { conv_wide_launch<128, 192, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<192, 192, 9, 128, CW_EPI_BF16>(s, c2); }
+                else { conv_wide_launch<192, 192, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<192, 192, 9, 0, CW_EPI_BF16>(s, c2); }
+                break;
+            default:
+                if (i == 0) { conv_wide_launch<128, 256, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<256, 256, 9, 128, CW_EPI_BF16>(s, c2); }
+                else { conv_wide_launch<256, 256, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<256, 256, 9, 0, CW_EPI_BF16>(s, c2); }
+            }
+        }
+        if (timing) hipEventRecord(e1, s);
+        WideConvArgs h; memset(&h, 0, sizeof(h));
+        h.in = X2; h.wgt = b16["heads.conv.w"]; h.shiftA = f32["heads.conv.bias"]; h.M = M; h.H = H; h.W = W;
+        h.feat_p = pfeat; h.feat_v = vfeat; h.p_fs = f32["p.bn0.scale"]; h.p_ft = f32["p.bn0.shift"]; h.v_fs = f32["v.bn0.scale"]; h.v_ft = f32["v.bn0.shift"];
+        if (filters == 64) conv_wide_launch<64, 32, 9, 0, CW_EPI_HEADS>(s, h);
+        else if (filters == 192) conv_wide_launch<192, 32, 9, 0, CW_EPI_HEADS>(s, h);
+        else conv_wide_launch<256, 32, 9, 0, CW_EPI_HEADS>(s, h);
+    }
     // Dense-1 (both heads) + tail: pfeat / vfeat rows [p0, p0 + n) -> policy / value
     void forward_heads(hipStream_t s, float* policy, float* value, int n, int p0) override {
         if (!loaded) return;
@@ -758,9 +844,16 @@ struct ResNetEvaluator : Evaluator {
     void timing_get(double* ms, int64_t* launches) override {
         double t = 0;
         for (size_t i = 0; i + 1 < tev.size(); i += 2) { float a = 0; hipEventElapsedTime(&a, tev[i], tev[i + 1]); t += a; }
-        *ms = t; *launches = fused && trunk ? (int64_t)(tev.size() / 2) : (int64_t)(tev.size() / 2) * (fused ? 1 : 2) * blocks;
+        *ms = t; *launches = filters != 128 || (fused && trunk) ? (int64_t)(tev.size() / 2) : (int64_t)(tev.size() / 2) * (fused ? 1 : 2) * blocks;
     }
     const char* dominant_kernel(int n, double* flops) override {
+        if (filters != 128) {                       // priced per forward: the bracket holds every trunk convolution (2 x blocks launches)
+            const double Fw = filters, rows = (double)n * HW;
+            *flops = 2.0 * rows * (9.0 * 128.0 * Fw + 9.0 * Fw * Fw + 128.0 * Fw) + 2.0 * rows * 2.0 * 9.0 * Fw * Fw * (blocks - 1);
+            dom_label = "k_conv_wide (the residual trunk at " + std::to_string(filters) + " filters, priced per forward: block 0 = 3x3 conv 128->F + 3x3 conv "
+                        "F->F with the 1x1 projection 128->F in one accumulator, then blocks - 1 x two 3x3 convs F->F; implicit GEMM on v_mfma_f32_32x32x16_bf16)";
+            return dom_label.c_str();
+        }
         const double conv = 2.0 * (double)n * HW * 128.0 * 1152.0;
         *flops = fused ? 2 * conv : conv;
         if (fused && trunk) {
@@ -805,6 +898,7 @@ struct GenericEvaluator : Evaluator {
     bool block0_in_trunk = true; bf16_t* trunk_w0 = nullptr; float* trunk_prm0 = nullptr;
     bool stem_in_trunk_ok = true;
     bf16_t* stem_frag = nullptr;
+    std::string wide_label;
 
     ~GenericEvaluator() override {
         if (side_stream) { hipStreamSynchronize(side_stream); hipEventDestroy(ev_fork); hipEventDestroy(ev_join); hipStreamDestroy(side_stream); }
@@ -831,6 +925,22 @@ struct GenericEvaluator : Evaluator {
         arrange_conv_weights(g->data, cout, cin, h.data(), f2bf_host, ntaps);
         bf16_t* d = dalloc<bf16_t>(numel); if (!d) { lerr = "hipMalloc"; return false; }
         hipMemcpy(d, h.data(), numel * 2, hipMemcpyHostToDevice); b16[name] = d; return true;
+    }
+
+    bool up_wide(const std::string& name, int cout, int cin, int ntaps) {      // F != 128: k_conv_wide operand order (arrange_wide_weights)
+        const int64_t numel = (int64_t)ntaps * cout * cin;
+        const gaz_tensor* g = need(name, numel); if (!g) return false;
+        std::vector<bf16_t> h(numel);
+        arrange_wide_weights(g->data, cout, cin, ntaps, h.data(), f2bf_host);
+        bf16_t* d = dalloc<bf16_t>(numel); if (!d) { lerr = "hipMalloc"; return false; }
+        hipMemcpy(d, h.data(), numel * 2, hipMemcpyHostToDevice); b16[name] = d; return true;
+    }
+    bool up_bias2p(const std::string& b, int F_) {  // conv2 and the projection share one accumulator and one fp32 bias b2 + bp
+        std::vector<float> h(F_);
+        const float* b2 = by[b + ".conv2.bias"]->data; const float* bp = by[b + ".proj.bias"]->data;
+        for (int c = 0; c < F_; ++c) h[c] = b2[c] + bp[c];
+        float* d = dalloc<float>(F_); if (!d) { lerr = "hipMalloc"; return false; }
+        hipMemcpy(d, h.data(), F_ * 4, hipMemcpyHostToDevice); f32[b + ".bias2p"] = d; return true;
     }
 
     // the 29 K = 128 weight slices of k_block0: conv1 low / high input half (9 taps each), conv2 (9), projection low / high
@@ -874,15 +984,18 @@ struct GenericEvaluator : Evaluator {
             const std::string b = "block" + std::to_string(i); const int cin = i == 0 ? SC : F;
             ok = up(b + ".bn1.scale", cin) && up(b + ".bn1.shift", cin) && up(b + ".conv1.scale", F) && up(b + ".conv1.shift", F) && up(b + ".conv2.bias", F);
             if (!ok) break;
-            if (gomoku && cin == F) ok = up_mfma_pair(b + ".conv1.w", b + ".conv2.w", F);
+            if (gomoku && F != 128) ok = up_wide(b + ".conv1.w", F, cin, 9) && up_wide(b + ".conv2.w", F, F, 9) && (cin == F || up_wide(b + ".proj.w", F, cin, 1));
+            else if (gomoku && cin == F) ok = up_mfma_pair(b + ".conv1.w", b + ".conv2.w", F);
             else if (gomoku) ok = up_mfma(b + ".conv1.w", F, cin, 9) && up_mfma(b + ".conv2.w", F, F, 9);
             else ok = up(b + ".conv1.w", 9LL * F * cin) && up(b + ".conv2.w", 9LL * F * F);
-            if (ok && cin != F) ok = (gomoku ? up_mfma(b + ".proj.w", F, cin, 1) : up(b + ".proj.w", (int64_t)F * cin)) && up(b + ".proj.bias", F);
+            if (ok && cin != F && gomoku && F != 128) ok = up(b + ".proj.bias", F) && up_bias2p(b, F);
+            else if (ok && cin != F) ok = (gomoku ? up_mfma(b + ".proj.w", F, cin, 1) : up(b + ".proj.w", (int64_t)F * cin)) && up(b + ".proj.bias", F);
             if (ok && gomoku && cin != F && F == 128 && cin == 256) ok = up_block0(b);
         }
         if (ok && gomoku) {
             ok = up("p.bn0.scale", F) && up("p.bn0.shift", F) && up("v.bn0.scale", F) && up("v.bn0.shift", F) &&
-                 up_mfma("p.c1.w", 32, F, 9) && up("p.c1.scale", 32) && up("p.c1.shift", 32) && up_mfma("v.c1.w", 32, F, 9) && up("v.c1.scale", 32) && up("v.c1.shift", 32) &&
+                 (F == 128 ? up_mfma("p.c1.w", 32, F, 9) && up_mfma("v.c1.w", 32, F, 9) : up_wide("p.c1.w", 32, F, 9) && up_wide("v.c1.w", 32, F, 9)) &&
+                 up("p.c1.scale", 32) && up("p.c1.shift", 32) && up("v.c1.scale", 32) && up("v.c1.shift", 32) &&
                  up("p.c2.w", 9 * 8 * 32) && up("p.c2.bias", 8) && up("p.bn2.scale", HW * 8) && up("p.bn2.shift", HW * 8) &&
                  up("v.c2.w", 4 * 32) && up("v.c2.bias", 4) && up("v.bn2.scale", HW * 4) && up("v.bn2.shift", HW * 4) &&
                  up("p.d1.w", (int64_t)HW * 8 * 512) && up("p.d1.scale", 512) && up("p.d1.shift", 512) && up("p.d2.w", 512LL * A) && up("p.d2.bias", A) &&
@@ -970,7 +1083,7 @@ struct GenericEvaluator : Evaluator {
         forward_trunk(s, in, n, timing, 0);
         forward_heads(s, policy, value, n, 0);
     }
-    bool fusable() const { return gomoku && fused && blocks > 1 && block0_in_trunk && trunk && trunk_m16 && trunk_w0 && HW <= 256; }
+    bool fusable() const { return gomoku && F == 128 && fused && blocks > 1 && block0_in_trunk && trunk && trunk_m16 && trunk_w0 && HW <= 256; }
     bool supports_split() const override { return loaded && fusable(); }
     TrunkLaunchPlan fused_plan;
     // the Gomoku trunk launch with the stem inside (trunk.hpp S0): it reads nothing but the int8 planes, so it can share a launch with the tree step
@@ -988,6 +1101,7 @@ struct GenericEvaluator : Evaluator {
     bool plan_uses_queue(const void* plan) const override { return plan && static_cast<const TrunkLaunchPlan*>(plan)->args.queue != nullptr; }
     void forward_trunk(hipStream_t s, const int8_t* in, int n, bool timing, int) override {
         if (!loaded) return;
+        if (gomoku && F != 128) { forward_trunk_wide(s, in, n, timing); return; }
         const int M = n * HW, SC = gomoku ? 256 : 128;
         StemGenArgs st; memset(&st, 0, sizeof(st));
         st.in = in; st.w = g("stem.w"); st.scale = g("stem.scale"); st.shift = g("stem.shift"); st.scaleB = g("block0.bn1.scale"); st.shiftB = g("block0.bn1.shift");
@@ -1090,6 +1204,65 @@ struct GenericEvaluator : Evaluator {
         if (timing) hipEventRecord(e1, s);
         trunk_out = cur; fuse_heads = fuse;
     }
+    // Gomoku at F != 128 (conv_wide.hpp): stem -> X0 (256 channels), a0 = relu(bn1_0(x0)) -> A0; block 0: conv1 256 -> F (A0 -> Hh),
+    // conv2 + the 256 -> F projection of x0 in one accumulator (F = 256: + the identity residual x0) -> X; blocks 1..: conv1 (Aa -> Hh),
+    // conv2 + residual (Hh, X -> X); every conv2 also writes relu(bn(bf16 x)) of the next block, the last one that of the policy head -> Aa.
+    bool wide_trunk = false;
+    void forward_trunk_wide(hipStream_t s, const int8_t* in, int n, bool timing) {
+        const int M = n * HW;
+        {
+            StemMArgs sm; memset(&sm, 0, sizeof(sm)); sm.in = in; sm.wfrag = reinterpret_cast<const uint4*>(stem_frag); sm.shift = g("stem.shift");
+            sm.out = X0; sm.M = M; sm.H = H; sm.W = W;
+            const int tiles = (M + 31) / 32;
+            sm.tiles_per_wave = std::max(1, (tiles + 1343) / 2688);
+            hipLaunchKernelGGL((k_stem_mfma<2, 256, false, false>), dim3((tiles + 4 * sm.tiles_per_wave - 1) / (4 * sm.tiles_per_wave)), dim3(256), 0, s, sm);
+            const long n8 = (long)M * 256 / 8;
+            hipLaunchKernelGGL(k_affine_relu, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, X0, g("block0.bn1.scale"), g("block0.bn1.shift"), A0, n8, 256);
+        }
+        hipEvent_t e0 = 0, e1 = 0;
+        if (timing) { hipEventCreate(&e0); hipEventCreate(&e1); tev.push_back(e0); tev.push_back(e1); hipEventRecord(e0, s); }
+        for (int i = 0; i < blocks; ++i) {
+            const std::string b = "block" + std::to_string(i), nb = "block" + std::to_string(i + 1);
+            const bool last = i + 1 == blocks;
+            WideConvArgs c1; memset(&c1, 0, sizeof(c1));
+            c1.in = i == 0 ? A0 : Aa; c1.wgt = b16[b + ".conv1.w"]; c1.scaleA = g(b + ".conv1.scale"); c1.shiftA = g(b + ".conv1.shift");
+            c1.out1 = Hh; c1.act1 = ACT_RELU; c1.M = M; c1.H = H; c1.W = W;
+            WideConvArgs c2; memset(&c2, 0, sizeof(c2));
+            c2.in = Hh; c2.wgt = b16[b + ".conv2.w"]; c2.out1 = X; c2.act1 = ACT_NONE; c2.M = M; c2.H = H; c2.W = W;
+            c2.scaleB = last ? g("p.bn0.scale") : g(nb + ".bn1.scale"); c2.shiftB = last ? g("p.bn0.shift") : g(nb + ".bn1.shift"); c2.out2 = Aa;
+            const bool proj = i == 0 && F != 256;
+            if (proj) { c2.in2 = X0; c2.wgt2 = b16[b + ".proj.w"]; c2.shiftA = g(b + ".bias2p"); }
+            else { c2.shiftA = g(b + ".conv2.bias"); c2.res = i == 0 ? X0 : X; }
+            switch (F) {
+            case 64:
+                if (i == 0) { conv_wide_launch<256, 64, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<64, 64, 9, 256, CW_EPI_BF16>(s, c2); }
+                else { conv_wide_launch<64, 64, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<64, 64, 9, 0, CW_EPI_BF16>(s, c2); }
+                break;
+            case 192:
+                if (i == 0) { conv_wide_launch<256, 192, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<192, 192, 9, 256, CW_EPI_BF16>(s, c2); }
+                else { conv_wide_launch<192, 192, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<192, 192, 9, 0, CW_EPI_BF16>(s, c2); }
+                break;
+            default:                                // 256: block 0 has no projection (256 -> 256)
+                conv_wide_launch<256, 256, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<256, 256, 9, 0, CW_EPI_BF16>(s, c2);
+            }
+        }
+        if (timing) hipEventRecord(e1, s);
+        trunk_out = X; fuse_heads = false; wide_trunk = true;
+    }
+    // heads' first convolutions at F != 128: relu(p.bn0(x)) came with the last conv2 (Aa), relu(v.bn0(x)) -> Va; 3x3 F -> 32 + BN + ReLU
+    void heads_conv_wide(hipStream_t s, int M) {
+        const long n8 = (long)M * F / 8;
+        hipLaunchKernelGGL(k_affine_relu, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, trunk_out, g("v.bn0.scale"), g("v.bn0.shift"), Va, n8, F);
+        for (int hd = 0; hd < 2; ++hd) {
+            const std::string p = hd == 0 ? "p" : "v";
+            WideConvArgs c; memset(&c, 0, sizeof(c));
+            c.in = hd == 0 ? Aa : Va; c.wgt = b16[p + ".c1.w"]; c.scaleA = g(p + ".c1.scale"); c.shiftA = g(p + ".c1.shift");
+            c.out1 = hd == 0 ? PH : VH; c.act1 = ACT_RELU; c.M = M; c.H = H; c.W = W;
+            if (F == 64) conv_wide_launch<64, 32, 9, 0, CW_EPI_BF16>(s, c);
+            else if (F == 192) conv_wide_launch<192, 32, 9, 0, CW_EPI_BF16>(s, c);
+            else conv_wide_launch<256, 32, 9, 0, CW_EPI_BF16>(s, c);
+        }
+    }
     // (measured and dropped, round 3: the heads on high-priority streams of their own, forked from / joined to the caller's stream — with two game
     // groups 2160 instead of 2312 positions/s: the priority kernels break into the other group's trunk rounds, and two more event hops per wave)
     void forward_heads(hipStream_t s, float* policy, float* value, int n, int) override {
@@ -1097,7 +1270,9 @@ struct GenericEvaluator : Evaluator {
         const int M = n * HW;
         bf16_t* const cur = trunk_out; const bool fuse = fuse_heads;
         if (gomoku) {
-            if (fuse) {                             // both heads' BN + ReLU + Conv3x3 128 -> 32 + BN + ReLU from the raw trunk output
+            if (F != 128) {
+                heads_conv_wide(s, M);
+            } else if (fuse) {                      // both heads' BN + ReLU + Conv3x3 128 -> 32 + BN + ReLU from the raw trunk output
                 Head32Args hh; memset(&hh, 0, sizeof(hh));
                 hh.in = cur; hh.wgt[0] = b16["p.c1.w"]; hh.wgt[1] = b16["v.c1.w"];
                 hh.s0[0] = g("p.bn0.scale"); hh.t0[0] = g("p.bn0.shift"); hh.s0[1] = g("v.bn0.scale"); hh.t0[1] = g("v.bn0.shift");
@@ -1149,9 +1324,17 @@ struct GenericEvaluator : Evaluator {
         for (size_t i = 0; i + 1 < tev.size(); i += 2) { float a = 0; hipEventElapsedTime(&a, tev[i], tev[i + 1]); t += a; }
         // launches of the dominant kernel inside the bracket: fused blocks (k_resblock3) or 128 -> 128 convs; block 0 of the
         // Gomoku net (256 -> 128 + projection) rides in the same bracket and is counted as one more launch-equivalent
-        *ms = t; *launches = (int64_t)(tev.size() / 2) * (one_launch ? 1 : (fused_blocks > 0 ? fused_blocks + (block0_fused ? 0 : 1) : (trunk_convs > 0 ? trunk_convs : 1)));
+        *ms = t; *launches = (int64_t)(tev.size() / 2) * (one_launch || wide_trunk ? 1 : (fused_blocks > 0 ? fused_blocks + (block0_fused ? 0 : 1) : (trunk_convs > 0 ? trunk_convs : 1)));
     }
     const char* dominant_kernel(int n, double* flops) override {
+        if (gomoku && F != 128) {                   // priced per forward, as the F = 128 one-launch trunk
+            const double Fw = F, rows = (double)n * HW;
+            *flops = 2.0 * rows * (9.0 * 256.0 * Fw + 9.0 * Fw * Fw + (F != 256 ? 256.0 * Fw : 0.0)) + 2.0 * rows * 2.0 * 9.0 * Fw * Fw * (blocks - 1);
+            wide_label = "k_conv_wide (the Gomoku trunk at " + std::to_string(F) + " filters, priced per forward: block 0 = 3x3 conv 256->F + 3x3 conv F->F "
+                         "with the 1x1 projection 256->F in one accumulator (none at F = 256), then blocks - 1 x two 3x3 convs F->F; implicit GEMM on "
+                         "v_mfma_f32_32x32x16_bf16)";
+            return wide_label.c_str();
+        }
         const double conv = 2.0 * (double)n * HW * 128.0 * 1152.0;
         if (!gomoku) { *flops = 0; return ""; }
         const bool fz = fused && blocks > 1;
@@ -1171,11 +1354,11 @@ struct GenericEvaluator : Evaluator {
 };
 
 static Evaluator* make_generic_evaluator(const gaz_engine_config& cfg, int H, int W, int C, int A, bool gomoku, std::string* err) {
-    if (gomoku && cfg.net_filters != 128) { *err = "Gomoku net: net_filters must be 128"; return nullptr; }
+    if (gomoku && !net_width_supported(cfg.net_filters)) { *err = "Gomoku net: " + net_width_error(cfg.net_filters); return nullptr; }
     if (!gomoku && cfg.net_filters != 64 && cfg.net_filters != 0 && cfg.net_filters != 128) { *err = "TicTacToe net uses 64 filters"; return nullptr; }
     if (cfg.net_blocks < 1 || cfg.net_blocks > 64) { *err = "net_blocks out of range"; return nullptr; }
     GenericEvaluator* e = new GenericEvaluator();
-    e->H = H; e->W = W; e->C = C; e->A = A; e->HW = H * W; e->blocks = cfg.net_blocks; e->F = gomoku ? 128 : 64; e->nmax = cfg.n_games;
+    e->H = H; e->W = W; e->C = C; e->A = A; e->HW = H * W; e->blocks = cfg.net_blocks; e->F = gomoku ? cfg.net_filters : 64; e->nmax = cfg.n_games;
     e->logits = cfg.policy_is_logits; e->gomoku = gomoku;
     e->fused = !(getenv("GAZ_FUSED") && atoi(getenv("GAZ_FUSED")) == 0);
     e->trunk = !(getenv("GAZ_TRUNK") && atoi(getenv("GAZ_TRUNK")) == 0);
@@ -1211,19 +1394,19 @@ Evaluator* make_resnet_evaluator(const gaz_engine_config& cfg, int H, int W, int
     if (H == 15 && W == 15) return make_generic_evaluator(cfg, H, W, C, A, true, err);
     if (H == 3 && W == 3) return make_generic_evaluator(cfg, H, W, C, A, false, err);
     if (!(H == 6 && W == 7 && C == 4)) { *err = "no network is defined for this board"; return nullptr; }
-    if (cfg.net_filters != 128) { *err = "net_filters must be 128"; return nullptr; }
+    if (!net_width_supported(cfg.net_filters)) { *err = net_width_error(cfg.net_filters); return nullptr; }
     if (cfg.net_blocks < 1 || cfg.net_blocks > 64) { *err = "net_blocks out of range"; return nullptr; }
     ResNetEvaluator* e = new ResNetEvaluator();
-    e->H = H; e->W = W; e->C = C; e->A = A; e->HW = H * W; e->blocks = cfg.net_blocks; e->filters = 128; e->nmax = cfg.n_games;
+    e->H = H; e->W = W; e->C = C; e->A = A; e->HW = H * W; e->blocks = cfg.net_blocks; e->filters = cfg.net_filters; e->nmax = cfg.n_games;
     e->logits = cfg.policy_is_logits;
-    const size_t M = (size_t)cfg.n_games * e->HW;
-    e->X2 = e->dalloc<bf16_t>(M * 128 + 1024); e->fused = !(getenv("GAZ_FUSED") && atoi(getenv("GAZ_FUSED")) == 0);
+    const size_t M = (size_t)cfg.n_games * e->HW, CW = std::max(cfg.net_filters, 128);     // activation buffers: the stem's 128 channels or F
+    e->X2 = e->dalloc<bf16_t>(M * CW + 1024); e->fused = !(getenv("GAZ_FUSED") && atoi(getenv("GAZ_FUSED")) == 0);
     e->trunk = !(getenv("GAZ_TRUNK") && atoi(getenv("GAZ_TRUNK")) == 0);
     e->trunk_whole = !(getenv("GAZ_TRUNK_WHOLE") && atoi(getenv("GAZ_TRUNK_WHOLE")) == 0);
     e->trunk_mix = !(getenv("GAZ_TRUNK_MIX") && atoi(getenv("GAZ_TRUNK_MIX")) == 0);
     e->trunk_m16 = !(getenv("GAZ_TRUNK_M16") && atoi(getenv("GAZ_TRUNK_M16")) == 0);
     { hipDeviceProp_t pr; int dev = 0; hipGetDevice(&dev); if (hipGetDeviceProperties(&pr, dev) == hipSuccess) e->n_cus = pr.multiProcessorCount; }
-    e->X = e->dalloc<bf16_t>(M * 128 + 1024); e->Aa = e->dalloc<bf16_t>(M * 128 + 1024); e->Hh = e->dalloc<bf16_t>(M * 128 + 1024);
+    e->X = e->dalloc<bf16_t>(M * CW + 1024); e->Aa = e->dalloc<bf16_t>(M * CW + 1024); e->Hh = e->dalloc<bf16_t>(M * CW + 1024);
     e->pfeat = e->dalloc<float>((size_t)cfg.n_games * e->HW * 8); e->vfeat = e->dalloc<float>((size_t)cfg.n_games * e->HW * 8);
     e->pd1 = e->dalloc<float>((size_t)cfg.n_games * 128); e->vd1 = e->dalloc<float>((size_t)cfg.n_games * 128);
     if (!e->X || !e->Aa || !e->Hh || !e->pfeat || !e->vfeat || !e->pd1 || !e->vd1) { *err = "hipMalloc failed"; delete e; return nullptr; }

@@ -151,6 +151,8 @@ class Connect4Net(nn.Module):
         (tests/test_evaluator_gpu.py) instead of the loose bf16-vs-fp32 one:
           stem     int8 planes x (hi + lo) bf16 split of w * bn_scale, + shift, exact GELU              -> x  = bf16(.)
           block    a = bf16(relu(x s1 + t1)); h = bf16(relu(conv(a, bf16 w1) s2 + t2')); x = bf16((conv(h, bf16 w2) + b2) + x)
+          block 0 at num_filters != 128 (csrc/conv_wide.hpp): a, h as above; conv2 and the 1x1 projection of the stem output in ONE
+                   accumulator with one fp32 bias: x = bf16((conv(h, bf16 w2) + conv1x1(x0, bf16 wp)) + (b2 + bp))
           heads    f = relu((conv(x, bf16 wh) + bh) fs + ft) in fp32; Dense / softmax / tanh in fp32
         Convolutions are summed in float64 and rounded to fp32 once (the MFMA's fp32 accumulation order differs from any host
         order by ~1e-6 relative; the test tolerance covers that and the rare bf16 roundings it flips).  Returns a dict of the head
@@ -158,8 +160,8 @@ class Connect4Net(nn.Module):
         bf = lambda t: t.float().to(torch.bfloat16).float()
         B = x.shape[0]
 
-        def conv(a, w):                                  # a [B,H,W,Cin] float32 (bf16-representable), w [3,3,Cin,Cout] -> float32 accumulators
-            y = F.conv2d(a.double().permute(0, 3, 1, 2), w.double().permute(3, 2, 0, 1), None, padding=1)
+        def conv(a, w, pad=1):                           # a [B,H,W,Cin] float32 (bf16-representable), w [k,k,Cin,Cout] -> float32 accumulators
+            y = F.conv2d(a.double().permute(0, 3, 1, 2), w.double().permute(3, 2, 0, 1), None, padding=pad)
             return y.permute(0, 2, 3, 1).float()
         s, t = self.stem_bn.affine()
         wv = (self.stem.weight * s).float()              # BN scale folded into the fp32 weights (resnet.hip stem_fragments)
@@ -169,7 +171,12 @@ class Connect4Net(nn.Module):
             s1, t1 = b.bn1.affine(); s2, t2 = b.bn2.affine()
             a = bf(F.relu(xs * s1 + t1))
             h = bf(F.relu(conv(a, bf(b.conv1.weight)) * s2 + (b.conv1.bias * s2 + t2)))
-            xs = bf((conv(h, bf(b.conv2.weight)) + b.conv2.bias) + xs)
+            if b.proj is not None:                       # one accumulator, summed here in float64 like every convolution
+                y = F.conv2d(h.double().permute(0, 3, 1, 2), bf(b.conv2.weight).double().permute(3, 2, 0, 1), None, padding=1) + \
+                    F.conv2d(xs.double().permute(0, 3, 1, 2), bf(b.proj.weight).double().permute(3, 2, 0, 1), None, padding=0)
+                xs = bf(y.permute(0, 2, 3, 1).float() + (b.conv2.bias + b.proj.bias))
+            else:
+                xs = bf((conv(h, bf(b.conv2.weight)) + b.conv2.bias) + xs)
         out = {}
         z = {}
         for pre in ("p", "v"):
@@ -204,12 +211,13 @@ class Connect4Net(nn.Module):
         s, t = self.stem_bn.affine()
         out["stem.w"] = conv_w(self.stem); out["stem.scale"] = s.numpy(); out["stem.shift"] = (self.stem.bias * s + t).numpy()
         for i, b in enumerate(self.blocks):
-            assert b.proj is None, "projection blocks are not exported yet"
             s1, t1 = b.bn1.affine(); s2, t2 = b.bn2.affine()
             out[f"block{i}.bn1.scale"] = s1.numpy(); out[f"block{i}.bn1.shift"] = t1.numpy()
             out[f"block{i}.conv1.w"] = conv_w(b.conv1)
             out[f"block{i}.conv1.scale"] = s2.numpy(); out[f"block{i}.conv1.shift"] = (b.conv1.bias * s2 + t2).numpy()
             out[f"block{i}.conv2.w"] = conv_w(b.conv2); out[f"block{i}.conv2.bias"] = b.conv2.bias.numpy()
+            if b.proj is not None:                       # block 0 at num_filters != 128: 1x1 conv 128 -> num_filters, [1, cout, cin]
+                out[f"block{i}.proj.w"] = _conv_w(b.proj); out[f"block{i}.proj.bias"] = b.proj.bias.numpy()
         # heads: one 3x3 conv with 16 real output channels (0-7 policy, 8-15 value), padded to 32 for the MFMA tile
         hw = np.zeros((9, 32, self.blocks[-1].conv2.weight.shape[3] if len(self.blocks) else 128), np.float32)
         hw[:, 0:8] = conv_w(self.p_conv); hw[:, 8:16] = conv_w(self.v_conv)
@@ -227,9 +235,13 @@ class Connect4Net(nn.Module):
 
 
 def flops_per_position(num_blocks=6, filters=128, H=6, W=7):
-    """Algorithmic FLOPs of one Connect4 evaluation (2 x MACs), by layer class."""
+    """Algorithmic FLOPs of one Connect4 evaluation (2 x MACs), by layer class.  Block 0 reads the 128-channel stem: at
+    filters != 128 its conv1 is 128 -> filters and it carries the 1x1 projection 128 -> filters."""
     hw = H * W
-    trunk = num_blocks * 2 * 2 * hw * 9 * filters * filters
+    trunk = 0
+    for i in range(num_blocks):
+        cin = 128 if i == 0 else filters
+        trunk += 2 * hw * 9 * (cin * filters + filters * filters) + (2 * hw * cin * filters if cin != filters else 0)
     stem = 2 * hw * 9 * 4 * 128
     heads = 2 * hw * 9 * filters * 16 + 2 * 2 * (hw * 8 * 128 + 128 * 64) + 2 * (64 * 7 + 64)
     return dict(trunk=trunk, stem=stem, heads=heads, total=trunk + stem + heads)
@@ -467,3 +479,39 @@ class TicTacToeNet(nn.Module):
 
 
 NETS = {"Connect4": Connect4Net, "Gomoku": GomokuNet, "TicTacToe": TicTacToeNet}
+
+# build_config["num_filters"] values the HIP evaluator runs for Connect4 and Gomoku (128: the fused trunk kernels; the others:
+# csrc/conv_wide.hpp).  TicTacToe's width is fixed at 64 by its reference model.
+SUPPORTED_FILTERS = (64, 128, 192, 256)
+
+
+def engine_weight_shapes(game, num_resnet_layers, num_filters=128):
+    """{tensor name: shape} that export_engine_weights() produces for this game and build_config (a throw-away network built
+    without touching the global torch RNG)."""
+    with torch.random.fork_rng(devices=[]):
+        if game == "TicTacToe":
+            net = TicTacToeNet(num_resnet_layers)
+        else:
+            net = NETS[game](num_resnet_layers, num_filters=num_filters)
+        return {k: tuple(v.shape) for k, v in net.export_engine_weights().items()}
+
+
+def check_engine_weights(game, num_resnet_layers, num_filters, weights):
+    """Refuse (EngineError naming num_filters) a width the evaluator does not run, or a `weights` dict whose tensor names / shapes
+    are not those that num_resnet_layers and num_filters imply.  Runs on the host only, before any engine exists."""
+    from .engine import EngineError
+    if game not in NETS:
+        return
+    F = int(num_filters)
+    if game != "TicTacToe" and F not in SUPPORTED_FILTERS:
+        raise EngineError(f"num_filters = {F} is not supported for {game}: supported widths are "
+                          f"{', '.join(str(f) for f in SUPPORTED_FILTERS)}")
+    want = engine_weight_shapes(game, int(num_resnet_layers), F)
+    for name, shape in want.items():
+        if name not in weights:
+            raise EngineError(f"weights do not match build_config (num_resnet_layers = {num_resnet_layers}, num_filters = {F}): "
+                              f"tensor {name!r} is missing")
+        got = tuple(np.shape(weights[name]))
+        if int(np.prod(got)) != int(np.prod(shape)) or (len(got) > 1 and got != shape):
+            raise EngineError(f"weights do not match build_config (num_resnet_layers = {num_resnet_layers}, num_filters = {F}): "
+                              f"tensor {name!r} has shape {got}, expected {shape}")

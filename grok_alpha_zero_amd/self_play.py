@@ -353,10 +353,9 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
         raise ValueError(f"generation {generation} needs network weights (weights=net.export_engine_weights()); "
                          "pass allow_synthetic=True to play with the synthetic evaluator on purpose")
     use_net = generation > 0 and weights is not None
-    if use_net and name == "Connect4" and int(build_config.get("num_filters", 128)) != 128:
-        from .engine import EngineError
-        raise EngineError("the Connect4 trunk kernels are built for num_filters = 128 (Connect4/Build_Model.py's default); "
-                          f"num_filters = {build_config.get('num_filters')} would need the block-0 projection path")
+    if use_net:                                     # width and weights against build_config, before any engine exists
+        from .net import check_engine_weights
+        check_engine_weights(name, build_config.get("num_resnet_layers", 0), build_config.get("num_filters", 128), weights)
     G = min(n_games, games_left)
     if seed is None:
         seed = int.from_bytes(os.urandom(8), "little")                 # np.random.seed() from OS entropy (Self_Play.py:221)

@@ -72,7 +72,10 @@ typedef struct {
     int32_t evaluator;            /* GAZ_EVAL_* */
     uint32_t hash_salt;
     int32_t device;               /* HIP device ordinal */
-    /* ResNet (evaluator == GAZ_EVAL_RESNET): trunk of `net_blocks` pre-activation blocks x `net_filters` */
+    /* ResNet (evaluator == GAZ_EVAL_RESNET): trunk of `net_blocks` pre-activation blocks x `net_filters`
+       (build_config["num_filters"]).  Connect4 and Gomoku: 64, 128, 192 or 256 — 128 runs the fused trunk kernels, the other
+       widths one k_conv_wide launch per convolution (separate launches, one game group by default); any other value fails
+       gaz_engine_create.  TicTacToe: 64 (0 and 128 are accepted and mean 64). */
     int32_t net_blocks, net_filters;
     int32_t policy_is_logits;     /* policy head: 0 = softmax (float64, Build_Model.py:60), 1 = raw logits (Gumbel),
                                      2 = stablemax (Net/Stablemax.py:8-12, build_config["use_stablemax"]) */
