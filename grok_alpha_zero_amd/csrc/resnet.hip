@@ -1106,7 +1106,9 @@ struct GenericEvaluator : Evaluator {
         StemGenArgs st; memset(&st, 0, sizeof(st));
         st.in = in; st.w = g("stem.w"); st.scale = g("stem.scale"); st.shift = g("stem.shift"); st.scaleB = g("block0.bn1.scale"); st.shiftB = g("block0.bn1.shift");
         st.out1 = X0; st.out2 = A0; st.M = M; st.H = H; st.W = W; st.CIN = C; st.COUT = SC; st.K = gomoku ? 3 : 5; st.act = gomoku ? NACT_RELU : NACT_GELU;
-        const bool fuse = gomoku && fused && blocks > 1;
+        // at every block count: a one-block net runs k_block0 straight into k_conv_head32 (trunk_w / trunk_w0 are null), so it rounds
+        // where the 2+ block launches round (GomokuNet.forward_engine_numerics)
+        const bool fuse = gomoku && fused;
         // round 3: the stem inside the one trunk launch too (trunk.hpp S0; GAZ_STEM_IN_TRUNK=1): no stem kernel, no 256-channel stem tensor,
         // bit-identical outputs (tests/test_evaluator_gpu.py) — and measured SLOWER on its own: with one 512-thread workgroup per CU nothing
         // overlaps the four half-image stem passes (trunk launch 2298 -> 2444 us per 2048 positions against the 86 us of k_stem_mfma it
@@ -1122,7 +1124,7 @@ struct GenericEvaluator : Evaluator {
             // round 2: with the fused first block (k_block0) the stem writes only the raw tensor — block 0 pre-activates its operand in
             // LDS — which halves this HBM-bound kernel's writes (236 MB less per forward at 2048 positions).  GAZ_STEM_A0=1: the old way
             static const bool stem_a0 = getenv("GAZ_STEM_A0") && atoi(getenv("GAZ_STEM_A0")) != 0;
-            block0_inplace = gomoku && fused && blocks > 1 && b16.count("block0.w29") && !stem_a0;
+            block0_inplace = fuse && b16.count("block0.w29") && !stem_a0;
             if (block0_inplace) hipLaunchKernelGGL((k_stem_mfma<2, 256, false, false>), dim3((tiles + 4 * sm.tiles_per_wave - 1) / (4 * sm.tiles_per_wave)), dim3(256), 0, s, sm);
             else hipLaunchKernelGGL((k_stem_mfma<2, 256, false, true>), dim3((tiles + 4 * sm.tiles_per_wave - 1) / (4 * sm.tiles_per_wave)), dim3(256), 0, s, sm);
         } else {
@@ -1337,6 +1339,11 @@ struct GenericEvaluator : Evaluator {
         }
         const double conv = 2.0 * (double)n * HW * 128.0 * 1152.0;
         if (!gomoku) { *flops = 0; return ""; }
+        if (fused && blocks == 1) {                 // the bracket holds k_block0 alone, priced as block 0 of the one-launch trunk below
+            *flops = 3.0 * conv + 2.0 * (double)n * HW * 256.0 * 128.0;
+            return "k_block0 (the one residual block of a one-block Gomoku network: 3x3 conv 256->128, 3x3 conv 128->128 and the 1x1 projection "
+                   "256->128 in one launch, implicit GEMM on MFMA 32x32x16 bf16)";
+        }
         const bool fz = fused && blocks > 1;
         *flops = fz ? 2 * conv : conv;
         if (fz && trunk && trunk_w && trunk_m16 && block0_in_trunk && trunk_w0 && HW <= 256) {

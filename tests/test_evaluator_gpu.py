@@ -215,14 +215,23 @@ def test_search_with_resnet_matches_oracle_with_same_outputs(oracle):
 def test_gomoku_search_with_resnet_matches_oracle_with_same_outputs(oracle):
     """The same composition check for Gomoku: the one-game-per-wavefront tree kernel + the Gomoku network (stem, block 0 inside the
     trunk launch, heads on two streams) against the oracle served by evaluate() on single rows."""
+    _gomoku_search_vs_oracle(oracle, 2)
+
+
+def test_one_block_gomoku_search_matches_oracle_with_same_outputs(oracle):
+    """The same with a one-block Gomoku network (num_resnet_layers = 1: stem, k_block0, k_conv_head32, no trunk launch)."""
+    _gomoku_search_vs_oracle(oracle, 1)
+
+
+def _gomoku_search_vs_oracle(oracle, blocks):
     from grok_alpha_zero_amd.engine import SelfPlayEngine, EVAL_RESNET
     from grok_alpha_zero_amd.net import NETS
     G, iters, plies = 5, 36, 3         # a Gomoku move runs >= 3 x (legal moves) simulations when the limit is below that count (MCTS.py:545-546): ~670 per ply
-    net = NETS["Gomoku"](2).eval()
+    net = NETS["Gomoku"](blocks).eval()
     net.randomize_bn()
     w = net.export_engine_weights()
-    eng = SelfPlayEngine("Gomoku", G, iters, plies, 3, 2, 4.5, 0.05, seed=3, evaluator=EVAL_RESNET, net_blocks=2, net_filters=128, ring_capacity=4 * G)
-    probe = SelfPlayEngine("Gomoku", 8, 1, plies, 3, 2, 4.5, 0.05, seed=0, evaluator=EVAL_RESNET, net_blocks=2, net_filters=128, ring_capacity=0)
+    eng = SelfPlayEngine("Gomoku", G, iters, plies, 3, 2, 4.5, 0.05, seed=3, evaluator=EVAL_RESNET, net_blocks=blocks, net_filters=128, ring_capacity=4 * G)
+    probe = SelfPlayEngine("Gomoku", 8, 1, plies, 3, 2, 4.5, 0.05, seed=0, evaluator=EVAL_RESNET, net_blocks=blocks, net_filters=128, ring_capacity=0)
     eng.load_weights(w); probe.load_weights(w)
     recs = []
     for _ in range(100):
@@ -601,7 +610,8 @@ def test_fused_launch_bounded_wait_recovers_without_changing_games(cache):
             np.testing.assert_array_equal(np.asarray(a[k][f]), np.asarray(b[k][f]), err_msg=f"{k} {f}")
 
 
-@pytest.mark.parametrize("blocks,active,n,b0", [(2, 1, 23, "1"), (2, -1, 9, "1"), (2, -1, 9, "0"), (10, 1, 12, "1"), (10, 5, 12, "1"), (10, 9, 33, "1"), (10, 9, 33, "0")])
+@pytest.mark.parametrize("blocks,active,n,b0", [(2, 1, 23, "1"), (2, -1, 9, "1"), (2, -1, 9, "0"), (10, 1, 12, "1"), (10, 5, 12, "1"), (10, 9, 33, "1"), (10, 9, 33, "0"),
+                                                (1, -1, 9, "1")])
 def test_gomoku_evaluator_matches_bf16_faithful_reference_per_layer(blocks, active, n, b0, monkeypatch):
     """The Gomoku network's kernels (k_stem_mfma; block 0 with its in-LDS pre-activation and the projection accumulated into conv2 —
     inside the 8-wave k_trunk launch (b0 = "1", the default) or as k_block0 ahead of it (GAZ_BLOCK0_IN_TRUNK=0); the 8-wave k_trunk for
@@ -613,7 +623,8 @@ def test_gomoku_evaluator_matches_bf16_faithful_reference_per_layer(blocks, acti
     alone — feature mean 7e-5, logits 3.8e-3, probabilities 1e-4; block 0 + one more — feature mean 6 - 12e-4 (isolated elements up to
     3.8e-2 of max(|f|, 1): flipped bf16 roundings two stages up), logits 2.2e-2, probabilities 2.3e-3.  Asserted with ~2x margin; a wrong
     tap at a board edge or a swapped channel group shows as O(1) feature errors, 20x above these bounds (the fp32 comparison above
-    allows 0.15 on probabilities).  active = -1: block 0 alone is live (both convolutions of block 1 zeroed)."""
+    allows 0.15 on probabilities).  active = -1: block 0 alone is live (both convolutions of block 1 zeroed), or the one-block network
+    (k_block0 straight into k_conv_head32: block 0 is also the last block; measured: feature mean 9.9e-5, logits 5.6e-3, probabilities 2.4e-4)."""
     import torch
     from grok_alpha_zero_amd.engine import SelfPlayEngine, EVAL_RESNET
     from grok_alpha_zero_amd.net import GomokuNet

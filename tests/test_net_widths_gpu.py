@@ -72,7 +72,9 @@ def _faithful(game, blocks, F, active, x):
 # layers sum more bf16 products per output (K = 9 x 256) into larger features, and more roundings flip: measured on the MI355X at F = 192 / 256,
 # feature mean up to 1.3e-4, logits 2.5e-3, probabilities 4.4e-4, tanh value 6.1e-4 (Connect4); Gomoku (as at 128, where its own test allows
 # more) feature mean up to 3.0e-4, isolated features 1.04e-2 of max(|f|, 1), logits 6.2e-3, probabilities 6.8e-4, tanh value 1.9e-3.  Asserted
-# with ~2x margin.  A wrong tap at a board edge or a swapped channel group shows as O(1) feature errors.
+# with ~2x margin.  A wrong tap at a board edge or a swapped channel group shows as O(1) feature errors.  Measured later, inside these bounds:
+# Gomoku at F = 192 (blocks 0 and 1, and the one-block network) features 1.36e-2, mean 1.7e-4, logits 7.7e-3, probabilities 2.5e-4, tanh value
+# 2.8e-3; the one-block networks at 64 / 256: Gomoku 1.27e-2, 2.4e-4, 4.4e-3, 3.9e-4, 4.8e-4; Connect4 9.7e-3, 2.8e-5, 1.1e-3, 1.2e-4, 6.6e-4.
 TIGHT = dict(rel=1e-2, mean=1e-4, logits=2e-3, prob=1e-3, value=1e-3)
 WIDE_C4 = dict(rel=1e-2, mean=2.5e-4, logits=5e-3, prob=1e-3, value=1.5e-3)
 WIDE_GMK = dict(rel=2e-2, mean=6e-4, logits=1.2e-2, prob=1.5e-3, value=4e-3)
@@ -91,10 +93,41 @@ def test_connect4_wide_matches_bf16_faithful_reference_per_layer(F, active, n):
 
 
 # Gomoku: 15 x 15 boards, halo 16 rows; 9 boards = 2025 rows = 15 tiles + 105 rows.  F = 256 has no projection (256 -> 256).
-@pytest.mark.parametrize("F,active,n", [(64, 0, 9), (64, 1, 9), (256, 0, 9), (256, 1, 3)])
+@pytest.mark.parametrize("F,active,n", [(64, 0, 9), (64, 1, 9), (192, 0, 9), (192, 1, 3), (256, 0, 9), (256, 1, 3)])
 def test_gomoku_wide_matches_bf16_faithful_reference_per_layer(F, active, n):
     rng = np.random.default_rng(F + 10 * active + n)
     _assert_bounds(_faithful("Gomoku", 2, F, active, _gmk_states(n, rng)), WIDE_GMK)
+
+
+# Block positions with their own argument wiring in forward_trunk_wide.  One block: block 0 is also the last block (Connect4: no second
+# output, the heads read its output; Gomoku: its second output is the policy head's relu(p.bn0(x)); at F = 256 the residual is the stem
+# output).  Three Gomoku blocks, active = 1: a middle block (residual read from and written to the same buffer, second output for the
+# next block's bn1), between two zeroed blocks.
+@pytest.mark.parametrize("game,F,n", [("Connect4", 64, 77), ("Connect4", 192, 77), ("Connect4", 256, 30), ("Gomoku", 64, 9), ("Gomoku", 192, 9),
+                                      ("Gomoku", 256, 3)])
+def test_one_block_wide_matches_bf16_faithful_reference(game, F, n):
+    rng = np.random.default_rng(F + n)
+    x = _c4_states(n, rng) if game == "Connect4" else _gmk_states(n, rng)
+    _assert_bounds(_faithful(game, 1, F, 0, x), WIDE_GMK if game == "Gomoku" else (TIGHT if F == 64 else WIDE_C4))
+
+
+#
+# Per element and on the logits the middle-block case is held to the bounds of the 128-filter Gomoku test with a live block behind block 0
+# (test_gomoku_evaluator_matches_bf16_faithful_reference_per_layer), not WIDE_GMK.  The policy head rounds its 32-channel conv output to bf16,
+# and ONE flipped rounding there moves a head feature by up to 5.3e-2 (|c1| up to 18, bound from this network's weights); which roundings
+# flip depends on the input.  Measured on the MI355X at F = 64 with these states: features 4.1e-2 of max(|f|, 1), logits 2.3e-2, while the
+# feature mean (2.8e-4), probabilities (3.8e-5) and tanh value (1.1e-3) stay inside WIDE_GMK.  The same network on other states: 5.0e-3
+# and 3.8e-3.  Over eight networks and inputs: up to 2.7e-2 and 9.1e-3.  The 3-block network with blocks 0 and 2 zeroed gave the same bits
+# as the 2-block network without block 2 (see also tests/test_net_paths_gpu.py), so none of this comes from the middle block's wiring.
+# F = 192: 1.3e-2 and 6.2e-3; F = 256: 1.1e-2 and 1.0e-2.  Mean, probabilities and value stay at WIDE_GMK: a wrong tap or channel group
+# moves thousands of features by O(1).
+GMK_LIVE_BLOCK = dict(WIDE_GMK, rel=8e-2, logits=4e-2)
+
+
+@pytest.mark.parametrize("F,n", [(64, 9), (192, 5), (256, 3)])
+def test_gomoku_wide_middle_block_matches_bf16_faithful_reference(F, n):
+    rng = np.random.default_rng(F + 7 * n)
+    _assert_bounds(_faithful("Gomoku", 3, F, 1, _gmk_states(n, rng)), GMK_LIVE_BLOCK)
 
 
 @pytest.mark.parametrize("game,F,n", [("Connect4", 64, 300), ("Connect4", 192, 131), ("Connect4", 256, 300), ("Gomoku", 64, 37),
