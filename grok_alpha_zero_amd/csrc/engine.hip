@@ -7,6 +7,7 @@
 #include "rt.hpp"
 #include "puct_core.hpp"
 #include "gumbel_core.hpp"
+#include "samples.hpp"
 #include "evaluator.hpp"
 
 using namespace gaz;
@@ -286,6 +287,11 @@ struct gaz_engine {
     virtual int evaluate(const int8_t*, int, float*, float*, int, double*) = 0;
     virtual int record_layout(gaz_record_layout*) = 0;
     virtual int drain(void* out, int max_records, int32_t* n_out) = 0;
+    virtual int sample_layout(gaz_sample_layout*) = 0;
+    // gaz_engine_drain_samples for one ring: the caller's arrays start at this call's first game / row, their augmentation planes are `plane_rows`
+    // rows apart, games[i][4] = row_base + the row in this call.  *blocked_T = plies of the oldest game when it alone is more than max_rows (else 0).
+    virtual int drain_samples(int max_games, int64_t max_rows, int64_t plane_rows, int64_t row_base, int32_t* games, int8_t* boards, float* policies,
+                              float* values, int32_t* n_games, int64_t* n_rows, int32_t* blocked_T) = 0;
     virtual int get_stats(uint64_t out[16]) = 0;
     virtual int synchronize() = 0;
     virtual int timing_reset(int enable) = 0;
@@ -342,6 +348,8 @@ template <class G> struct EngineT : gaz_engine {
         }
         delete eval;
         for (void* p : allocs) hipFree(p);
+        if (dSamples) hipFree(dSamples);
+        if (hSamples) hipHostFree(hSamples);
         for (hipEvent_t e : ev) hipEventDestroy(e);
         if (pipeline_ready) {
             hipStreamSynchronize(tstream); hipStreamSynchronize(hstream);
@@ -927,6 +935,93 @@ template <class G> struct EngineT : gaz_engine {
         return check_device_error();
     }
 
+    // ---- gaz_engine_drain_samples (samples.hpp): one staging buffer on the device [boards | policies | values] and its pinned twin on the
+    // host, both grown on demand; per call one header gather, one build launch and ONE device-to-host copy, then the augmentation planes
+    // are copied apart into the caller's arrays
+    int32_t* dPlan = nullptr;                        // [ring_cap][4] gathered headers | [2][ring_cap] ring slots, row0
+    uint8_t* dSamples = nullptr; uint8_t* hSamples = nullptr; size_t samples_cap = 0;
+    static size_t al256(size_t n) { return (n + 255) / 256 * 256; }
+    int sample_layout(gaz_sample_layout* o) override {
+        o->n_aug = SampleAug<G>::N; o->state_bytes = G::HW * G::C; o->A = G::A; o->max_T = G::MAXT;
+        return 0;
+    }
+    // the R rows of the n games of `plan` (ring slots, then row0) -> the caller's arrays
+    int build_samples(const std::vector<int32_t>& plan, int n, int64_t R, int64_t plane_rows, int8_t* boards, float* policies, float* values) {
+        constexpr int SB = G::HW * G::C, NA = SampleAug<G>::N;
+        const size_t off_p = al256((size_t)NA * R * SB), off_v = off_p + al256((size_t)NA * R * G::A * 4), total = off_v + al256((size_t)R * 4);
+        if (total > samples_cap) {
+            if (dSamples) HIP_OK(hipFree(dSamples));
+            if (hSamples) HIP_OK(hipHostFree(hSamples));
+            dSamples = nullptr; hSamples = nullptr;
+            const size_t want = total > 2 * samples_cap ? total : 2 * samples_cap;
+            samples_cap = 0;
+            void* d = nullptr; void* hp = nullptr;
+            HIP_OK(hipMalloc(&d, want));
+            dSamples = (uint8_t*)d;
+            HIP_OK(hipHostMalloc(&hp, want, 0));
+            hSamples = (uint8_t*)hp; samples_cap = want;
+        }
+        int32_t* d_plan = dPlan + (size_t)4 * E.ring_cap;
+        HIP_OK(hipMemcpyAsync(d_plan, plan.data(), plan.size() * 4, hipMemcpyHostToDevice, stream));
+#ifdef GAZ_HOST_EMU
+        const int threads = 1;
+#else
+        const int threads = SAMPLES_THREADS;
+#endif
+        GAZ_LAUNCH(k_build_samples<G>, n, threads, stream, (const uint8_t*)E.ring, E.ring_cap, (const int32_t*)d_plan, n, (long long)R,
+                   reinterpret_cast<int8_t*>(dSamples), reinterpret_cast<float*>(dSamples + off_p), reinterpret_cast<float*>(dSamples + off_v));
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(hSamples, dSamples, off_v + (size_t)R * 4, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        for (int k = 0; k < NA; ++k) {
+            memcpy(boards + (size_t)k * plane_rows * SB, hSamples + (size_t)k * R * SB, (size_t)R * SB);
+            memcpy(policies + (size_t)k * plane_rows * G::A, hSamples + off_p + (size_t)k * R * G::A * 4, (size_t)R * G::A * 4);
+        }
+        memcpy(values, hSamples + off_v, (size_t)R * 4);
+        return 0;
+    }
+    int drain_samples(int max_games, int64_t max_rows, int64_t plane_rows, int64_t row_base, int32_t* games, int8_t* boards, float* policies,
+                      float* values, int32_t* n_games, int64_t* n_rows, int32_t* blocked_T) override {
+        *n_games = 0; *n_rows = 0; *blocked_T = 0;
+        if (E.ring_cap <= 0) return 0;
+        HIP_OK(hipStreamSynchronize(stream));
+        if (poll_fuse_fault()) return 1;            // a host synchronisation point, as drain()
+        uint32_t head[2];
+        HIP_OK(hipMemcpy(head, E.ring_head, sizeof(head), hipMemcpyDeviceToHost));
+        uint32_t avail = head[0] - ring_consumed;
+        if (avail > (uint32_t)E.ring_cap) avail = (uint32_t)E.ring_cap;
+        if ((int64_t)avail > (int64_t)max_games) avail = (uint32_t)(max_games > 0 ? max_games : 0);
+        if (!avail) return check_device_error();
+        if (!dPlan && dalloc(&dPlan, (size_t)6 * E.ring_cap)) return 1;
+#ifdef GAZ_HOST_EMU
+        GAZ_LAUNCH(k_sample_headers<G>, (int)avail, 1, stream, (const uint8_t*)E.ring, E.ring_cap, ring_consumed, (int)avail, dPlan);
+#else
+        GAZ_LAUNCH(k_sample_headers<G>, ((int)avail + SAMPLES_THREADS - 1) / SAMPLES_THREADS, SAMPLES_THREADS, stream, (const uint8_t*)E.ring, E.ring_cap, ring_consumed, (int)avail, dPlan);
+#endif
+        HIP_OK(hipGetLastError());
+        std::vector<int32_t> hdr((size_t)4 * avail);
+        HIP_OK(hipMemcpyAsync(hdr.data(), dPlan, hdr.size() * 4, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        int n = 0; int64_t R = 0;                    // whole games, oldest first, while they fit
+        std::vector<int32_t> plan;
+        for (; n < (int)avail; ++n) {
+            const int T = sample_plies<G>(hdr[4 * n]);
+            if (R + T > max_rows) { if (n == 0) *blocked_T = T; break; }
+            plan.push_back((int32_t)((ring_consumed + (uint32_t)n) % (uint32_t)E.ring_cap));
+            games[6 * n] = T; games[6 * n + 1] = hdr[4 * n + 1]; games[6 * n + 2] = hdr[4 * n + 2]; games[6 * n + 3] = hdr[4 * n + 3];
+            games[6 * n + 4] = (int32_t)(row_base + R); games[6 * n + 5] = 0;
+            R += T;
+        }
+        if (!n) return check_device_error();
+        if (row_base + R > 0x7fffffffLL) return fail("drain_samples: more than 2^31 rows in one call");
+        for (int i = 0; i < n; ++i) plan.push_back(games[6 * i + 4] - (int32_t)row_base);
+        if (R > 0 && build_samples(plan, n, R, plane_rows, boards, policies, values)) return 1;
+        ring_consumed += (uint32_t)n;
+        HIP_OK(hipMemcpy(E.ring_head + 1, &ring_consumed, sizeof(uint32_t), hipMemcpyHostToDevice));
+        *n_games = n; *n_rows = R;
+        return check_device_error();
+    }
+
     int get_stats(uint64_t out[16]) override {
         for (int i = 0; i < 16; ++i) out[i] = 0;
         int32_t c[10];
@@ -1220,6 +1315,24 @@ struct GroupEngine : gaz_engine {
         *n_out = total;
         return 0;
     }
+    int sample_layout(gaz_sample_layout* o) override { return up(kid[0], kid[0]->sample_layout(o)); }
+    int drain_samples(int max_games, int64_t max_rows, int64_t plane_rows, int64_t row_base, int32_t* games, int8_t* boards, float* policies,
+                      float* values, int32_t* n_games, int64_t* n_rows, int32_t* blocked_T) override {
+        gaz_sample_layout sl;
+        if (sample_layout(&sl)) return 1;
+        int total = 0, blocked = 0; int64_t rows = 0;
+        for (int i = 0; i < K() && total < max_games; ++i) {         // children append at the running game / row offset
+            gaz_engine* k = kid[(drain_from + i) % K()];
+            int32_t got = 0, b = 0; int64_t r = 0;
+            if (up(k, k->drain_samples(max_games - total, max_rows - rows, plane_rows, row_base + rows, games + (size_t)6 * total, boards + (size_t)rows * sl.state_bytes,
+                                       policies + (size_t)rows * sl.A, values + rows, &got, &r, &b))) return 1;
+            if (b && !blocked) blocked = b;
+            total += got; rows += r;
+        }
+        drain_from = (drain_from + 1) % K();
+        *n_games = total; *n_rows = rows; *blocked_T = total ? 0 : blocked;
+        return 0;
+    }
     int get_stats(uint64_t out[16]) override {
         for (int i = 0; i < 16; ++i) out[i] = 0;
         out[12] = 1;
@@ -1347,6 +1460,18 @@ int gaz_engine_write_outputs(gaz_engine* h, const float* p, const float* v) { re
 int gaz_engine_evaluate(gaz_engine* h, const int8_t* in, int32_t n, float* p, float* v, int32_t repeats, double* ms) { return h->evaluate(in, n, p, v, repeats, ms); }
 int gaz_engine_record_layout(gaz_engine* h, gaz_record_layout* o) { return h->record_layout(o); }
 int gaz_engine_drain_finished(gaz_engine* h, void* out, int32_t max_records, int32_t* n_out) { return h->drain(out, max_records, n_out); }
+int gaz_engine_sample_layout(gaz_engine* h, gaz_sample_layout* o) { return o ? h->sample_layout(o) : h->fail("sample_layout: null argument"); }
+int gaz_engine_drain_samples(gaz_engine* h, int32_t max_games, int64_t max_rows, int32_t* games, int8_t* boards, float* policies, float* values,
+                             int32_t* n_games, int64_t* n_rows) {
+    if (!games || !boards || !policies || !values || !n_games || !n_rows) return h->fail("drain_samples: null argument");
+    if (max_games < 0 || max_rows < 0) return h->fail("drain_samples: max_games and max_rows must be >= 0");
+    int32_t blocked = 0;
+    if (h->drain_samples(max_games, max_rows, max_rows, 0, games, boards, policies, values, n_games, n_rows, &blocked)) return 1;
+    if (*n_games == 0 && blocked)
+        return h->fail("drain_samples: the oldest finished game has " + std::to_string(blocked) + " rows, max_rows is " + std::to_string(max_rows) +
+                       " (no game was taken: call again with room for at least max_T rows)");
+    return 0;
+}
 int gaz_engine_get_stats(gaz_engine* h, uint64_t out[16]) { return h->get_stats(out); }
 int gaz_engine_synchronize(gaz_engine* h) { return h->synchronize(); }
 int gaz_engine_timing_reset(gaz_engine* h, int32_t enable) { return h->timing_reset(enable); }

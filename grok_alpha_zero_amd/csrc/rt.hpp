@@ -16,6 +16,8 @@ inline const char* hipGetErrorString(hipError_t) { return "emu"; }
 inline hipError_t hipSetDevice(int) { return 0; }
 inline hipError_t hipMalloc(void** p, size_t n) { *p = calloc(n ? n : 1, 1); return *p ? 0 : 1; }
 inline hipError_t hipFree(void* p) { free(p); return 0; }
+inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { *p = malloc(n ? n : 1); return *p ? 0 : 1; }
+inline hipError_t hipHostFree(void* p) { free(p); return 0; }
 inline hipError_t hipMemset(void* p, int v, size_t n) { memset(p, v, n); return 0; }
 inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { memset(p, v, n); return 0; }
 enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };

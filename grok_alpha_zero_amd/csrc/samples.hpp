@@ -1,0 +1,157 @@
+// samples.hpp — finished games leave the device as TRAINING SAMPLES (gaz_engine_drain_samples): what Self_Play.play() collects per
+// game (Self_Play.py:159-175: input states before every move, improved policies, values = 0.5 (z + q)) and what augment_sample makes of
+// it (Guide.py:255-283; Connect4.py:442-443, Gomoku.py:265-303, Tictactoe.py:321-358), built from the records in the ring.
+//
+// The host definition of every byte is self_play._fast_states + games.augment_sample + engine.decode_record; this is a gather of it:
+//   * no board is replayed.  fill[cell] = the ply at which the cell was filled (from the action list; Connect4: the row is the number
+//     of earlier moves in the column), the stone there is the mover of that ply (even plies: -1), and the board "k moves back" at
+//     ply t is  fill[cell] < t - k ? stone : 0.
+//   * every output element is then an independent function of (ply, augmentation, cell / action); the symmetry is applied on the
+//     READ side (output cell -> source cell), so a game's rows of one augmentation are one contiguous range that is written as
+//     whole 16-byte vectors (single elements only at the ragged ends: a row is 18 / 168 / 450 bytes, a range starts anywhere).
+// One workgroup per game; fill table and action list in LDS.
+#pragma once
+#include "tree.hpp"
+
+namespace gaz {
+
+#ifdef GAZ_HOST_EMU
+#define GAZ_SAMPLES_BOUNDS
+GAZ_DEV void group_sync() {}
+#else
+#define GAZ_SAMPLES_BOUNDS __launch_bounds__(256)
+GAZ_DEV void group_sync() { __syncthreads(); }
+#endif
+constexpr int SAMPLES_THREADS = 256;
+
+template <class G> struct SampleAug { static constexpr int N = 8; };          // the 8 symmetries of a square board
+template <> struct SampleAug<Game<GAME_C4>> { static constexpr int N = 2; };  // [identity, np.fliplr]
+
+// plies of a record as the sample builder counts them (a header is data: never trust it with an index)
+template <class G> GAZ_HD int sample_plies(int T) { return T < 0 ? 0 : (T > G::MAXT ? G::MAXT : T); }
+
+// output cell (y, x) of augmentation k -> the cell of the un-augmented board it shows.
+// games._GridGame.augment_sample: id, flipud, fliplr, rot90, flipud(rot90), fliplr(rot90), rot180, rot270 (np.rot90: counter-clockwise,
+// rot90(m)[y][x] = m[x][n-1-y]).  games.Connect4.augment_sample: np.fliplr of the [T,6,7,4] states reverses axis 1 = the board ROWS.
+template <class G> GAZ_DEV int board_src_cell(int k, int y, int x) {
+    if (G::ID == GAME_C4) return (k ? G::H - 1 - y : y) * G::W + x;
+    const int n = G::W - 1;
+    int sy = y, sx = x;
+    switch (k) {
+        case 1: sy = n - y; break;
+        case 2: sx = n - x; break;
+        case 3: sy = x; sx = n - y; break;
+        case 4: sy = x; sx = y; break;
+        case 5: sy = n - x; sx = n - y; break;
+        case 6: sy = n - y; sx = n - x; break;
+        case 7: sy = n - x; sx = y; break;
+        default: break;
+    }
+    return sy * G::W + sx;
+}
+// the same for a policy index; Connect4's [T,7] policy is mirrored along the COLUMNS (Connect4.py:442-443: kept as the reference has it)
+template <class G> GAZ_DEV int policy_src_index(int k, int a) {
+    if (G::ID == GAME_C4) return k ? G::A - 1 - a : a;
+    return board_src_cell<G>(k, a / G::W, a % G::W);
+}
+
+// element r of the input state before ply t, augmentation k (get_input_state_MCTS, [H][W][C] int8)
+template <class G> GAZ_DEV int8_t state_element(const int* fill, int t, int k, int r) {
+    const int c = r % G::C, cell = r / G::C;
+    const int f = fill[board_src_cell<G>(k, cell / G::W, cell % G::W)];
+    const int stone = (f & 1) ? 1 : -1;                                   // the first mover is -1
+    if (G::ID == GAME_C4) {
+        // plane 3 = board, planes 2 / 1 = one / two moves back once 2 / 3 moves were played, plane 0 = minus the next player until four
+        // moves were played and the board three moves back after that (Connect4.py:340-345)
+        const int back = 3 - c;
+        if (back == 0 || t > back) return (int8_t)(f < t - back ? stone : 0);
+        return (int8_t)(c == 0 ? ((t & 1) ? -1 : 1) : 0);
+    }
+    if (c == 0) return (int8_t)((t & 1) ? 1 : -1);                        // the mover, on every cell
+    return (int8_t)(f < t ? stone : 0);
+}
+
+// dst[start + i] = f(i) for i in [0, count): 16-byte vector stores wherever start + i is a multiple of VEC = 16 / sizeof(T), single
+// elements before the first and after the last whole vector.  dst itself is 16-byte aligned (an allocation's base).
+template <class T, class F> GAZ_DEV void emit_range(T* dst, size_t start, int count, int t, int nT, F f) {
+    constexpr int VEC = 16 / (int)sizeof(T);
+    const int head0 = (int)((VEC - start % VEC) % VEC);
+    const int head = head0 < count ? head0 : count;
+    const int n_vec = (count - head) / VEC;
+    for (int i = t; i < head; i += nT) dst[start + i] = f(i);
+    for (int v = t; v < n_vec; v += nT) {
+        T tmp[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) tmp[j] = f(head + v * VEC + j);
+        uint4 u;
+        memcpy(&u, tmp, 16);
+        *reinterpret_cast<uint4*>(dst + start + head + (size_t)v * VEC) = u;
+    }
+    for (int i = head + n_vec * VEC + t; i < count; i += nT) dst[start + i] = f(i);
+}
+
+// the [T, winner, slot, game_seq] headers of `n` ring slots from `first` on, dense: what the host needs to choose the games of a drain
+template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_sample_headers(const uint8_t* ring, int ring_cap, uint32_t first, int n, int32_t* out) {
+#ifdef GAZ_HOST_EMU
+    const int i = block_id();
+#else
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+#endif
+    if (i >= n) return;
+    const int32_t* hdr = reinterpret_cast<const int32_t*>(ring + (size_t)((first + (uint32_t)i) % (uint32_t)ring_cap) * RecLayout<G>::SIZE + RecLayout<G>::OFF_HDR);
+    for (int j = 0; j < 4; ++j) out[4 * i + j] = hdr[j];
+}
+
+// plan[i] = ring slot of the drain's i-th game, plan[n + i] = row0[i] = the exclusive prefix sum of the games' plies.  The drain has R rows;
+// augmentation k of an output array starts k * R rows in.
+template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_build_samples(const uint8_t* ring, int ring_cap, const int32_t* plan, int n, long long R,
+                                                                       int8_t* boards, float* policies, float* values) {
+    using RL = RecLayout<G>;
+    constexpr int SB = G::HW * G::C, NA = SampleAug<G>::N, NEVER = 0x7ffffffe;
+#ifdef GAZ_HOST_EMU
+    const int b = block_id(), nT = 1, t = 0;
+#else
+    const int b = blockIdx.x, nT = blockDim.x, t = threadIdx.x;
+#endif
+    GAZ_SHARED int fill[G::HW];
+    GAZ_SHARED uint8_t act[G::TPAD];
+    if (b >= n) return;
+    const int slot = plan[b];
+    if (slot < 0 || slot >= ring_cap) return;
+    const uint8_t* rec = ring + (size_t)slot * RL::SIZE;
+    const int32_t* hdr = reinterpret_cast<const int32_t*>(rec + RL::OFF_HDR);
+    const int T = sample_plies<G>(hdr[0]), winner = hdr[1];
+    const long long row0 = plan[n + b];
+    if (row0 < 0 || row0 + T > R) return;                                 // (the host built row0 from these very headers)
+    for (int i = t; i < G::HW; i += nT) fill[i] = NEVER;
+    for (int i = t; i < T; i += nT) act[i] = rec[RL::OFF_ACT + i];
+    group_sync();
+    if (G::ID == GAME_C4) {
+        for (int p = t; p < T; p += nT) {                                 // row = 5 - the earlier moves in the same column
+            const int a = act[p];
+            int below = 0;
+            for (int e = 0; e < p; ++e) below += act[e] == a;
+            if (a < G::W && below < G::H) fill[(G::H - 1 - below) * G::W + a] = p;
+        }
+    } else {
+        for (int p = t; p < T; p += nT) if (act[p] < G::HW) fill[act[p]] = p;
+    }
+    group_sync();
+    const float* q = reinterpret_cast<const float*>(rec + RL::OFF_Q);
+    const float* pol = reinterpret_cast<const float*>(rec + RL::OFF_POL);
+    // z as engine.py decode_record derives it: the mover of the ply (Self_Play.py:127), all signs turned when -1 won and made the last
+    // move, zeros for a draw
+    const bool flip = winner == -1 && T > 0 && ((T - 1) & 1) == 0;
+    for (int p = t; p < T; p += nT) {
+        float z = (p & 1) ? 1.0f : -1.0f;
+        if (flip) z = z * -1.0f; else if (winner == 0) z = 0.0f;
+        values[row0 + p] = 0.5f * (z + q[p]);
+    }
+    for (int k = 0; k < NA; ++k) {
+        const size_t row = (size_t)k * (size_t)R + (size_t)row0;
+        emit_range<int8_t>(boards, row * SB, T * SB, t, nT, [&](int i) { return state_element<G>(fill, i / SB, k, i % SB); });
+        emit_range<float>(policies, row * G::A, T * G::A, t, nT, [&](int i) { return pol[(i / G::A) * G::A + policy_src_index<G>(k, i % G::A)]; });
+    }
+}
+
+}  // namespace gaz

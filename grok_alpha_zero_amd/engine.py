@@ -19,7 +19,7 @@ EVAL_HASH, EVAL_RESNET, EVAL_EXTERNAL = 0, 1, 2
 PH_WAIT_HOST, PH_HALT, PH_IDLE = 5, 8, 9
 
 
-ABI_VERSION = 4               # GAZ_ENGINE_ABI_VERSION of include/gaz_engine.h this binding was written against
+ABI_VERSION = 5               # GAZ_ENGINE_ABI_VERSION of include/gaz_engine.h this binding was written against
 
 
 class EngineConfig(C.Structure):       # gaz_engine_config — tests/test_abi.py checks names, order and sizeof against the header
@@ -49,6 +49,10 @@ class Tensor(C.Structure):
 class RecordLayout(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("record_bytes", "max_T", "A", "t_pad", "off_hdr", "off_actions", "off_q",
                                          "off_root_visits", "off_evals", "off_policy", "off_N", "off_W", "off_P")]
+
+
+class SampleLayout(C.Structure):        # gaz_sample_layout
+    _fields_ = [(n, C.c_int32) for n in ("n_aug", "state_bytes", "A", "max_T")]
 
 
 _LIBS = {}
@@ -84,6 +88,9 @@ def load_library(lib_path=None):
     L.gaz_engine_evaluate.argtypes = [H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
     L.gaz_engine_record_layout.argtypes = [H, C.POINTER(RecordLayout)]
     L.gaz_engine_drain_finished.argtypes = [H, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    L.gaz_engine_sample_layout.argtypes = [H, C.POINTER(SampleLayout)]
+    L.gaz_engine_drain_samples.argtypes = [H, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.gaz_engine_get_stats.argtypes = [H, C.POINTER(C.c_uint64)]
     L.gaz_engine_synchronize.argtypes = [H]
     L.gaz_engine_timing_reset.argtypes = [H, C.c_int32]
@@ -102,7 +109,7 @@ def load_library(lib_path=None):
     L.gaz_engine_timing_get.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     for f in ("create", "load_weights", "reset_games", "run_move", "get_root_stats", "apply_moves", "run_waves", "wave_begin",
-              "wave_end", "batch_ptrs", "read_batch", "write_outputs", "evaluate", "record_layout", "drain_finished", "get_stats",
+              "wave_end", "batch_ptrs", "read_batch", "write_outputs", "evaluate", "record_layout", "drain_finished", "sample_layout", "drain_samples", "get_stats",
               "synchronize", "timing_reset", "timing_get", "dominant_kernel", "set_position", "set_search_params", "start_search", "stop_search",
               "set_hyperparams", "probe_rules", "read_head_features", "set_fused_wave", "debug_fused_fault", "read_positions", "repack"):
         getattr(L, "gaz_engine_" + f).restype = C.c_int
@@ -112,6 +119,41 @@ def load_library(lib_path=None):
 
 class EngineError(RuntimeError):
     pass
+
+
+class SampleBatch:
+    """The finished games of one SelfPlayEngine.drain_samples() call as training samples (include/gaz_engine.h, gaz_engine_drain_samples):
+    `games` int32 [n, 6] (T, winner, slot, game_seq, first row, 0), `boards` int8 [n_aug, R, H, W, C], `policies` f32 [n_aug, R, A],
+    `values` f32 [R, 1]; rows = the games in the order handed out, plies in order."""
+
+    def __init__(self, games, boards, policies, values):
+        self.games, self.boards, self.policies, self.values = games, boards, policies, values
+
+    @property
+    def n(self):
+        return self.games.shape[0]
+
+    def __len__(self):
+        return self.games.shape[0]
+
+    @property
+    def rows(self):
+        return self.values.shape[0]
+
+    @property
+    def nbytes(self):
+        return self.games.nbytes + self.boards.nbytes + self.policies.nbytes + self.values.nbytes
+
+    def copy(self):
+        """an owning, compact copy (what another thread may keep)"""
+        return SampleBatch(self.games.copy(), self.boards.copy(), self.policies.copy(), self.values.copy())
+
+    def game(self, i):
+        """game i as ReplayStore.append_game takes it: (boards [n_aug, T, H, W, C], policies [n_aug, T, A], values [n_aug, T, 1],
+        game_length, n_positions, winner) — views, no copy"""
+        T, winner, r0 = int(self.games[i, 0]), int(self.games[i, 1]), int(self.games[i, 4]) - int(self.games[0, 4])
+        v = np.broadcast_to(self.values[None, r0:r0 + T], (self.policies.shape[0], T, 1))
+        return self.boards[:, r0:r0 + T], self.policies[:, r0:r0 + T], v, T, T, winner
 
 
 class SelfPlayEngine:
@@ -317,6 +359,34 @@ class SelfPlayEngine:
         n = C.c_int32()
         self._ck(self.L.gaz_engine_drain_finished(self.h, buf.ctypes.data, cap, C.byref(n)))
         return [self.decode_record(buf[i]) for i in range(n.value)]
+
+    sample_buffer_bytes = 256 << 20     # host buffers of drain_samples (at least one game of max_T plies)
+
+    def drain_samples(self, max_games=None, max_rows=None):
+        """Finished games as training samples, built on the device (gaz_engine_drain_samples): a SampleBatch of the games that have
+        finished, oldest first; what the buffers (or `max_games` / `max_rows`) do not hold stays in the engine for the next call; a
+        `max_rows` below the oldest game's length is an EngineError.  May be mixed with drain_finished():
+        a game is handed out once.  The host buffers are allocated once per engine and REUSED: the batch's arrays are views into them,
+        valid until the next drain_samples() of this engine — a batch that goes to another thread, or is kept, is copied first
+        (SampleBatch.copy(); run_self_play does that before it hands a batch to its writer thread)."""
+        if getattr(self, "_sbuf", None) is None:
+            sl = SampleLayout()
+            self._ck(self.L.gaz_engine_sample_layout(self.h, C.byref(sl)))
+            cap_games = max(int(self.cfg.ring_capacity), 1)
+            row_bytes = sl.n_aug * (sl.state_bytes + 4 * sl.A) + 4
+            cap_rows = max(min(cap_games * sl.max_T, self.sample_buffer_bytes // row_bytes), sl.max_T)
+            self._sbuf = (sl, cap_games, cap_rows, np.empty((cap_games, 6), np.int32), np.empty((sl.n_aug, cap_rows, self.H, self.W, self.Cc), np.int8),
+                          np.empty((sl.n_aug, cap_rows, sl.A), np.float32), np.empty((cap_rows, 1), np.float32))
+        sl, cap_games, cap_rows, games, boards, policies, values = self._sbuf
+        n, r = C.c_int32(), C.c_int64()
+        take_rows, b, p = cap_rows, boards, policies
+        if max_rows is not None and int(max_rows) < cap_rows:        # the augmentation planes are max_rows apart: arrays of that shape
+            take_rows = int(max_rows)
+            b = np.empty((sl.n_aug, max(take_rows, 1), self.H, self.W, self.Cc), np.int8)
+            p = np.empty((sl.n_aug, max(take_rows, 1), sl.A), np.float32)
+        self._ck(self.L.gaz_engine_drain_samples(self.h, min(int(max_games), cap_games) if max_games else cap_games, take_rows, games.ctypes.data,
+                                                 b.ctypes.data, p.ctypes.data, values.ctypes.data, C.byref(n), C.byref(r)))
+        return SampleBatch(games[:n.value], b[:, :r.value], p[:, :r.value], values[:r.value])
 
     def decode_record(self, raw):
         lay, A = self.layout, self.A

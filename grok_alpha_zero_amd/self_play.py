@@ -14,6 +14,9 @@ names / dtypes / shapes / libver either way.
 """
 import logging
 import os
+import queue
+import threading
+import time
 
 import numpy as np
 
@@ -320,11 +323,83 @@ def record_to_samples(game_class, rec):
     return aug_b, aug_p, aug_v, n_plies
 
 
+class _ReplayWriter:
+    """The generation's writer thread: the only user of the ReplayStore while it lives, inside one `writing()` session.  The loop that
+    queues the waves hands it work with put(); work is a SampleBatch (every game of it is appended, in order) or one game's
+    append_game arguments.  The queue is bounded in BYTES: put() blocks while more than `max_pending_bytes` wait, which is the
+    back-pressure that keeps host memory finite when the file is slower than the GPU (one item is always admitted).  An exception
+    of the writer is re-raised by the next put() or by close(); close() lets the writer finish what is queued and joins it."""
+
+    def __init__(self, store, max_pending_bytes):
+        self.store, self.max_bytes = store, max(int(max_pending_bytes), 1)
+        self.q, self.cv, self.pending, self.error = queue.Queue(), threading.Condition(), 0, None
+        self.write_seconds = self.wait_seconds = 0.0
+        self.thread = threading.Thread(target=self._run, name="gaz-replay-writer", daemon=True)
+        self.thread.start()
+
+    def _run(self):
+        try:
+            with self.store.writing():
+                while True:
+                    item = self.q.get()
+                    if item is None:
+                        break
+                    work, nbytes = item
+                    t0 = time.perf_counter()
+                    try:
+                        if self.error is None:              # after a failure: only release the queue
+                            if isinstance(work, tuple):
+                                self.store.append_game(*work)
+                            else:
+                                for i in range(work.n):
+                                    self.store.append_game(*work.game(i))
+                    except BaseException as e:              # noqa: BLE001 — handed to the caller
+                        self.error = e
+                    finally:
+                        self.write_seconds += time.perf_counter() - t0
+                        with self.cv:
+                            self.pending -= nbytes
+                            self.cv.notify_all()
+                t0 = time.perf_counter()                    # (the session's last flush happens on leaving the with block)
+            self.write_seconds += time.perf_counter() - t0
+        except BaseException as e:                          # noqa: BLE001
+            if self.error is None:
+                self.error = e
+            with self.cv:
+                self.pending = 0
+                self.cv.notify_all()
+
+    def put(self, work, nbytes):
+        t0 = time.perf_counter()
+        with self.cv:
+            while self.pending > 0 and self.pending + nbytes > self.max_bytes and self.error is None and self.thread.is_alive():
+                self.cv.wait(0.5)
+            self.pending += nbytes
+        self.wait_seconds += time.perf_counter() - t0
+        if self.error is not None:
+            raise self.error
+        self.q.put((work, nbytes))
+
+    def close(self, reraise=True):
+        self.q.put(None)
+        self.thread.join()
+        if reraise and self.error is not None:
+            raise self.error
+
+
 def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, *, n_games=1024, seed=None, weights=None,
                   device=0, slot_offset=0, hash_salt=0, lib_path=None, progress=None, eval_cache_log2=22, generation=None,
-                  first_game_seq=None, allow_synthetic=False, engine_stats=None, game_groups=0):
+                  first_game_seq=None, allow_synthetic=False, engine_stats=None, game_groups=0, device_samples=None,
+                  max_pending_bytes=1 << 30):
     """Generate `games_per_generation - game_stats[2]` self-play games into `folder_path` (Self_Play.py:259-272).
-    (`engine_stats`: a dict that receives the engine's counters — evaluator calls, simulations, waves — when the generation is done.
+    (`engine_stats`: a dict that receives the engine's counters — evaluator calls, simulations, waves — when the generation is done,
+    and the host's timers: `gpu_wait_seconds` / `sample_seconds` / `queue_wait_seconds` of the thread that queues the waves (waiting for
+    the launches; obtaining the samples of finished games; blocked by the writer's full queue) and `writer_seconds` of the writer thread.
+    `device_samples`: finished games leave the device as training samples (SelfPlayEngine.drain_samples: the states, augmentations and
+    values are built by a kernel, one call per drain) instead of as records that record_to_samples converts game by game.  None = on
+    for the three built-in plugins of games.py, off for any other plugin class — its own get_input_state / augment_sample have to run;
+    False = the host path; True with a foreign plugin is a ValueError.  The file is the same byte for byte.  Either way the file is
+    written by a thread of its own, fed through a queue of at most `max_pending_bytes` of samples.
     `game_groups`: gaz_engine_config.game_groups, scheduling only: 0 = the library's choice, 1 = one batch.)
     `configs` = (build_config, train_config[, optimizer_config]).  `weights` = dict from net.export_engine_weights()
     (generation > 0); generation 0 (folder name "0") plays with the synthetic evaluator like the reference's
@@ -337,6 +412,11 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
     starts at `first_game_seq` (default: the games already in the file), so a resumed generation never replays a game even
     with the same seed."""
     build_config, train_config = configs[0], configs[1]
+    from . import games as _builtin
+    builtin = game_class in (_builtin.Connect4, _builtin.Gomoku, _builtin.TicTacToe)     # (the test record_to_samples makes)
+    if device_samples and not builtin:
+        raise ValueError(f"device_samples=True: {game_class.__name__} is not one of the built-in plugins; its own augment_sample has to run on the host")
+    device_samples = builtin if device_samples is None else bool(device_samples)
     store = ReplayStore(folder_path)
     if not store.exists():
         raise ValueError("Dataset file hasn't been created. Self play depends on that file!")     # Self_Play.py:264-265
@@ -391,29 +471,54 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
         eng.load_weights(weights)
     written = 0
     launch = G                                          # slots the launches cover (shrinks in the generation's tail, see repack)
+    clock = time.perf_counter
+    t_wait = t_samples = 0.0
+    writer = None
     try:
-        with store.writing():
-            eng.run_waves(64)
-            idle = 0
-            while written < games_left:
-                recs = eng.drain_finished()             # waits for the launches queued so far
-                # tail of the generation: every game has been started and the slots halt one by one, but a wave still evaluates all
-                # of them — once half of the covered slots are idle, move the live games together and shrink the launches
-                remaining = games_left - written - len(recs)          # games not finished yet >= games still running
-                if 0 < remaining and remaining * 2 <= launch and launch > 16:
-                    _, launch = eng.repack()
-                eng.run_waves(64)                       # queue the next ones right away: the GPU works while the host converts and writes
-                for rec in recs:                        # every record is one of the admitted games (games_budget)
+        writer = _ReplayWriter(store, max_pending_bytes)
+        eng.run_waves(64)
+        idle = 0
+        while written < games_left:
+            t0 = clock()
+            eng.synchronize()                       # waits for the launches queued so far
+            t1 = clock()
+            if device_samples:
+                batch = eng.drain_samples()
+                got = batch.n
+                batch = batch.copy() if got else None               # the engine reuses its buffers: the writer gets a copy
+            else:
+                recs = eng.drain_finished()
+                got = len(recs)
+            t_wait += t1 - t0; t_samples += clock() - t1
+            # tail of the generation: every game has been started and the slots halt one by one, but a wave still evaluates all
+            # of them — once half of the covered slots are idle, move the live games together and shrink the launches
+            remaining = games_left - written - got                  # games not finished yet >= games still running
+            if 0 < remaining and remaining * 2 <= launch and launch > 16:
+                _, launch = eng.repack()
+            eng.run_waves(64)                       # queue the next ones right away: the GPU works while the host converts and writes
+            if device_samples:                      # every game is one of the admitted games (games_budget)
+                if got:
+                    writer.put(batch, batch.nbytes)
+            else:
+                for rec in recs:
+                    t0 = clock()
                     aug_b, aug_p, aug_v, length = record_to_samples(game_class, rec)
-                    store.append_game(aug_b, aug_p, aug_v, length, rec["T"], rec["winner"])
-                    written += 1
-                    if progress:
-                        progress(written, games_left)
-                idle = 0 if recs else idle + 1
-                if idle > 100000:
-                    raise RuntimeError("self-play made no progress")
+                    t_samples += clock() - t0
+                    writer.put((aug_b, aug_p, aug_v, length, rec["T"], rec["winner"]), aug_b.nbytes + aug_p.nbytes + aug_v.nbytes)
+            if progress:
+                for i in range(got):
+                    progress(written + i + 1, games_left)
+            written += got
+            idle = 0 if got else idle + 1
+            if idle > 100000:
+                raise RuntimeError("self-play made no progress")
+        w, writer = writer, None
+        w.close()                                   # everything queued is in the file; a failure of the writer surfaces here
         if engine_stats is not None:
             engine_stats.update({k: v for k, v in eng.stats().items() if k != "game_stats"})
+            engine_stats.update(gpu_wait_seconds=t_wait, sample_seconds=t_samples, queue_wait_seconds=w.wait_seconds, writer_seconds=w.write_seconds)
     finally:
+        if writer is not None:                      # an error above: what was queued is still written, the thread is joined, the error stays the caller's
+            writer.close(reraise=False)
         eng.close()
     return written

@@ -49,7 +49,7 @@ enum { GAZ_EVAL_HASH = 0,      /* synthetic bit-reproducible evaluator (parity t
        GAZ_EVAL_RESNET = 1,    /* the ResNet policy/value network, HIP MFMA kernels */
        GAZ_EVAL_EXTERNAL = 2   /* caller evaluates the batch between wave_begin / wave_end */ };
 
-#define GAZ_ENGINE_ABI_VERSION 4   /* bumped whenever gaz_engine_config / gaz_search_hyperparams / an entry point changes */
+#define GAZ_ENGINE_ABI_VERSION 5   /* bumped whenever gaz_engine_config / gaz_search_hyperparams / an entry point changes */
 
 typedef struct {
     uint32_t struct_size;         /* = sizeof(gaz_engine_config) of the header the caller was built against; gaz_engine_create
@@ -208,6 +208,28 @@ int gaz_engine_read_head_features(gaz_engine* h, int32_t n, float* p_feat, float
 
 int gaz_engine_record_layout(gaz_engine* h, gaz_record_layout* out);
 int gaz_engine_drain_finished(gaz_engine* h, void* out, int32_t max_records, int32_t* n_out);
+
+/* Finished games as TRAINING SAMPLES, built on the device from the same ring gaz_engine_drain_finished empties: the arrays
+ * Self_Play.play() collects and augments for the replay file (Self_Play.py:159-175; augment_sample, Guide.py:255-283 —
+ * Connect4.py:442-443 [identity, np.fliplr], Gomoku.py:265-303 / Tictactoe.py:321-358 the 8 symmetries in the reference's order).
+ * For the R = sum of T rows of the games taken, row = games in the order handed out, plies in order:
+ *   boards   int8 [n_aug][R][state_bytes]   get_input_state() before the move ([H][W][C]), augmented
+ *   policies f32  [n_aug][R][A]             the improved policy of the ply, same augmentation
+ *   values   f32  [R]                       0.5 * (z + q)  (the replay file repeats it per augmentation)
+ *   games    int32 [n][6]                   T, winner, slot, game_seq, first row of the game, 0
+ * The augmentation planes of the caller's arrays are max_rows rows apart (plane k of boards starts at boards + k * max_rows *
+ * state_bytes), so they are allocated once: boards n_aug * max_rows * state_bytes bytes, policies n_aug * max_rows * A floats, values
+ * max_rows floats, games 6 * max_games ints.  Games leave the ring oldest first, as many WHOLE games as fit in max_games and max_rows;
+ * the rest stays for the next call.  The call may be mixed with gaz_engine_drain_finished: a game is handed out once, by either.  An
+ * oldest game longer than max_rows is an error (last_error says so); max_rows >= max_T always makes progress.  ring_capacity = 0:
+ * nothing to drain.  Rows of a gaz_engine_set_position prefix carry the zeros of their record (policy, q).  With game groups the groups'
+ * rings are visited in turn, as drain_finished does.  A host synchronisation point like gaz_engine_drain_finished. */
+typedef struct { int32_t n_aug, state_bytes, A, max_T; } gaz_sample_layout;
+int gaz_engine_sample_layout(gaz_engine* h, gaz_sample_layout* out);
+int gaz_engine_drain_samples(gaz_engine* h, int32_t max_games, int64_t max_rows,
+                             int32_t* games, int8_t* boards, float* policies, float* values,
+                             int32_t* n_games, int64_t* n_rows);
+
 int gaz_engine_get_stats(gaz_engine* h, uint64_t out[16]);  /* [0..5] game_stats, [6] evaluator calls, [7] simulations,
                                                                [8] plies played (= positions, incl. games in progress), [9] waves launched,
                                                                [10] evaluations answered by the evaluation cache, [11] groups of the group pipeline (0 = off),
