@@ -26,15 +26,11 @@
 #include "resblock.hpp"
 #include "trunk.hpp"
 #include "tile_perm.hpp"
+#include "net_host.hpp"
 #include "puct_core.hpp"      // the fused tree + trunk launch at the end of this file steps the games with the tree kernel's device code
 #include "gumbel_core.hpp"
 
 namespace gaz {
-
-static bf16_t f2bf_host(float f) {
-    unsigned u; memcpy(&u, &f, 4);
-    return (bf16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
 
 // k_resblock3 tiling: tile height 64 * TM, either with a halo (valid rows 64 TM - 2 (W + 1), conv1 recomputes the halo) or
 // board-aligned (k = floor(64 TM / HW) whole boards per tile, no halo).  Cost = rounds of (2 workgroups x n_cus) x TM; ties go
@@ -224,6 +220,12 @@ static std::vector<bf16_t> stem_fragments(const float* w, const float* sc, int C
         h[(((size_t)ks2 * 2 + half) * COUT + ch) * 8 + j] = ks2 < KST ? hi : f2bf_host(wv - hf);
     }
     return h;
+}
+// host: the k_stem_mfma launch for sm.M cells.  ~2.7k waves: ten per CU, each amortising the weight stage (24 KB at 4 planes x 128 channels)
+template <int CIN, int COUT, bool GELU, bool OUT2> static void launch_stem_mfma(hipStream_t s, StemMArgs& sm) {
+    const int tiles = (sm.M + 31) / 32;
+    sm.tiles_per_wave = std::max(1, (tiles + 1343) / 2688);
+    hipLaunchKernelGGL((k_stem_mfma<CIN, COUT, GELU, OUT2>), dim3((tiles + 4 * sm.tiles_per_wave - 1) / (4 * sm.tiles_per_wave)), dim3(256), 0, s, sm);
 }
 
 // ---- Dense(K -> N) + optional per-output scale / shift + activation on the matrix cores, exact fp32 (v_mfma_f32_32x32x2_f32).
@@ -485,8 +487,7 @@ static std::string net_width_error(int f) {
 
 struct ResNetEvaluator : Evaluator {
     int H, W, C, A, HW, blocks, filters, nmax, logits;
-    std::map<std::string, float*> f32;              // device fp32 tensors by name
-    std::map<std::string, bf16_t*> b16;             // device bf16 conv weights by name
+    DeviceStore st;                                 // device tensors by name (net_host.hpp)
     bf16_t *X = nullptr, *Aa = nullptr, *Hh = nullptr, *X2 = nullptr;
     bool fused = true;
     int stamp_calls = 0, n_cus = 256;
@@ -500,114 +501,57 @@ struct ResNetEvaluator : Evaluator {
     uint8_t *perm_big = nullptr, *perm_small = nullptr;    // TrunkArgs::perm for the 128-row and the 96-row tile (tile_perm.hpp tile_layout; GAZ_TILE_PERM=0: none)
     unsigned boff_big = 0, boff_small = 0; int perm_clashes = 0;      // TrunkArgs::boff; residue clashes the layout could not avoid (0: no LDS conflict in any fragment read)
     float *pfeat = nullptr, *vfeat = nullptr, *pd1 = nullptr, *vd1 = nullptr;
-    std::vector<void*> allocs;
     bool loaded = false;
-    std::vector<hipEvent_t> tev;                    // pairs around the trunk conv chain
+    TrunkTimer timer;                               // brackets around the trunk conv chain
     int64_t n_trunk_launches = 0;
 
-    ~ResNetEvaluator() override { for (void* p : allocs) hipFree(p); for (auto e : tev) hipEventDestroy(e); }
-
-    template <class T> T* dalloc(size_t n) { void* p = nullptr; if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return nullptr; allocs.push_back(p); return (T*)p; }
-
     int load(const gaz_tensor* t, int n, hipStream_t s, std::string* err) override {
-        std::map<std::string, const gaz_tensor*> by;
-        for (int i = 0; i < n; ++i) by[t[i].name] = &t[i];
-        auto need = [&](const std::string& name, int64_t numel) -> const gaz_tensor* {
-            auto it = by.find(name);
-            if (it == by.end()) { *err = "missing tensor " + name; return nullptr; }
-            if (it->second->numel != numel) { *err = "tensor " + name + " has " + std::to_string(it->second->numel) + " elements, expected " + std::to_string(numel); return nullptr; }
-            return it->second;
-        };
-        auto up_f32 = [&](const std::string& name, int64_t numel) -> bool {
-            const gaz_tensor* g = need(name, numel); if (!g) return false;
-            float* d = dalloc<float>(numel); if (!d) { *err = "hipMalloc"; return false; }
-            hipMemcpy(d, g->data, numel * 4, hipMemcpyHostToDevice); f32[name] = d; return true;
-        };
-        // a block's conv1 / conv2 weights share one allocation (conv2 right behind conv1): k_resblock3 walks them as 18 slices
-        bool pair_first = false; bf16_t* pair_next = nullptr;
-        auto up_b16 = [&](const std::string& name, int64_t numel) -> bool {      // conv weights [9][cout][cin] -> fragment order
-            const gaz_tensor* g = need(name, numel); if (!g) return false;
-            std::vector<bf16_t> h(numel);
-            const int cin = 128, cout = (int)(numel / (9 * cin));
-            arrange_conv_weights(g->data, cout, cin, h.data(), f2bf_host);
-            bf16_t* d = pair_next ? pair_next : dalloc<bf16_t>(numel * (pair_first ? 2 : 1)); if (!d) { *err = "hipMalloc"; return false; }
-            pair_next = pair_first ? d + numel : nullptr; pair_first = false;
-            hipMemcpy(d, h.data(), numel * 2, hipMemcpyHostToDevice); b16[name] = d; return true;
-        };
-        auto up_wide = [&](const std::string& name, int cout, int cin, int ntaps) -> bool {   // [ntaps][cout][cin] -> arrange_wide_weights order
-            const int64_t numel = (int64_t)ntaps * cout * cin;
-            const gaz_tensor* g = need(name, numel); if (!g) return false;
-            std::vector<bf16_t> h(numel);
-            arrange_wide_weights(g->data, cout, cin, ntaps, h.data(), f2bf_host);
-            bf16_t* d = dalloc<bf16_t>(numel); if (!d) { *err = "hipMalloc"; return false; }
-            hipMemcpy(d, h.data(), numel * 2, hipMemcpyHostToDevice); b16[name] = d; return true;
-        };
-        auto up_bias2p = [&](int Fc) -> bool {      // block 0: conv2 and the projection share one accumulator and one fp32 bias b2 + bp
-            std::vector<float> h(Fc);
-            const float* b2 = by["block0.conv2.bias"]->data; const float* bp = by["block0.proj.bias"]->data;
-            for (int c = 0; c < Fc; ++c) h[c] = b2[c] + bp[c];
-            float* d = dalloc<float>(Fc); if (!d) { *err = "hipMalloc"; return false; }
-            hipMemcpy(d, h.data(), Fc * 4, hipMemcpyHostToDevice); f32["block0.bias2p"] = d; return true;
-        };
+        st.set_tensors(t, n);
+        if (!load_tensors()) { *err = st.err; return 1; }
+        hipStreamSynchronize(s);
+        loaded = true;
+        return 0;
+    }
+    bool load_tensors() {
         const int Fc = filters, F = HW * 8;
-        if (!up_f32("stem.w", 9 * 128 * C) || !up_f32("stem.scale", 128) || !up_f32("stem.shift", 128)) return 1;
+        if (!st.up_f32("stem.w", 9 * 128 * C) || !st.up_f32("stem.scale", 128) || !st.up_f32("stem.shift", 128)) return false;
         {   // MFMA stem operand, BN scale folded into the weights
-            if (C != 4) { *err = "stem expects 4 input planes"; return 1; }
-            const std::vector<bf16_t> h = stem_fragments(by["stem.w"]->data, by["stem.scale"]->data, 4, 128);
-            stem_frag = dalloc<bf16_t>(h.size()); if (!stem_frag) { *err = "hipMalloc"; return 1; }
-            hipMemcpy(stem_frag, h.data(), h.size() * 2, hipMemcpyHostToDevice);
+            if (C != 4) { st.err = "stem expects 4 input planes"; return false; }
+            const std::vector<bf16_t> h = stem_fragments(st.by["stem.w"]->data, st.by["stem.scale"]->data, 4, 128);
+            if (!(stem_frag = st.upload(h.data(), h.size()))) return false;
         }
-        if (Fc != 128) {                            // k_conv_wide operands (conv_wide.hpp); block 0 projects the 128-channel stem
-            for (int i = 0; i < blocks; ++i) {
-                const std::string b = "block" + std::to_string(i); const int cin = i == 0 ? 128 : Fc;
-                if (!up_f32(b + ".bn1.scale", cin) || !up_f32(b + ".bn1.shift", cin) || !up_wide(b + ".conv1.w", Fc, cin, 9) ||
-                    !up_f32(b + ".conv1.scale", Fc) || !up_f32(b + ".conv1.shift", Fc) || !up_wide(b + ".conv2.w", Fc, Fc, 9) ||
-                    !up_f32(b + ".conv2.bias", Fc)) return 1;
-            }
-            if (blocks > 0 && (!up_wide("block0.proj.w", Fc, 128, 1) || !up_f32("block0.proj.bias", Fc) || !up_bias2p(Fc))) return 1;
+        for (int i = 0; i < blocks; ++i) {
+            // 128 filters: k_resblock3 / k_trunk operands; other widths: k_conv_wide operands (conv_wide.hpp), block 0 projects the 128-channel stem
+            const std::string b = "block" + std::to_string(i); const int cin = i == 0 && Fc != 128 ? 128 : Fc;
+            if (!st.up_f32(b + ".bn1.scale", cin) || !st.up_f32(b + ".bn1.shift", cin)) return false;
+            if (Fc == 128 ? !st.up_conv_pair(b + ".conv1.w", b + ".conv2.w", Fc)
+                          : !st.up_conv(b + ".conv1.w", Fc, cin, 9, CONV_WIDE) || !st.up_conv(b + ".conv2.w", Fc, Fc, 9, CONV_WIDE)) return false;
+            if (!st.up_f32(b + ".conv1.scale", Fc) || !st.up_f32(b + ".conv1.shift", Fc) || !st.up_f32(b + ".conv2.bias", Fc)) return false;
         }
-        for (int i = 0; Fc == 128 && i < blocks; ++i) {
-            const std::string b = "block" + std::to_string(i);
-            pair_first = true;
-            if (!up_f32(b + ".bn1.scale", Fc) || !up_f32(b + ".bn1.shift", Fc) || !up_b16(b + ".conv1.w", 9LL * Fc * Fc) ||
-                !up_f32(b + ".conv1.scale", Fc) || !up_f32(b + ".conv1.shift", Fc) || !up_b16(b + ".conv2.w", 9LL * Fc * Fc) ||
-                !up_f32(b + ".conv2.bias", Fc)) return 1;
-        }
-        if (blocks > 0 && Fc == 128) {   // k_trunk operands: the slices of all blocks as one array, the per-block parameters as [block][5][128]
-            const size_t WB = 18 * (size_t)Fc * Fc;
-            trunk_w = dalloc<bf16_t>(blocks * WB); trunk_prm = dalloc<float>((size_t)blocks * TR_PRM);
-            if (!trunk_w || !trunk_prm) { *err = "hipMalloc"; return 1; }
-            for (int i = 0; i < blocks; ++i) {
-                const std::string b = "block" + std::to_string(i);
-                hipMemcpy(trunk_w + i * WB, b16[b + ".conv1.w"], WB * 2, hipMemcpyDeviceToDevice);     // conv2 sits right behind conv1
-                const char* names[5] = {".bn1.scale", ".bn1.shift", ".conv1.scale", ".conv1.shift", ".conv2.bias"};
-                for (int k = 0; k < 5; ++k) hipMemcpy(trunk_prm + ((size_t)i * 5 + k) * 128, f32[b + names[k]], 128 * 4, hipMemcpyDeviceToDevice);
-            }
-        }
-        if (!(getenv("GAZ_TILE_PERM") && atoi(getenv("GAZ_TILE_PERM")) == 0) && !perm_big && 96 / HW >= 1 && Fc == 128) {
+        if (Fc != 128 && (!st.up_conv("block0.proj.w", Fc, 128, 1, CONV_WIDE) || !st.up_f32("block0.proj.bias", Fc) ||
+                          !st.up_bias_sum("block0.bias2p", "block0.conv2.bias", "block0.proj.bias"))) return false;
+        if (Fc == 128 && !st.pack_trunk(0, blocks, &trunk_w, &trunk_prm)) return false;
+        if (env_on("GAZ_TILE_PERM", true) && !perm_big && 96 / HW >= 1 && Fc == 128) {
             // the kernels' static sit-out masks (trunk.hpp conv9): 128-row tile = two wave rows (y = 0 | x = 0) and (y = H - 1 | x = W - 1); 96-row
             // tile = one wave row (y = 0 | y = H - 1 | x = 0).  Both permutations must deliver exactly that, or neither is used.
             unsigned want_big[8] = {0x007u, 0x049u, 0, 0, 0x1C0u, 0x124u, 0, 0}, want_small[6] = {0x007u, 0x1C0u, 0x049u, 0, 0, 0};
             const TileLayout lb = tile_layout(H, W, 128 / HW, 128, 64, 2, want_big), ls = tile_layout(H, W, 96 / HW, 96, 96, 3, want_small);
             const bool ok = !lb.perm.empty() && !ls.perm.empty() && lb.boff.size() <= 3 && ls.boff.size() <= 3;
-            if (ok && (perm_big = dalloc<uint8_t>(lb.perm.size())) && (perm_small = dalloc<uint8_t>(ls.perm.size()))) {
-                hipMemcpy(perm_big, lb.perm.data(), lb.perm.size(), hipMemcpyHostToDevice); hipMemcpy(perm_small, ls.perm.data(), ls.perm.size(), hipMemcpyHostToDevice);
+            if (ok && (perm_big = st.upload(lb.perm.data(), lb.perm.size())) && (perm_small = st.upload(ls.perm.data(), ls.perm.size()))) {
                 boff_big = boff_small = 0;
                 for (size_t b = 0; b < lb.boff.size(); ++b) boff_big |= (unsigned)lb.boff[b] << (8 * b);
                 for (size_t b = 0; b < ls.boff.size(); ++b) boff_small |= (unsigned)ls.boff[b] << (8 * b);
                 perm_clashes = lb.clashes + ls.clashes;
             } else { perm_big = perm_small = nullptr; }
         }
-        if (!(Fc == 128 ? up_b16("heads.conv.w", 9LL * 32 * Fc) : up_wide("heads.conv.w", 32, Fc, 9)) || !up_f32("heads.conv.bias", 32)) return 1;
+        if (!st.up_conv("heads.conv.w", 32, Fc, 9, Fc == 128 ? CONV_MFMA : CONV_WIDE) || !st.up_f32("heads.conv.bias", 32)) return false;
         for (const char* pre : {"p", "v"}) {
             const std::string p = pre; const int nout = p == "p" ? A : 1;
-            if (!up_f32(p + ".bn0.scale", F) || !up_f32(p + ".bn0.shift", F) || !up_f32(p + ".d1.w", (int64_t)F * 128) ||
-                !up_f32(p + ".d1.scale", 128) || !up_f32(p + ".d1.shift", 128) || !up_f32(p + ".d2.w", 128 * 64) ||
-                !up_f32(p + ".d2.bias", 64) || !up_f32(p + ".d3.w", 64 * nout) || !up_f32(p + ".d3.bias", nout)) return 1;
+            if (!st.up_f32(p + ".bn0.scale", F) || !st.up_f32(p + ".bn0.shift", F) || !st.up_f32(p + ".d1.w", (int64_t)F * 128) ||
+                !st.up_f32(p + ".d1.scale", 128) || !st.up_f32(p + ".d1.shift", 128) || !st.up_f32(p + ".d2.w", 128 * 64) ||
+                !st.up_f32(p + ".d2.bias", 64) || !st.up_f32(p + ".d3.w", 64 * nout) || !st.up_f32(p + ".d3.bias", nout)) return false;
         }
-        hipStreamSynchronize(s);
-        loaded = true;
-        return 0;
+        return true;
     }
 
     void conv_trunk(hipStream_t s, const bf16_t* in, const bf16_t* w, const float* sA, const float* tA, const bf16_t* res,
@@ -615,7 +559,7 @@ struct ResNetEvaluator : Evaluator {
         ConvArgs a; memset(&a, 0, sizeof(a));
         a.in = in; a.wgt = w; a.scaleA = sA; a.shiftA = tA; a.res = res; a.out1 = out1; a.act1 = act1;
         a.scaleB = sB; a.shiftB = tB; a.out2 = out2; a.M = M; a.H = H; a.W = W;
-        static const int variant = getenv("GAZ_CONV_VARIANT") ? atoi(getenv("GAZ_CONV_VARIANT")) : 0;
+        static const int variant = env_int("GAZ_CONV_VARIANT", 0);
         if (variant == 0) {          // 256 rows / 512 threads / whole-tap slices, one workgroup per CU
             const size_t lds = conv_lds_bytes<128, 128, 256, 1>();
             hipLaunchKernelGGL((k_conv3x3<128, 128, 256, 4, 2, 2, 2, 1, 1, 0>), dim3((M + 255) / 256), dim3(512), lds, s, a);
@@ -629,34 +573,26 @@ struct ResNetEvaluator : Evaluator {
     bool supports_row_base() const override { return true; }
     bool head_features(const float** p, const float** v, int* pr, int* vr) override { *p = pfeat; *v = vfeat; *pr = HW * 8; *vr = HW * 8; return true; }
     bool supports_split() const override { return filters == 128 && fused && trunk && trunk_whole && blocks > 0 && HW <= 128; }
-    // kernel arguments + grid of the whole-trunk launch for rows [p0, p0 + n) (k_trunk_mix / k_trunk with stem and heads inside)
-    bool make_trunk_plan(const int8_t* in, int n, int p0, TrunkLaunchPlan& P) {
-        if (!loaded || !supports_split()) return false;
-        const int M = n * HW;
+    // kernel arguments + grid of the k_trunk / k_trunk_mix launch for rows [p0, p0 + n): the ONE place that fills them.  The whole-trunk
+    // variants (stem and heads inside) read every field; the blocks-only variant (GAZ_TRUNK_WHOLE=0) ignores planes ... v_feat and never mixes.
+    void make_trunk_plan(const int8_t* in, int n, int p0, bool mix_allowed, bool fill_big, TrunkLaunchPlan& P) {
         TrunkArgs& r = P.args; memset(&r, 0, sizeof(r));
-        r.xin = this->X + (size_t)p0 * HW * 128; r.xout = this->X2 + (size_t)p0 * HW * 128; r.w = trunk_w; r.prm = trunk_prm; r.M = M; r.H = H; r.W = W; r.nblocks = blocks;
+        r.xin = this->X + (size_t)p0 * HW * 128; r.xout = this->X2 + (size_t)p0 * HW * 128; r.w = trunk_w; r.prm = trunk_prm; r.M = n * HW; r.H = H; r.W = W; r.nblocks = blocks;
         r.tile_rows = (128 / HW) * HW; r.stamps = nullptr; r.perm = perm_big; r.perm_small = perm_small; r.boff = boff_big; r.boff_small = boff_small;
-        r.planes = in; r.stem_frag = reinterpret_cast<const uint4*>(stem_frag); r.stem_shift = f32["stem.shift"];
-        r.hw = b16["heads.conv.w"]; r.hbias = f32["heads.conv.bias"]; r.p_fs = f32["p.bn0.scale"]; r.p_ft = f32["p.bn0.shift"];
-        r.v_fs = f32["v.bn0.scale"]; r.v_ft = f32["v.bn0.shift"];
+        r.planes = in; r.stem_frag = reinterpret_cast<const uint4*>(stem_frag); r.stem_shift = st.g("stem.shift");
+        r.hw = st.w("heads.conv.w"); r.hbias = st.g("heads.conv.bias"); r.p_fs = st.g("p.bn0.scale"); r.p_ft = st.g("p.bn0.shift");
+        r.v_fs = st.g("v.bn0.scale"); r.v_ft = st.g("v.bn0.shift");
         r.p_feat = this->pfeat + (size_t)p0 * HW * 8; r.v_feat = this->vfeat + (size_t)p0 * HW * 8;
-        int nwg = (M + r.tile_rows - 1) / r.tile_rows;
-        bool mix = false;
-        if (trunk_mix && 96 / HW >= 1 && 96 / HW < 128 / HW) {    // whole rounds of 128-row tiles, the rest in 96-row tiles (k_trunk_mix)
-            const int slots = 2 * n_cus, bb = 128 / HW, sb = 96 / HW;
-            int nb = (n / (bb * slots)) * slots, ns = (n - nb * bb + sb - 1) / sb;
-            const double cost_mix = nb / slots + 0.78 * ((ns + slots - 1) / slots), cost_big = (nwg + slots - 1) / slots;
-            // one of several game groups: the other groups' tiles fill a ragged last round, so every board that fits one goes into a 3-board tile
-            // (46 us per board and slot against 51 in a 2-board tile) and only the remainder into 2-board tiles
-            if (shared_chip && perm_big && perm_small) { nb = n / bb; ns = (n - nb * bb + sb - 1) / sb; }
-            if (cost_mix < cost_big || (shared_chip && perm_big && perm_small)) { mix = true; r.n_big = nb; r.small_rows = sb * HW; nwg = nb + ns; }
-        }
-        P.nwg = nwg; P.mix = mix; P.lds_bytes = (unsigned)trunk_lds_bytes(128);
-        return true;
+        const TrunkSplit sp = trunk_split(n, HW, n_cus, mix_allowed, fill_big);      // whole rounds of 128-row tiles, the rest in 96-row tiles (k_trunk_mix)
+        if (sp.mix) { r.n_big = sp.n_big; r.small_rows = (96 / HW) * HW; }
+        P.nwg = sp.nwg; P.mix = sp.mix; P.lds_bytes = (unsigned)trunk_lds_bytes(128);
     }
     TrunkLaunchPlan fused_plan;
     const void* trunk_plan(const int8_t* in, int n, int p0, const FuseHandoff& h) override {
-        if (!trunk_m16 || !make_trunk_plan(in, n, p0, fused_plan)) return nullptr;
+        if (!trunk_m16 || !loaded || !supports_split()) return nullptr;
+        // one of several game groups: the other groups' tiles fill a ragged last round, so every board that fits one goes into a 3-board tile
+        // (46 us per board and slot against 51 in a 2-board tile) and only the remainder into 2-board tiles (tile_perm.hpp trunk_split, fill_big)
+        make_trunk_plan(in, n, p0, trunk_mix, shared_chip && perm_big && perm_small, fused_plan);
         TrunkArgs& r = fused_plan.args;
         r.ready = h.ready; r.epoch = h.epoch; r.eval_done = h.eval_done; r.fuse_fault = h.fuse_fault; r.spin_ticks = h.spin_ticks; r.test_fault_mod = h.test_fault_mod; r.stamps = h.stamps;
         r.queue = (perm_big && perm_small && fused_plan.mix) ? h.queue : nullptr;       // the completion queue needs the variant that maps image rows to games itself
@@ -664,7 +600,7 @@ struct ResNetEvaluator : Evaluator {
     }
     bool plan_uses_queue(const void* plan) const override { return plan && static_cast<const TrunkLaunchPlan*>(plan)->args.queue != nullptr; }
     bool shared_chip = false;
-    void set_shared_chip(bool on) override { static const bool off = getenv("GAZ_GROUP_BIG_TILES") && atoi(getenv("GAZ_GROUP_BIG_TILES")) == 0; shared_chip = on && !off; }
+    void set_shared_chip(bool on) override { static const bool off = !env_on("GAZ_GROUP_BIG_TILES", true); shared_chip = on && !off; }
     int round_rows() const override { return 2 * n_cus * (128 / HW); }
     void forward(hipStream_t s, const int8_t* in, float* policy, float* value, int n, bool timing, int p0 = 0) override {
         forward_trunk(s, in, n, timing, p0);
@@ -679,149 +615,93 @@ struct ResNetEvaluator : Evaluator {
         bf16_t* const X = this->X + (size_t)p0 * HW * 128; bf16_t* const X2 = this->X2 + (size_t)p0 * HW * 128;
         bf16_t* const Aa = this->Aa + (size_t)p0 * HW * 128; bf16_t* const Hh = this->Hh + (size_t)p0 * HW * 128;
         float* const pfeat = this->pfeat + (size_t)p0 * HW * 8; float* const vfeat = this->vfeat + (size_t)p0 * HW * 8;
-        StemArgs st; st.in = in; st.w = f32["stem.w"]; st.scale = f32["stem.scale"]; st.shift = f32["stem.shift"];
-        st.scaleB = blocks ? f32["block0.bn1.scale"] : f32["stem.scale"]; st.shiftB = blocks ? f32["block0.bn1.shift"] : f32["stem.shift"];
-        st.out1 = X; st.out2 = fused ? nullptr : Aa; st.M = M; st.H = H; st.W = W;    // the fused blocks pre-activate on load
+        StemArgs sa; sa.in = in; sa.w = st.g("stem.w"); sa.scale = st.g("stem.scale"); sa.shift = st.g("stem.shift");
+        sa.scaleB = blocks ? st.g("block0.bn1.scale") : st.g("stem.scale"); sa.shiftB = blocks ? st.g("block0.bn1.shift") : st.g("stem.shift");
+        sa.out1 = X; sa.out2 = fused ? nullptr : Aa; sa.M = M; sa.H = H; sa.W = W;    // the fused blocks pre-activate on load
         const bool use_trunk = fused && trunk && blocks > 0 && HW <= 128;
         const bool whole = use_trunk && trunk_whole;     // stem and heads' first convolution inside k_trunk as well
         if (whole) {
         } else if (fused) {
-            StemMArgs sm; memset(&sm, 0, sizeof(sm)); sm.in = in; sm.wfrag = reinterpret_cast<const uint4*>(stem_frag); sm.shift = f32["stem.shift"]; sm.out = X;
+            StemMArgs sm; memset(&sm, 0, sizeof(sm)); sm.in = in; sm.wfrag = reinterpret_cast<const uint4*>(stem_frag); sm.shift = st.g("stem.shift"); sm.out = X;
             sm.M = M; sm.H = H; sm.W = W;
-            const int tiles = (M + 31) / 32;
-            sm.tiles_per_wave = std::max(1, (tiles + 1343) / 2688);     // ~2.7k waves: ten per CU, each amortising the 24-KB weight stage
-            hipLaunchKernelGGL((k_stem_mfma<4, 128, true, false>), dim3((tiles + 4 * sm.tiles_per_wave - 1) / (4 * sm.tiles_per_wave)), dim3(256), 0, s, sm);
+            launch_stem_mfma<4, 128, true, false>(s, sm);
         } else {
-            hipLaunchKernelGGL(k_stem, dim3((M + 63) / 64), dim3(256), 0, s, st);
+            hipLaunchKernelGGL(k_stem, dim3((M + 63) / 64), dim3(256), 0, s, sa);
         }
-        hipEvent_t e0 = 0, e1 = 0;
-        if (timing) { hipEventCreate(&e0); hipEventCreate(&e1); tev.push_back(e0); tev.push_back(e1); hipEventRecord(e0, s); }
+        timer.begin(s, timing);
         bf16_t* cur = X;
         if (use_trunk) {                            // every block in one kernel, k whole boards per workgroup (trunk.hpp)
-            TrunkArgs r; memset(&r, 0, sizeof(r)); r.xin = X; r.xout = X2; r.w = trunk_w; r.prm = trunk_prm; r.M = M; r.H = H; r.W = W; r.nblocks = blocks;
-            r.tile_rows = (128 / HW) * HW; r.stamps = nullptr; r.perm = perm_big; r.perm_small = perm_small; r.boff = boff_big; r.boff_small = boff_small;
-            r.planes = in; r.stem_frag = reinterpret_cast<const uint4*>(stem_frag); r.stem_shift = f32["stem.shift"];
-            r.hw = b16["heads.conv.w"]; r.hbias = f32["heads.conv.bias"]; r.p_fs = f32["p.bn0.scale"]; r.p_ft = f32["p.bn0.shift"];
-            r.v_fs = f32["v.bn0.scale"]; r.v_ft = f32["v.bn0.shift"]; r.p_feat = pfeat; r.v_feat = vfeat;
-            int nwg = (M + r.tile_rows - 1) / r.tile_rows;
-            bool mix = false;
-            if (whole && trunk_mix && 96 / HW >= 1 && 96 / HW < 128 / HW) {    // whole rounds of 128-row tiles, the rest in 96-row tiles (k_trunk_mix)
-                const int slots = 2 * n_cus, bb = 128 / HW, sb = 96 / HW;
-                const int nb = (n / (bb * slots)) * slots, ns = (n - nb * bb + sb - 1) / sb;
-                const double cost_mix = nb / slots + 0.78 * ((ns + slots - 1) / slots), cost_big = (nwg + slots - 1) / slots;
-                if (cost_mix < cost_big) { mix = true; r.n_big = nb; r.small_rows = sb * HW; nwg = nb + ns; }
-            }
+            // a launch of its own has the chip to itself: whole rounds of 3-board tiles only (trunk_split without fill_big), whatever shared_chip says
+            TrunkLaunchPlan P; make_trunk_plan(in, n, p0, whole && trunk_mix, false, P);
+            TrunkArgs& r = P.args;
+            const int nwg = P.nwg; const bool mix = P.mix;
             static const char* stamp_path = getenv("GAZ_TRUNK_STAMPS");    // diagnostic: phase stamps of the third launch -> file
-            const bool stamp = stamp_path && ++stamp_calls == 3;
-            if (stamp) { hipMalloc((void**)&r.stamps, (size_t)nwg * 128 * 8); hipMemsetAsync(r.stamps, 0, (size_t)nwg * 128 * 8, s); }
+            StampDump stamps(stamp_path && ++stamp_calls == 3 ? stamp_path : nullptr, (size_t)nwg * 128, s);
+            r.stamps = stamps.dev;
             if (mix && trunk_m16 && r.perm && r.perm_small) hipLaunchKernelGGL((k_trunk_mix<8, 2, true, true, true, true>), dim3(nwg), dim3(TR_THREADS), trunk_lds_bytes(128), s, r);
             else if (mix && trunk_m16) hipLaunchKernelGGL((k_trunk_mix<8, 2, true, true, true>), dim3(nwg), dim3(TR_THREADS), trunk_lds_bytes(128), s, r);
             else if (whole && trunk_m16) hipLaunchKernelGGL((k_trunk<2, 2, 8, 2, true, true, false, true>), dim3(nwg), dim3(TR_THREADS), trunk_lds_bytes(128), s, r);
             else if (mix) hipLaunchKernelGGL((k_trunk_mix<8, 2, true, true>), dim3(nwg), dim3(TR_THREADS), trunk_lds_bytes(128), s, r);
             else if (whole) hipLaunchKernelGGL((k_trunk<2, 2, 8, 2, true, true>), dim3(nwg), dim3(TR_THREADS), trunk_lds_bytes(128), s, r);
             else hipLaunchKernelGGL((k_trunk<2, 2, 8, 2, false, false>), dim3(nwg), dim3(TR_THREADS), trunk_lds_bytes(128), s, r);
-            if (stamp) {
-                std::vector<unsigned long long> hst((size_t)nwg * 128);
-                hipStreamSynchronize(s);
-                hipMemcpy(hst.data(), r.stamps, hst.size() * 8, hipMemcpyDeviceToHost); hipFree(r.stamps);
-                if (FILE* f = fopen(stamp_path, "wb")) { fwrite(hst.data(), 8, hst.size(), f); fclose(f); }
-            }
+            stamps.finish();
             cur = X2;
         }
         for (int i = 0; fused && !use_trunk && i < blocks; ++i) {             // one kernel per residual block (resblock.hpp)
             const std::string b = "block" + std::to_string(i);
-            ResBlockArgs r; r.xin = cur; r.xout = cur == X ? X2 : X; r.w1 = b16[b + ".conv1.w"]; r.w2 = b16[b + ".conv2.w"];
-            r.s1 = f32[b + ".bn1.scale"]; r.t1 = f32[b + ".bn1.shift"]; r.s2 = f32[b + ".conv1.scale"]; r.t2 = f32[b + ".conv1.shift"];
-            r.b2 = f32[b + ".conv2.bias"]; r.M = M; r.H = H; r.W = W; r.stamps = nullptr;
-            static const int rbv = getenv("GAZ_RB") ? atoi(getenv("GAZ_RB")) : 3;
-            static const int rb_tm = getenv("GAZ_RB_TM") ? atoi(getenv("GAZ_RB_TM")) : 0;
-            static const int rb_ring = getenv("GAZ_RB_RING") ? atoi(getenv("GAZ_RB_RING")) : 8;
+            ResBlockArgs r; r.xin = cur; r.xout = cur == X ? X2 : X; r.w1 = st.w(b + ".conv1.w"); r.w2 = st.w(b + ".conv2.w");
+            r.s1 = st.g(b + ".bn1.scale"); r.t1 = st.g(b + ".bn1.shift"); r.s2 = st.g(b + ".conv1.scale"); r.t2 = st.g(b + ".conv1.shift");
+            r.b2 = st.g(b + ".conv2.bias"); r.M = M; r.H = H; r.W = W; r.stamps = nullptr;
+            static const int rbv = env_int("GAZ_RB", 3);
+            static const int rb_tm = env_int("GAZ_RB_TM", 0);
+            static const int rb_ring = env_int("GAZ_RB_RING", 8);
             Rb3Plan plan = rb3_plan(M, H, W, n_cus);
             if (rb_tm) plan = Rb3Plan{rb_tm, W + 1, 64 * rb_tm - 2 * (W + 1)};
             const int bmo = rbv == 3 ? plan.tile_rows : RB_ROWS - 2 * (W + 1);
             const size_t lds = conv_lds_bytes<128, 128, 256, 1>();
             const int nwg = (M + bmo - 1) / bmo;
             static const char* stamp_path = getenv("GAZ_RB_STAMPS");       // diagnostic: phase stamps of one launch -> file
-            const bool stamp = stamp_path && i == 1 && ++stamp_calls == 3;
-            if (stamp) { hipMalloc((void**)&r.stamps, (size_t)nwg * RB_STAMPS * 8); hipMemsetAsync(r.stamps, 0, (size_t)nwg * RB_STAMPS * 8, s); }
+            StampDump stamps(stamp_path && i == 1 && ++stamp_calls == 3 ? stamp_path : nullptr, (size_t)nwg * RB_STAMPS, s);
+            r.stamps = stamps.dev;
             if (rbv == 3) rb3_launch(s, r, plan, rb_ring);
             else hipLaunchKernelGGL(k_resblock, dim3(nwg), dim3(RB_THREADS), lds, s, r);
-            if (stamp) {
-                std::vector<unsigned long long> hst((size_t)nwg * RB_STAMPS);
-                hipStreamSynchronize(s);
-                hipMemcpy(hst.data(), r.stamps, hst.size() * 8, hipMemcpyDeviceToHost); hipFree(r.stamps);
-                if (FILE* f = fopen(stamp_path, "wb")) { fwrite(hst.data(), 8, hst.size(), f); fclose(f); }
-            }
+            stamps.finish();
             cur = r.xout;
         }
         for (int i = 0; !fused && i < blocks; ++i) {
             const std::string b = "block" + std::to_string(i), nb = "block" + std::to_string(i + 1);
-            conv_trunk(s, Aa, b16[b + ".conv1.w"], f32[b + ".conv1.scale"], f32[b + ".conv1.shift"], nullptr, Hh, ACT_RELU,
+            conv_trunk(s, Aa, st.w(b + ".conv1.w"), st.g(b + ".conv1.scale"), st.g(b + ".conv1.shift"), nullptr, Hh, ACT_RELU,
                        nullptr, nullptr, nullptr, M);
             const bool last = i + 1 == blocks;
-            conv_trunk(s, Hh, b16[b + ".conv2.w"], nullptr, f32[b + ".conv2.bias"], X, X, ACT_NONE,
-                       last ? nullptr : f32[nb + ".bn1.scale"], last ? nullptr : f32[nb + ".bn1.shift"], last ? nullptr : Aa, M);
+            conv_trunk(s, Hh, st.w(b + ".conv2.w"), nullptr, st.g(b + ".conv2.bias"), X, X, ACT_NONE,
+                       last ? nullptr : st.g(nb + ".bn1.scale"), last ? nullptr : st.g(nb + ".bn1.shift"), last ? nullptr : Aa, M);
         }
-        if (timing) hipEventRecord(e1, s);
+        timer.end(s);
         if (!whole) {   // first conv of both heads + flat BN + ReLU (k_conv_heads)
-            HeadsConvArgs hc; hc.in = cur; hc.wgt = b16["heads.conv.w"]; hc.bias = f32["heads.conv.bias"];
-            hc.p_fs = f32["p.bn0.scale"]; hc.p_ft = f32["p.bn0.shift"]; hc.v_fs = f32["v.bn0.scale"]; hc.v_ft = f32["v.bn0.shift"];
+            HeadsConvArgs hc; hc.in = cur; hc.wgt = st.w("heads.conv.w"); hc.bias = st.g("heads.conv.bias");
+            hc.p_fs = st.g("p.bn0.scale"); hc.p_ft = st.g("p.bn0.shift"); hc.v_fs = st.g("v.bn0.scale"); hc.v_ft = st.g("v.bn0.shift");
             hc.p_feat = pfeat; hc.v_feat = vfeat; hc.M = M; hc.H = H; hc.W = W;
             hipLaunchKernelGGL(k_conv_heads, dim3((M + HC_ROWS - 1) / HC_ROWS), dim3(RB3_THREADS), hc_lds_bytes(), s, hc);
         }
     }
-    // F != 128 (conv_wide.hpp): stem -> X (128 channels), a0 = relu(bn1_0(x0)) -> X2; block 0: conv1 128 -> F (X2 -> Hh), conv2 + the
-    // 128 -> F projection of x0 in one accumulator (Hh, X -> X2); blocks 1..: conv1 (Aa -> Hh), conv2 + residual (Hh, X2 -> X2); every
-    // conv2 also writes the next block's operand relu(bn1(bf16 x)) -> Aa; heads' first convolution F -> 32 -> pfeat / vfeat.  Separate
-    // launches only (no fused tree + trunk launch at these widths: supports_split() is false).
+    // F != 128 (net_host.hpp forward_trunk_wide): stem -> X (128 channels), a0 -> X2, the residual stream in X2 as well, operands in Aa / Hh;
+    // then the heads' first convolution F -> 32 -> pfeat / vfeat.  Separate launches only (no fused tree + trunk launch at these widths:
+    // supports_split() is false).
     void forward_trunk_wide(hipStream_t s, const int8_t* in, int n, bool timing, int p0) {
         const int M = n * HW, CW = std::max(filters, 128);
         bf16_t* const X = this->X + (size_t)p0 * HW * CW; bf16_t* const X2 = this->X2 + (size_t)p0 * HW * CW;
         bf16_t* const Aa = this->Aa + (size_t)p0 * HW * CW; bf16_t* const Hh = this->Hh + (size_t)p0 * HW * CW;
         float* const pfeat = this->pfeat + (size_t)p0 * HW * 8; float* const vfeat = this->vfeat + (size_t)p0 * HW * 8;
-        {
-            StemMArgs sm; memset(&sm, 0, sizeof(sm)); sm.in = in; sm.wfrag = reinterpret_cast<const uint4*>(stem_frag); sm.shift = f32["stem.shift"]; sm.out = X;
-            sm.M = M; sm.H = H; sm.W = W;
-            const int tiles = (M + 31) / 32;
-            sm.tiles_per_wave = std::max(1, (tiles + 1343) / 2688);
-            hipLaunchKernelGGL((k_stem_mfma<4, 128, true, false>), dim3((tiles + 4 * sm.tiles_per_wave - 1) / (4 * sm.tiles_per_wave)), dim3(256), 0, s, sm);
-            const long n8 = (long)M * 128 / 8;
-            hipLaunchKernelGGL(k_affine_relu, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, X, f32["block0.bn1.scale"], f32["block0.bn1.shift"], X2, n8, 128);
-        }
-        hipEvent_t e0 = 0, e1 = 0;
-        if (timing) { hipEventCreate(&e0); hipEventCreate(&e1); tev.push_back(e0); tev.push_back(e1); hipEventRecord(e0, s); }
-        for (int i = 0; i < blocks; ++i) {
-            const std::string b = "block" + std::to_string(i), nb = "block" + std::to_string(i + 1);
-            const bool last = i + 1 == blocks;
-            WideConvArgs c1; memset(&c1, 0, sizeof(c1));
-            c1.in = i == 0 ? X2 : Aa; c1.wgt = b16[b + ".conv1.w"]; c1.scaleA = f32[b + ".conv1.scale"]; c1.shiftA = f32[b + ".conv1.shift"];
-            c1.out1 = Hh; c1.act1 = ACT_RELU; c1.M = M; c1.H = H; c1.W = W;
-            WideConvArgs c2; memset(&c2, 0, sizeof(c2));
-            c2.in = Hh; c2.wgt = b16[b + ".conv2.w"]; c2.out1 = X2; c2.act1 = ACT_NONE; c2.M = M; c2.H = H; c2.W = W;
-            if (!last) { c2.scaleB = f32[nb + ".bn1.scale"]; c2.shiftB = f32[nb + ".bn1.shift"]; c2.out2 = Aa; }
-            if (i == 0) { c2.in2 = X; c2.wgt2 = b16["block0.proj.w"]; c2.shiftA = f32["block0.bias2p"]; }
-            else { c2.shiftA = f32[b + ".conv2.bias"]; c2.res = X2; }
-            switch (filters) {
-            case 64:
-                if (i == 0) { conv_wide_launch<128, 64, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<64, 64, 9, 128, CW_EPI_BF16>(s, c2); }
-                else { conv_wide_launch<64, 64, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<64, 64, 9, 0, CW_EPI_BF16>(s, c2); }
-                break;
-            case 192:
-                if (i == 0) { conv_wide_launch<128, 192, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<192, 192, 9, 128, CW_EPI_BF16>(s, c2); }
-                else { conv_wide_launch<192, 192, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<192, 192, 9, 0, CW_EPI_BF16>(s, c2); }
-                break;
-            default:
-                if (i == 0) { conv_wide_launch<128, 256, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<256, 256, 9, 128, CW_EPI_BF16>(s, c2); }
-                else { conv_wide_launch<256, 256, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<256, 256, 9, 0, CW_EPI_BF16>(s, c2); }
-            }
-        }
-        if (timing) hipEventRecord(e1, s);
+        StemMArgs sm; memset(&sm, 0, sizeof(sm)); sm.in = in; sm.wfrag = reinterpret_cast<const uint4*>(stem_frag); sm.shift = st.g("stem.shift"); sm.out = X;
+        sm.M = M; sm.H = H; sm.W = W;
+        launch_stem_mfma<4, 128, true, false>(s, sm);
+        WideTrunk t; t.stem_c = 128; t.F = filters; t.blocks = blocks; t.M = M; t.H = H; t.W = W;
+        t.x0 = X; t.a0 = X2; t.x = X2; t.a = Aa; t.h = Hh; t.policy_preact = false;
+        gaz::forward_trunk_wide(s, st, timer, timing, t);
         WideConvArgs h; memset(&h, 0, sizeof(h));
-        h.in = X2; h.wgt = b16["heads.conv.w"]; h.shiftA = f32["heads.conv.bias"]; h.M = M; h.H = H; h.W = W;
-        h.feat_p = pfeat; h.feat_v = vfeat; h.p_fs = f32["p.bn0.scale"]; h.p_ft = f32["p.bn0.shift"]; h.v_fs = f32["v.bn0.scale"]; h.v_ft = f32["v.bn0.shift"];
-        if (filters == 64) conv_wide_launch<64, 32, 9, 0, CW_EPI_HEADS>(s, h);
-        else if (filters == 192) conv_wide_launch<192, 32, 9, 0, CW_EPI_HEADS>(s, h);
-        else conv_wide_launch<256, 32, 9, 0, CW_EPI_HEADS>(s, h);
+        h.in = X2; h.wgt = st.w("heads.conv.w"); h.shiftA = st.g("heads.conv.bias"); h.M = M; h.H = H; h.W = W;
+        h.feat_p = pfeat; h.feat_v = vfeat; h.p_fs = st.g("p.bn0.scale"); h.p_ft = st.g("p.bn0.shift"); h.v_fs = st.g("v.bn0.scale"); h.v_ft = st.g("v.bn0.shift");
+        with_width(filters, [&](auto Fc) { conv_wide_launch<decltype(Fc)::value, 32, 9, 0, CW_EPI_HEADS>(s, h); });
     }
     // Dense-1 (both heads) + tail: pfeat / vfeat rows [p0, p0 + n) -> policy / value
     void forward_heads(hipStream_t s, float* policy, float* value, int n, int p0) override {
@@ -830,21 +710,23 @@ struct ResNetEvaluator : Evaluator {
         float* const pd1 = this->pd1 + (size_t)p0 * 128; float* const vd1 = this->vd1 + (size_t)p0 * 128;
         const int F = HW * 8;
         Dense1Args d; d.B = n; d.F = F;
-        d.feat[0] = pfeat; d.w[0] = f32["p.d1.w"]; d.scale[0] = f32["p.d1.scale"]; d.shift[0] = f32["p.d1.shift"]; d.out[0] = pd1;
-        d.feat[1] = vfeat; d.w[1] = f32["v.d1.w"]; d.scale[1] = f32["v.d1.scale"]; d.shift[1] = f32["v.d1.shift"]; d.out[1] = vd1;
+        d.feat[0] = pfeat; d.w[0] = st.g("p.d1.w"); d.scale[0] = st.g("p.d1.scale"); d.shift[0] = st.g("p.d1.shift"); d.out[0] = pd1;
+        d.feat[1] = vfeat; d.w[1] = st.g("v.d1.w"); d.scale[1] = st.g("v.d1.scale"); d.shift[1] = st.g("v.d1.shift"); d.out[1] = vd1;
         hipLaunchKernelGGL(k_dense1_mfma, dim3((n + 31) / 32, 2), dim3(D1_THREADS), (size_t)32 * ((F + 15) / 16 * 16 + 1) * 4 + 4 * 16 * 64 * 4, s, d);
-        TailArgs t; t.p_d1 = pd1; t.v_d1 = vd1; t.p_w2 = f32["p.d2.w"]; t.p_b2 = f32["p.d2.bias"]; t.p_w3 = f32["p.d3.w"];
-        t.p_b3 = f32["p.d3.bias"]; t.v_w2 = f32["v.d2.w"]; t.v_b2 = f32["v.d2.bias"]; t.v_w3 = f32["v.d3.w"]; t.v_b3 = f32["v.d3.bias"];
+        TailArgs t; t.p_d1 = pd1; t.v_d1 = vd1; t.p_w2 = st.g("p.d2.w"); t.p_b2 = st.g("p.d2.bias"); t.p_w3 = st.g("p.d3.w");
+        t.p_b3 = st.g("p.d3.bias"); t.v_w2 = st.g("v.d2.w"); t.v_b2 = st.g("v.d2.bias"); t.v_w3 = st.g("v.d3.w"); t.v_b3 = st.g("v.d3.bias");
         t.policy = policy; t.value = value; t.B = n; t.A = A; t.logits = logits;
         hipLaunchKernelGGL(k_tail, dim3((n + 15) / 16, 2), dim3(128), 0, s, t);
     }
 
     bool ready() const override { return loaded; }
-    void timing_reset() override { for (auto e : tev) hipEventDestroy(e); tev.clear(); n_trunk_launches = 0; }
+    void timing_reset() override { timer.reset(); n_trunk_launches = 0; }
     void timing_get(double* ms, int64_t* launches) override {
-        double t = 0;
-        for (size_t i = 0; i + 1 < tev.size(); i += 2) { float a = 0; hipEventElapsedTime(&a, tev[i], tev[i + 1]); t += a; }
-        *ms = t; *launches = filters != 128 || (fused && trunk) ? (int64_t)(tev.size() / 2) : (int64_t)(tev.size() / 2) * (fused ? 1 : 2) * blocks;
+        *ms = timer.total_ms();
+        // launches of the priced kernel per bracket: one where the bracket is priced as a whole (k_conv_wide per forward, k_trunk); otherwise
+        // one k_resblock3 per block, or two k_conv3x3 per block without the fused blocks
+        const bool per_forward = filters != 128 || (fused && trunk);
+        *launches = timer.brackets() * (per_forward ? 1 : (fused ? 1 : 2) * blocks);
     }
     const char* dominant_kernel(int n, double* flops) override {
         if (filters != 128) {                       // priced per forward: the bracket holds every trunk convolution (2 x blocks launches)
@@ -860,10 +742,10 @@ struct ResNetEvaluator : Evaluator {
             *flops = 2 * conv * blocks;
             if (trunk_whole && trunk_m16 && trunk_mix && perm_big && perm_small) {
                 // MFMA rows x taps actually issued / counted (n HW rows x 9 taps): 128-row tiles run 30 of 36 tile-taps per wave, 96-row tiles 45 of 54
-                const int slots = 2 * n_cus, bb = 128 / HW, sb = 96 / HW, nb = (n / (bb * slots)) * slots, ns = (n - nb * bb + sb - 1) / sb;
-                const int nwg = (n + bb - 1) / bb;
-                const bool mix = nb / slots + 0.78 * ((ns + slots - 1) / slots) < (double)((nwg + slots - 1) / slots);      // make_trunk_plan's choice
-                const double share = n > 0 && mix ? (nb * 128.0 * 30.0 / 36.0 + ns * 96.0 * 45.0 / 54.0) / ((double)n * HW) : 1.0;
+                // the split of a launch of its own over the n positions (trunk_split without fill_big: the figure is measured on one batch of all the games)
+                const TrunkSplit sp = trunk_split(n, HW, n_cus, true, false);
+                const bool mix = sp.mix;
+                const double share = n > 0 && mix ? (sp.n_big * 128.0 * 30.0 / 36.0 + sp.n_small * 96.0 * 45.0 / 54.0) / ((double)n * HW) : 1.0;
                 char buf[640];
                 snprintf(buf, sizeof(buf), "k_trunk_mix (stem + the whole residual trunk + heads' first conv in one launch: blocks x two 3x3 convs 128->128 counted, "
                          "implicit GEMM on v_mfma_f32_16x16x32_bf16, activations resident in LDS; the cells of each board edge form whole MFMA tiles that sit out "
@@ -886,11 +768,11 @@ struct ResNetEvaluator : Evaluator {
 // CIN = 256 / 128-row instantiation (3x3 conv1 and the 1x1 residual projection); narrow layers go through netops.hpp.
 struct GenericEvaluator : Evaluator {
     int H, W, C, A, HW, blocks, F, nmax, logits; bool gomoku;
-    std::map<std::string, float*> f32; std::map<std::string, bf16_t*> b16; std::map<std::string, const gaz_tensor*> by;
-    std::vector<void*> allocs; bool loaded = false; std::string lerr;
+    DeviceStore st;                                 // device tensors by name (net_host.hpp)
+    bool loaded = false;
     bf16_t *X0 = nullptr, *A0 = nullptr, *X = nullptr, *Aa = nullptr, *Hh = nullptr, *Va = nullptr, *PH = nullptr, *VH = nullptr;
     float *pfeat = nullptr, *vfeat = nullptr, *pd1 = nullptr, *vd1 = nullptr, *pd2 = nullptr, *vd2 = nullptr, *plog = nullptr;
-    std::vector<hipEvent_t> tev; int trunk_convs = 0; bool one_launch = false;   // one_launch: the bracket holds ONE kernel (the whole trunk, block 0 included)
+    TrunkTimer timer; int trunk_convs = 0; bool one_launch = false;   // one_launch: the bracket holds ONE kernel (the whole trunk, block 0 included)
     bool fused = true, block0_fused = false, block0_inplace = false; int n_cus = 256, fused_blocks = 0;
     hipStream_t side_stream = 0; hipEvent_t ev_fork = 0, ev_join = 0;     // value head next to the policy head (Gomoku)   // Gomoku: k_block0 + k_resblock3 (one kernel per block)
     bool trunk = true, trunk_m16 = true; bf16_t* trunk_w = nullptr; float* trunk_prm = nullptr;      // ... or k_block0 + ONE k_trunk launch for blocks 1.. (GAZ_TRUNK=0: per block)
@@ -902,51 +784,13 @@ struct GenericEvaluator : Evaluator {
 
     ~GenericEvaluator() override {
         if (side_stream) { hipStreamSynchronize(side_stream); hipEventDestroy(ev_fork); hipEventDestroy(ev_join); hipStreamDestroy(side_stream); }
-        for (void* p : allocs) hipFree(p); for (auto e : tev) hipEventDestroy(e);
     }
-    template <class T> T* dalloc(size_t n) { void* p = nullptr; if (hipMalloc(&p, (n + 64) * sizeof(T)) != hipSuccess) return nullptr; allocs.push_back(p); return (T*)p; }
     bool ready() const override { return loaded; }
-
-    const gaz_tensor* need(const std::string& name, int64_t numel) {
-        auto it = by.find(name);
-        if (it == by.end()) { lerr = "missing tensor " + name; return nullptr; }
-        if (it->second->numel != numel) { lerr = "tensor " + name + ": " + std::to_string(it->second->numel) + " elements, expected " + std::to_string(numel); return nullptr; }
-        return it->second;
-    }
-    bool up(const std::string& name, int64_t numel) {
-        const gaz_tensor* g = need(name, numel); if (!g) return false;
-        float* d = dalloc<float>(numel); if (!d) { lerr = "hipMalloc"; return false; }
-        hipMemcpy(d, g->data, numel * 4, hipMemcpyHostToDevice); f32[name] = d; return true;
-    }
-    bool up_mfma(const std::string& name, int cout, int cin, int ntaps) {
-        const int64_t numel = (int64_t)ntaps * cout * cin;
-        const gaz_tensor* g = need(name, numel); if (!g) return false;
-        std::vector<bf16_t> h(numel);
-        arrange_conv_weights(g->data, cout, cin, h.data(), f2bf_host, ntaps);
-        bf16_t* d = dalloc<bf16_t>(numel); if (!d) { lerr = "hipMalloc"; return false; }
-        hipMemcpy(d, h.data(), numel * 2, hipMemcpyHostToDevice); b16[name] = d; return true;
-    }
-
-    bool up_wide(const std::string& name, int cout, int cin, int ntaps) {      // F != 128: k_conv_wide operand order (arrange_wide_weights)
-        const int64_t numel = (int64_t)ntaps * cout * cin;
-        const gaz_tensor* g = need(name, numel); if (!g) return false;
-        std::vector<bf16_t> h(numel);
-        arrange_wide_weights(g->data, cout, cin, ntaps, h.data(), f2bf_host);
-        bf16_t* d = dalloc<bf16_t>(numel); if (!d) { lerr = "hipMalloc"; return false; }
-        hipMemcpy(d, h.data(), numel * 2, hipMemcpyHostToDevice); b16[name] = d; return true;
-    }
-    bool up_bias2p(const std::string& b, int F_) {  // conv2 and the projection share one accumulator and one fp32 bias b2 + bp
-        std::vector<float> h(F_);
-        const float* b2 = by[b + ".conv2.bias"]->data; const float* bp = by[b + ".proj.bias"]->data;
-        for (int c = 0; c < F_; ++c) h[c] = b2[c] + bp[c];
-        float* d = dalloc<float>(F_); if (!d) { lerr = "hipMalloc"; return false; }
-        hipMemcpy(d, h.data(), F_ * 4, hipMemcpyHostToDevice); f32[b + ".bias2p"] = d; return true;
-    }
 
     // the 29 K = 128 weight slices of k_block0: conv1 low / high input half (9 taps each), conv2 (9), projection low / high
     bool up_block0(const std::string& b) {
-        const gaz_tensor* c1 = need(b + ".conv1.w", 9LL * 128 * 256); const gaz_tensor* c2 = need(b + ".conv2.w", 9LL * 128 * 128);
-        const gaz_tensor* pj = need(b + ".proj.w", 128LL * 256); if (!c1 || !c2 || !pj) return false;
+        const gaz_tensor* c1 = st.need(b + ".conv1.w", 9LL * 128 * 256); const gaz_tensor* c2 = st.need(b + ".conv2.w", 9LL * 128 * 128);
+        const gaz_tensor* pj = st.need(b + ".proj.w", 128LL * 256); if (!c1 || !c2 || !pj) return false;
         const size_t SL = (size_t)128 * 128;                           // bf16 elements per slice
         std::vector<bf16_t> full1(9 * 2 * SL), fullp(2 * SL), h(29 * SL);
         arrange_conv_weights(c1->data, 128, 256, full1.data(), f2bf_host, 9);     // [tap][16 k-steps][2][128][8]: k-steps 0-7 = channels 0-127
@@ -956,45 +800,54 @@ struct GenericEvaluator : Evaluator {
                 memcpy(&h[((size_t)half * 9 + tap) * SL], &full1[((size_t)tap * 2 + half) * SL], SL * sizeof(bf16_t));
         arrange_conv_weights(c2->data, 128, 128, &h[18 * SL], f2bf_host, 9);
         memcpy(&h[27 * SL], &fullp[0], 2 * SL * sizeof(bf16_t));
-        bf16_t* d = dalloc<bf16_t>(h.size()); if (!d) { lerr = "hipMalloc"; return false; }
-        hipMemcpy(d, h.data(), h.size() * 2, hipMemcpyHostToDevice); b16[b + ".w29"] = d; return true;
+        return (st.b16[b + ".w29"] = st.upload(h.data(), h.size())) != nullptr;
     }
-
-    // conv1 / conv2 of a 128 -> 128 block in ONE allocation (conv2 right behind conv1): k_resblock3 walks them as 18 slices
-    bool up_mfma_pair(const std::string& n1, const std::string& n2, int F_) {
-        const int64_t numel = 9LL * F_ * F_;
-        const gaz_tensor* g1 = need(n1, numel); const gaz_tensor* g2 = need(n2, numel); if (!g1 || !g2) return false;
-        std::vector<bf16_t> h(2 * numel);
-        arrange_conv_weights(g1->data, F_, F_, h.data(), f2bf_host, 9);
-        arrange_conv_weights(g2->data, F_, F_, h.data() + numel, f2bf_host, 9);
-        bf16_t* d = dalloc<bf16_t>(2 * numel); if (!d) { lerr = "hipMalloc"; return false; }
-        hipMemcpy(d, h.data(), 2 * numel * 2, hipMemcpyHostToDevice); b16[n1] = d; b16[n2] = d + numel; return true;
+    // block 0 inside the one trunk launch: its 29 slices ahead of the blocks' 18 each (TrunkArgs::w), its parameters as TrunkArgs::prm0
+    bool pack_trunk0() {
+        const size_t S0 = 29 * (size_t)F * F, WB = 18 * (size_t)F * F; const int nb = blocks - 1;
+        std::vector<float> h(1024, 0.0f), b2p;
+        if (!st.bias_sum("block0.conv2.bias", "block0.proj.bias", b2p)) return false;
+        memcpy(&h[0], st.by["block0.bn1.scale"]->data, 256 * 4); memcpy(&h[256], st.by["block0.bn1.shift"]->data, 256 * 4);
+        memcpy(&h[640], st.by["block0.conv1.scale"]->data, 128 * 4); memcpy(&h[768], st.by["block0.conv1.shift"]->data, 128 * 4);
+        memcpy(&h[896], b2p.data(), 128 * 4);
+        trunk_w0 = st.dalloc<bf16_t>(S0 + nb * WB); trunk_prm0 = st.upload(h.data(), h.size());
+        if (!trunk_w0 || !trunk_prm0) return false;
+        hipMemcpy(trunk_w0, st.w("block0.w29"), S0 * 2, hipMemcpyDeviceToDevice);
+        hipMemcpy(trunk_w0 + S0, trunk_w, nb * WB * 2, hipMemcpyDeviceToDevice);
+        return true;
     }
 
     int load(const gaz_tensor* t, int n, hipStream_t s, std::string* err) override {
-        by.clear(); for (int i = 0; i < n; ++i) by[t[i].name] = &t[i];
+        st.set_tensors(t, n);
+        const bool ok = load_tensors();
+        hipStreamSynchronize(s);
+        if (!ok) { *err = st.err; return 1; }
+        loaded = true; return 0;
+    }
+    bool load_tensors() {
+        auto up = [&](const std::string& name, int64_t numel) { return st.up_f32(name, numel); };
         const int SC = gomoku ? 256 : 128, K = gomoku ? 3 : 5;
+        const ConvOrder order = F == 128 ? CONV_MFMA : CONV_WIDE;      // Gomoku: k_conv3x3 / k_resblock3 / k_trunk operands, or k_conv_wide's at F != 128
         bool ok = up("stem.w", (int64_t)K * K * SC * C) && up("stem.scale", SC) && up("stem.shift", SC);
         if (ok && gomoku) {                         // MFMA stem operand (2 planes x 9 taps -> 256 channels), BN scale folded in
-            const std::vector<bf16_t> h = stem_fragments(by["stem.w"]->data, by["stem.scale"]->data, 2, 256);
-            stem_frag = dalloc<bf16_t>(h.size()); ok = stem_frag != nullptr;
-            if (ok) hipMemcpy(stem_frag, h.data(), h.size() * 2, hipMemcpyHostToDevice);
+            const std::vector<bf16_t> h = stem_fragments(st.by["stem.w"]->data, st.by["stem.scale"]->data, 2, 256);
+            ok = (stem_frag = st.upload(h.data(), h.size())) != nullptr;
         }
         for (int i = 0; ok && i < blocks; ++i) {
             const std::string b = "block" + std::to_string(i); const int cin = i == 0 ? SC : F;
             ok = up(b + ".bn1.scale", cin) && up(b + ".bn1.shift", cin) && up(b + ".conv1.scale", F) && up(b + ".conv1.shift", F) && up(b + ".conv2.bias", F);
             if (!ok) break;
-            if (gomoku && F != 128) ok = up_wide(b + ".conv1.w", F, cin, 9) && up_wide(b + ".conv2.w", F, F, 9) && (cin == F || up_wide(b + ".proj.w", F, cin, 1));
-            else if (gomoku && cin == F) ok = up_mfma_pair(b + ".conv1.w", b + ".conv2.w", F);
-            else if (gomoku) ok = up_mfma(b + ".conv1.w", F, cin, 9) && up_mfma(b + ".conv2.w", F, F, 9);
+            if (gomoku && F != 128) ok = st.up_conv(b + ".conv1.w", F, cin, 9, CONV_WIDE) && st.up_conv(b + ".conv2.w", F, F, 9, CONV_WIDE) && (cin == F || st.up_conv(b + ".proj.w", F, cin, 1, CONV_WIDE));
+            else if (gomoku && cin == F) ok = st.up_conv_pair(b + ".conv1.w", b + ".conv2.w", F);
+            else if (gomoku) ok = st.up_conv(b + ".conv1.w", F, cin, 9, CONV_MFMA) && st.up_conv(b + ".conv2.w", F, F, 9, CONV_MFMA);
             else ok = up(b + ".conv1.w", 9LL * F * cin) && up(b + ".conv2.w", 9LL * F * F);
-            if (ok && cin != F && gomoku && F != 128) ok = up(b + ".proj.bias", F) && up_bias2p(b, F);
-            else if (ok && cin != F) ok = (gomoku ? up_mfma(b + ".proj.w", F, cin, 1) : up(b + ".proj.w", (int64_t)F * cin)) && up(b + ".proj.bias", F);
+            if (ok && cin != F && gomoku && F != 128) ok = up(b + ".proj.bias", F) && st.up_bias_sum(b + ".bias2p", b + ".conv2.bias", b + ".proj.bias");
+            else if (ok && cin != F) ok = (gomoku ? st.up_conv(b + ".proj.w", F, cin, 1, CONV_MFMA) : up(b + ".proj.w", (int64_t)F * cin)) && up(b + ".proj.bias", F);
             if (ok && gomoku && cin != F && F == 128 && cin == 256) ok = up_block0(b);
         }
         if (ok && gomoku) {
             ok = up("p.bn0.scale", F) && up("p.bn0.shift", F) && up("v.bn0.scale", F) && up("v.bn0.shift", F) &&
-                 (F == 128 ? up_mfma("p.c1.w", 32, F, 9) && up_mfma("v.c1.w", 32, F, 9) : up_wide("p.c1.w", 32, F, 9) && up_wide("v.c1.w", 32, F, 9)) &&
+                 st.up_conv("p.c1.w", 32, F, 9, order) && st.up_conv("v.c1.w", 32, F, 9, order) &&
                  up("p.c1.scale", 32) && up("p.c1.shift", 32) && up("v.c1.scale", 32) && up("v.c1.shift", 32) &&
                  up("p.c2.w", 9 * 8 * 32) && up("p.c2.bias", 8) && up("p.bn2.scale", HW * 8) && up("p.bn2.shift", HW * 8) &&
                  up("v.c2.w", 4 * 32) && up("v.c2.bias", 4) && up("v.bn2.scale", HW * 4) && up("v.bn2.shift", HW * 4) &&
@@ -1006,35 +859,9 @@ struct GenericEvaluator : Evaluator {
                  up("p.d1.w", HW * 8 * 128) && up("p.d1.bias", 128) && up("p.d2.w", 128 * 64) && up("p.d2.bias", 64) && up("p.d3.w", 64 * A) && up("p.d3.bias", A) &&
                  up("v.d1.w", HW * 4 * 128) && up("v.d1.bias", 128) && up("v.d2.w", 128 * 64) && up("v.d2.bias", 64) && up("v.d3.w", 64) && up("v.d3.bias", 1);
         }
-        if (ok && gomoku && blocks > 1 && F == 128) {     // k_trunk operands of blocks 1..: slices as one array, parameters as [block][5][128]
-            const size_t WB = 18 * (size_t)F * F; const int nb = blocks - 1;
-            trunk_w = dalloc<bf16_t>(nb * WB); trunk_prm = dalloc<float>((size_t)nb * TR_PRM);
-            ok = trunk_w && trunk_prm; if (!ok) lerr = "hipMalloc";
-            for (int i = 1; ok && i < blocks; ++i) {
-                const std::string b = "block" + std::to_string(i);
-                hipMemcpy(trunk_w + (i - 1) * WB, b16[b + ".conv1.w"], WB * 2, hipMemcpyDeviceToDevice);       // conv2 sits right behind conv1 (up_mfma_pair)
-                const char* names[5] = {".bn1.scale", ".bn1.shift", ".conv1.scale", ".conv1.shift", ".conv2.bias"};
-                for (int k = 0; k < 5; ++k) hipMemcpy(trunk_prm + ((size_t)(i - 1) * 5 + k) * 128, f32[b + names[k]], 128 * 4, hipMemcpyDeviceToDevice);
-            }
-            if (ok && b16.count("block0.w29")) {     // block 0 inside the launch: its slices ahead of the blocks', its parameters as TrunkArgs::prm0
-                const size_t S0 = 29 * (size_t)F * F;
-                trunk_w0 = dalloc<bf16_t>(S0 + nb * WB); trunk_prm0 = dalloc<float>(1024);
-                ok = trunk_w0 && trunk_prm0; if (!ok) lerr = "hipMalloc";
-                if (ok) {
-                    hipMemcpy(trunk_w0, b16["block0.w29"], S0 * 2, hipMemcpyDeviceToDevice);
-                    hipMemcpy(trunk_w0 + S0, trunk_w, nb * WB * 2, hipMemcpyDeviceToDevice);
-                    std::vector<float> h(1024, 0.0f);
-                    const float* b2 = by["block0.conv2.bias"]->data; const float* bp = by["block0.proj.bias"]->data;
-                    memcpy(&h[0], by["block0.bn1.scale"]->data, 256 * 4); memcpy(&h[256], by["block0.bn1.shift"]->data, 256 * 4);
-                    memcpy(&h[640], by["block0.conv1.scale"]->data, 128 * 4); memcpy(&h[768], by["block0.conv1.shift"]->data, 128 * 4);
-                    for (int c = 0; c < 128; ++c) h[896 + c] = b2[c] + bp[c];
-                    hipMemcpy(trunk_prm0, h.data(), 1024 * 4, hipMemcpyHostToDevice);
-                }
-            }
-        }
-        hipStreamSynchronize(s);
-        if (!ok) { *err = lerr; return 1; }
-        loaded = true; return 0;
+        // k_trunk operands of blocks 1.., and — where block 0 has its 29 slices — of the launch with block 0 inside
+        if (ok && gomoku && blocks > 1 && F == 128) ok = st.pack_trunk(1, blocks - 1, &trunk_w, &trunk_prm) && (!st.b16.count("block0.w29") || pack_trunk0());
+        return ok;
     }
 
     template <int CIN, int NT> void conv_mfma(hipStream_t s, const bf16_t* in, const bf16_t* w, const float* sA, const float* tA, const bf16_t* res,
@@ -1067,13 +894,13 @@ struct GenericEvaluator : Evaluator {
     }
     void dense(hipStream_t s, const float* in, const std::string& w, const float* sc, const float* sh, float* out, int n, int K, int N, int act) {
         if (gomoku && N >= 32) {                    // fp32 MFMA path
-            DenseMArgs d; d.in = in; d.w = f32[w]; d.scale = sc; d.shift = sh; d.out = out; d.B = n; d.K = K; d.N = N; d.act = act;
+            DenseMArgs d; d.in = in; d.w = st.g(w); d.scale = sc; d.shift = sh; d.out = out; d.B = n; d.K = K; d.N = N; d.act = act;
             hipLaunchKernelGGL(k_dense_mfma, dim3((n + 31) / 32, (N + 127) / 128), dim3(256), (size_t)32 * (DM_KC + 1) * 4, s, d);
             return;
         }
-        hipLaunchKernelGGL(k_dense, dim3((n + 7) / 8), dim3(128), (size_t)8 * K * 4, s, in, f32[w], sc, sh, out, n, K, N, act);
+        hipLaunchKernelGGL(k_dense, dim3((n + 7) / 8), dim3(128), (size_t)8 * K * 4, s, in, st.g(w), sc, sh, out, n, K, N, act);
     }
-    float* g(const std::string& k) { return f32[k]; }
+    float* g(const std::string& k) const { return st.g(k); }
     bool head_features(const float** p, const float** v, int* pr, int* vr) override { *p = pfeat; *v = vfeat; *pr = HW * 8; *vr = HW * 4; return true; }
 
     // ---- the forward pass in two parts (engine.hip: the fused tree + trunk launch replaces forward_trunk by its own launch of the same kernel)
@@ -1083,15 +910,20 @@ struct GenericEvaluator : Evaluator {
         forward_trunk(s, in, n, timing, 0);
         forward_heads(s, policy, value, n, 0);
     }
-    bool fusable() const { return gomoku && F == 128 && fused && blocks > 1 && block0_in_trunk && trunk && trunk_m16 && trunk_w0 && HW <= 256; }
+    // the whole trunk, block 0 included, as ONE k_trunk launch: its operands were packed (pack_trunk0) and no switch asks for less
+    bool one_launch_ok() const { return block0_in_trunk && trunk && trunk_m16 && trunk_w0 && HW <= 256; }
+    void one_launch_args(TrunkArgs& t, const int8_t* in, int n) {
+        memset(&t, 0, sizeof(t));
+        t.prm0 = trunk_prm0; t.xout = Hh; t.w = trunk_w0; t.prm = trunk_prm; t.M = n * HW; t.H = H; t.W = W; t.nblocks = blocks - 1; t.tile_rows = HW;
+        t.planes = in; t.stem_frag = reinterpret_cast<const uint4*>(stem_frag); t.stem_shift = g("stem.shift");
+    }
+    bool fusable() const { return gomoku && F == 128 && fused && blocks > 1 && one_launch_ok(); }
     bool supports_split() const override { return loaded && fusable(); }
     TrunkLaunchPlan fused_plan;
     // the Gomoku trunk launch with the stem inside (trunk.hpp S0): it reads nothing but the int8 planes, so it can share a launch with the tree step
     const void* trunk_plan(const int8_t* in, int n, int p0, const FuseHandoff& h) override {
         if (!supports_split() || p0 != 0) return nullptr;
-        TrunkArgs& t = fused_plan.args; memset(&t, 0, sizeof(t));
-        t.prm0 = trunk_prm0; t.xout = Hh; t.w = trunk_w0; t.prm = trunk_prm; t.M = n * HW; t.H = H; t.W = W; t.nblocks = blocks - 1; t.tile_rows = HW;
-        t.planes = in; t.stem_frag = reinterpret_cast<const uint4*>(stem_frag); t.stem_shift = g("stem.shift");
+        TrunkArgs& t = fused_plan.args; one_launch_args(t, in, n);      // x0 stays null: the stem runs inside the launch
         t.ready = h.ready; t.epoch = h.epoch; t.eval_done = h.eval_done; t.fuse_fault = h.fuse_fault; t.spin_ticks = h.spin_ticks; t.test_fault_mod = h.test_fault_mod;
         t.stamps = h.stamps; t.queue = h.queue;
         fused_plan.nwg = n; fused_plan.mix = 0; fused_plan.lds_bytes = (unsigned)trunk_lds_bytes_s0();
@@ -1103,9 +935,9 @@ struct GenericEvaluator : Evaluator {
         if (!loaded) return;
         if (gomoku && F != 128) { forward_trunk_wide(s, in, n, timing); return; }
         const int M = n * HW, SC = gomoku ? 256 : 128;
-        StemGenArgs st; memset(&st, 0, sizeof(st));
-        st.in = in; st.w = g("stem.w"); st.scale = g("stem.scale"); st.shift = g("stem.shift"); st.scaleB = g("block0.bn1.scale"); st.shiftB = g("block0.bn1.shift");
-        st.out1 = X0; st.out2 = A0; st.M = M; st.H = H; st.W = W; st.CIN = C; st.COUT = SC; st.K = gomoku ? 3 : 5; st.act = gomoku ? NACT_RELU : NACT_GELU;
+        StemGenArgs sg; memset(&sg, 0, sizeof(sg));
+        sg.in = in; sg.w = g("stem.w"); sg.scale = g("stem.scale"); sg.shift = g("stem.shift"); sg.scaleB = g("block0.bn1.scale"); sg.shiftB = g("block0.bn1.shift");
+        sg.out1 = X0; sg.out2 = A0; sg.M = M; sg.H = H; sg.W = W; sg.CIN = C; sg.COUT = SC; sg.K = gomoku ? 3 : 5; sg.act = gomoku ? NACT_RELU : NACT_GELU;
         // at every block count: a one-block net runs k_block0 straight into k_conv_head32 (trunk_w / trunk_w0 are null), so it rounds
         // where the 2+ block launches round (GomokuNet.forward_engine_numerics)
         const bool fuse = gomoku && fused;
@@ -1114,41 +946,36 @@ struct GenericEvaluator : Evaluator {
         // overlaps the four half-image stem passes (trunk launch 2298 -> 2444 us per 2048 positions against the 86 us of k_stem_mfma it
         // replaces: evaluator pass 2702 -> 2762 us, gpurun_out r03 gmk1 / gmk2).  Kept as an opt-in: it is what lets the launch depend on
         // nothing but the int8 planes, i.e. what a fused tree + trunk launch for Gomoku needs.
-        const bool stem_in_trunk = fuse && stem_in_trunk_ok && block0_in_trunk && trunk && trunk_m16 && trunk_w0 && HW <= 256;
+        const bool stem_in_trunk = fuse && stem_in_trunk_ok && one_launch_ok();
         if (stem_in_trunk) {
         } else if (gomoku) {
             StemMArgs sm; memset(&sm, 0, sizeof(sm)); sm.in = in; sm.wfrag = reinterpret_cast<const uint4*>(stem_frag); sm.shift = g("stem.shift");
             sm.out = X0; sm.scaleB = g("block0.bn1.scale"); sm.shiftB = g("block0.bn1.shift"); sm.out2 = A0; sm.M = M; sm.H = H; sm.W = W;
-            const int tiles = (M + 31) / 32;
-            sm.tiles_per_wave = std::max(1, (tiles + 1343) / 2688);
             // round 2: with the fused first block (k_block0) the stem writes only the raw tensor — block 0 pre-activates its operand in
             // LDS — which halves this HBM-bound kernel's writes (236 MB less per forward at 2048 positions).  GAZ_STEM_A0=1: the old way
-            static const bool stem_a0 = getenv("GAZ_STEM_A0") && atoi(getenv("GAZ_STEM_A0")) != 0;
-            block0_inplace = fuse && b16.count("block0.w29") && !stem_a0;
-            if (block0_inplace) hipLaunchKernelGGL((k_stem_mfma<2, 256, false, false>), dim3((tiles + 4 * sm.tiles_per_wave - 1) / (4 * sm.tiles_per_wave)), dim3(256), 0, s, sm);
-            else hipLaunchKernelGGL((k_stem_mfma<2, 256, false, true>), dim3((tiles + 4 * sm.tiles_per_wave - 1) / (4 * sm.tiles_per_wave)), dim3(256), 0, s, sm);
+            static const bool stem_a0 = env_on("GAZ_STEM_A0", false);
+            block0_inplace = fuse && st.b16.count("block0.w29") && !stem_a0;
+            if (block0_inplace) launch_stem_mfma<2, 256, false, false>(s, sm);
+            else launch_stem_mfma<2, 256, false, true>(s, sm);
         } else {
-            hipLaunchKernelGGL(k_stem_generic, dim3((unsigned)(((long)M * (SC / 8) + 255) / 256)), dim3(256), 0, s, st);
+            hipLaunchKernelGGL(k_stem_generic, dim3((unsigned)(((long)M * (SC / 8) + 255) / 256)), dim3(256), 0, s, sg);
         }
-        hipEvent_t e0 = 0, e1 = 0;
-        if (timing) { hipEventCreate(&e0); hipEventCreate(&e1); tev.push_back(e0); tev.push_back(e1); hipEventRecord(e0, s); }
+        timer.begin(s, timing);
         trunk_convs = 0; fused_blocks = 0; one_launch = false;
         bf16_t* cur = X;                            // raw trunk activation after the last block
         for (int i = 0; i < blocks; ++i) {
             const std::string b = "block" + std::to_string(i), nb = "block" + std::to_string(i + 1);
             const bool first = i == 0, last = i + 1 == blocks;
-            if (fuse && first && block0_in_trunk && trunk && trunk_m16 && trunk_w0 && HW <= 256) {      // the whole trunk, block 0 included, in one launch
-                TrunkArgs t; memset(&t, 0, sizeof(t));
-                t.x0 = X0; t.prm0 = trunk_prm0; t.xout = Hh; t.w = trunk_w0; t.prm = trunk_prm; t.M = M; t.H = H; t.W = W; t.nblocks = blocks - 1; t.tile_rows = HW;
-                t.planes = in; t.stem_frag = reinterpret_cast<const uint4*>(stem_frag); t.stem_shift = g("stem.shift");
+            if (fuse && first && one_launch_ok()) {      // the whole trunk, block 0 included, in one launch
+                TrunkArgs t; one_launch_args(t, in, n); t.x0 = X0;
                 if (stem_in_trunk) hipLaunchKernelGGL((k_trunk<2, 2, 8, 2, false, false, false, true, 8, true, 0, true>), dim3(n), dim3(512), trunk_lds_bytes_s0(), s, t);
                 else hipLaunchKernelGGL((k_trunk<2, 2, 8, 2, false, false, false, true, 8, true>), dim3(n), dim3(512), trunk_lds_bytes(256), s, t);
                 cur = Hh; fused_blocks += blocks; block0_fused = true; one_launch = true;
                 break;
             }
-            if (fuse && first && b16.count(b + ".w29")) {          // the 256 -> 128 block with its projection, one kernel (k_block0)
+            if (fuse && first && st.b16.count(b + ".w29")) {          // the 256 -> 128 block with its projection, one kernel (k_block0)
                 Block0Args r; memset(&r, 0, sizeof(r));
-                r.a0 = block0_inplace ? nullptr : A0; r.x0 = X0; r.xout = X; r.w = b16[b + ".w29"]; r.s2 = g(b + ".conv1.scale"); r.t2 = g(b + ".conv1.shift");
+                r.a0 = block0_inplace ? nullptr : A0; r.x0 = X0; r.xout = X; r.w = st.w(b + ".w29"); r.s2 = g(b + ".conv1.scale"); r.t2 = g(b + ".conv1.shift");
                 r.s1 = g(b + ".bn1.scale"); r.t1 = g(b + ".bn1.shift");
                 r.b2 = g(b + ".conv2.bias"); r.bp = g(b + ".proj.bias"); r.M = M; r.H = H; r.W = W;
                 const Rb3Plan plan = rb3_plan(M, H, W, n_cus);
@@ -1172,7 +999,7 @@ struct GenericEvaluator : Evaluator {
             }
             if (fuse && !first) {                   // whole block in one kernel: raw x in, raw x out (pre-activation on load)
                 ResBlockArgs r; memset(&r, 0, sizeof(r));
-                r.xin = cur; r.xout = cur == X ? Hh : X; r.w1 = b16[b + ".conv1.w"]; r.w2 = b16[b + ".conv2.w"];
+                r.xin = cur; r.xout = cur == X ? Hh : X; r.w1 = st.w(b + ".conv1.w"); r.w2 = st.w(b + ".conv2.w");
                 r.s1 = g(b + ".bn1.scale"); r.t1 = g(b + ".bn1.shift"); r.s2 = g(b + ".conv1.scale"); r.t2 = g(b + ".conv1.shift");
                 r.b2 = g(b + ".conv2.bias"); r.M = M; r.H = H; r.W = W;
                 const Rb3Plan plan = rb3_plan(M, H, W, n_cus);
@@ -1186,13 +1013,13 @@ struct GenericEvaluator : Evaluator {
             bf16_t* o2 = sB ? Aa : nullptr;
             if (gomoku) {
                 if (first) {
-                    conv_mfma<256, 9>(s, ain, b16[b + ".conv1.w"], g(b + ".conv1.scale"), g(b + ".conv1.shift"), nullptr, Hh, ACT_RELU, nullptr, nullptr, nullptr, M);
-                    conv_mfma<256, 1>(s, X0, b16[b + ".proj.w"], nullptr, g(b + ".proj.bias"), nullptr, X, ACT_NONE, nullptr, nullptr, nullptr, M);
+                    conv_mfma<256, 9>(s, ain, st.w(b + ".conv1.w"), g(b + ".conv1.scale"), g(b + ".conv1.shift"), nullptr, Hh, ACT_RELU, nullptr, nullptr, nullptr, M);
+                    conv_mfma<256, 1>(s, X0, st.w(b + ".proj.w"), nullptr, g(b + ".proj.bias"), nullptr, X, ACT_NONE, nullptr, nullptr, nullptr, M);
                 } else {
-                    conv_mfma<128, 9>(s, ain, b16[b + ".conv1.w"], g(b + ".conv1.scale"), g(b + ".conv1.shift"), nullptr, Hh, ACT_RELU, nullptr, nullptr, nullptr, M);
+                    conv_mfma<128, 9>(s, ain, st.w(b + ".conv1.w"), g(b + ".conv1.scale"), g(b + ".conv1.shift"), nullptr, Hh, ACT_RELU, nullptr, nullptr, nullptr, M);
                     trunk_convs++;
                 }
-                conv_mfma<128, 9>(s, Hh, b16[b + ".conv2.w"], nullptr, g(b + ".conv2.bias"), X, X, ACT_NONE, sB, tB, o2, M);
+                conv_mfma<128, 9>(s, Hh, st.w(b + ".conv2.w"), nullptr, g(b + ".conv2.bias"), X, X, ACT_NONE, sB, tB, o2, M);
                 trunk_convs++;
             } else {
                 const int cin = first ? SC : F;
@@ -1203,52 +1030,20 @@ struct GenericEvaluator : Evaluator {
                 conv_direct(s, Hh, g(b + ".conv2.w"), F, F, 3, nullptr, g(b + ".conv2.bias"), X, X, NACT_NONE, sB, tB, o2, nullptr, nullptr, nullptr, 0, M);
             }
         }
-        if (timing) hipEventRecord(e1, s);
+        timer.end(s);
         trunk_out = cur; fuse_heads = fuse;
     }
-    // Gomoku at F != 128 (conv_wide.hpp): stem -> X0 (256 channels), a0 = relu(bn1_0(x0)) -> A0; block 0: conv1 256 -> F (A0 -> Hh),
-    // conv2 + the 256 -> F projection of x0 in one accumulator (F = 256: + the identity residual x0) -> X; blocks 1..: conv1 (Aa -> Hh),
-    // conv2 + residual (Hh, X -> X); every conv2 also writes relu(bn(bf16 x)) of the next block, the last one that of the policy head -> Aa.
+    // Gomoku at F != 128 (net_host.hpp forward_trunk_wide): stem -> X0 (256 channels), a0 -> A0, the residual stream in X, operands in Aa / Hh;
+    // the last conv2 also writes relu(p.bn0(bf16 x)) -> Aa for the policy head.
     bool wide_trunk = false;
     void forward_trunk_wide(hipStream_t s, const int8_t* in, int n, bool timing) {
         const int M = n * HW;
-        {
-            StemMArgs sm; memset(&sm, 0, sizeof(sm)); sm.in = in; sm.wfrag = reinterpret_cast<const uint4*>(stem_frag); sm.shift = g("stem.shift");
-            sm.out = X0; sm.M = M; sm.H = H; sm.W = W;
-            const int tiles = (M + 31) / 32;
-            sm.tiles_per_wave = std::max(1, (tiles + 1343) / 2688);
-            hipLaunchKernelGGL((k_stem_mfma<2, 256, false, false>), dim3((tiles + 4 * sm.tiles_per_wave - 1) / (4 * sm.tiles_per_wave)), dim3(256), 0, s, sm);
-            const long n8 = (long)M * 256 / 8;
-            hipLaunchKernelGGL(k_affine_relu, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, X0, g("block0.bn1.scale"), g("block0.bn1.shift"), A0, n8, 256);
-        }
-        hipEvent_t e0 = 0, e1 = 0;
-        if (timing) { hipEventCreate(&e0); hipEventCreate(&e1); tev.push_back(e0); tev.push_back(e1); hipEventRecord(e0, s); }
-        for (int i = 0; i < blocks; ++i) {
-            const std::string b = "block" + std::to_string(i), nb = "block" + std::to_string(i + 1);
-            const bool last = i + 1 == blocks;
-            WideConvArgs c1; memset(&c1, 0, sizeof(c1));
-            c1.in = i == 0 ? A0 : Aa; c1.wgt = b16[b + ".conv1.w"]; c1.scaleA = g(b + ".conv1.scale"); c1.shiftA = g(b + ".conv1.shift");
-            c1.out1 = Hh; c1.act1 = ACT_RELU; c1.M = M; c1.H = H; c1.W = W;
-            WideConvArgs c2; memset(&c2, 0, sizeof(c2));
-            c2.in = Hh; c2.wgt = b16[b + ".conv2.w"]; c2.out1 = X; c2.act1 = ACT_NONE; c2.M = M; c2.H = H; c2.W = W;
-            c2.scaleB = last ? g("p.bn0.scale") : g(nb + ".bn1.scale"); c2.shiftB = last ? g("p.bn0.shift") : g(nb + ".bn1.shift"); c2.out2 = Aa;
-            const bool proj = i == 0 && F != 256;
-            if (proj) { c2.in2 = X0; c2.wgt2 = b16[b + ".proj.w"]; c2.shiftA = g(b + ".bias2p"); }
-            else { c2.shiftA = g(b + ".conv2.bias"); c2.res = i == 0 ? X0 : X; }
-            switch (F) {
-            case 64:
-                if (i == 0) { conv_wide_launch<256, 64, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<64, 64, 9, 256, CW_EPI_BF16>(s, c2); }
-                else { conv_wide_launch<64, 64, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<64, 64, 9, 0, CW_EPI_BF16>(s, c2); }
-                break;
-            case 192:
-                if (i == 0) { conv_wide_launch<256, 192, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<192, 192, 9, 256, CW_EPI_BF16>(s, c2); }
-                else { conv_wide_launch<192, 192, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<192, 192, 9, 0, CW_EPI_BF16>(s, c2); }
-                break;
-            default:                                // 256: block 0 has no projection (256 -> 256)
-                conv_wide_launch<256, 256, 9, 0, CW_EPI_BF16>(s, c1); conv_wide_launch<256, 256, 9, 0, CW_EPI_BF16>(s, c2);
-            }
-        }
-        if (timing) hipEventRecord(e1, s);
+        StemMArgs sm; memset(&sm, 0, sizeof(sm)); sm.in = in; sm.wfrag = reinterpret_cast<const uint4*>(stem_frag); sm.shift = g("stem.shift");
+        sm.out = X0; sm.M = M; sm.H = H; sm.W = W;
+        launch_stem_mfma<2, 256, false, false>(s, sm);
+        WideTrunk t; t.stem_c = 256; t.F = F; t.blocks = blocks; t.M = M; t.H = H; t.W = W;
+        t.x0 = X0; t.a0 = A0; t.x = X; t.a = Aa; t.h = Hh; t.policy_preact = true;
+        gaz::forward_trunk_wide(s, st, timer, timing, t);
         trunk_out = X; fuse_heads = false; wide_trunk = true;
     }
     // heads' first convolutions at F != 128: relu(p.bn0(x)) came with the last conv2 (Aa), relu(v.bn0(x)) -> Va; 3x3 F -> 32 + BN + ReLU
@@ -1258,11 +1053,9 @@ struct GenericEvaluator : Evaluator {
         for (int hd = 0; hd < 2; ++hd) {
             const std::string p = hd == 0 ? "p" : "v";
             WideConvArgs c; memset(&c, 0, sizeof(c));
-            c.in = hd == 0 ? Aa : Va; c.wgt = b16[p + ".c1.w"]; c.scaleA = g(p + ".c1.scale"); c.shiftA = g(p + ".c1.shift");
+            c.in = hd == 0 ? Aa : Va; c.wgt = st.w(p + ".c1.w"); c.scaleA = g(p + ".c1.scale"); c.shiftA = g(p + ".c1.shift");
             c.out1 = hd == 0 ? PH : VH; c.act1 = ACT_RELU; c.M = M; c.H = H; c.W = W;
-            if (F == 64) conv_wide_launch<64, 32, 9, 0, CW_EPI_BF16>(s, c);
-            else if (F == 192) conv_wide_launch<192, 32, 9, 0, CW_EPI_BF16>(s, c);
-            else conv_wide_launch<256, 32, 9, 0, CW_EPI_BF16>(s, c);
+            with_width(F, [&](auto Fc) { conv_wide_launch<decltype(Fc)::value, 32, 9, 0, CW_EPI_BF16>(s, c); });
         }
     }
     // (measured and dropped, round 3: the heads on high-priority streams of their own, forked from / joined to the caller's stream — with two game
@@ -1276,19 +1069,19 @@ struct GenericEvaluator : Evaluator {
                 heads_conv_wide(s, M);
             } else if (fuse) {                      // both heads' BN + ReLU + Conv3x3 128 -> 32 + BN + ReLU from the raw trunk output
                 Head32Args hh; memset(&hh, 0, sizeof(hh));
-                hh.in = cur; hh.wgt[0] = b16["p.c1.w"]; hh.wgt[1] = b16["v.c1.w"];
+                hh.in = cur; hh.wgt[0] = st.w("p.c1.w"); hh.wgt[1] = st.w("v.c1.w");
                 hh.s0[0] = g("p.bn0.scale"); hh.t0[0] = g("p.bn0.shift"); hh.s0[1] = g("v.bn0.scale"); hh.t0[1] = g("v.bn0.shift");
                 hh.s1[0] = g("p.c1.scale"); hh.t1[0] = g("p.c1.shift"); hh.s1[1] = g("v.c1.scale"); hh.t1[1] = g("v.c1.shift");
                 hh.out[0] = PH; hh.out[1] = VH; hh.M = M; hh.H = H; hh.W = W;
                 hipLaunchKernelGGL(k_conv_head32, dim3((M + HC_ROWS - 1) / HC_ROWS, 2), dim3(RB3_THREADS), hc_lds_bytes(), s, hh);
             } else {
                 hipLaunchKernelGGL(k_affine_relu, dim3((unsigned)(((long)M * F / 8 + 255) / 256)), dim3(256), 0, s, cur, g("v.bn0.scale"), g("v.bn0.shift"), Va, (long)M * F / 8, F);
-                conv_mfma32(s, Aa, b16["p.c1.w"], g("p.c1.scale"), g("p.c1.shift"), PH, M);
-                conv_mfma32(s, Va, b16["v.c1.w"], g("v.c1.scale"), g("v.c1.shift"), VH, M);
+                conv_mfma32(s, Aa, st.w("p.c1.w"), g("p.c1.scale"), g("p.c1.shift"), PH, M);
+                conv_mfma32(s, Va, st.w("v.c1.w"), g("v.c1.scale"), g("v.c1.shift"), VH, M);
             }
             // the two heads are independent chains of small kernels (policy ~0.22 ms, value ~0.08 ms per 2048 positions): the value head
             // runs on a side stream next to the policy head and joins before the softmax (round 2; GAZ_HEADS_2STREAMS=0 -> one stream)
-            static const bool two = !(getenv("GAZ_HEADS_2STREAMS") && atoi(getenv("GAZ_HEADS_2STREAMS")) == 0);
+            static const bool two = env_on("GAZ_HEADS_2STREAMS", true);
             hipStream_t sv = s;
             if (two) {
                 if (!side_stream) { hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking); hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming); hipEventCreateWithFlags(&ev_join, hipEventDisableTiming); }
@@ -1320,13 +1113,14 @@ struct GenericEvaluator : Evaluator {
         }
         hipLaunchKernelGGL(k_softmax_rows, dim3(n), dim3(64), 0, s, plog, policy, n, A, logits);
     }
-    void timing_reset() override { for (auto e : tev) hipEventDestroy(e); tev.clear(); }
+    void timing_reset() override { timer.reset(); }
     void timing_get(double* ms, int64_t* launches) override {
-        double t = 0;
-        for (size_t i = 0; i + 1 < tev.size(); i += 2) { float a = 0; hipEventElapsedTime(&a, tev[i], tev[i + 1]); t += a; }
-        // launches of the dominant kernel inside the bracket: fused blocks (k_resblock3) or 128 -> 128 convs; block 0 of the
-        // Gomoku net (256 -> 128 + projection) rides in the same bracket and is counted as one more launch-equivalent
-        *ms = t; *launches = (int64_t)(tev.size() / 2) * (one_launch || wide_trunk ? 1 : (fused_blocks > 0 ? fused_blocks + (block0_fused ? 0 : 1) : (trunk_convs > 0 ? trunk_convs : 1)));
+        *ms = timer.total_ms();
+        // launches of the dominant kernel inside one bracket (counts of the last forward pass): one where the bracket is priced as a whole (the
+        // one-launch trunk, k_conv_wide per forward); else the fused blocks (k_resblock3), where an unfused block 0 (256 -> 128 + projection) rides
+        // in the same bracket as one more launch-equivalent; else the 128 -> 128 convolutions, at least one
+        const int per_bracket = one_launch || wide_trunk ? 1 : fused_blocks > 0 ? fused_blocks + (block0_fused ? 0 : 1) : std::max(trunk_convs, 1);
+        *launches = timer.brackets() * per_bracket;
     }
     const char* dominant_kernel(int n, double* flops) override {
         if (gomoku && F != 128) {                   // priced per forward, as the F = 128 one-launch trunk
@@ -1346,7 +1140,7 @@ struct GenericEvaluator : Evaluator {
         }
         const bool fz = fused && blocks > 1;
         *flops = fz ? 2 * conv : conv;
-        if (fz && trunk && trunk_w && trunk_m16 && block0_in_trunk && trunk_w0 && HW <= 256) {
+        if (fz && trunk_w && one_launch_ok()) {
             // priced per LAUNCH: the one kernel runs block 0 (3x3 256->128 = two 128-channel convolutions, 3x3 128->128, the 1x1
             // projection 256->128) and blocks - 1 regular blocks of two 3x3 convolutions each
             *flops = (2.0 * (blocks - 1) + 3.0) * conv + 2.0 * (double)n * HW * 256.0 * 128.0;
@@ -1367,17 +1161,17 @@ static Evaluator* make_generic_evaluator(const gaz_engine_config& cfg, int H, in
     GenericEvaluator* e = new GenericEvaluator();
     e->H = H; e->W = W; e->C = C; e->A = A; e->HW = H * W; e->blocks = cfg.net_blocks; e->F = gomoku ? cfg.net_filters : 64; e->nmax = cfg.n_games;
     e->logits = cfg.policy_is_logits; e->gomoku = gomoku;
-    e->fused = !(getenv("GAZ_FUSED") && atoi(getenv("GAZ_FUSED")) == 0);
-    e->trunk = !(getenv("GAZ_TRUNK") && atoi(getenv("GAZ_TRUNK")) == 0);
-    e->trunk_m16 = !(getenv("GAZ_TRUNK_M16") && atoi(getenv("GAZ_TRUNK_M16")) == 0);
-    e->block0_in_trunk = !(getenv("GAZ_BLOCK0_IN_TRUNK") && atoi(getenv("GAZ_BLOCK0_IN_TRUNK")) == 0);
-    e->stem_in_trunk_ok = getenv("GAZ_STEM_IN_TRUNK") && atoi(getenv("GAZ_STEM_IN_TRUNK")) != 0;
+    e->fused = env_on("GAZ_FUSED", true);
+    e->trunk = env_on("GAZ_TRUNK", true);
+    e->trunk_m16 = env_on("GAZ_TRUNK_M16", true);
+    e->block0_in_trunk = env_on("GAZ_BLOCK0_IN_TRUNK", true);
+    e->stem_in_trunk_ok = env_on("GAZ_STEM_IN_TRUNK", false);
     { hipDeviceProp_t pr; int dev = 0; hipGetDevice(&dev); if (hipGetDeviceProperties(&pr, dev) == hipSuccess) e->n_cus = pr.multiProcessorCount; }
     const size_t M = (size_t)cfg.n_games * e->HW, SC = gomoku ? 256 : 128, F = e->F, n = cfg.n_games;
-    e->X0 = e->dalloc<bf16_t>(M * SC); e->A0 = e->dalloc<bf16_t>(M * SC); e->X = e->dalloc<bf16_t>(M * F); e->Aa = e->dalloc<bf16_t>(M * F);
-    e->Hh = e->dalloc<bf16_t>(M * F); e->Va = e->dalloc<bf16_t>(M * F); e->PH = e->dalloc<bf16_t>(M * 32); e->VH = e->dalloc<bf16_t>(M * 32);
-    e->pfeat = e->dalloc<float>(n * e->HW * 8); e->vfeat = e->dalloc<float>(n * e->HW * 8); e->pd1 = e->dalloc<float>(n * 512); e->vd1 = e->dalloc<float>(n * 256);
-    e->pd2 = e->dalloc<float>(n * 128); e->vd2 = e->dalloc<float>(n * 128); e->plog = e->dalloc<float>(n * 256);
+    e->X0 = e->st.dalloc<bf16_t>(M * SC); e->A0 = e->st.dalloc<bf16_t>(M * SC); e->X = e->st.dalloc<bf16_t>(M * F); e->Aa = e->st.dalloc<bf16_t>(M * F);
+    e->Hh = e->st.dalloc<bf16_t>(M * F); e->Va = e->st.dalloc<bf16_t>(M * F); e->PH = e->st.dalloc<bf16_t>(M * 32); e->VH = e->st.dalloc<bf16_t>(M * 32);
+    e->pfeat = e->st.dalloc<float>(n * e->HW * 8); e->vfeat = e->st.dalloc<float>(n * e->HW * 8); e->pd1 = e->st.dalloc<float>(n * 512); e->vd1 = e->st.dalloc<float>(n * 256);
+    e->pd2 = e->st.dalloc<float>(n * 128); e->vd2 = e->st.dalloc<float>(n * 128); e->plog = e->st.dalloc<float>(n * 256);
     if (!e->X0 || !e->A0 || !e->X || !e->Aa || !e->Hh || !e->Va || !e->PH || !e->VH || !e->pfeat || !e->vfeat || !e->pd1 || !e->vd1 || !e->pd2 || !e->vd2 || !e->plog) {
         *err = "hipMalloc failed"; delete e; return nullptr;
     }
@@ -1407,15 +1201,15 @@ Evaluator* make_resnet_evaluator(const gaz_engine_config& cfg, int H, int W, int
     e->H = H; e->W = W; e->C = C; e->A = A; e->HW = H * W; e->blocks = cfg.net_blocks; e->filters = cfg.net_filters; e->nmax = cfg.n_games;
     e->logits = cfg.policy_is_logits;
     const size_t M = (size_t)cfg.n_games * e->HW, CW = std::max(cfg.net_filters, 128);     // activation buffers: the stem's 128 channels or F
-    e->X2 = e->dalloc<bf16_t>(M * CW + 1024); e->fused = !(getenv("GAZ_FUSED") && atoi(getenv("GAZ_FUSED")) == 0);
-    e->trunk = !(getenv("GAZ_TRUNK") && atoi(getenv("GAZ_TRUNK")) == 0);
-    e->trunk_whole = !(getenv("GAZ_TRUNK_WHOLE") && atoi(getenv("GAZ_TRUNK_WHOLE")) == 0);
-    e->trunk_mix = !(getenv("GAZ_TRUNK_MIX") && atoi(getenv("GAZ_TRUNK_MIX")) == 0);
-    e->trunk_m16 = !(getenv("GAZ_TRUNK_M16") && atoi(getenv("GAZ_TRUNK_M16")) == 0);
+    e->X2 = e->st.dalloc<bf16_t>(M * CW + 1024); e->fused = env_on("GAZ_FUSED", true);
+    e->trunk = env_on("GAZ_TRUNK", true);
+    e->trunk_whole = env_on("GAZ_TRUNK_WHOLE", true);
+    e->trunk_mix = env_on("GAZ_TRUNK_MIX", true);
+    e->trunk_m16 = env_on("GAZ_TRUNK_M16", true);
     { hipDeviceProp_t pr; int dev = 0; hipGetDevice(&dev); if (hipGetDeviceProperties(&pr, dev) == hipSuccess) e->n_cus = pr.multiProcessorCount; }
-    e->X = e->dalloc<bf16_t>(M * CW + 1024); e->Aa = e->dalloc<bf16_t>(M * CW + 1024); e->Hh = e->dalloc<bf16_t>(M * CW + 1024);
-    e->pfeat = e->dalloc<float>((size_t)cfg.n_games * e->HW * 8); e->vfeat = e->dalloc<float>((size_t)cfg.n_games * e->HW * 8);
-    e->pd1 = e->dalloc<float>((size_t)cfg.n_games * 128); e->vd1 = e->dalloc<float>((size_t)cfg.n_games * 128);
+    e->X = e->st.dalloc<bf16_t>(M * CW + 1024); e->Aa = e->st.dalloc<bf16_t>(M * CW + 1024); e->Hh = e->st.dalloc<bf16_t>(M * CW + 1024);
+    e->pfeat = e->st.dalloc<float>((size_t)cfg.n_games * e->HW * 8); e->vfeat = e->st.dalloc<float>((size_t)cfg.n_games * e->HW * 8);
+    e->pd1 = e->st.dalloc<float>((size_t)cfg.n_games * 128); e->vd1 = e->st.dalloc<float>((size_t)cfg.n_games * 128);
     if (!e->X || !e->Aa || !e->Hh || !e->pfeat || !e->vfeat || !e->pd1 || !e->vd1) { *err = "hipMalloc failed"; delete e; return nullptr; }
     // dynamic LDS above 64 KB needs the attribute
     hipFuncSetAttribute((const void*)k_resblock, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1524,16 +1318,22 @@ __global__ __launch_bounds__(512, 1) void k_wave_trunk_gmk(DevParams<GGMK> E, in
     trunk_tile<2, 2, 8, false, false, false, true, 8, true, 0, true>(a, (long)bid * a.tile_rows, a.tile_rows, nullptr, 0);
 }
 
-bool launch_wave_trunk_gmk(hipStream_t s, const void* dev_params, int g0, int g1, const void* plan) {
+// host: one fused launch = the tree blocks of games [g0, g1) ahead of the plan's trunk workgroups.  A tree block steps queue_gpb games with the
+// completion queue (tree_role), else the games its teams hold (games_per_block).  false = no plan or no tree parameters: not launched.
+template <class GP> static bool wave_trunk_launch(void (*kernel)(DevParams<GP>, int, int, int, TrunkArgs), int threads, int games_per_block, hipStream_t s,
+                                                  const void* dev_params, int g0, int g1, const void* plan) {
     if (!plan || !dev_params) return false;
     const TrunkLaunchPlan& P = *static_cast<const TrunkLaunchPlan*>(plan);
-    const DevParams<GGMK>& E = *static_cast<const DevParams<GGMK>*>(dev_params);
-    const int per_block = E.done_queue ? E.queue_gpb : 8;
-    const int n_tree = (g1 - g0 + per_block - 1) / per_block;
+    const DevParams<GP>& E = *static_cast<const DevParams<GP>*>(dev_params);
+    const int per_block = E.done_queue ? E.queue_gpb : games_per_block, n_tree = (g1 - g0 + per_block - 1) / per_block;
+    hipLaunchKernelGGL(kernel, dim3(n_tree + P.nwg), dim3(threads), P.lds_bytes, s, E, g0, g1, n_tree, P.args);
+    return true;
+}
+
+bool launch_wave_trunk_gmk(hipStream_t s, const void* dev_params, int g0, int g1, const void* plan) {
     static bool attr = false;
     if (!attr) { hipFuncSetAttribute((const void*)k_wave_trunk_gmk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes_s0()); attr = true; }
-    hipLaunchKernelGGL(k_wave_trunk_gmk, dim3(n_tree + P.nwg), dim3(512), P.lds_bytes, s, E, g0, g1, n_tree, P.args);
-    return true;
+    return wave_trunk_launch<GGMK>(k_wave_trunk_gmk, 512, 8, s, dev_params, g0, g1, plan);
 }
 
 // The Gumbel search (MCTS_Gumbel.py:562-679) in the same launch shape.  TEAMS: four games per wavefront (16 games per tree block, as the PUCT
@@ -1544,31 +1344,18 @@ template <bool MIX, bool SKIP, bool TEAMS> __global__ __launch_bounds__(TR_THREA
 }
 
 bool launch_wave_trunk_c4_gumbel(hipStream_t s, const void* dev_params, int g0, int g1, const void* plan) {
-    if (!plan || !dev_params) return false;
-    const TrunkLaunchPlan& P = *static_cast<const TrunkLaunchPlan*>(plan);
-    const DevParams<Game<GAME_C4>>& E = *static_cast<const DevParams<Game<GAME_C4>>*>(dev_params);
-    static const bool teams = !(getenv("GAZ_FUSE_GUMBEL_TEAMS") && atoi(getenv("GAZ_FUSE_GUMBEL_TEAMS")) == 0);
-    const int per_block = E.done_queue ? E.queue_gpb : (TR_THREADS / WAVE) * (teams ? WAVE / GP4::TEAM : 1);
-    const int n_tree = (g1 - g0 + per_block - 1) / per_block;
-    const bool skip = P.args.perm && P.args.perm_small;
-    if (!P.mix || !skip) return false;              // only the headline trunk variant is built for this launch
-    if (teams) hipLaunchKernelGGL((k_wave_trunk_gumbel<true, true, true>), dim3(n_tree + P.nwg), dim3(TR_THREADS), P.lds_bytes, s, E, g0, g1, n_tree, P.args);
-    else hipLaunchKernelGGL((k_wave_trunk_gumbel<true, true, false>), dim3(n_tree + P.nwg), dim3(TR_THREADS), P.lds_bytes, s, E, g0, g1, n_tree, P.args);
-    return true;
+    static const bool teams = env_on("GAZ_FUSE_GUMBEL_TEAMS", true);
+    const TrunkLaunchPlan* P = static_cast<const TrunkLaunchPlan*>(plan);
+    if (!P || !P->mix || !(P->args.perm && P->args.perm_small)) return false;      // only the headline trunk variant is built for this launch
+    return wave_trunk_launch<Game<GAME_C4>>(teams ? k_wave_trunk_gumbel<true, true, true> : k_wave_trunk_gumbel<true, true, false>, TR_THREADS,
+                                            (TR_THREADS / WAVE) * (teams ? WAVE / GP4::TEAM : 1), s, dev_params, g0, g1, plan);
 }
 
 bool launch_wave_trunk_c4(hipStream_t s, const void* dev_params, int g0, int g1, const void* plan) {
-    if (!plan || !dev_params) return false;
-    const TrunkLaunchPlan& P = *static_cast<const TrunkLaunchPlan*>(plan);
-    const DevParams<GP4>& E = *static_cast<const DevParams<GP4>*>(dev_params);
-    constexpr int GAMES_PER_BLOCK = (TR_THREADS / WAVE) * (WAVE / GP4::TEAM);
-    const int per_block = E.done_queue ? E.queue_gpb : GAMES_PER_BLOCK;
-    const int n_tree = (g1 - g0 + per_block - 1) / per_block;
-    const bool skip = P.args.perm && P.args.perm_small;       // both tile shapes carry an edge-tile permutation (checked by the evaluator)
-    if (P.mix && skip) hipLaunchKernelGGL((k_wave_trunk<true, true>), dim3(n_tree + P.nwg), dim3(TR_THREADS), P.lds_bytes, s, E, g0, g1, n_tree, P.args);
-    else if (P.mix) hipLaunchKernelGGL((k_wave_trunk<true, false>), dim3(n_tree + P.nwg), dim3(TR_THREADS), P.lds_bytes, s, E, g0, g1, n_tree, P.args);
-    else hipLaunchKernelGGL((k_wave_trunk<false, false>), dim3(n_tree + P.nwg), dim3(TR_THREADS), P.lds_bytes, s, E, g0, g1, n_tree, P.args);
-    return true;
+    const TrunkLaunchPlan* P = static_cast<const TrunkLaunchPlan*>(plan);
+    const bool mix = P && P->mix, skip = P && P->args.perm && P->args.perm_small;      // skip: both tile shapes carry an edge-tile permutation (checked by the evaluator)
+    return wave_trunk_launch<GP4>(mix && skip ? k_wave_trunk<true, true> : mix ? k_wave_trunk<true, false> : k_wave_trunk<false, false>, TR_THREADS,
+                                  (TR_THREADS / WAVE) * (WAVE / GP4::TEAM), s, dev_params, g0, g1, plan);
 }
 
 }  // namespace gaz

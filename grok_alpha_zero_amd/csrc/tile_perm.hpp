@@ -170,4 +170,29 @@ inline TileLayout tile_layout(int H, int W, int boards, int rows, int wave_rows,
     return best;
 }
 
+// How the whole-trunk launch of n boards of HW cells is cut into workgroup tiles (trunk.hpp k_trunk / k_trunk_mix).  A 128-row tile holds
+// 128 / HW whole boards, a 96-row tile 96 / HW; 2 x n_cus tiles run at a time (one round).  One tile shape leaves the last round ragged, so the
+// mixed launch gives whole rounds to 128-row tiles (n_big) and the rest of the boards to 96-row tiles (n_small); it is taken when its rounds cost
+// less, a round of 96-row tiles priced at 0.78 of a 128-row round: the 96-row tile issues three quarters of the MFMAs, and the phase stamps show
+// 137 us against 174-176 us.  n_big / n_small are that split whether or not it is taken (mix); nwg is the resulting grid.
+// fill_big: every board that fits goes into a 128-row tile, and the launch is mixed whatever the rounds cost.  Only a fused launch that shares the
+// chip with other game groups asks for it: their tiles fill its ragged last round, and a board costs less in the larger tile.  A separate launch
+// has the chip to itself, and the figure bench.py prices is measured on one batch of all the games: forward_trunk and dominant_kernel pass false.
+// No mixed launch where the 96-row tile holds no board or as many as the 128-row tile, or where a tile would hold more than the three boards
+// the kernels keep track of (Gomoku: 96 / 225 = 0; TicTacToe: 14 boards per tile).
+struct TrunkSplit { int n_big, n_small, nwg; bool mix; };
+inline TrunkSplit trunk_split(int n, int HW, int n_cus, bool mix_allowed, bool fill_big) {
+    TrunkSplit s{0, 0, 0, false};
+    const int bb = HW > 0 ? 128 / HW : 0, sb = HW > 0 ? 96 / HW : 0, slots = 2 * n_cus;
+    if (bb < 1 || slots < 1) return s;               // no whole board fits a tile: no whole-trunk launch
+    s.nwg = (n + bb - 1) / bb;
+    if (!mix_allowed || sb < 1 || sb >= bb || bb > 3) return s;
+    s.n_big = (n / (bb * slots)) * slots; s.n_small = (n - s.n_big * bb + sb - 1) / sb;
+    const double cost_mix = s.n_big / slots + 0.78 * ((s.n_small + slots - 1) / slots), cost_big = (s.nwg + slots - 1) / slots;
+    if (fill_big) { s.n_big = n / bb; s.n_small = (n - s.n_big * bb + sb - 1) / sb; }
+    s.mix = fill_big || cost_mix < cost_big;
+    if (s.mix) s.nwg = s.n_big + s.n_small;
+    return s;
+}
+
 }  // namespace gaz

@@ -23,3 +23,9 @@ extern "C" int gaz_test_tile_perm(int H, int W, int boards, int rows, int wave_r
     if (clashes_out) *clashes_out = L.clashes;
     return (int)L.perm.size();
 }
+
+// test hook (tests/test_trunk_split.py): how the whole-trunk launch of a batch is cut into 128-row and 96-row tiles
+extern "C" void gaz_test_trunk_split(int n, int HW, int n_cus, int mix_allowed, int fill_big, int* n_big, int* n_small, int* nwg, int* mix) {
+    const gaz::TrunkSplit s = gaz::trunk_split(n, HW, n_cus, mix_allowed != 0, fill_big != 0);
+    *n_big = s.n_big; *n_small = s.n_small; *nwg = s.nwg; *mix = s.mix ? 1 : 0;
+}
