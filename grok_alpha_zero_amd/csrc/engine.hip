@@ -30,6 +30,39 @@ template <class G> GAZ_DEV void wave_body(const DevParams<G>& E, int g0, int g1)
 template <class G> GAZ_KERNEL k_wave(DevParams<G> E, int g0, int g1) { wave_body<G>(E, g0, g1); }
 template <class G> GAZ_KERNEL_TEAMS k_wave_teams(DevParams<G> E, int g0, int g1) { wave_body<G>(E, g0, g1); }
 
+// leaf-batched PUCT search (gaz_engine_config::leaf_batch > 1): the same launch shapes, the K-leaf step of puct_core.hpp
+template <class G> GAZ_DEV void wave_body_lb(const DevParams<G>& E, const LeafBatch& B, int g0, int g1) {
+    constexpr int PER = WAVE / G::TEAM;
+    GAZ_SHARED Scratch<G> S[PER];
+    GAZ_SHARED PuctLocal<G> L[PER];
+    const int t = team_in_wave<G>();
+    const int g = g0 + block_id() * PER + t;
+    if (g < g1) game_step_lb<G>(E, B, g, S[t], L[t]);
+}
+template <class G> GAZ_KERNEL_TEAMS k_wave_lb(DevParams<G> E, LeafBatch B, int g0, int g1) { wave_body_lb<G>(E, B, g0, g1); }
+
+// gaz_engine_read_batch with leaf batching: pending[g * K + j] = the request in row g * K + j (0 = none)
+template <class G> GAZ_KERNEL k_gather_pending_lb(DevParams<G> E, int K, int32_t* out) {
+    const int g = block_id();
+    if (g >= E.n_games) return;
+    const GameState<G>& gs = E.games[g];
+    const int n = gs.pend_kind == PEND_ROOT ? 1 : (gs.pend_kind == PEND_EXPAND ? gs.pend_depth : 0);
+    for (int j = lane_id(); j < K; j += WAVE) out[(size_t)g * K + j] = j < n ? gs.pend_kind : PEND_NONE;
+}
+
+// gaz_engine_get_stats [15] with leaf batching: the reserved counts (NodeHdr::pad[0]) of every node record the trees have allocated, summed —
+// 0 whenever no search is between two launches of a move (a move never ends with a leaf in flight)
+template <class G> GAZ_KERNEL k_count_reserved(DevParams<G> E, unsigned long long* out) {
+    const int g = block_id();
+    if (g >= E.n_games) return;
+    unsigned long long sum = 0;
+    for (int t = 0; t < 2; ++t) {
+        const int n = (int)E.trees[(size_t)g * 2 + t].n_nodes;
+        for (int i = lane_id(); i < n; i += WAVE) sum += node_at(E, g, t, i).hdr()->pad[0];
+    }
+    if (sum) atomic_add(out, sum);
+}
+
 template <class G> GAZ_DEV void wave_body_gumbel(const DevParams<G>& E, int g0, int g1) {
     constexpr int PER = WAVE / G::TEAM;
     GAZ_SHARED Scratch<G> S[PER];
@@ -283,6 +316,7 @@ struct gaz_engine {
     virtual int wave_end() = 0;
     virtual int batch_ptrs(void**, void**, void**) = 0;
     virtual int read_batch(int8_t*, int32_t*) = 0;
+    virtual int batch_rows(int32_t*) = 0;
     virtual int write_outputs(const float*, const float*) = 0;
     virtual int evaluate(const int8_t*, int, float*, float*, int, double*) = 0;
     virtual int record_layout(gaz_record_layout*) = 0;
@@ -327,6 +361,8 @@ template <class G> struct EngineT : gaz_engine {
     int64_t n_waves_total = 0, n_waves_timed = 0;
     static constexpr int TIMING_STRIDE = 8;
     std::vector<void*> allocs;
+    // leaf-batched search: K leaves per game and wave (1 = off), rows = n_games * K rows in the evaluator batch, descriptors of the leaves in flight
+    int lbk = 1; size_t rows = 0; LeafBatch LB{1, nullptr};
 
     template <class T> int dalloc(T** p, size_t n) {
         void* q = nullptr;
@@ -372,6 +408,7 @@ template <class G> struct EngineT : gaz_engine {
         E.node_bytes = gumbel ? gumbel_node_bytes<G>() : NodeLayout<G>::SIZE;
         // re-root compaction: needed where a whole-game arena does not fit (Gomoku: 4.2 KB records); 0 = auto
         E.compact = gumbel ? 0 : (cfg.compact_trees == 0 ? (G::ID == GAME_GMK ? 1 : 0) : (cfg.compact_trees > 0 ? 1 : 0));
+        lbk = cfg.leaf_batch > 1 ? cfg.leaf_batch : 1; rows = (size_t)n * lbk;
         E.n_games = n; n_eff = n; E.run_iterations = cfg.run_iterations; E.max_actions = cfg.max_actions;
         if (cfg.max_actions > G::MAXT || cfg.max_actions <= 0) return fail("max_actions out of range for this game");
         E.explore_first = cfg.num_explore_actions_first; E.explore_second = cfg.num_explore_actions_second;
@@ -380,12 +417,12 @@ template <class G> struct EngineT : gaz_engine {
         if (npt <= 0 && gumbel) npt = 2 * ((cfg.move_time_limit > 0.0 && 3 * G::A > cfg.run_iterations ? 3 * G::A : cfg.run_iterations) + cfg.gumbel_m) + 3 * G::A + 64;   // fresh tree every move
         if (npt <= 0 && E.compact) {   // per half: kept subtree + one run; generous bound, ERR_ARENA_FULL if a game exceeds it
             const int its = cfg.run_iterations < 3 * G::A ? 3 * G::A : cfg.run_iterations;
-            npt = 4 * its + 3 * G::A + 64;
+            npt = 4 * its + 3 * G::A + 64 + (lbk > 1 ? lbk : 0);
         }
         if (npt <= 0) {   // a tree lives for the whole game and gains <= 1 record per simulation of its own moves
             const int own_moves = (cfg.max_actions + 1) / 2 + 1;
             int its = cfg.run_iterations < 3 * G::A ? 3 * G::A : cfg.run_iterations;
-            npt = own_moves * (its + 2) + 64;
+            npt = own_moves * (its + 2) + 64 + (lbk > 1 ? lbk : 0);
         }
         E.nodes_per_tree = npt;
         E.ring_cap = cfg.ring_capacity; E.single_tree = cfg.single_tree;
@@ -424,14 +461,15 @@ template <class G> struct EngineT : gaz_engine {
         allocs.push_back(a); E.arena = (uint8_t*)a;
         if (dalloc(&E.trees, (size_t)n * 2)) return 1;
         if (dalloc(&E.games, (size_t)n)) return 1;
-        if (dalloc(&E.paths, (size_t)n * PathCap<G>::V)) return 1;
+        if (dalloc(&E.paths, rows * PathCap<G>::V)) return 1;
+        if (lbk > 1) { LB.K = lbk; if (dalloc(&LB.pend, rows)) return 1; }
         if (gumbel) { GumbelState<G>* gp = nullptr; if (dalloc(&gp, (size_t)n)) return 1; E.gstate = gp; }
         if (dalloc(&E.recs, (size_t)n * RL::SIZE)) return 1;
         if (dalloc(&E.ring, (size_t)(cfg.ring_capacity > 0 ? cfg.ring_capacity : 1) * RL::SIZE)) return 1;
         if (dalloc(&E.ring_head, 4)) return 1;
-        if (dalloc(&E.nn_in, (size_t)n * G::HW * G::C + 64)) return 1;
-        if (dalloc(&E.nn_policy, (size_t)n * G::A + 64)) return 1;
-        if (dalloc(&E.nn_value, (size_t)n + 64)) return 1;
+        if (dalloc(&E.nn_in, rows * G::HW * G::C + 64)) return 1;
+        if (dalloc(&E.nn_policy, rows * G::A + 64)) return 1;
+        if (dalloc(&E.nn_value, rows + 64)) return 1;
         if (cfg.eval_cache_log2 < 0 || cfg.eval_cache_log2 > 28) return fail("eval_cache_log2 out of range (0 = off, at most 28)");
         if (cfg.eval_cache_log2 > 0) {
             const size_t slots = (size_t)1 << cfg.eval_cache_log2;
@@ -450,9 +488,10 @@ template <class G> struct EngineT : gaz_engine {
         if (dalloc(&E.error, 4)) return 1;
         if (dalloc(&dN, (size_t)n * G::A) || dalloc(&dW, (size_t)n * G::A) || dalloc(&dP, (size_t)n * G::A) ||
             dalloc(&dPol, (size_t)n * G::A) || dalloc(&dRV, n) || dalloc(&dQ, n) || dalloc(&dChosen, n) ||
-            dalloc(&dPhase, n) || dalloc(&dPending, n) || dalloc(&dCount, 16) || dalloc(&dMoves, (size_t)n + G::MAXT) || dalloc(&dSlots, n)) return 1;
+            dalloc(&dPhase, n) || dalloc(&dPending, rows) || dalloc(&dCount, 16) || dalloc(&dMoves, (size_t)n + G::MAXT) || dalloc(&dSlots, n)) return 1;
         std::string e2;
-        eval = make_evaluator(cfg, G::H, G::W, G::C, G::A, &e2);
+        gaz_engine_config ecfg = cfg; ecfg.n_games = (int32_t)rows;           // the evaluator's buffers hold every row of the batch
+        eval = make_evaluator(ecfg, G::H, G::W, G::C, G::A, &e2);
         if (!eval && cfg.evaluator != GAZ_EVAL_EXTERNAL) return fail("evaluator: " + e2);
         GAZ_LAUNCH(k_init_games<G>, n, WAVE, stream, E, (int)cfg.first_game_seq);
         HIP_OK(hipGetLastError());
@@ -509,6 +548,13 @@ template <class G> struct EngineT : gaz_engine {
     void launch_wave(hipStream_t st, int g0, int g1, const DevParams<G>& E) {
         // the small boards run four games per wavefront (PuctVariant: same records, 16-lane teams); GAZ_TREE_TEAMS=0 -> one per wave
         typedef typename PuctVariant<G>::type GP;
+        if (lbk > 1) {                                // (PUCT only, no evaluation cache: gaz_engine_create refuses the rest)
+            // one register budget for all three games (the four-games-per-wavefront one): the K-leaf step serves few games, occupancy is
+            // not what limits it, and with it the step needs no scratch (Gomoku under k_wave's budget: 156 spilled VGPRs)
+            constexpr int PER = WAVE / GP::TEAM;
+            GAZ_LAUNCH(k_wave_lb<GP>, (g1 - g0 + PER - 1) / PER, WAVE, st, *reinterpret_cast<const DevParams<GP>*>(&E), LB, g0, g1);
+            return;
+        }
         if (cfg.search == GAZ_SEARCH_GUMBEL) {
             static const int gteams_env = getenv("GAZ_TREE_TEAMS") ? atoi(getenv("GAZ_TREE_TEAMS")) : -1;
             constexpr int GPER = WAVE / GP::TEAM;
@@ -562,6 +608,7 @@ template <class G> struct EngineT : gaz_engine {
         if (fuse_state == 0 && fault_strikes > 0 && fault_strikes <= REARM_STRIKES && d_queue_or_done() && waves_launched - fault_wave >= REARM_WAVES) fuse_state = 1;
         if (fuse_state >= 0) return fuse_state == 1;
         fuse_state = 0;
+        if (lbk > 1) return false;                   // K rows per game: the one-launch form hands over one row per game
         static const bool off = getenv("GAZ_FUSE_WAVE") && atoi(getenv("GAZ_FUSE_WAVE")) == 0;
         typedef typename PuctVariant<G>::type GP;
         // with the evaluation cache too (measured 67.5 k vs 64.3 k positions/s): a team's probe reads its OWN row, and the table is
@@ -590,6 +637,7 @@ template <class G> struct EngineT : gaz_engine {
         return true;
     }
     int debug_fused_fault(int mod) override {
+        if (lbk > 1 && mod > 0) return fail("debug_fused_fault: leaf_batch > 1 runs separate launches only");
         if (mod > 0 && !ensure_skip_buffers()) return 1;
         debug_fault_mod = mod > 0 ? (unsigned)mod : 0u;
         return 0;
@@ -603,6 +651,7 @@ template <class G> struct EngineT : gaz_engine {
     int32_t* dMoveList = nullptr;
     int repack(int32_t* n_active_out, int32_t* n_eff_out) override {
         if (E.sync_moves) return fail("repack needs continuous self-play (sync_moves = 0)");
+        if (lbk > 1) return fail("repack: not with leaf_batch > 1 (a game owns leaf_batch rows of the batch)");
         HIP_OK(hipStreamSynchronize(stream));
         if (pipeline_ready) { HIP_OK(hipStreamSynchronize(tstream)); HIP_OK(hipStreamSynchronize(hstream)); }
         GAZ_LAUNCH(k_gather_root<G>, E.n_games, WAVE, stream, E, dN, dW, dP, dPol, dRV, dQ, dChosen, dPhase, dPending);
@@ -706,7 +755,7 @@ template <class G> struct EngineT : gaz_engine {
         launch_wave(stream, 0, n_eff, P);
         prev_marked = false;                         // the separately launched evaluator pass covers every row
         if (timing) hipEventRecord(e1, stream);
-        if (with_eval && eval) eval->forward(stream, E.nn_in, E.nn_policy, E.nn_value, n_eff, timing);
+        if (with_eval && eval) eval->forward(stream, E.nn_in, E.nn_policy, E.nn_value, n_eff * lbk, timing);
         if (timing) { hipEventRecord(e2, stream); ev_tree.push_back({e0, e1}); ev_eval.push_back({e1, e2}); n_waves_timed++; }
         P.eval_done = nullptr;
         if (with_eval && eval && debug_fault_mod && d_evaldone) {      // test hook: this wave behaves as a fused launch with workgroups that gave up
@@ -733,7 +782,7 @@ template <class G> struct EngineT : gaz_engine {
         static const char* spec = getenv("GAZ_PIPELINE");
         if (!spec || !*spec || atoi(spec) == 0) return false;
         // (the evaluation cache is read by tree kernels and written by k_cache_insert: they must not run concurrently)
-        if (E.sync_moves || !eval || !eval->supports_split() || E.n_games < 1024 || E.cache || n_eff != E.n_games) return false;
+        if (lbk > 1 || E.sync_moves || !eval || !eval->supports_split() || E.n_games < 1024 || E.cache || n_eff != E.n_games) return false;
         if (!pipeline_ready) {
             // GAZ_PIPELINE=1: groups of one full trunk round (1536 boards), remainder last; GAZ_PIPELINE=a,b,c: explicit sizes
             std::vector<int> sizes;
@@ -801,13 +850,14 @@ template <class G> struct EngineT : gaz_engine {
         if (!E.sync_moves) return fail("run_move needs sync_moves = 1");
         if (!eval) return fail("run_move needs a built-in evaluator (use wave_begin/wave_end with GAZ_EVAL_EXTERNAL)");
         if (!eval->ready()) return fail("run_move: evaluator weights not loaded (gaz_engine_load_weights)");
-        // a move needs at most iter_limit + 2 evaluations (both roots); poll the device every 16 waves
+        // a move needs at most iter_limit + 2 evaluations (both roots); poll the device every 16 waves (4 with leaf batching)
         // PUCT: a move needs at most iter_limit + 2 evaluations; Gumbel can overshoot its budget (vpc >= 1 per survivor)
         const int max_waves = cfg.search == GAZ_SEARCH_GUMBEL ? 4 * (E.run_iterations + 3 * G::A) + 64
                                                              : (E.run_iterations < 3 * G::A ? 3 * G::A : E.run_iterations) + 8;
         int32_t c[10];
-        for (int w = 0; w < max_waves + 16; w += 16) {
-            for (int i = 0; i < 16; ++i) one_wave(true);
+        const int poll = lbk > 1 ? 4 : 16;           // a K-leaf move is a few dozen launches: look more often, every launch evaluates all rows
+        for (int w = 0; w < max_waves + 16; w += poll) {
+            for (int i = 0; i < poll; ++i) one_wave(true);
             if (counts(c)) return 1;
             if (check_device_error()) return 1;
             if (c[0] == 0) break;
@@ -841,7 +891,7 @@ template <class G> struct EngineT : gaz_engine {
         HIP_OK(hipGetLastError());
         // run the APPLY phase (do_action, win check, prune) up to the next evaluation request
         launch_wave();
-        if (eval) eval->forward(stream, E.nn_in, E.nn_policy, E.nn_value, E.n_games, false);
+        if (eval) eval->forward(stream, E.nn_in, E.nn_policy, E.nn_value, (int)rows, false);
         if (eval && E.cache) { GAZ_LAUNCH(k_cache_insert<G>, E.n_games, WAVE, stream, E, 0, E.n_games); E.cache_epoch++; }
         HIP_OK(hipGetLastError());
         return check_device_error();
@@ -862,18 +912,20 @@ template <class G> struct EngineT : gaz_engine {
     int batch_ptrs(void** a, void** b, void** c) override {
         if (a) *a = E.nn_in; if (b) *b = E.nn_policy; if (c) *c = E.nn_value; return 0;
     }
+    int batch_rows(int32_t* out) override { if (!out) return fail("batch_rows: null argument"); *out = (int32_t)rows; return 0; }
     int read_batch(int8_t* inputs, int32_t* pending) override {
-        if (inputs) HIP_OK(hipMemcpyAsync(inputs, E.nn_in, (size_t)E.n_games * G::HW * G::C, hipMemcpyDeviceToHost, stream));
+        if (inputs) HIP_OK(hipMemcpyAsync(inputs, E.nn_in, rows * G::HW * G::C, hipMemcpyDeviceToHost, stream));
         if (pending) {
-            GAZ_LAUNCH(k_gather_root<G>, E.n_games, WAVE, stream, E, dN, dW, dP, dPol, dRV, dQ, dChosen, dPhase, dPending);
-            HIP_OK(hipMemcpyAsync(pending, dPending, (size_t)E.n_games * 4, hipMemcpyDeviceToHost, stream));
+            if (lbk > 1) GAZ_LAUNCH(k_gather_pending_lb<G>, E.n_games, WAVE, stream, E, lbk, dPending);
+            else GAZ_LAUNCH(k_gather_root<G>, E.n_games, WAVE, stream, E, dN, dW, dP, dPol, dRV, dQ, dChosen, dPhase, dPending);
+            HIP_OK(hipMemcpyAsync(pending, dPending, rows * 4, hipMemcpyDeviceToHost, stream));
         }
         HIP_OK(hipStreamSynchronize(stream));
         return check_device_error();
     }
     int write_outputs(const float* policy, const float* value) override {
-        HIP_OK(hipMemcpyAsync(E.nn_policy, policy, (size_t)E.n_games * G::A * 4, hipMemcpyHostToDevice, stream));
-        HIP_OK(hipMemcpyAsync(E.nn_value, value, (size_t)E.n_games * 4, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(E.nn_policy, policy, rows * G::A * 4, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(E.nn_value, value, rows * 4, hipMemcpyHostToDevice, stream));
         if (E.cache) { GAZ_LAUNCH(k_cache_insert<G>, E.n_games, WAVE, stream, E, 0, E.n_games); E.cache_epoch++; }
         HIP_OK(hipStreamSynchronize(stream));
         return 0;
@@ -882,7 +934,7 @@ template <class G> struct EngineT : gaz_engine {
     int evaluate(const int8_t* in, int n, float* pol, float* val, int repeats, double* ms) override {
         if (!eval) return fail("evaluate: no built-in evaluator");
         if (!eval->ready()) return fail("evaluate: evaluator weights not loaded");
-        if (n <= 0 || n > E.n_games) return fail("evaluate: n must be in [1, n_games]");
+        if (n <= 0 || (size_t)n > rows) return fail("evaluate: n must be in [1, " + std::to_string(rows) + "] (the rows of the evaluator batch: n_games, or n_games * leaf_batch)");
         HIP_OK(hipMemcpyAsync(E.nn_in, in, (size_t)n * G::HW * G::C, hipMemcpyHostToDevice, stream));
         hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
         eval->forward(stream, E.nn_in, E.nn_policy, E.nn_value, n, false);      // warm-up / the measured result
@@ -1035,6 +1087,13 @@ template <class G> struct EngineT : gaz_engine {
         if (poll_fuse_fault()) return 1;             // counts() synchronised the stream
         out[12] = (fuse_state == 1 && fuse_enabled) ? 1 : 0;
         out[13] = fuse_faults;
+        if (lbk > 1) {
+            unsigned long long* d = reinterpret_cast<unsigned long long*>(dCount);
+            HIP_OK(hipMemsetAsync(d, 0, sizeof(*d), stream));
+            GAZ_LAUNCH(k_count_reserved<G>, E.n_games, WAVE, stream, E, d);
+            HIP_OK(hipMemcpyAsync(&out[15], d, sizeof(*d), hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+        }
         return check_device_error();
     }
 
@@ -1287,6 +1346,7 @@ struct GroupEngine : gaz_engine {
     int wave_end() override { return no_batch(); }
     int batch_ptrs(void**, void**, void**) override { return no_batch(); }
     int read_batch(int8_t*, int32_t*) override { return no_batch(); }
+    int batch_rows(int32_t*) override { return no_batch(); }
     int write_outputs(const float*, const float*) override { return no_batch(); }
     // rows [first[c], first[c + 1]) go through group c's evaluator (and stay in ITS head-feature buffers: read_head_features below); ms: the sum
     int evaluate(const int8_t* in, int n, float* p, float* v, int rep, double* ms) override {
@@ -1400,6 +1460,7 @@ struct GroupEngine : gaz_engine {
 // auto (game_groups = 0): two groups where that was measured to pay (see above; measured at num_filters = 128 only, so other widths run one group); GAZ_GAME_GROUPS overrides the automatic choice only
 static int choose_game_groups(const gaz_engine_config& c) {
     if (c.game_groups != 0) return c.game_groups;
+    if (c.leaf_batch > 1) return 1;                  // K rows per game: one batch
     static const int env = getenv("GAZ_GAME_GROUPS") ? atoi(getenv("GAZ_GAME_GROUPS")) : 0;
     const bool able = !c.sync_moves && c.evaluator != GAZ_EVAL_EXTERNAL && !(c.games_budget > 0 && c.games_budget < c.n_games);
     if (env > 0) return (able && env <= c.n_games) ? env : 1;
@@ -1430,6 +1491,12 @@ int gaz_engine_create(const gaz_engine_config* cfg, gaz_engine** out) {
         return 1;
     }
     if (cfg->game_groups < 0) { g_create_error = "game_groups must be >= 0"; return 1; }
+    if (cfg->leaf_batch < 0 || cfg->leaf_batch > 64) { g_create_error = "leaf_batch must be in [0, 64] (0 and 1 = one leaf per game and wave)"; return 1; }
+    if (cfg->leaf_batch > 1) {                       // the K-leaf step exists for the PUCT search with one batch and no evaluation cache
+        if (cfg->search == GAZ_SEARCH_GUMBEL) { g_create_error = "leaf_batch > 1 needs search = GAZ_SEARCH_PUCT (the Gumbel search plans its simulations itself)"; return 1; }
+        if (cfg->eval_cache_log2 > 0) { g_create_error = "leaf_batch > 1 cannot be combined with eval_cache_log2 > 0"; return 1; }
+        if (cfg->game_groups > 1) { g_create_error = "leaf_batch > 1 cannot be combined with game_groups > 1"; return 1; }
+    }
     const int groups = choose_game_groups(*cfg);
     if (groups <= 1) {
         gaz_engine* h = make_single_engine(*cfg, &g_create_error);
@@ -1456,6 +1523,7 @@ int gaz_engine_wave_begin(gaz_engine* h) { return h->wave_begin(); }
 int gaz_engine_wave_end(gaz_engine* h) { return h->wave_end(); }
 int gaz_engine_batch_ptrs(gaz_engine* h, void** a, void** b, void** c) { return h->batch_ptrs(a, b, c); }
 int gaz_engine_read_batch(gaz_engine* h, int8_t* in, int32_t* pending) { return h->read_batch(in, pending); }
+int gaz_engine_batch_rows(gaz_engine* h, int32_t* rows) { return h->batch_rows(rows); }
 int gaz_engine_write_outputs(gaz_engine* h, const float* p, const float* v) { return h->write_outputs(p, v); }
 int gaz_engine_evaluate(gaz_engine* h, const int8_t* in, int32_t n, float* p, float* v, int32_t repeats, double* ms) { return h->evaluate(in, n, p, v, repeats, ms); }
 int gaz_engine_record_layout(gaz_engine* h, gaz_record_layout* o) { return h->record_layout(o); }

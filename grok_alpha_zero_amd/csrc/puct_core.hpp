@@ -22,6 +22,12 @@
 // runs tree-only simulations until it needs an evaluation, writes its leaf into the batch and stops; one
 // forward pass evaluates all G leaves; the next launch first consumes the result (expand_post + backup)
 // and carries on.  Tree updates need no atomics.
+//
+// Leaf-batched search (gaz_engine_config::leaf_batch = K > 1, DESIGN.md "Leaf-batched PUCT search"; no reference counterpart — the
+// reference's roadmap lists it, README.md:59): a game may hold up to K leaves in flight per wave, rows g * K + j of the batch.  A leaf on
+// its way carries a virtual loss (N + 1, W - 1 on every edge of its path) so that the next descent goes elsewhere; the next launch applies
+// the K results in reservation order.  That step is a kernel instantiation of its own (game_step_body<G, true>): the launches of K = 1 run
+// the code they ran before.
 #pragma once
 #include "det.hpp"
 #include "tree.hpp"
@@ -93,6 +99,15 @@ template <class G> struct DevParams {
     int32_t handoff_release;           // 1: the leaf row was written with plain stores -> agent-scope release before the flag / entry (Gomoku: rows not dword-aligned)
     unsigned long long* done_queue;    // [n_games] or null (then done_flag is used)
     int32_t queue_gpb, queue_nfull, queue_rem;   // games per tree block; blocks with that many games; games of the last, partial block
+};
+
+// leaf-batched search: what the K > 1 kernels get next to DevParams (whose nn_in / nn_policy / nn_value then hold n_games * K rows and paths
+// [n_games][K][PathCap]).  The number of leaves a game has in flight is GameState::pend_depth, the number of reserved children of a node
+// NodeHdr::pad[0].
+struct PendLeaf { int32_t parent, slot, node, depth; };   // expand_post's arguments for one reserved leaf (depth = edges of its parked path)
+struct LeafBatch {
+    int32_t K;                 // leaves per game and wave; 1 = off (pend is null)
+    PendLeaf* pend;            // [n_games][K], in reservation order
 };
 
 // stores / loads that meet at the device's point of coherence (no L1 / per-XCD L2 copy): used for the leaf rows and the done flags
@@ -408,7 +423,8 @@ template <class G> GAZ_DEV int alloc_node(const DevParams<G>& E, TreeState& ts) 
 
 // K12 first half: create_expand_root for tree t at the game's current position.  Returns true when the
 // root needs an evaluation (input row written), false when it was completed here (terminal root).
-template <class G> GAZ_DEV bool root_pre(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S) {
+// `row`: the game's row of the evaluator batch (g; g * K with leaf batching)
+template <class G> GAZ_DEV bool root_pre(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S, int row) {
     if (tlane<G>() == 0) { ts.n_nodes = 0; ts.root = -1; ts.root_visits = 0; }
     wave_sync();
     copy_board<G>(S.board, gs.board);
@@ -436,7 +452,7 @@ template <class G> GAZ_DEV bool root_pre(const DevParams<G>& E, int g, GameState
         wave_sync();
         return false;
     }
-    encode_input<G>(S.board, -gs.next_player, h3, gs.n_hist, E.nn_in + (size_t)g * (G::HW * G::C), E.done_flag != nullptr);
+    encode_input<G>(S.board, -gs.next_player, h3, gs.n_hist, E.nn_in + (size_t)row * (G::HW * G::C), E.done_flag != nullptr);
     wave_sync();
     return true;
 }
@@ -457,7 +473,9 @@ template <class G> GAZ_DEV void root_post(const DevParams<G>& E, int g, GameStat
 
 // K2: descend from the root.  Returns 0 = expand `node` (its next un-popped child), 1 = terminal leaf hit
 // (value in leaf_win).  S.path receives the edge list root..selected, depth its length.
-template <class G> GAZ_DEV int puct_select(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S,
+// LB (leaf-batched search): the statistics include the virtual losses of the leaves in flight, "next un-popped child" is slot
+// n_children + the node's reserved children, and 2 = the best child is one of those reserved ones (a collision: nothing was changed).
+template <class G, bool LB = false> GAZ_DEV int puct_select(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S,
                                            int& node, int& depth, bool& leaf_win) {
     node = ts.root; depth = 0;
     uint64_t pv = ts.root_visits;
@@ -513,8 +531,10 @@ template <class G> GAZ_DEV int puct_select(const DevParams<G>& E, int g, GameSta
             return 1;
         }
         const int best = best_puct_slot<G>(nd, n_actions, fs, fc);
-        if (best == n_children) { wave_sync(); return 0; }          // MCTS.py:217-218
-        if (best > n_children) { set_error(E.error, ERR_BAD_SELECT); return -1; }
+        const int n_reserved = LB ? tuni<G>((int)h.pad[0]) : 0;
+        if (best == n_children + n_reserved) { wave_sync(); return 0; }          // MCTS.py:217-218
+        if (best > n_children + n_reserved) { set_error(E.error, ERR_BAD_SELECT); return -1; }
+        if (LB && best >= n_children) { wave_sync(); return 2; }
         S.path[depth].node = node; S.path[depth].slot = best; depth++;
         pv = tuni<G>(nd.N()[best]);
         node = tuni<G>(nd.child()[best]);
@@ -683,6 +703,109 @@ template <class G> GAZ_DEV void expand_post(const DevParams<G>& E, int g, GameSt
     }
     wave_sync();
     backup<G>(E, g, t, ts, S.path, depth, -value, 1u);                 // MCTS.py:511
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Leaf-batched search.  lb_reserve = expand_pre for the node's next child that is neither expanded nor reserved, as leaf j of the game:
+// the leaf row goes to batch row g * K + j, the path is parked at paths[g][j], and instead of waiting for the value every edge of the
+// path takes a virtual loss (N + 1, W - 1; root_visits + 1).  Returns 0 = reserved, 1 = the simulation completed here (terminal parent
+// created and backed up, as expand_pre does), 2 = deferred: the child would be a terminal parent while earlier children of the node are
+// still reserved — linking it now would break "children [0, n_children) are linked, the next n reserved" — so nothing is written and
+// the game yields; the same descent succeeds once those leaves have been applied.  -1 = error.
+template <class G> GAZ_DEV int lb_reserve(const DevParams<G>& E, const LeafBatch& B, int g, int j, TreeState& ts, int t, Scratch<G>& S,
+                                          int node, int depth, bool staged) {
+    NodeRef<G> pn = node_at(E, g, t, node);
+    const NodeRef<G> ps = staged ? NodeRef<G>{reinterpret_cast<uint8_t*>(S.node)} : pn;
+    const NodeHdr ph = *ps.hdr();
+    const int n_reserved = tuni<G>((int)ph.pad[0]);
+    const int slot = tuni<G>((int)ph.n_children) + n_reserved;
+    const int action = tuni<G>((int)ps.act()[slot]);
+    const int mover = -(int)tuni<G>((int)ph.player);
+    copy_board<G>(S.board, ps.board());
+    wave_sync();
+    const int cell = landing_cell<G>(S.board, action);
+    wave_sync();
+    if (tlane<G>() == 0) S.board[cell] = (int8_t)mover;
+    wave_sync();
+    const int n_legal = build_legal<G>(S.board, S.legal);
+    bool any_win;
+    const int nt = terminal_probe<G>(S.board, S.legal, n_legal, -mover, S.tact, S.twin, any_win, E.fast_find_win != 0);
+    if (nt > 0 && n_reserved > 0) return 2;
+    const int idx = alloc_node(E, ts);
+    if (idx < 0) return -1;
+    NodeRef<G> nd = node_at(E, g, t, idx);
+    if (tlane<G>() == 0) {
+        NodeHdr h; memset(&h, 0, sizeof(h));
+        h.parent = node; h.slot = (int16_t)slot; h.player = (int8_t)mover; h.n_hist = (uint16_t)(ph.n_hist + 1);
+        h.hist3[0] = (uint8_t)action; h.hist3[1] = ph.hist3[0]; h.hist3[2] = ph.hist3[1]; h.action = (uint8_t)action;
+        if (nt > 0) { h.n_actions = (uint8_t)nt; h.n_children = (uint8_t)nt; h.flags = NF_TERMINAL_PARENT; }
+        *nd.hdr() = h;
+    }
+    S.path[depth].node = node; S.path[depth].slot = slot;
+    wave_sync();
+    if (nt > 0) {                                                      // as expand_pre: real backup, no virtual loss
+        write_terminal_children<G>(nd, S, nt, any_win, false);
+        if (tlane<G>() == 0) { pn.child()[slot] = idx; pn.hdr()->n_children = (uint8_t)(slot + 1); }
+        wave_sync();
+        backup<G>(E, g, t, ts, S.path, depth + 1, any_win ? -(float)nt : 0.0f, (uint32_t)nt);
+        return 1;
+    }
+    const size_t row = (size_t)g * B.K + j;
+    copy_board<G>(nd.board(), S.board);
+    uint8_t h3[3] = {(uint8_t)action, ph.hist3[0], ph.hist3[1]};
+    encode_input<G>(S.board, mover, h3, (int)ph.n_hist + 1, E.nn_in + row * (G::HW * G::C));
+    PathEnt* gp = E.paths + row * PathCap<G>::V;
+    for (int d = tlane<G>(); d <= depth; d += G::TEAM) gp[d] = S.path[d];
+    if (tlane<G>() == 0) {
+        PendLeaf pd; pd.parent = node; pd.slot = slot; pd.node = idx; pd.depth = depth + 1;
+        B.pend[row] = pd;
+        pn.hdr()->pad[0] = (uint32_t)(n_reserved + 1);
+    }
+    for (int d = tlane<G>(); d <= depth; d += G::TEAM) {              // virtual loss on every edge, the new one included
+        NodeRef<G> e = node_at(E, g, t, S.path[d].node);
+        const int s = S.path[d].slot;
+        e.N()[s] = e.N()[s] + 1u;
+        e.W()[s] = e.W()[s] - 1.0f;
+    }
+    if (tlane<G>() == 0) ts.root_visits += 1;
+    wave_sync();
+    return 0;
+}
+
+// expand_post for leaf j of the game (row g * K + j), then the virtual loss comes off every edge of its parked path and the value goes
+// on: W = (W + 1) + v, two float32 additions in this order; N and root_visits keep the visit they were given at reservation.
+template <class G> GAZ_DEV void lb_apply(const DevParams<G>& E, const LeafBatch& B, int g, int j, GameState<G>& gs, TreeState& ts, int t,
+                                         Scratch<G>& S) {
+    const size_t row = (size_t)g * B.K + j;
+    const PendLeaf pd = B.pend[row];
+    const int node = tuni<G>(pd.parent), slot = tuni<G>(pd.slot), idx = tuni<G>(pd.node), depth = tuni<G>(pd.depth);
+    NodeRef<G> nd = node_at(E, g, t, idx);
+    const float value = E.nn_value[row];
+    const float* policy = E.nn_policy + row * G::A;
+    for (int a = tlane<G>(); a < G::A; a += G::TEAM) S.aux[a] = policy[a];
+    const PathEnt* gp = E.paths + row * PathCap<G>::V;
+    for (int d = tlane<G>(); d < depth; d += G::TEAM) S.path[d] = gp[d];
+    copy_board<G>(S.board, nd.board());
+    wave_sync();
+    const int n_legal = build_legal<G>(S.board, S.legal);
+    make_priors<G>(E, g, gs, ts, t, S, S.aux, n_legal);
+    write_children_from_scratch<G>(nd, S, n_legal);
+    NodeRef<G> pn = node_at(E, g, t, node);
+    if (tlane<G>() == 0) {
+        nd.hdr()->n_actions = (uint8_t)n_legal; nd.hdr()->n_children = 0;
+        pn.child()[slot] = idx; pn.hdr()->n_children = (uint8_t)(slot + 1); pn.hdr()->pad[0] -= 1u;
+    }
+    wave_sync();
+    for (int d = tlane<G>(); d < depth; d += G::TEAM) {
+        NodeRef<G> e = node_at(E, g, t, S.path[d].node);
+        const float v = ((depth - 1 - d) & 1) ? value : -value;       // backup(-value): the leaf edge takes -value, alternating upward
+        const int s = S.path[d].slot;
+        float w = e.W()[s];
+        w = w + 1.0f;
+        w = w + v;
+        e.W()[s] = w;
+    }
+    wave_sync();
 }
 
 // Re-root with compaction (the arena is double-buffered): breadth-first copy of the subtree under `root_old` into the other
@@ -859,15 +982,26 @@ template <class G> GAZ_DEV bool ring_push(const DevParams<G>& E, int g, GameStat
 // left it (the compiler gives a divergent loop one exit), so a game that needed a single simulation used to publish its leaf row when the
 // slowest game of its wavefront was done — 53 us instead of 22 at the median (tools/fused_timeline.py).  The loop therefore runs until every
 // team of the wavefront has yielded, a team that has yielded sitting out the remaining iterations.
-template <class G, class Fin> GAZ_DEV void game_step_body(const DevParams<G>& E, int g, Scratch<G>& S, GameState<G>& gs, TreeState* trees, Fin&& fin) {
+// LB = the leaf-batched search (its own kernels): up to B.K leaves of a game in flight, see lb_reserve / lb_apply.
+template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const DevParams<G>& E, int g, Scratch<G>& S, GameState<G>& gs, TreeState* trees, Fin&& fin,
+                                                                           const LeafBatch& B = LeafBatch{1, nullptr}) {
     using RL = RecLayout<G>;
+    const int row0 = LB ? g * B.K : g;               // the game's first row of the evaluator batch
 
     const long long tp0 = GAZ_PROF_NOW();
     if (E.prof && tlane<G>() == 0) E.prof[(size_t)g * 8 + 7] += 1;
     if (tuni<G>(gs.pend_kind) == PEND_ROOT) {
         const int t = tuni<G>(gs.pend_tree);
-        root_post<G>(E, g, gs, trees[t], t, S, E.nn_policy + (size_t)g * G::A);
+        root_post<G>(E, g, gs, trees[t], t, S, E.nn_policy + (size_t)row0 * G::A);
         if (tlane<G>() == 0) { gs.pend_kind = PEND_NONE; gs.roots_todo &= ~(1 << t); gs.n_evals += 1; }
+        wave_sync();
+    } else if (LB && tuni<G>(gs.pend_kind) == PEND_EXPAND) {           // the leaves reserved by the previous launch, in reservation order
+        const int t = tuni<G>(gs.pend_tree), n = tuni<G>(gs.pend_depth);
+        for (int j = 0; j < n; ++j) lb_apply<G>(E, B, g, j, gs, trees[t], t, S);
+        if (tlane<G>() == 0) {
+            gs.pend_kind = PEND_NONE; gs.pend_depth = 0;
+            gs.sims_done += n; gs.n_evals += (uint64_t)n; gs.n_sims += (uint64_t)n; gs.move_evals += (uint32_t)n;
+        }
         wave_sync();
     } else if (tuni<G>(gs.pend_kind) == PEND_EXPAND) {
         const int t = tuni<G>(gs.pend_tree);
@@ -893,7 +1027,7 @@ template <class G, class Fin> GAZ_DEV void game_step_body(const DevParams<G>& E,
             const int todo = tuni<G>(gs.roots_todo);
             if (todo == 0) { if (tlane<G>() == 0) gs.phase = PH_MOVE_BEGIN; wave_sync(); return false; }
             const int t = (todo & 1) ? 0 : 1;
-            if (root_pre<G>(E, g, gs, trees[t], t, S)) {
+            if (root_pre<G>(E, g, gs, trees[t], t, S, row0)) {
                 const uint8_t* hit = E.cache ? cache_probe<G>(E, g) : nullptr;
                 if (hit) {                                             // evaluation cache hit: the root is complete in this launch
                     root_post<G>(E, g, gs, trees[t], t, S, reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_POL));
@@ -924,12 +1058,24 @@ template <class G, class Fin> GAZ_DEV void game_step_body(const DevParams<G>& E,
                 if (E.move_time_ticks) gs.move_t0 = (uint64_t)wall_clock64();
                 gs.phase = PH_SIMS;
             }
+            if (LB) tree_only = 0;                                     // which leaves share a launch decides the result there: a move does not inherit the count of the move before it
             wave_sync();
         } else if (phase == PH_SIMS) {                                 // MCTS.run loop body (MCTS.py:560-587)
             // (only once every root child has been visited: stopping earlier, the reference divides by zero visits at MCTS.py:594-595 under its
             // np.seterr(all="raise") — a limit that short is an error there, a floor of one visit per root child here)
             const bool out_of_time = E.move_time_ticks && tuni<G>(gs.fully_visited) && tuni<G>((int)((uint64_t)wall_clock64() - gs.move_t0 > E.move_time_ticks));
-            if (tuni<G>(gs.sims_done) >= tuni<G>(gs.iter_limit) || ((E.stop_search || out_of_time) && tuni<G>(gs.sims_done) > 0)) { if (tlane<G>() == 0) gs.phase = PH_MOVE_END; wave_sync(); return false; }
+            if (LB) {
+                // a leaf in flight has its visit already: reservations stop at sims_done + in flight = iter_limit (or K, or a stop request), and
+                // the move ends once nothing is in flight
+                const int fl = tuni<G>(gs.pend_depth), done = tuni<G>(gs.sims_done), lim = tuni<G>(gs.iter_limit);
+                if (done >= lim || ((E.stop_search || out_of_time) && done > 0)) {
+                    if (fl > 0) return true;
+                    if (tlane<G>() == 0) gs.phase = PH_MOVE_END;
+                    wave_sync();
+                    return false;
+                }
+                if (done + fl >= lim || fl >= B.K) return true;
+            } else if (tuni<G>(gs.sims_done) >= tuni<G>(gs.iter_limit) || ((E.stop_search || out_of_time) && tuni<G>(gs.sims_done) > 0)) { if (tlane<G>() == 0) gs.phase = PH_MOVE_END; wave_sync(); return false; }
             const int t = tuni<G>(gs.runner);
             TreeState& ts = trees[t];
             NodeRef<G> r = node_at(E, g, t, ts.root);
@@ -982,13 +1128,27 @@ template <class G, class Fin> GAZ_DEV void game_step_body(const DevParams<G>& E,
                 return false;
             }
             if (tree_only >= E.max_tree_sims) return true;                  // bound the launch's tail; resume next wave
-            tree_only++;
+            if (!LB) tree_only++;                                           // (LB: only the simulations that complete without an evaluation count)
             int node, depth; bool leaf_win = false; int kind;
             const long long ts0 = GAZ_PROF_NOW();
             if (!tuni<G>(gs.fully_visited)) { node = ts.root; depth = 0; kind = 0; }
-            else kind = puct_select<G>(E, g, gs, ts, t, S, node, depth, leaf_win);
+            else kind = puct_select<G, LB>(E, g, gs, ts, t, S, node, depth, leaf_win);
             GAZ_PROF(1, ts0);
             if (kind < 0) return true;
+            if (LB && kind == 2) return true;                               // collision with a leaf in flight: collecting ends for this launch
+            if (LB && kind == 0) {
+                const int fl = tuni<G>(gs.pend_depth);
+                const int r = lb_reserve<G>(E, B, g, fl, ts, t, S, node, depth, tuni<G>(gs.fully_visited) != 0);
+                if (r < 0 || r == 2) return true;
+                if (tlane<G>() == 0) {
+                    if (r == 1) { gs.sims_done += 1; gs.n_sims += 1; }
+                    else { gs.pend_kind = PEND_EXPAND; gs.pend_tree = t; gs.pend_depth = fl + 1; }
+                }
+                wave_sync();
+                if (r == 1) tree_only++;
+                return false;
+            }
+            if (LB) tree_only++;
             if (kind == 1) {                                           // terminal leaf: value 1 / 0, visits 1 (MCTS.py:573-575)
                 const long long tb0 = GAZ_PROF_NOW();
                 backup<G>(E, g, t, ts, S.path, depth, leaf_win ? 1.0f : 0.0f, 1u);
@@ -1141,6 +1301,19 @@ template <class G> GAZ_DEV void game_step(const DevParams<G>& E, int g, Scratch<
         publish_done<G>(E, g, block_rank, block);
         GAZ_PROF(6, tw0);
     });
+}
+
+// the leaf-batched step of game g (separate launches only: no hand-over to a trunk workgroup, every row is evaluated every wave)
+template <class G> GAZ_DEV void game_step_lb(const DevParams<G>& E, const LeafBatch& B, int g, Scratch<G>& S, PuctLocal<G>& L) {
+    GameState<G>* gsG = &E.games[g];
+    TreeState* tsG = E.trees + (size_t)g * 2;
+    if (E.compact) { game_step_body<G, true>(E, g, S, *gsG, tsG, []() {}, B); return; }
+    copy_state_words<G>(&L.gs, gsG); copy_state_words<G>(&L.ts[0], &tsG[0]); copy_state_words<G>(&L.ts[1], &tsG[1]);
+    wave_sync();
+    game_step_body<G, true>(E, g, S, L.gs, L.ts, [&]() {
+        wave_sync();
+        copy_state_words<G>(gsG, &L.gs); copy_state_words<G>(&tsG[0], &L.ts[0]); copy_state_words<G>(&tsG[1], &L.ts[1]);
+    }, B);
 }
 
 }  // namespace gaz

@@ -29,7 +29,7 @@ struct NodeHdr {          // 32 bytes
     uint16_t n_hist;      // len(action_history) of this position
     uint8_t hist3[3];     // last three actions of the path, newest first (Connect4 input planes)
     uint8_t action;       // action_history[-1]
-    uint32_t pad[4];
+    uint32_t pad[4];      // pad[0]: leaf-batched search (puct_core.hpp LeafBatch) — children of this node reserved and not yet applied
 };
 static_assert(sizeof(NodeHdr) == 32, "NodeHdr must be 32 bytes");
 
@@ -84,7 +84,7 @@ template <class G> struct GameState {
     int32_t runner;            // tree running the current move
     int32_t sims_done, iter_limit, fully_visited;
     int32_t tau_on[2];         // tau = 1.0 (1) or 0 (0) per tree (Self_Play.py:86-95)
-    int32_t pend_kind, pend_tree, pend_parent, pend_slot, pend_node, pend_depth;
+    int32_t pend_kind, pend_tree, pend_parent, pend_slot, pend_node, pend_depth;   // leaf-batched search: pend_depth = leaves in flight, their descriptors in LeafBatch::pend
     int32_t chosen;            // action sampled at MOVE_END
     int32_t host_move;         // sync mode: host override, -1 = use chosen
     int32_t winner;

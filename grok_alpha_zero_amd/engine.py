@@ -19,7 +19,7 @@ EVAL_HASH, EVAL_RESNET, EVAL_EXTERNAL = 0, 1, 2
 PH_WAIT_HOST, PH_HALT, PH_IDLE = 5, 8, 9
 
 
-ABI_VERSION = 5               # GAZ_ENGINE_ABI_VERSION of include/gaz_engine.h this binding was written against
+ABI_VERSION = 6               # GAZ_ENGINE_ABI_VERSION of include/gaz_engine.h this binding was written against
 
 
 class EngineConfig(C.Structure):       # gaz_engine_config — tests/test_abi.py checks names, order and sizeof against the header
@@ -33,7 +33,8 @@ class EngineConfig(C.Structure):       # gaz_engine_config — tests/test_abi.py
                 ("gumbel_m", C.c_int32), ("c_visit", C.c_double), ("c_scale", C.c_double), ("compact_trees", C.c_int32),
                 ("single_tree", C.c_int32), ("n_opening", C.c_int32), ("opening_actions", C.c_int32 * 8),
                 ("opening_weights", C.c_double * 8), ("max_tree_sims_per_wave", C.c_int32), ("eval_cache_log2", C.c_int32), ("gumbel_stablemax", C.c_int32), ("fast_find_win", C.c_int32),
-                ("no_gumbel_noise", C.c_int32), ("first_game_seq", C.c_uint32), ("games_budget", C.c_int64), ("tau", C.c_double), ("move_time_limit", C.c_double), ("game_groups", C.c_int32)]
+                ("no_gumbel_noise", C.c_int32), ("first_game_seq", C.c_uint32), ("games_budget", C.c_int64), ("tau", C.c_double), ("move_time_limit", C.c_double), ("game_groups", C.c_int32),
+                ("leaf_batch", C.c_int32)]
 
 
 class SearchHyperparams(C.Structure):  # gaz_search_hyperparams
@@ -85,6 +86,7 @@ def load_library(lib_path=None):
     L.gaz_engine_batch_ptrs.argtypes = [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.gaz_engine_read_batch.argtypes = [H, C.c_void_p, C.c_void_p]
     L.gaz_engine_write_outputs.argtypes = [H, C.c_void_p, C.c_void_p]
+    L.gaz_engine_batch_rows.argtypes = [H, C.POINTER(C.c_int32)]
     L.gaz_engine_evaluate.argtypes = [H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
     L.gaz_engine_record_layout.argtypes = [H, C.POINTER(RecordLayout)]
     L.gaz_engine_drain_finished.argtypes = [H, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
@@ -109,7 +111,7 @@ def load_library(lib_path=None):
     L.gaz_engine_timing_get.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     for f in ("create", "load_weights", "reset_games", "run_move", "get_root_stats", "apply_moves", "run_waves", "wave_begin",
-              "wave_end", "batch_ptrs", "read_batch", "write_outputs", "evaluate", "record_layout", "drain_finished", "sample_layout", "drain_samples", "get_stats",
+              "wave_end", "batch_ptrs", "read_batch", "write_outputs", "batch_rows", "evaluate", "record_layout", "drain_finished", "sample_layout", "drain_samples", "get_stats",
               "synchronize", "timing_reset", "timing_get", "dominant_kernel", "set_position", "set_search_params", "start_search", "stop_search",
               "set_hyperparams", "probe_rules", "read_head_features", "set_fused_wave", "debug_fused_fault", "read_positions", "repack"):
         getattr(L, "gaz_engine_" + f).restype = C.c_int
@@ -166,7 +168,7 @@ class SelfPlayEngine:
                  evaluator=EVAL_HASH, hash_salt=0, device=0, net_blocks=0, net_filters=128, search=SEARCH_PUCT,
                  policy_is_logits=False, max_tree_sims_per_wave=0, gumbel_m=0, c_visit=50.0, c_scale=1.0,
                  compact_trees=0, single_tree=False, opening_actions=None, eval_cache_log2=0, gumbel_stablemax=False, fast_find_win=False,
-                 use_gumbel_noise=True, first_game_seq=0, games_budget=0, tau=-1.0, move_time_limit=0.0, game_groups=0, lib_path=None):
+                 use_gumbel_noise=True, first_game_seq=0, games_budget=0, tau=-1.0, move_time_limit=0.0, game_groups=0, leaf_batch=1, lib_path=None):
         self.L = load_library(lib_path)
         self.game_id = GAME_IDS[game] if isinstance(game, str) else int(game)
         self.H, self.W, self.Cc, self.A = GAME_DIMS[self.game_id]
@@ -184,7 +186,8 @@ class SelfPlayEngine:
                                 max_tree_sims_per_wave=max_tree_sims_per_wave, eval_cache_log2=int(eval_cache_log2),
                                 gumbel_stablemax=int(gumbel_stablemax), fast_find_win=int(fast_find_win),
                                 no_gumbel_noise=int(not use_gumbel_noise), first_game_seq=int(first_game_seq), games_budget=int(games_budget),
-                                tau=float(tau), move_time_limit=float(move_time_limit or 0.0), game_groups=int(game_groups))
+                                tau=float(tau), move_time_limit=float(move_time_limit or 0.0), game_groups=int(game_groups),
+                                leaf_batch=int(leaf_batch))
         for i, (a, w) in enumerate(opening_actions or []):       # [(action index, weight)] — train_config["opening_actions"]
             self.cfg.opening_actions[i] = int(a); self.cfg.opening_weights[i] = float(w); self.cfg.n_opening = i + 1
         self.h = C.c_void_p()
@@ -192,6 +195,11 @@ class SelfPlayEngine:
             raise EngineError(self.L.gaz_engine_last_error(None).decode())
         self.layout = RecordLayout()
         self._ck(self.L.gaz_engine_record_layout(self.h, C.byref(self.layout)))
+        self.batch_rows = n_games            # rows of the evaluator batch: n_games * leaf_batch with leaf_batch > 1 (row g * K + j = leaf j of game g)
+        if self.cfg.game_groups <= 1 and self.cfg.leaf_batch > 1:
+            r = C.c_int32()
+            self._ck(self.L.gaz_engine_batch_rows(self.h, C.byref(r)))
+            self.batch_rows = int(r.value)
 
     def _ck(self, rc):
         if rc:
@@ -328,14 +336,14 @@ class SelfPlayEngine:
         self._ck(self.L.gaz_engine_wave_begin(self.h))
 
     def read_batch(self):
-        x = np.zeros((self.n_games, self.H, self.W, self.Cc), np.int8)
-        pend = np.zeros(self.n_games, np.int32)
+        x = np.zeros((self.batch_rows, self.H, self.W, self.Cc), np.int8)
+        pend = np.zeros(self.batch_rows, np.int32)
         self._ck(self.L.gaz_engine_read_batch(self.h, x.ctypes.data, pend.ctypes.data))
         return x, pend
 
     def write_outputs(self, policy, value):
         p = np.ascontiguousarray(policy, np.float32); v = np.ascontiguousarray(value, np.float32)
-        assert p.shape == (self.n_games, self.A) and v.size == self.n_games
+        assert p.shape == (self.batch_rows, self.A) and v.size == self.batch_rows
         self._ck(self.L.gaz_engine_write_outputs(self.h, p.ctypes.data, v.ctypes.data))
 
     def batch_ptrs(self):
@@ -348,7 +356,7 @@ class SelfPlayEngine:
         out = (C.c_uint64 * 16)()
         self._ck(self.L.gaz_engine_get_stats(self.h, out))
         s = [int(x) for x in out]
-        return dict(game_stats=np.array(s[:6], np.uint64), evals=s[6], sims=s[7], plies=s[8], waves=s[9], cache_hits=s[10], pipeline_groups=s[11], fused_wave=s[12], fused_faults=s[13], game_groups=max(int(s[14]), 1))
+        return dict(game_stats=np.array(s[:6], np.uint64), evals=s[6], sims=s[7], plies=s[8], waves=s[9], cache_hits=s[10], pipeline_groups=s[11], fused_wave=s[12], fused_faults=s[13], game_groups=max(int(s[14]), 1), reserved_children=s[15])
 
     def drain_finished(self, max_records=None):
         """Finished games as dicts: actions, policies [T,A], q, z, values (=0.5(z+q), Self_Play.py:165-172),

@@ -2,7 +2,9 @@
 one-game engine: same constructor arguments, `run(iteration_limit, time_limit, use_bar) -> (move, rows)`,
 `prune_tree(action, create_new_root)`, `update_hyperparams(**kw)`.  The tree, select / expand / backup, noise and move
 sampling run in the HIP kernels; `session.run(["policy", "value"], {"inputs": x})` (MCTS.py:224-235) is called once per
-simulation with a batch of one, exactly where the reference calls it.  `session=None` selects the synthetic evaluator
+simulation with a batch of one, exactly where the reference calls it.  `MCTS(..., leaf_batch=K)` (no reference counterpart: its
+roadmap's "Virtual Loss for Parallel MCTS") lets the tree keep up to K leaves in flight: `session.run` then gets the pending leaves
+of a wave stacked into one batch `[n_pending, H, W, C]` — a different, deterministic search (DESIGN.md "Leaf-batched PUCT search").  `session=None` selects the synthetic evaluator
 (the reference's uniform-random dummy, MCTS.py:237-241, is not reproducible by construction).
 
 For throughput use `SelfPlayEngine` / `run_self_play` (thousands of games per launch); these classes exist so code written
@@ -71,10 +73,12 @@ class _EngineSearch:
                         return
                     continue
                 x, pend = eng.read_batch()
-                if pend[0]:
-                    policy, value = self.session.run(output_names=["policy", "value"],
-                                                     input_feed={"inputs": np.expand_dims(x[0].astype(np.float32), 0)})
-                    eng.write_outputs(np.asarray(policy, np.float32).reshape(1, -1), np.asarray(value, np.float32).reshape(-1))
+                rows = np.flatnonzero(pend)                      # one row per simulation; with leaf_batch = K up to K rows of a wave
+                if rows.size:
+                    policy, value = self.session.run(output_names=["policy", "value"], input_feed={"inputs": x[rows].astype(np.float32)})
+                    pol = np.zeros((eng.batch_rows, eng.A), np.float32); val = np.zeros(eng.batch_rows, np.float32)
+                    pol[rows] = np.asarray(policy, np.float32).reshape(rows.size, -1); val[rows] = np.asarray(value, np.float32).reshape(-1)
+                    eng.write_outputs(pol, val)
                 elif eng.root_stats()["phase"][0] in (PH_WAIT_HOST, PH_HALT, PH_IDLE):
                     return
                 eng.wave_begin()
@@ -106,14 +110,14 @@ class MCTS(_EngineSearch):
 
     def __init__(self, game, session=None, use_njit=None, c_puct_init=2.5, c_puct_base=19_652, use_dirichlet=True,
                  dirichlet_alpha=1.11, dirichlet_epsilon=0.25, tau=1.0, fast_find_win=False, *, seed=None, hash_salt=0,
-                 max_actions=None, lib_path=None):
+                 max_actions=None, leaf_batch=1, lib_path=None):
         self.c_puct_init, self.c_puct_base = c_puct_init, c_puct_base
         self.use_dirichlet, self.dirichlet_alpha, self.dirichlet_epsilon = use_dirichlet, dirichlet_alpha, dirichlet_epsilon
         self.tau = 0.0 if (tau != 0.0 and tau < 5e-3) else tau                          # MCTS.py:116-120
         self._attach(game, session, seed, lib_path, max_actions=max_actions or int(np.prod(game.board.shape)),
                      c_puct_init=c_puct_init, c_puct_base=c_puct_base, dirichlet_alpha=dirichlet_alpha,
                      dirichlet_epsilon=dirichlet_epsilon, use_dirichlet=use_dirichlet, hash_salt=hash_salt, search=SEARCH_PUCT,
-                     fast_find_win=bool(fast_find_win))
+                     fast_find_win=bool(fast_find_win), leaf_batch=int(leaf_batch))
 
     def update_hyperparams(self, **kwargs):
         """MCTS.py:134-168: invalid values are ignored with a warning, valid ones take effect at the next simulation."""

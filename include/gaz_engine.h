@@ -33,6 +33,8 @@
  *                                  spin on the server's flag, Client_Server.py:42-55)
  *   gaz_engine_evaluate        sess.run on a stacked batch (evaluator probe)   Compute_Speed.py:40-63, Client_Server.py:199-206
  *   gaz_engine_read_head_features  intermediate tensors of that probe (numerics tests)  Connect4/Build_Model.py:41-47,62-66
+ *   gaz_engine_config.leaf_batch / gaz_engine_batch_rows  (no reference counterpart: several leaves of one tree per evaluator batch, kept
+ *                                  apart by a virtual loss — the first open item of the reference's roadmap, README.md:59)
  */
 #ifndef GAZ_ENGINE_H
 #define GAZ_ENGINE_H
@@ -49,7 +51,7 @@ enum { GAZ_EVAL_HASH = 0,      /* synthetic bit-reproducible evaluator (parity t
        GAZ_EVAL_RESNET = 1,    /* the ResNet policy/value network, HIP MFMA kernels */
        GAZ_EVAL_EXTERNAL = 2   /* caller evaluates the batch between wave_begin / wave_end */ };
 
-#define GAZ_ENGINE_ABI_VERSION 5   /* bumped whenever gaz_engine_config / gaz_search_hyperparams / an entry point changes */
+#define GAZ_ENGINE_ABI_VERSION 6   /* bumped whenever gaz_engine_config / gaz_search_hyperparams / an entry point changes */
 
 typedef struct {
     uint32_t struct_size;         /* = sizeof(gaz_engine_config) of the header the caller was built against; gaz_engine_create
@@ -87,7 +89,9 @@ typedef struct {
     int32_t opening_actions[8];
     double opening_weights[8];
     int32_t max_tree_sims_per_wave; /* evaluation-free simulations a game may run per launch before it yields (0 = the configuration's measured default: 4 .. 32);
-                                       scheduling only — results do not depend on it */
+                                       scheduling only — results do not depend on it.  With leaf_batch > 1 it is part of the search (which leaves share a launch
+                                       decides the result): only simulations that complete without an evaluation count, reserved leaves do not, and the count
+                                       starts again with every move */
     int32_t eval_cache_log2;      /* on-device evaluation cache with 2^n entries, keyed by the encoded leaf state (replaces
                                      Session_Cache.Cache_Wrapper, Session_Cache.py:4-26 / Self_Play.py:234-236); 0 = off.
                                      A hit returns the bits the evaluator produced for the same input: results do not change */
@@ -117,6 +121,13 @@ typedef struct {
                                      another group's tree step starts or its heads run (continuous self-play with a built-in evaluator only; the
                                      wave_begin / batch API is refused).  1 = one batch.  0 = automatic: 2 where measured to pay (Connect4 PUCT +
                                      ResNet from 3072 games: +9.7 % evaluations/s; Gomoku PUCT + ResNet from 2048 games: +8.6 %; Connect4 Gumbel + ResNet from 6144 games: +6 %), else 1.  With the evaluation cache every group keeps a table of its own */
+    int32_t leaf_batch;           /* PUCT search only.  0 / 1: one leaf per game and wave (the search of the reference, bit for bit).  K in 2..64: a game may
+                                     hold up to K leaves in flight per wave; a leaf on its way carries a virtual loss (N + 1, W - 1 on every edge of its
+                                     path) and the next wave applies the K results in the order they were reserved — a different, deterministic search
+                                     (DESIGN.md "Leaf-batched PUCT search") that fills the evaluator batch from few games.  The batch then has n_games * K
+                                     rows (gaz_engine_batch_rows), row g * K + j = leaf j of game g; game_groups = 0 resolves to 1 and the tree step and the
+                                     evaluator run as separate launches.  Refused by gaz_engine_create with search = GAZ_SEARCH_GUMBEL, eval_cache_log2 > 0,
+                                     game_groups > 1, or a value above 64; gaz_engine_repack is refused on such an engine */
 } gaz_engine_config;
 
 /* MCTS.update_hyperparams(**kwargs) (MCTS.py:134-168) / MCTS_Gumbel.update_hyperparams (MCTS_Gumbel.py:186-210): values take
@@ -166,8 +177,12 @@ int gaz_engine_run_waves(gaz_engine* h, int32_t n_waves);
 int gaz_engine_wave_begin(gaz_engine* h);
 int gaz_engine_wave_end(gaz_engine* h);
 int gaz_engine_batch_ptrs(gaz_engine* h, void** d_inputs_i8, void** d_policy_f32, void** d_value_f32);   /* device pointers */
-int gaz_engine_read_batch(gaz_engine* h, int8_t* inputs, int32_t* pending);    /* host copies: [n_games][H*W*C], [n_games] */
-int gaz_engine_write_outputs(gaz_engine* h, const float* policy, const float* value);   /* host -> device rows */
+int gaz_engine_read_batch(gaz_engine* h, int8_t* inputs, int32_t* pending);    /* host copies: [rows][H*W*C], [rows] */
+int gaz_engine_write_outputs(gaz_engine* h, const float* policy, const float* value);   /* host -> device rows: [rows][A], [rows] */
+/* rows of the evaluator batch: n_games, or n_games * leaf_batch with leaf_batch > 1 — then read_batch, write_outputs and batch_ptrs address
+ * that many rows, pending[g * leaf_batch + j] says whether row g * leaf_batch + j (leaf j of game g) carries a request, and
+ * gaz_engine_evaluate takes up to that many rows.  Rows nobody requested are evaluated and ignored. */
+int gaz_engine_batch_rows(gaz_engine* h, int32_t* rows);
 
 /* place one slot at the position reached by `n` actions from the empty board (new roots are built there).  The game keeps its
  * game_seq, the next player follows from the parity of n, both trees start fresh (event counter 0), and the tau schedule, the
@@ -239,7 +254,9 @@ int gaz_engine_get_stats(gaz_engine* h, uint64_t out[16]);  /* [0..5] game_stats
                                                                     one-launch form is tried again after 20000 waves, at most twice),
                                                                [14] game groups (gaz_engine_config::game_groups as resolved; 0 = one batch): with groups, [0] (the longest
                                                                     game) is the maximum over the groups, [1..8], [10], [13] are sums over the groups and [12] says that every
-                                                                    group runs the one-launch form */
+                                                                    group runs the one-launch form,
+                                                               [15] leaf_batch > 1: reserved children (leaves in flight) summed over every node of every tree — 0 whenever
+                                                                    every game waits for the host or has ended: a move never ends with a leaf in flight */
 int gaz_engine_synchronize(gaz_engine* h);
 
 /* Connect4 PUCT with the ResNet evaluator runs the tree step and the trunk kernel of a wave as ONE launch (k_wave_trunk: the trunk
