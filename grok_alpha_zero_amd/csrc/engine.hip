@@ -74,6 +74,27 @@ template <class G> GAZ_DEV void wave_body_gumbel(const DevParams<G>& E, int g0, 
 template <class G> GAZ_KERNEL k_wave_gumbel(DevParams<G> E, int g0, int g1) { wave_body_gumbel<G>(E, g0, g1); }
 template <class G> GAZ_KERNEL_TEAMS k_wave_gumbel_teams(DevParams<G> E, int g0, int g1) { wave_body_gumbel<G>(E, g0, g1); }
 
+// batched sequential halving (gaz_engine_config::gumbel_batch > 1): the same launch shapes, the chunk step of gumbel_core.hpp
+template <class G> GAZ_DEV void wave_body_gb(const DevParams<G>& E, const GumbelBatch& B, int g0, int g1) {
+    constexpr int PER = WAVE / G::TEAM;
+    GAZ_SHARED Scratch<G> S[PER];
+    GAZ_SHARED GumbelLocal<G> L[PER];
+    const int t = team_in_wave<G>();
+    const int g = g0 + block_id() * PER + t;
+    if (g < g1) g_game_step_gb<G>(E, B, g, S[t], L[t]);
+}
+template <class G> GAZ_KERNEL_TEAMS k_wave_gb(DevParams<G> E, GumbelBatch B, int g0, int g1) { wave_body_gb<G>(E, B, g0, g1); }
+
+// gaz_engine_read_batch with gumbel_batch = K: pending[g * K + j] = the request in row g * K + j (0 = none).  Rows of a chunk can be idle
+// while others wait (a candidate that used its visits, or whose visit ended at a terminal), so every row answers for itself
+template <class G> GAZ_KERNEL k_gather_pending_gb(DevParams<G> E, GumbelBatch B, int32_t* out) {
+    const int g = block_id();
+    if (g >= E.n_games) return;
+    const int kind = E.games[g].pend_kind;               // (PEND_NONE after a reset: stale rows of a game reset mid-move are not reported)
+    for (int j = lane_id(); j < B.K; j += WAVE)
+        out[(size_t)g * B.K + j] = kind == PEND_ROOT ? (j == 0 ? PEND_ROOT : PEND_NONE) : (kind == PEND_EXPAND && B.rows[(size_t)g * B.K + j].pend ? PEND_EXPAND : PEND_NONE);
+}
+
 // evaluation cache: store (state row, outputs) of every request the evaluator just answered; runs between the evaluator
 // pass and the next tree launch, so the tree kernels only ever read the table
 template <class G> GAZ_KERNEL k_cache_insert(DevParams<G> E, int g0, int g1) {
@@ -363,6 +384,8 @@ template <class G> struct EngineT : gaz_engine {
     std::vector<void*> allocs;
     // leaf-batched search: K leaves per game and wave (1 = off), rows = n_games * K rows in the evaluator batch, descriptors of the leaves in flight
     int lbk = 1; size_t rows = 0; LeafBatch LB{1, nullptr};
+    // batched sequential halving (Gumbel search, gumbel_batch = K > 1): lbk = K as well — the rows plumbing is the same — and the per-row state
+    int gbk = 1; GumbelBatch GB{1, nullptr};
 
     template <class T> int dalloc(T** p, size_t n) {
         void* q = nullptr;
@@ -408,7 +431,8 @@ template <class G> struct EngineT : gaz_engine {
         E.node_bytes = gumbel ? gumbel_node_bytes<G>() : NodeLayout<G>::SIZE;
         // re-root compaction: needed where a whole-game arena does not fit (Gomoku: 4.2 KB records); 0 = auto
         E.compact = gumbel ? 0 : (cfg.compact_trees == 0 ? (G::ID == GAME_GMK ? 1 : 0) : (cfg.compact_trees > 0 ? 1 : 0));
-        lbk = cfg.leaf_batch > 1 ? cfg.leaf_batch : 1; rows = (size_t)n * lbk;
+        gbk = gumbel && cfg.gumbel_batch > 1 ? cfg.gumbel_batch : 1;
+        lbk = gbk > 1 ? gbk : (cfg.leaf_batch > 1 ? cfg.leaf_batch : 1); rows = (size_t)n * lbk;
         E.n_games = n; n_eff = n; E.run_iterations = cfg.run_iterations; E.max_actions = cfg.max_actions;
         if (cfg.max_actions > G::MAXT || cfg.max_actions <= 0) return fail("max_actions out of range for this game");
         E.explore_first = cfg.num_explore_actions_first; E.explore_second = cfg.num_explore_actions_second;
@@ -462,7 +486,8 @@ template <class G> struct EngineT : gaz_engine {
         if (dalloc(&E.trees, (size_t)n * 2)) return 1;
         if (dalloc(&E.games, (size_t)n)) return 1;
         if (dalloc(&E.paths, rows * PathCap<G>::V)) return 1;
-        if (lbk > 1) { LB.K = lbk; if (dalloc(&LB.pend, rows)) return 1; }
+        if (lbk > 1 && gbk <= 1) { LB.K = lbk; if (dalloc(&LB.pend, rows)) return 1; }
+        if (gbk > 1) { GB.K = gbk; if (dalloc(&GB.rows, rows)) return 1; }
         if (gumbel) { GumbelState<G>* gp = nullptr; if (dalloc(&gp, (size_t)n)) return 1; E.gstate = gp; }
         if (dalloc(&E.recs, (size_t)n * RL::SIZE)) return 1;
         if (dalloc(&E.ring, (size_t)(cfg.ring_capacity > 0 ? cfg.ring_capacity : 1) * RL::SIZE)) return 1;
@@ -548,6 +573,11 @@ template <class G> struct EngineT : gaz_engine {
     void launch_wave(hipStream_t st, int g0, int g1, const DevParams<G>& E) {
         // the small boards run four games per wavefront (PuctVariant: same records, 16-lane teams); GAZ_TREE_TEAMS=0 -> one per wave
         typedef typename PuctVariant<G>::type GP;
+        if (gbk > 1) {                                // (Gumbel only, no evaluation cache: gaz_engine_create refuses the rest; the register budget of k_wave_lb)
+            constexpr int PER = WAVE / GP::TEAM;
+            GAZ_LAUNCH(k_wave_gb<GP>, (g1 - g0 + PER - 1) / PER, WAVE, st, *reinterpret_cast<const DevParams<GP>*>(&E), GB, g0, g1);
+            return;
+        }
         if (lbk > 1) {                                // (PUCT only, no evaluation cache: gaz_engine_create refuses the rest)
             // one register budget for all three games (the four-games-per-wavefront one): the K-leaf step serves few games, occupancy is
             // not what limits it, and with it the step needs no scratch (Gomoku under k_wave's budget: 156 spilled VGPRs)
@@ -637,7 +667,7 @@ template <class G> struct EngineT : gaz_engine {
         return true;
     }
     int debug_fused_fault(int mod) override {
-        if (lbk > 1 && mod > 0) return fail("debug_fused_fault: leaf_batch > 1 runs separate launches only");
+        if (lbk > 1 && mod > 0) return fail(std::string("debug_fused_fault: ") + (gbk > 1 ? "gumbel_batch" : "leaf_batch") + " > 1 runs separate launches only");
         if (mod > 0 && !ensure_skip_buffers()) return 1;
         debug_fault_mod = mod > 0 ? (unsigned)mod : 0u;
         return 0;
@@ -651,6 +681,7 @@ template <class G> struct EngineT : gaz_engine {
     int32_t* dMoveList = nullptr;
     int repack(int32_t* n_active_out, int32_t* n_eff_out) override {
         if (E.sync_moves) return fail("repack needs continuous self-play (sync_moves = 0)");
+        if (gbk > 1) return fail("repack: not with gumbel_batch > 1 (a game owns gumbel_batch rows of the batch)");
         if (lbk > 1) return fail("repack: not with leaf_batch > 1 (a game owns leaf_batch rows of the batch)");
         HIP_OK(hipStreamSynchronize(stream));
         if (pipeline_ready) { HIP_OK(hipStreamSynchronize(tstream)); HIP_OK(hipStreamSynchronize(hstream)); }
@@ -916,7 +947,8 @@ template <class G> struct EngineT : gaz_engine {
     int read_batch(int8_t* inputs, int32_t* pending) override {
         if (inputs) HIP_OK(hipMemcpyAsync(inputs, E.nn_in, rows * G::HW * G::C, hipMemcpyDeviceToHost, stream));
         if (pending) {
-            if (lbk > 1) GAZ_LAUNCH(k_gather_pending_lb<G>, E.n_games, WAVE, stream, E, lbk, dPending);
+            if (gbk > 1) GAZ_LAUNCH(k_gather_pending_gb<G>, E.n_games, WAVE, stream, E, GB, dPending);
+            else if (lbk > 1) GAZ_LAUNCH(k_gather_pending_lb<G>, E.n_games, WAVE, stream, E, lbk, dPending);
             else GAZ_LAUNCH(k_gather_root<G>, E.n_games, WAVE, stream, E, dN, dW, dP, dPol, dRV, dQ, dChosen, dPhase, dPending);
             HIP_OK(hipMemcpyAsync(pending, dPending, rows * 4, hipMemcpyDeviceToHost, stream));
         }
@@ -934,7 +966,7 @@ template <class G> struct EngineT : gaz_engine {
     int evaluate(const int8_t* in, int n, float* pol, float* val, int repeats, double* ms) override {
         if (!eval) return fail("evaluate: no built-in evaluator");
         if (!eval->ready()) return fail("evaluate: evaluator weights not loaded");
-        if (n <= 0 || (size_t)n > rows) return fail("evaluate: n must be in [1, " + std::to_string(rows) + "] (the rows of the evaluator batch: n_games, or n_games * leaf_batch)");
+        if (n <= 0 || (size_t)n > rows) return fail("evaluate: n must be in [1, " + std::to_string(rows) + "] (the rows of the evaluator batch: n_games, or n_games * leaf_batch / gumbel_batch)");
         HIP_OK(hipMemcpyAsync(E.nn_in, in, (size_t)n * G::HW * G::C, hipMemcpyHostToDevice, stream));
         hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
         eval->forward(stream, E.nn_in, E.nn_policy, E.nn_value, n, false);      // warm-up / the measured result
@@ -1087,7 +1119,7 @@ template <class G> struct EngineT : gaz_engine {
         if (poll_fuse_fault()) return 1;             // counts() synchronised the stream
         out[12] = (fuse_state == 1 && fuse_enabled) ? 1 : 0;
         out[13] = fuse_faults;
-        if (lbk > 1) {
+        if (lbk > 1 && gbk <= 1) {
             unsigned long long* d = reinterpret_cast<unsigned long long*>(dCount);
             HIP_OK(hipMemsetAsync(d, 0, sizeof(*d), stream));
             GAZ_LAUNCH(k_count_reserved<G>, E.n_games, WAVE, stream, E, d);
@@ -1460,7 +1492,7 @@ struct GroupEngine : gaz_engine {
 // auto (game_groups = 0): two groups where that was measured to pay (see above; measured at num_filters = 128 only, so other widths run one group); GAZ_GAME_GROUPS overrides the automatic choice only
 static int choose_game_groups(const gaz_engine_config& c) {
     if (c.game_groups != 0) return c.game_groups;
-    if (c.leaf_batch > 1) return 1;                  // K rows per game: one batch
+    if (c.leaf_batch > 1 || c.gumbel_batch > 1) return 1;   // K rows per game: one batch
     static const int env = getenv("GAZ_GAME_GROUPS") ? atoi(getenv("GAZ_GAME_GROUPS")) : 0;
     const bool able = !c.sync_moves && c.evaluator != GAZ_EVAL_EXTERNAL && !(c.games_budget > 0 && c.games_budget < c.n_games);
     if (env > 0) return (able && env <= c.n_games) ? env : 1;
@@ -1491,6 +1523,13 @@ int gaz_engine_create(const gaz_engine_config* cfg, gaz_engine** out) {
         return 1;
     }
     if (cfg->game_groups < 0) { g_create_error = "game_groups must be >= 0"; return 1; }
+    if (cfg->gumbel_batch < 0 || cfg->gumbel_batch > 64) { g_create_error = "gumbel_batch must be in [0, 64] (0 and 1 = one candidate of sequential halving per game and wave)"; return 1; }
+    if (cfg->gumbel_batch > 1) {                     // the chunk step exists for the Gumbel search with one batch and no evaluation cache
+        if (cfg->leaf_batch > 1) { g_create_error = "gumbel_batch > 1 cannot be combined with leaf_batch > 1"; return 1; }
+        if (cfg->search != GAZ_SEARCH_GUMBEL) { g_create_error = "gumbel_batch > 1 needs search = GAZ_SEARCH_GUMBEL (the PUCT search has leaf_batch)"; return 1; }
+        if (cfg->eval_cache_log2 > 0) { g_create_error = "gumbel_batch > 1 cannot be combined with eval_cache_log2 > 0"; return 1; }
+        if (cfg->game_groups > 1) { g_create_error = "gumbel_batch > 1 cannot be combined with game_groups > 1"; return 1; }
+    }
     if (cfg->leaf_batch < 0 || cfg->leaf_batch > 64) { g_create_error = "leaf_batch must be in [0, 64] (0 and 1 = one leaf per game and wave)"; return 1; }
     if (cfg->leaf_batch > 1) {                       // the K-leaf step exists for the PUCT search with one batch and no evaluation cache
         if (cfg->search == GAZ_SEARCH_GUMBEL) { g_create_error = "leaf_batch > 1 needs search = GAZ_SEARCH_PUCT (the Gumbel search plans its simulations itself)"; return 1; }

@@ -27,6 +27,23 @@ template <class G> struct GumbelState {          // per game, lives across launc
     uint8_t top_ids[G::APAD];
 };
 
+// batched sequential halving (gaz_engine_config::gumbel_batch = K > 1): what the K > 1 kernel gets next to DevParams (whose nn_in / nn_policy /
+// nn_value then hold n_games * K rows and paths [n_games][K][PathCap]).  A phase's candidate list top_ids[0 .. n_top) is served in consecutive
+// chunks of K; GumbelState::cand is the first candidate of the chunk in progress (stage 0 = its rows are not set up yet), and row j of the game
+// belongs to candidate cand + j.  Everything a visit touches belongs to its root child (the subtree, the child's own N / W slot of the root, the
+// integer root.visits), so the candidates of a chunk advance interleaved and the statistics come out as if they had been visited one by one.
+struct GbRow {
+    int32_t stage;             // 0: the root child has not been looked at, 1: visits
+    int32_t sims_left;         // visits of this phase still to run
+    int32_t counts;            // the request in flight is a visit (an iteration); 0 = the root child's own expansion, which is none
+    int32_t pend;              // 1 = a request is in flight in this row: g_expand_post's arguments follow, the path is parked in the row's paths slice
+    int32_t parent, slot, node, depth;
+};
+struct GumbelBatch {
+    int32_t K;                 // candidates in flight per game and wave; 1 = off (rows is null)
+    GbRow* rows;               // [n_games][K]
+};
+
 template <class G> GAZ_DEV float* node_raw(const NodeRef<G>& nd) {
     return reinterpret_cast<float*>(nd.p + NodeLayout<G>::SIZE);      // RAW[APAD] is appended after the PUCT record
 }
@@ -316,8 +333,8 @@ template <class G> GAZ_DEV bool g_halving(const DevParams<G>& E, GumbelState<G>&
     return take > 1;
 }
 
-// create_expand_root, first half
-template <class G> GAZ_DEV bool g_root_pre(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, Scratch<G>& S) {
+// create_expand_root, first half.  `row`: the game's row of the evaluator batch that takes the request (g, or g * K with gumbel_batch = K)
+template <class G> GAZ_DEV bool g_root_pre(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, Scratch<G>& S, int row) {
     if (tlane<G>() == 0) { ts.n_nodes = 0; ts.root = -1; ts.root_visits = 0; }
     wave_sync();
     copy_board<G>(S.board, gs.board);
@@ -349,7 +366,7 @@ template <class G> GAZ_DEV bool g_root_pre(const DevParams<G>& E, int g, GameSta
         wave_sync();
         return false;
     }
-    encode_input<G>(S.board, -gs.next_player, h3, gs.n_hist, E.nn_in + (size_t)g * (G::HW * G::C), E.done_flag != nullptr);
+    encode_input<G>(S.board, -gs.next_player, h3, gs.n_hist, E.nn_in + (size_t)row * (G::HW * G::C), E.done_flag != nullptr);
     wave_sync();
     return true;
 }
@@ -370,8 +387,9 @@ template <class G> GAZ_DEV void g_write_children(const DevParams<G>& E, int g, c
 
 // _expand of child `index` of `node`; path[0..depth) leads to node.  true = evaluation pending
 // `staged`: the descent left this node's header + child blocks in S.node (saves two dependent round trips)
+// `row`: the row of the evaluator batch (and of E.paths) that takes the request
 template <class G> GAZ_DEV bool g_expand_pre(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, Scratch<G>& S,
-                                             int node, int index, int depth, bool staged = false) {
+                                             int node, int index, int depth, int row, bool staged = false) {
     NodeRef<G> pn = node_at(E, g, 0, node);
     const NodeRef<G> ps = staged ? NodeRef<G>{reinterpret_cast<uint8_t*>(S.node)} : pn;
     const NodeHdr ph = *ps.hdr();
@@ -412,8 +430,8 @@ template <class G> GAZ_DEV bool g_expand_pre(const DevParams<G>& E, int g, GameS
         return false;
     }
     uint8_t h3[3] = {(uint8_t)action, ph.hist3[0], ph.hist3[1]};
-    encode_input<G>(S.board, mover, h3, (int)ph.n_hist + 1, E.nn_in + (size_t)g * (G::HW * G::C), E.done_flag != nullptr);
-    PathEnt* gp = E.paths + (size_t)g * PathCap<G>::V;
+    encode_input<G>(S.board, mover, h3, (int)ph.n_hist + 1, E.nn_in + (size_t)row * (G::HW * G::C), E.done_flag != nullptr);
+    PathEnt* gp = E.paths + (size_t)row * PathCap<G>::V;
     for (int d = tlane<G>(); d <= depth; d += G::TEAM) gp[d] = S.path[d];
     if (tlane<G>() == 0) {
         gs.pend_kind = PEND_EXPAND; gs.pend_tree = 0; gs.pend_parent = node; gs.pend_slot = index; gs.pend_node = idx;
@@ -424,7 +442,7 @@ template <class G> GAZ_DEV bool g_expand_pre(const DevParams<G>& E, int g, GameS
 }
 
 template <class G> GAZ_DEV void g_expand_post(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, Scratch<G>& S,
-                                              const float* policy, const float* value_p, bool fresh = false) {
+                                              const float* policy, const float* value_p, int row, bool fresh = false) {
     const int node = gs.pend_parent, index = gs.pend_slot, idx = gs.pend_node, depth = gs.pend_depth;
     NodeRef<G> nd = node_at(E, g, 0, idx);
     g_write_children<G>(E, g, nd, S, policy, fresh);
@@ -432,7 +450,7 @@ template <class G> GAZ_DEV void g_expand_post(const DevParams<G>& E, int g, Game
     const float value = *value_p;
     if (tlane<G>() == 0) { pn.child()[index] = idx; node_raw<G>(pn)[index] = value; }       // MCTS_Gumbel.py:516-517
     if (!fresh) {
-        const PathEnt* gp = E.paths + (size_t)g * PathCap<G>::V;
+        const PathEnt* gp = E.paths + (size_t)row * PathCap<G>::V;
         for (int d = tlane<G>(); d < depth; d += G::TEAM) S.path[d] = gp[d];
     }
     wave_sync();
@@ -470,23 +488,139 @@ template <class G> GAZ_DEV void g_move_end(const DevParams<G>& E, int g, GameSta
     wave_sync();
 }
 
+// gumbel_batch > 1: one simulation below root child `id` (MCTS_Gumbel.py:626-645) — the descent of g_game_step_body's PH_SIMS, which keeps its
+// own copy because it goes on to the evaluation cache.  It ends at an unexpanded edge (`pending`: its evaluation request was written to row
+// `row` of the batch, or it made a terminal parent and was backed up) or at a terminal child, backed up here.  false = a device error was raised
+template <class G> GAZ_DEV bool g_visit(const DevParams<G>& E, int g, GameState<G>& gs, GumbelState<G>& gu, TreeState& ts, Scratch<G>& S, int id, int row,
+                                        bool& pending) {
+    int node = ts.root, depth = 0, slot = id;
+    bool staged = false;
+    pending = false;
+    const long long td0 = GAZ_PROF_NOW();
+    for (;;) {
+        // below the root the record of `node` is already in LDS (staged for its deterministic_selection)
+        const int c = staged ? tuni<G>(NodeRef<G>{reinterpret_cast<uint8_t*>(S.node)}.child()[slot]) : tuni<G>(node_at(E, g, 0, node).child()[slot]);
+        if (depth >= PathCap<G>::V - 1) { set_error(E.error, ERR_PATH_OVERFLOW); return false; }
+        if (c == CHILD_NONE) {                                         // expand (node, slot)
+            if (tlane<G>() == 0) gu.pend_counts = 1;
+            wave_sync();
+            const long long te0 = GAZ_PROF_NOW();
+            pending = g_expand_pre<G>(E, g, gs, ts, S, node, slot, depth, row, staged);
+            GAZ_PROF(2, te0);
+            break;
+        }
+        S.path[depth].node = node; S.path[depth].slot = slot; depth++;
+        if (c == CHILD_LEAF_WIN || c == CHILD_LEAF_DRAW) {             // terminal child: value 1 / 0 (:635-637)
+            wave_sync();
+            backup<G>(E, g, 0, ts, S.path, depth, c == CHILD_LEAF_WIN ? 1.0f : 0.0f, 1u);
+            break;
+        }
+        node = c;
+        NodeRef<G> cn = g_stage_node<G>(E, g, node, S); staged = true;
+        slot = g_det_select<G>(E, cn, S.raw, tuni<G>((int)cn.hdr()->n_actions), S);
+    }
+    GAZ_PROF(1, td0);                                              // descent incl. its expand_pre (slot 2 is counted twice)
+    return true;
+}
+
+// gumbel_batch = K > 1: the chunk of candidates [cand, cand + K) of the current phase, one launch's worth.  Every candidate of the chunk advances
+// until it needs the network, has used its visits, or has started max_tree_sims visits in this launch; the team walks the rows one after the other
+// and the visits of one candidate stay strictly sequential.  true = the game yields (requests in flight, or visits left for the next launch)
+template <class G> GAZ_DEV bool g_chunk_step(const DevParams<G>& E, const GumbelBatch& B, int g, GameState<G>& gs, GumbelState<G>& gu, TreeState& ts,
+                                             Scratch<G>& S) {
+    GbRow* R = B.rows + (size_t)g * B.K;
+    const int cand0 = tuni<G>(gu.cand), n_top = tuni<G>(gu.n_top);
+    const int nrow = n_top - cand0 < B.K ? n_top - cand0 : B.K;
+    if (tuni<G>(gu.stage) == 0) {                                              // a new chunk: every row starts at its root child
+        // ALL K rows, not only the chunk's: the rows live outside GameState, so a game that was reset or repositioned with requests in flight
+        // (gaz_engine_reset_games / gaz_engine_set_position clear GameState::pend_kind, and PH_MOVE_BEGIN brings the game back here with
+        // stage 0) may have left pend = 1 in a row this chunk does not use
+        const int vpc = tuni<G>(gu.vpc);
+        for (int j = tlane<G>(); j < B.K; j += G::TEAM) { R[j].stage = 0; R[j].sims_left = vpc; R[j].counts = 0; R[j].pend = 0; }
+        if (tlane<G>() == 0) gu.stage = 1;
+        wave_sync();
+    }
+    bool open = false;                                                         // a row has a request in flight or visits left
+    for (int j = 0; j < nrow; ++j) {
+        const int id = tuni<G>((int)gu.top_ids[cand0 + j]);
+        const int row = g * B.K + j;
+        for (int started = 0;;) {
+            if (tuni<G>(R[j].stage) == 0) {                                        // expand the root child first (not an iteration)
+                if (tlane<G>() == 0) R[j].stage = 1;
+                wave_sync();
+                if (tuni<G>(node_at(E, g, 0, ts.root).child()[id]) != CHILD_NONE) continue;
+                if (g_expand_pre<G>(E, g, gs, ts, S, ts.root, id, 0, row)) {
+                    if (tlane<G>() == 0) { R[j].counts = 0; R[j].pend = 1; R[j].parent = gs.pend_parent; R[j].slot = gs.pend_slot; R[j].node = gs.pend_node; R[j].depth = gs.pend_depth; }
+                    wave_sync();
+                    open = true;
+                    break;
+                }
+                if (tuni<G>(*E.error)) return true;
+                continue;
+            }
+            if (tuni<G>(R[j].sims_left) <= 0) break;                               // this candidate has used its visits
+            // per candidate, not per launch: one whose visits all end at terminals must not hold back the requests of the others.  The worst
+            // launch is K x max_tree_sims evaluation-free visits of one team one after the other (K = 64 at the default 4: 256 short descents)
+            if (started >= E.max_tree_sims) { open = true; break; }
+            started++;
+            bool pending;
+            if (!g_visit<G>(E, g, gs, gu, ts, S, id, row, pending)) return true;
+            if (tuni<G>(*E.error)) return true;
+            if (pending) {
+                if (tlane<G>() == 0) { R[j].counts = 1; R[j].pend = 1; R[j].parent = gs.pend_parent; R[j].slot = gs.pend_slot; R[j].node = gs.pend_node; R[j].depth = gs.pend_depth; }
+                wave_sync();
+                open = true;
+                break;
+            }
+            if (tlane<G>() == 0) { R[j].sims_left -= 1; gu.cur_iter += 1; gs.n_sims += 1; }
+            wave_sync();
+        }
+    }
+    if (open) return true;
+    if (tlane<G>() == 0) { gu.cand = cand0 + nrow; gu.stage = 0; }      // chunk finished: the next one, or the end of the phase
+    wave_sync();
+    return false;
+}
+
 // (fin: see puct_core.hpp game_step_body — the game's epilogue runs inside the phase loop, where the game yields)
-template <class G, class Fin> GAZ_DEV void g_game_step_body(const DevParams<G>& E, int g, Scratch<G>& S, GameState<G>& gs, GumbelState<G>& gu, TreeState& ts, Fin&& fin) {
+// GB: the gumbel_batch > 1 step (B.K rows per game; no evaluation cache, no hand-over to a trunk workgroup: gaz_engine_create refuses the rest)
+template <class G, bool GB = false, class Fin> GAZ_DEV void g_game_step_body(const DevParams<G>& E, int g, Scratch<G>& S, GameState<G>& gs, GumbelState<G>& gu, TreeState& ts, Fin&& fin,
+                                                                             const GumbelBatch& B = GumbelBatch{1, nullptr}) {
     using RL = RecLayout<G>;
+    const int row0 = GB ? g * B.K : g;              // the game's first row of the evaluator batch
 
     const long long tp0 = GAZ_PROF_NOW();
     if (E.prof && tlane<G>() == 0) E.prof[(size_t)g * 8 + 7] += 1;
     if (tuni<G>(gs.pend_kind) == PEND_ROOT) {
-        g_write_children<G>(E, g, node_at(E, g, 0, ts.root), S, E.nn_policy + (size_t)g * G::A);
+        g_write_children<G>(E, g, node_at(E, g, 0, ts.root), S, E.nn_policy + (size_t)row0 * G::A);
         if (tlane<G>() == 0) { gs.pend_kind = PEND_NONE; gs.roots_todo = 0; gs.n_evals += 1; }
         wave_sync();
     } else if (tuni<G>(gs.pend_kind) == PEND_EXPAND) {
-        g_expand_post<G>(E, g, gs, ts, S, E.nn_policy + (size_t)g * G::A, E.nn_value + g);
+        if constexpr (GB) {                         // every row the evaluator pass answered, in row order
+            // (PEND_EXPAND is only ever set inside a chunk in progress: its rows are [0, min(K, n_top - cand)), the ones g_chunk_step set up)
+            GbRow* R = B.rows + (size_t)g * B.K;
+            const int left = tuni<G>(gu.n_top) - tuni<G>(gu.cand), nrow = left < B.K ? (left > 0 ? left : 0) : B.K;
+            for (int j = 0; j < nrow; ++j) {
+                if (!tuni<G>(R[j].pend)) continue;
+                if (tlane<G>() == 0) { gs.pend_parent = R[j].parent; gs.pend_slot = R[j].slot; gs.pend_node = R[j].node; gs.pend_depth = R[j].depth; }
+                wave_sync();
+                g_expand_post<G>(E, g, gs, ts, S, E.nn_policy + (size_t)(row0 + j) * G::A, E.nn_value + row0 + j, row0 + j);
+                if (tlane<G>() == 0) {
+                    R[j].pend = 0; gs.n_evals += 1; gs.move_evals += 1;
+                    if (R[j].counts) { R[j].sims_left -= 1; gu.cur_iter += 1; gs.n_sims += 1; }
+                }
+                wave_sync();
+            }
+            if (tlane<G>() == 0) gs.pend_kind = PEND_NONE;
+            wave_sync();
+        } else {
+        g_expand_post<G>(E, g, gs, ts, S, E.nn_policy + (size_t)g * G::A, E.nn_value + g, g);
         if (tlane<G>() == 0) {
             gs.pend_kind = PEND_NONE; gs.n_evals += 1; gs.move_evals += 1;
             if (gu.pend_counts) { gu.sims_left -= 1; gu.cur_iter += 1; gs.n_sims += 1; }
         }
         wave_sync();
+        }
     }
 
     GAZ_PROF(0, tp0);
@@ -503,7 +637,7 @@ template <class G, class Fin> GAZ_DEV void g_game_step_body(const DevParams<G>& 
         } else if (phase == PH_ROOT) {
             if (tuni<G>(gs.roots_todo) == 0) { if (tlane<G>() == 0) gs.phase = PH_MOVE_BEGIN; wave_sync(); return false; }
             if (tlane<G>() == 0) gs.move_evals = 0;
-            if (g_root_pre<G>(E, g, gs, ts, S)) {
+            if (g_root_pre<G>(E, g, gs, ts, S, row0)) {
                 const uint8_t* hit = E.cache ? cache_probe<G>(E, g) : nullptr;
                 if (hit) {                                                     // evaluation cache hit
                     g_write_children<G>(E, g, node_at(E, g, 0, ts.root), S, reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_POL), true);
@@ -556,16 +690,17 @@ template <class G, class Fin> GAZ_DEV void g_game_step_body(const DevParams<G>& 
                 if (!go) { if (tlane<G>() == 0) gs.phase = PH_MOVE_END; wave_sync(); }
                 return false;
             }
+            if constexpr (GB) return g_chunk_step<G>(E, B, g, gs, gu, ts, S);
             const int id = tuni<G>((int)gu.top_ids[tuni<G>(gu.cand)]);
             if (tuni<G>(gu.stage) == 0) {                                          // expand the root child first (not an iteration)
                 if (tlane<G>() == 0) { gu.stage = 1; gu.sims_left = gu.vpc; gu.pend_counts = 0; }
                 wave_sync();
                 if (tuni<G>(r.child()[id]) == CHILD_NONE) {
-                    if (g_expand_pre<G>(E, g, gs, ts, S, ts.root, id, 0)) {
+                    if (g_expand_pre<G>(E, g, gs, ts, S, ts.root, id, 0, g)) {
                         const uint8_t* hit = E.cache ? cache_probe<G>(E, g) : nullptr;
                         if (!hit) return true;
                         g_expand_post<G>(E, g, gs, ts, S, reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_POL),
-                                         reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_VAL), true);   // hit: not an iteration (pend_counts = 0)
+                                         reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_VAL), g, true);   // hit: not an iteration (pend_counts = 0)
                         if (tlane<G>() == 0) { gs.pend_kind = PEND_NONE; gs.n_evals += 1; gs.move_evals += 1; gs.n_hits += 1; }
                         wave_sync();
                     }
@@ -576,7 +711,7 @@ template <class G, class Fin> GAZ_DEV void g_game_step_body(const DevParams<G>& 
             if (tuni<G>(gu.sims_left) <= 0) { if (tlane<G>() == 0) { gu.cand += 1; gu.stage = 0; } wave_sync(); return false; }
             if (tree_only >= E.max_tree_sims) return true;
             tree_only++;
-            // one simulation below root child `id`
+            // one simulation below root child `id` (g_visit is this descent for the batched step; this one goes on to the evaluation cache)
             int node = ts.root, depth = 0, slot = id;
             bool done = false, pending = false, staged = false;
             const long long td0 = GAZ_PROF_NOW();
@@ -588,7 +723,7 @@ template <class G, class Fin> GAZ_DEV void g_game_step_body(const DevParams<G>& 
                     if (tlane<G>() == 0) gu.pend_counts = 1;
                     wave_sync();
                     const long long te0 = GAZ_PROF_NOW();
-                    pending = g_expand_pre<G>(E, g, gs, ts, S, node, slot, depth, staged);
+                    pending = g_expand_pre<G>(E, g, gs, ts, S, node, slot, depth, g, staged);
                     GAZ_PROF(2, te0);
                     done = !pending;
                     break;
@@ -612,7 +747,7 @@ template <class G, class Fin> GAZ_DEV void g_game_step_body(const DevParams<G>& 
                 if (!hit) return true;
                 const long long tx0 = GAZ_PROF_NOW();
                 g_expand_post<G>(E, g, gs, ts, S, reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_POL),
-                                 reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_VAL), true);   // hit: the simulation completes in this launch
+                                 reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_VAL), g, true);   // hit: the simulation completes in this launch
                 GAZ_PROF(4, tx0);
                 if (tlane<G>() == 0) { gs.pend_kind = PEND_NONE; gs.n_evals += 1; gs.move_evals += 1; gs.n_hits += 1; }
                 wave_sync();
@@ -694,6 +829,19 @@ template <class G> GAZ_DEV void g_game_step(const DevParams<G>& E, int g, Scratc
         publish_done<G>(E, g, block_rank, block);
         GAZ_PROF(6, tw0);
     });
+}
+
+// the gumbel_batch > 1 step of game g (separate launches only: no hand-over to a trunk workgroup, every row is evaluated every wave)
+template <class G> GAZ_DEV void g_game_step_gb(const DevParams<G>& E, const GumbelBatch& B, int g, Scratch<G>& S, GumbelLocal<G>& L) {
+    GameState<G>* gsG = &E.games[g];
+    GumbelState<G>* guG = &reinterpret_cast<GumbelState<G>*>(E.gstate)[g];
+    TreeState* tsG = &E.trees[(size_t)g * 2];
+    copy_state_words<G>(&L.gs, gsG); copy_state_words<G>(&L.gu, guG); copy_state_words<G>(&L.ts, tsG);
+    wave_sync();
+    g_game_step_body<G, true>(E, g, S, L.gs, L.gu, L.ts, [&]() {
+        wave_sync();
+        copy_state_words<G>(gsG, &L.gs); copy_state_words<G>(guG, &L.gu); copy_state_words<G>(tsG, &L.ts);
+    }, B);
 }
 
 }  // namespace gaz

@@ -19,7 +19,7 @@ EVAL_HASH, EVAL_RESNET, EVAL_EXTERNAL = 0, 1, 2
 PH_WAIT_HOST, PH_HALT, PH_IDLE = 5, 8, 9
 
 
-ABI_VERSION = 6               # GAZ_ENGINE_ABI_VERSION of include/gaz_engine.h this binding was written against
+ABI_VERSION = 7               # GAZ_ENGINE_ABI_VERSION of include/gaz_engine.h this binding was written against
 
 
 class EngineConfig(C.Structure):       # gaz_engine_config — tests/test_abi.py checks names, order and sizeof against the header
@@ -34,7 +34,7 @@ class EngineConfig(C.Structure):       # gaz_engine_config — tests/test_abi.py
                 ("single_tree", C.c_int32), ("n_opening", C.c_int32), ("opening_actions", C.c_int32 * 8),
                 ("opening_weights", C.c_double * 8), ("max_tree_sims_per_wave", C.c_int32), ("eval_cache_log2", C.c_int32), ("gumbel_stablemax", C.c_int32), ("fast_find_win", C.c_int32),
                 ("no_gumbel_noise", C.c_int32), ("first_game_seq", C.c_uint32), ("games_budget", C.c_int64), ("tau", C.c_double), ("move_time_limit", C.c_double), ("game_groups", C.c_int32),
-                ("leaf_batch", C.c_int32)]
+                ("leaf_batch", C.c_int32), ("gumbel_batch", C.c_int32)]
 
 
 class SearchHyperparams(C.Structure):  # gaz_search_hyperparams
@@ -168,7 +168,8 @@ class SelfPlayEngine:
                  evaluator=EVAL_HASH, hash_salt=0, device=0, net_blocks=0, net_filters=128, search=SEARCH_PUCT,
                  policy_is_logits=False, max_tree_sims_per_wave=0, gumbel_m=0, c_visit=50.0, c_scale=1.0,
                  compact_trees=0, single_tree=False, opening_actions=None, eval_cache_log2=0, gumbel_stablemax=False, fast_find_win=False,
-                 use_gumbel_noise=True, first_game_seq=0, games_budget=0, tau=-1.0, move_time_limit=0.0, game_groups=0, leaf_batch=1, lib_path=None):
+                 use_gumbel_noise=True, first_game_seq=0, games_budget=0, tau=-1.0, move_time_limit=0.0, game_groups=0, leaf_batch=1, gumbel_batch=1,
+                 lib_path=None):
         self.L = load_library(lib_path)
         self.game_id = GAME_IDS[game] if isinstance(game, str) else int(game)
         self.H, self.W, self.Cc, self.A = GAME_DIMS[self.game_id]
@@ -187,7 +188,7 @@ class SelfPlayEngine:
                                 gumbel_stablemax=int(gumbel_stablemax), fast_find_win=int(fast_find_win),
                                 no_gumbel_noise=int(not use_gumbel_noise), first_game_seq=int(first_game_seq), games_budget=int(games_budget),
                                 tau=float(tau), move_time_limit=float(move_time_limit or 0.0), game_groups=int(game_groups),
-                                leaf_batch=int(leaf_batch))
+                                leaf_batch=int(leaf_batch), gumbel_batch=int(gumbel_batch))
         for i, (a, w) in enumerate(opening_actions or []):       # [(action index, weight)] — train_config["opening_actions"]
             self.cfg.opening_actions[i] = int(a); self.cfg.opening_weights[i] = float(w); self.cfg.n_opening = i + 1
         self.h = C.c_void_p()
@@ -195,8 +196,10 @@ class SelfPlayEngine:
             raise EngineError(self.L.gaz_engine_last_error(None).decode())
         self.layout = RecordLayout()
         self._ck(self.L.gaz_engine_record_layout(self.h, C.byref(self.layout)))
-        self.batch_rows = n_games            # rows of the evaluator batch: n_games * leaf_batch with leaf_batch > 1 (row g * K + j = leaf j of game g)
-        if self.cfg.game_groups <= 1 and self.cfg.leaf_batch > 1:
+        # rows of the evaluator batch: n_games * K with leaf_batch = K > 1 (row g * K + j = leaf j of game g) or gumbel_batch = K > 1 (row g * K + j =
+        # candidate j of game g's current chunk of sequential halving)
+        self.batch_rows = n_games
+        if self.cfg.game_groups <= 1 and (self.cfg.leaf_batch > 1 or self.cfg.gumbel_batch > 1):
             r = C.c_int32()
             self._ck(self.L.gaz_engine_batch_rows(self.h, C.byref(r)))
             self.batch_rows = int(r.value)

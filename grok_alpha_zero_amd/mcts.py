@@ -4,7 +4,9 @@ one-game engine: same constructor arguments, `run(iteration_limit, time_limit, u
 sampling run in the HIP kernels; `session.run(["policy", "value"], {"inputs": x})` (MCTS.py:224-235) is called once per
 simulation with a batch of one, exactly where the reference calls it.  `MCTS(..., leaf_batch=K)` (no reference counterpart: its
 roadmap's "Virtual Loss for Parallel MCTS") lets the tree keep up to K leaves in flight: `session.run` then gets the pending leaves
-of a wave stacked into one batch `[n_pending, H, W, C]` — a different, deterministic search (DESIGN.md "Leaf-batched PUCT search").  `session=None` selects the synthetic evaluator
+of a wave stacked into one batch `[n_pending, H, W, C]` — a different, deterministic search (DESIGN.md "Leaf-batched PUCT search").
+`MCTS_Gumbel(..., gumbel_batch=K)` keeps up to K candidates of a sequential-halving phase in flight and stacks their requests the same
+way — the same search, bit for bit, in fewer `session.run` calls (DESIGN.md "Batched sequential halving").  `session=None` selects the synthetic evaluator
 (the reference's uniform-random dummy, MCTS.py:237-241, is not reproducible by construction).
 
 For throughput use `SelfPlayEngine` / `run_self_play` (thousands of games per launch); these classes exist so code written
@@ -73,7 +75,7 @@ class _EngineSearch:
                         return
                     continue
                 x, pend = eng.read_batch()
-                rows = np.flatnonzero(pend)                      # one row per simulation; with leaf_batch = K up to K rows of a wave
+                rows = np.flatnonzero(pend)                      # one row per simulation; with leaf_batch / gumbel_batch = K up to K rows of a wave
                 if rows.size:
                     policy, value = self.session.run(output_names=["policy", "value"], input_feed={"inputs": x[rows].astype(np.float32)})
                     pol = np.zeros((eng.batch_rows, eng.A), np.float32); val = np.zeros(eng.batch_rows, np.float32)
@@ -174,13 +176,14 @@ class MCTS(_EngineSearch):
 
 class MCTS_Gumbel(_EngineSearch):
     def __init__(self, game, session, use_gumbel_noise=False, use_njit=None, m=16, c_visit=50.0, c_scale=0.1,
-                 activation_fn="softmax", fast_find_win=False, *, seed=None, hash_salt=0, max_actions=None, lib_path=None):
+                 activation_fn="softmax", fast_find_win=False, *, seed=None, hash_salt=0, max_actions=None, gumbel_batch=1,
+                 lib_path=None):
         if activation_fn not in ("softmax", "stablemax"):
             raise ValueError("activation_fn must be 'softmax' or 'stablemax'")
         self.m, self.c_visit, self.c_scale, self.use_gumbel_noise = m, c_visit, c_scale, use_gumbel_noise
         self._attach(game, session, seed, lib_path, max_actions=max_actions or int(np.prod(game.board.shape)), hash_salt=hash_salt,
                      search=SEARCH_GUMBEL, gumbel_m=m, c_visit=c_visit, c_scale=c_scale, gumbel_stablemax=activation_fn == "stablemax",
-                     fast_find_win=bool(fast_find_win), use_gumbel_noise=bool(use_gumbel_noise))
+                     fast_find_win=bool(fast_find_win), use_gumbel_noise=bool(use_gumbel_noise), gumbel_batch=int(gumbel_batch))
 
     def update_hyperparams(self, *args, **kwargs):                                       # MCTS_Gumbel.py:186-210
         upd = {k: kwargs[k] for k in ("m", "c_visit", "c_scale") if kwargs.get(k) is not None}

@@ -390,7 +390,7 @@ class _ReplayWriter:
 def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, *, n_games=1024, seed=None, weights=None,
                   device=0, slot_offset=0, hash_salt=0, lib_path=None, progress=None, eval_cache_log2=22, generation=None,
                   first_game_seq=None, allow_synthetic=False, engine_stats=None, game_groups=0, device_samples=None,
-                  max_pending_bytes=1 << 30, leaf_batch=1):
+                  max_pending_bytes=1 << 30, leaf_batch=1, gumbel_batch=1):
     """Generate `games_per_generation - game_stats[2]` self-play games into `folder_path` (Self_Play.py:259-272).
     (`engine_stats`: a dict that receives the engine's counters — evaluator calls, simulations, waves — when the generation is done,
     and the host's timers: `gpu_wait_seconds` / `sample_seconds` / `queue_wait_seconds` of the thread that queues the waves (waiting for
@@ -402,7 +402,10 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
     written by a thread of its own, fed through a queue of at most `max_pending_bytes` of samples.
     `game_groups`: gaz_engine_config.game_groups, scheduling only: 0 = the library's choice, 1 = one batch.
     `leaf_batch`: gaz_engine_config.leaf_batch; above 1 (PUCT only) every game keeps up to that many leaves in flight per wave — a
-    different search, for generations of few games; the evaluation cache and the repack of generation tails are off then.)
+    different search, for generations of few games; the evaluation cache and the repack of generation tails are off then.
+    `gumbel_batch`: gaz_engine_config.gumbel_batch; above 1 (use_gumbel only) every game keeps up to that many candidates of a halving
+    phase in flight per wave — the same games byte for byte in fewer launches, for generations of few games; the evaluation cache
+    and the repack of generation tails are off then.)
     `configs` = (build_config, train_config[, optimizer_config]).  `weights` = dict from net.export_engine_weights()
     (generation > 0); generation 0 (folder name "0") plays with the synthetic evaluator like the reference's
     session=None dummy (Self_Play.py:40, MCTS.py:237-241).
@@ -460,12 +463,12 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
                          evaluator=EVAL_RESNET if use_net else EVAL_HASH, hash_salt=hash_salt,
                          net_blocks=build_config.get("num_resnet_layers", 0) if use_net else 0,
                          net_filters=build_config.get("num_filters", 128), ring_capacity=max(4 * G, 64), lib_path=lib_path,
-                         eval_cache_log2=0 if leaf_batch > 1 else eval_cache_log2,    # on-device Session_Cache (Self_Play.py:234-236): same games, fewer waves
+                         eval_cache_log2=0 if leaf_batch > 1 or gumbel_batch > 1 else eval_cache_log2,    # on-device Session_Cache (Self_Play.py:234-236): same games, fewer waves
                          games_budget=games_left, first_game_seq=first_game_seq,
                          # Self_Play.py:35,100-112: every MCTS.run gets time_limit = MCTS_time_limit next to its iteration limit; the engine keeps a
                          # wall clock per game and move (PUCT) / runs 3 x legal moves iterations per move (Gumbel, MCTS_Gumbel.py:576-578)
                          move_time_limit=float(train_config.get("MCTS_time_limit") or 0.0), game_groups=game_groups,
-                         leaf_batch=leaf_batch)
+                         leaf_batch=leaf_batch, gumbel_batch=gumbel_batch)
     if train_config.get("MCTS_time_limit") and gumbel:
         logging.getLogger("grok_alpha_zero_amd").warning("Time limit isn't allowed for gumbel MCTS defaulting to use 3 * len_legal_actions")   # MCTS_Gumbel.py:578
     logging.getLogger("grok_alpha_zero_amd").info("run_self_play: generation %d, %d games on %d slots, evaluator = %s, game_seq from %d",
@@ -496,7 +499,7 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
             # tail of the generation: every game has been started and the slots halt one by one, but a wave still evaluates all
             # of them — once half of the covered slots are idle, move the live games together and shrink the launches
             remaining = games_left - written - got                  # games not finished yet >= games still running
-            if 0 < remaining and remaining * 2 <= launch and launch > 16 and leaf_batch <= 1:
+            if 0 < remaining and remaining * 2 <= launch and launch > 16 and leaf_batch <= 1 and gumbel_batch <= 1:
                 _, launch = eng.repack()
             eng.run_waves(64)                       # queue the next ones right away: the GPU works while the host converts and writes
             if device_samples:                      # every game is one of the admitted games (games_budget)

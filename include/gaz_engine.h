@@ -35,6 +35,8 @@
  *   gaz_engine_read_head_features  intermediate tensors of that probe (numerics tests)  Connect4/Build_Model.py:41-47,62-66
  *   gaz_engine_config.leaf_batch / gaz_engine_batch_rows  (no reference counterpart: several leaves of one tree per evaluator batch, kept
  *                                  apart by a virtual loss — the first open item of the reference's roadmap, README.md:59)
+ *   gaz_engine_config.gumbel_batch  (scheduling of MCTS_Gumbel.run's loop over the surviving root children, MCTS_Gumbel.py:625-645: the
+ *                                  candidates of one halving phase in one evaluator batch, same results)
  */
 #ifndef GAZ_ENGINE_H
 #define GAZ_ENGINE_H
@@ -51,7 +53,7 @@ enum { GAZ_EVAL_HASH = 0,      /* synthetic bit-reproducible evaluator (parity t
        GAZ_EVAL_RESNET = 1,    /* the ResNet policy/value network, HIP MFMA kernels */
        GAZ_EVAL_EXTERNAL = 2   /* caller evaluates the batch between wave_begin / wave_end */ };
 
-#define GAZ_ENGINE_ABI_VERSION 6   /* bumped whenever gaz_engine_config / gaz_search_hyperparams / an entry point changes */
+#define GAZ_ENGINE_ABI_VERSION 7   /* bumped whenever gaz_engine_config / gaz_search_hyperparams / an entry point changes */
 
 typedef struct {
     uint32_t struct_size;         /* = sizeof(gaz_engine_config) of the header the caller was built against; gaz_engine_create
@@ -128,6 +130,21 @@ typedef struct {
                                      rows (gaz_engine_batch_rows), row g * K + j = leaf j of game g; game_groups = 0 resolves to 1 and the tree step and the
                                      evaluator run as separate launches.  Refused by gaz_engine_create with search = GAZ_SEARCH_GUMBEL, eval_cache_log2 > 0,
                                      game_groups > 1, or a value above 64; gaz_engine_repack is refused on such an engine */
+    int32_t gumbel_batch;         /* Gumbel search only.  0 / 1: one candidate of sequential halving per game and wave.  K in 2..64: a game keeps up to K
+                                     candidates of the current halving phase in flight per wave, each with a leaf of its own.  The phase's candidate list is
+                                     served in consecutive chunks of K (the last one may be shorter); a chunk is finished when every one of its candidates
+                                     has its root child expanded and has used its visits, then the next chunk starts, and after the last one the phase ends
+                                     as with 1.  A launch first applies every row the previous evaluator pass answered, in row order, then every candidate
+                                     of the chunk advances until it needs the network again, has used its visits, or has started max_tree_sims_per_wave
+                                     visits in this launch (scheduling only here); within one candidate the visits stay strictly sequential, and a move
+                                     ends only with nothing in flight.  Everything a visit touches belongs to its root child, so the SAME search comes out,
+                                     bit for bit: records, evaluator calls, simulations, root visits and RNG events per move are those of gumbel_batch = 1
+                                     (node indices inside the arena may differ) — in fewer launches (DESIGN.md "Batched sequential halving").
+                                     The batch then has n_games * K rows (gaz_engine_batch_rows), row g * K + j = candidate chunk * K + j of game g;
+                                     game_groups = 0 resolves to 1 and the tree step and the evaluator run as separate launches.  Raising gumbel_m above K
+                                     with gaz_engine_set_hyperparams is legal (more chunks).  Refused by gaz_engine_create with search = GAZ_SEARCH_PUCT,
+                                     eval_cache_log2 > 0, game_groups > 1, leaf_batch > 1, or a value above 64; gaz_engine_repack and
+                                     gaz_engine_debug_fused_fault are refused on such an engine */
 } gaz_engine_config;
 
 /* MCTS.update_hyperparams(**kwargs) (MCTS.py:134-168) / MCTS_Gumbel.update_hyperparams (MCTS_Gumbel.py:186-210): values take
@@ -181,7 +198,8 @@ int gaz_engine_read_batch(gaz_engine* h, int8_t* inputs, int32_t* pending);    /
 int gaz_engine_write_outputs(gaz_engine* h, const float* policy, const float* value);   /* host -> device rows: [rows][A], [rows] */
 /* rows of the evaluator batch: n_games, or n_games * leaf_batch with leaf_batch > 1 — then read_batch, write_outputs and batch_ptrs address
  * that many rows, pending[g * leaf_batch + j] says whether row g * leaf_batch + j (leaf j of game g) carries a request, and
- * gaz_engine_evaluate takes up to that many rows.  Rows nobody requested are evaluated and ignored. */
+ * gaz_engine_evaluate takes up to that many rows.  Rows nobody requested are evaluated and ignored.  The same with gumbel_batch = K > 1:
+ * n_games * K rows, and pending[] is per row — the rows of a game that carry a request need not be its first ones. */
 int gaz_engine_batch_rows(gaz_engine* h, int32_t* rows);
 
 /* place one slot at the position reached by `n` actions from the empty board (new roots are built there).  The game keeps its
