@@ -1,6 +1,7 @@
 // engine.hip — host side of libgaz_engine.so: owns the HBM state, launches the wave kernel + evaluator
 // once per simulation wave on one HIP stream, and implements the C ABI of include/gaz_engine.h.
 #include <stdio.h>
+#include <functional>
 #include <string>
 #include <vector>
 #include "../../include/gaz_engine.h"
@@ -8,6 +9,7 @@
 #include "puct_core.hpp"
 #include "gumbel_core.hpp"
 #include "samples.hpp"
+#include "tree_export.hpp"
 #include "evaluator.hpp"
 
 using namespace gaz;
@@ -361,8 +363,26 @@ struct gaz_engine {
     virtual int set_fused_wave(int) = 0;
     virtual int debug_fused_fault(int) = 0;
     virtual int read_positions(int32_t*, uint8_t*, int) = 0;
+    // gaz_engine_read_trees / gaz_engine_read_pv behind the argument checks of the C entry points (slots in range, tree id valid for this engine)
+    // node_first / edge_first are always filled.  With `want_records`, `place` is then asked ONCE, with the totals, where the records go: it
+    // returns non-zero to refuse (its own error text stands), or sets both pointers to arrays of at least that size
+    typedef std::function<int(int64_t n_nodes, int64_t n_edges, gaz_tree_node** nodes, gaz_tree_edge** edges)> TreePlace;
+    virtual int read_trees(const int32_t* slots, int n_slots, int tree, int max_depth, uint32_t min_visits, int64_t* node_first, int64_t* edge_first,
+                           bool want_records, const TreePlace& place) = 0;
+    virtual int read_pv(int tree, const int32_t* first_action, int max_len, uint8_t* actions, uint32_t* N, float* W, int32_t* len) = 0;
+    int short_capacity(int64_t need_nodes, int64_t need_edges, int64_t max_nodes, int64_t max_edges) {
+        return fail("read_trees: the export needs " + std::to_string(need_nodes) + " nodes and " + std::to_string(need_edges) + " edges, max_nodes is " +
+                    std::to_string(max_nodes) + " and max_edges is " + std::to_string(max_edges));
+    }
     virtual int repack(int32_t*, int32_t*) = 0;
     virtual int probe_rules(const int32_t*, const int32_t*, int, int, int8_t*, uint8_t*, int32_t*, int8_t*, int32_t*, const float*, float*) = 0;
+};
+
+// device allocations that live for one call (gaz_engine_read_trees / gaz_engine_read_pv)
+struct CallScratch {
+    std::vector<void*> p;
+    ~CallScratch() { for (void* q : p) hipFree(q); }
+    template <class T> T* get(size_t n) { void* q = nullptr; if (hipMalloc(&q, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr; p.push_back(q); return (T*)q; }
 };
 
 template <class G> struct EngineT : gaz_engine {
@@ -1172,6 +1192,82 @@ template <class G> struct EngineT : gaz_engine {
         }
         return 0;
     }
+    // ---- gaz_engine_read_trees / gaz_engine_read_pv (tree_export.hpp).  Scratch and staging are allocated per call, from the sizes of the
+    // requested trees (the queue: their TreeState::n_nodes) and of the export itself — nothing scales with n_games x nodes_per_tree.
+    int read_trees(const int32_t* slots, int n, int tree, int max_depth, uint32_t min_visits, int64_t* node_first, int64_t* edge_first,
+                   bool want_records, const TreePlace& place) override {
+        typedef typename PuctVariant<G>::type GP;
+        constexpr int PER = WAVE / GP::TEAM;
+        node_first[0] = 0; edge_first[0] = 0;
+        if (n == 0) { HIP_OK(hipStreamSynchronize(stream)); return 0; }
+        const DevParams<GP>& EP = *reinterpret_cast<const DevParams<GP>*>(&E);
+        CallScratch cs;
+        int32_t* d_slots = cs.get<int32_t>(n); int32_t* d_cap = cs.get<int32_t>(n);
+        long long* d_qfirst = cs.get<long long>((size_t)n + 1); long long* d_counts = cs.get<long long>((size_t)2 * n);
+        if (!d_slots || !d_cap || !d_qfirst || !d_counts) return fail("read_trees: out of device memory");
+        HIP_OK(hipMemcpyAsync(d_slots, slots, sizeof(int32_t) * n, hipMemcpyHostToDevice, stream));
+#ifdef GAZ_HOST_EMU
+        GAZ_LAUNCH(k_tree_caps<G>, n, 1, stream, E, (const int32_t*)d_slots, n, tree, d_cap);
+#else
+        GAZ_LAUNCH(k_tree_caps<G>, (n + 255) / 256, 256, stream, E, (const int32_t*)d_slots, n, tree, d_cap);
+#endif
+        HIP_OK(hipGetLastError());
+        std::vector<int32_t> cap(n);
+        HIP_OK(hipMemcpyAsync(cap.data(), d_cap, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        std::vector<long long> first((size_t)n + 1, 0);
+        for (int i = 0; i < n; ++i) first[i + 1] = first[i] + cap[i];
+        ExportQ* d_queue = cs.get<ExportQ>((size_t)first[n]);
+        if (!d_queue) return fail("read_trees: out of device memory");
+        HIP_OK(hipMemcpyAsync(d_qfirst, first.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, stream));
+        TreeExportArgs X; memset(&X, 0, sizeof(X));
+        X.slots = d_slots; X.n_slots = n; X.tree = tree; X.max_depth = max_depth; X.min_visits = min_visits;
+        X.queue = d_queue; X.q_first = d_qfirst; X.counts = d_counts;
+        GAZ_LAUNCH((k_tree_export<GP, false>), (n + PER - 1) / PER, WAVE, stream, EP, X);
+        HIP_OK(hipGetLastError());
+        std::vector<long long> counts((size_t)2 * n);
+        HIP_OK(hipMemcpyAsync(counts.data(), d_counts, sizeof(long long) * 2 * (size_t)n, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        std::vector<long long> nf((size_t)n + 1, 0), ef((size_t)n + 1, 0);
+        for (int i = 0; i < n; ++i) { nf[i + 1] = nf[i] + counts[2 * i]; ef[i + 1] = ef[i] + counts[2 * i + 1]; }
+        for (int i = 0; i <= n; ++i) { node_first[i] = nf[i]; edge_first[i] = ef[i]; }
+        if (!want_records) return 0;
+        gaz_tree_node* nodes = nullptr; gaz_tree_edge* edges = nullptr;
+        if (place(nf[n], ef[n], &nodes, &edges)) return 1;
+        if (nf[n] == 0) return 0;
+        long long* d_nf = cs.get<long long>((size_t)n + 1); long long* d_ef = cs.get<long long>((size_t)n + 1);
+        gaz_tree_node* d_nodes = cs.get<gaz_tree_node>((size_t)nf[n]); gaz_tree_edge* d_edges = cs.get<gaz_tree_edge>((size_t)ef[n]);
+        if (!d_nf || !d_ef || !d_nodes || !d_edges) return fail("read_trees: out of device memory");
+        HIP_OK(hipMemcpyAsync(d_nf, nf.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(d_ef, ef.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, stream));
+        X.node_first = d_nf; X.edge_first = d_ef; X.nodes = d_nodes; X.edges = d_edges;
+        GAZ_LAUNCH((k_tree_export<GP, true>), (n + PER - 1) / PER, WAVE, stream, EP, X);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(nodes, d_nodes, sizeof(gaz_tree_node) * (size_t)nf[n], hipMemcpyDeviceToHost, stream));
+        if (ef[n]) HIP_OK(hipMemcpyAsync(edges, d_edges, sizeof(gaz_tree_edge) * (size_t)ef[n], hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    int read_pv(int tree, const int32_t* first_action, int max_len, uint8_t* actions, uint32_t* N, float* W, int32_t* len) override {
+        typedef typename PuctVariant<G>::type GP;
+        constexpr int PER = WAVE / GP::TEAM;
+        const size_t n = (size_t)E.n_games, cells = n * (size_t)max_len;
+        CallScratch cs;
+        int32_t* d_first = first_action ? cs.get<int32_t>(n) : nullptr;
+        uint8_t* d_act = cs.get<uint8_t>(cells); uint32_t* d_N = cs.get<uint32_t>(cells); float* d_W = cs.get<float>(cells); int32_t* d_len = cs.get<int32_t>(n);
+        if ((first_action && !d_first) || !d_act || !d_N || !d_W || !d_len) return fail("read_pv: out of device memory");
+        if (first_action) HIP_OK(hipMemcpyAsync(d_first, first_action, sizeof(int32_t) * n, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemsetAsync(d_act, 0, cells, stream)); HIP_OK(hipMemsetAsync(d_N, 0, cells * 4, stream)); HIP_OK(hipMemsetAsync(d_W, 0, cells * 4, stream));
+        GAZ_LAUNCH(k_tree_pv<GP>, (E.n_games + PER - 1) / PER, WAVE, stream, *reinterpret_cast<const DevParams<GP>*>(&E), tree, (const int32_t*)d_first, max_len,
+                   d_act, d_N, d_W, d_len);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(actions, d_act, cells, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipMemcpyAsync(N, d_N, cells * 4, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipMemcpyAsync(W, d_W, cells * 4, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipMemcpyAsync(len, d_len, n * 4, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        return 0;
+    }
     int start_search() override { GAZ_LAUNCH(k_start_search<G>, E.n_games, WAVE, stream, E); HIP_OK(hipGetLastError()); return 0; }
     int stop_search(int stop) override { E.stop_search = stop != 0; return 0; }
     // tau != 0 and tau <= 5e-3 -> 0 (MCTS.py:116-120,163-168); negative = Self_Play's schedule
@@ -1479,6 +1575,42 @@ struct GroupEngine : gaz_engine {
         if (!n_hist || !hist || stride < lay.max_T) return fail("read_positions: hist must hold at least max_T actions per slot");
         return each([&](gaz_engine* k, int c) { return k->read_positions(n_hist + first[c], hist + (size_t)first[c] * stride, stride); });
     }
+    // the slots of every group in ONE call of that group, into staging arrays of the group's own size; the trees are then placed at the caller's positions
+    int read_trees(const int32_t* slots, int n, int tree, int max_depth, uint32_t min_visits, int64_t* node_first, int64_t* edge_first,
+                   bool want_records, const TreePlace& place) override {
+        std::vector<std::vector<int32_t>> local(K()), pos(K());
+        for (int i = 0; i < n; ++i) { const int c = group_of(slots[i]); local[c].push_back(slots[i] - first[c]); pos[c].push_back(i); }
+        std::vector<std::vector<int64_t>> nf(K()), ef(K());
+        std::vector<std::vector<gaz_tree_node>> tn(K()); std::vector<std::vector<gaz_tree_edge>> te(K());
+        std::vector<int64_t> cn((size_t)n, 0), ce((size_t)n, 0);
+        for (int c = 0; c < K(); ++c) {
+            const int m = (int)local[c].size();
+            nf[c].assign((size_t)m + 1, 0); ef[c].assign((size_t)m + 1, 0);
+            const TreePlace stage = [&, c](int64_t nn, int64_t ne, gaz_tree_node** pn, gaz_tree_edge** pe) {
+                tn[c].resize((size_t)nn + 1); te[c].resize((size_t)ne + 1); *pn = tn[c].data(); *pe = te[c].data(); return 0;
+            };
+            if (up(kid[c], kid[c]->read_trees(local[c].data(), m, tree, max_depth, min_visits, nf[c].data(), ef[c].data(), want_records, stage))) return 1;
+            for (int j = 0; j < m; ++j) { cn[pos[c][j]] = nf[c][j + 1] - nf[c][j]; ce[pos[c][j]] = ef[c][j + 1] - ef[c][j]; }
+        }
+        node_first[0] = 0; edge_first[0] = 0;
+        for (int i = 0; i < n; ++i) { node_first[i + 1] = node_first[i] + cn[i]; edge_first[i + 1] = edge_first[i] + ce[i]; }
+        if (!want_records) return 0;
+        gaz_tree_node* nodes = nullptr; gaz_tree_edge* edges = nullptr;
+        if (place(node_first[n], edge_first[n], &nodes, &edges)) return 1;
+        for (int c = 0; c < K(); ++c)
+            for (size_t j = 0; j < pos[c].size(); ++j) {
+                const int i = pos[c][j];
+                if (cn[i]) memcpy(nodes + node_first[i], tn[c].data() + nf[c][j], sizeof(gaz_tree_node) * (size_t)cn[i]);
+                if (ce[i]) memcpy(edges + edge_first[i], te[c].data() + ef[c][j], sizeof(gaz_tree_edge) * (size_t)ce[i]);
+            }
+        return 0;
+    }
+    int read_pv(int tree, const int32_t* fa, int max_len, uint8_t* actions, uint32_t* N, float* W, int32_t* len) override {
+        return each([&](gaz_engine* k, int c) {
+            const size_t o = (size_t)first[c] * (size_t)max_len;
+            return k->read_pv(tree, fa ? fa + first[c] : fa, max_len, actions + o, N + o, W + o, len + first[c]);
+        });
+    }
     int repack(int32_t* n_active, int32_t* n_launch) override {      // every group packs its own live games; the sums are reported
         int32_t a = 0, l = 0;
         if (each([&](gaz_engine* k, int) { int32_t x = 0, y = 0; if (k->repack(&x, &y)) return 1; a += x; l += y; return 0; })) return 1;
@@ -1590,6 +1722,36 @@ int gaz_engine_set_hyperparams(gaz_engine* h, const gaz_search_hyperparams* hp) 
 int gaz_engine_set_fused_wave(gaz_engine* h, int32_t on) { return h->set_fused_wave(on); }
 int gaz_engine_debug_fused_fault(gaz_engine* h, int32_t mod) { return h->debug_fused_fault(mod); }
 int gaz_engine_read_positions(gaz_engine* h, int32_t* n_hist, uint8_t* hist, int32_t stride) { return h->read_positions(n_hist, hist, stride); }
+// a tree id this engine has: 0 / 1, or -1 = the tree running the move; single_tree and Gumbel engines keep one tree per game
+static int check_tree_arg(gaz_engine* h, const char* fn, int32_t tree) {
+    if (tree < -1 || tree > 1) return h->fail(std::string(fn) + ": tree must be 0, 1 or -1 (the tree running the game's move), not " + std::to_string(tree));
+    if (tree == 1 && (h->cfg.single_tree || h->cfg.search == GAZ_SEARCH_GUMBEL))
+        return h->fail(std::string(fn) + ": tree = 1 on an engine with one tree per game (single_tree or the Gumbel search); use tree = 0 or -1");
+    return 0;
+}
+int gaz_engine_read_trees(gaz_engine* h, const int32_t* slots, int32_t n_slots, int32_t tree, int32_t max_depth, uint32_t min_visits, int64_t max_nodes,
+                          int64_t max_edges, gaz_tree_node* nodes, gaz_tree_edge* edges, int64_t* node_first, int64_t* edge_first) {
+    if (n_slots < 0) return h->fail("read_trees: n_slots must be >= 0, not " + std::to_string(n_slots));
+    if (!node_first || !edge_first || (n_slots > 0 && !slots)) return h->fail("read_trees: slots, node_first and edge_first must not be null");
+    if (check_tree_arg(h, "read_trees", tree)) return 1;
+    if ((nodes == nullptr) != (edges == nullptr)) return h->fail("read_trees: nodes and edges must both be given, or both be null (counting call)");
+    if (nodes && (max_nodes < 0 || max_edges < 0)) return h->fail("read_trees: max_nodes and max_edges must be >= 0");
+    for (int32_t i = 0; i < n_slots; ++i)
+        if (slots[i] < 0 || slots[i] >= h->cfg.n_games)
+            return h->fail("read_trees: slots[" + std::to_string(i) + "] = " + std::to_string(slots[i]) + " is out of range [0, " + std::to_string(h->cfg.n_games) + ")");
+    // too little capacity: refused before anything is written to the caller's arrays
+    const gaz_engine::TreePlace place = [&](int64_t nn, int64_t ne, gaz_tree_node** pn, gaz_tree_edge** pe) {
+        if (nn > max_nodes || ne > max_edges) return h->short_capacity(nn, ne, max_nodes, max_edges);
+        *pn = nodes; *pe = edges; return 0;
+    };
+    return h->read_trees(slots, n_slots, tree, max_depth, min_visits, node_first, edge_first, nodes != nullptr, place);
+}
+int gaz_engine_read_pv(gaz_engine* h, int32_t tree, const int32_t* first_action, int32_t max_len, uint8_t* actions, uint32_t* N, float* W, int32_t* len) {
+    if (max_len <= 0) return h->fail("read_pv: max_len must be positive, not " + std::to_string(max_len));
+    if (!actions || !N || !W || !len) return h->fail("read_pv: actions, N, W and len must not be null");
+    if (check_tree_arg(h, "read_pv", tree)) return 1;
+    return h->read_pv(tree, first_action, max_len, actions, N, W, len);
+}
 int gaz_engine_repack(gaz_engine* h, int32_t* n_active, int32_t* n_launch) { return h->repack(n_active, n_launch); }
 int gaz_engine_read_head_features(gaz_engine* h, int32_t n, float* p, float* v, int32_t* p_row, int32_t* v_row) { return h->read_head_features(n, p, v, p_row, v_row); }
 int gaz_engine_probe_rules(gaz_engine* h, const int32_t* actions, const int32_t* n_actions, int32_t n_positions, int32_t stride, int8_t* board,

@@ -19,7 +19,7 @@ EVAL_HASH, EVAL_RESNET, EVAL_EXTERNAL = 0, 1, 2
 PH_WAIT_HOST, PH_HALT, PH_IDLE = 5, 8, 9
 
 
-ABI_VERSION = 7               # GAZ_ENGINE_ABI_VERSION of include/gaz_engine.h this binding was written against
+ABI_VERSION = 8               # GAZ_ENGINE_ABI_VERSION of include/gaz_engine.h this binding was written against
 
 
 class EngineConfig(C.Structure):       # gaz_engine_config — tests/test_abi.py checks names, order and sizeof against the header
@@ -55,6 +55,13 @@ class RecordLayout(C.Structure):
 class SampleLayout(C.Structure):        # gaz_sample_layout
     _fields_ = [(n, C.c_int32) for n in ("n_aug", "state_bytes", "A", "max_T")]
 
+
+# gaz_tree_node / gaz_tree_edge (include/gaz_engine.h): the records of SelfPlayEngine.read_trees
+TREE_NODE_DTYPE = np.dtype([(n, np.int32) for n in ("parent", "slot", "depth", "edge0", "n_actions", "n_children", "flags", "n_reserved", "player",
+                                                   "action", "n_hist", "reserved_")])
+TREE_EDGE_DTYPE = np.dtype([("action", np.int32), ("N", np.uint32), ("W", np.float32), ("P", np.float32), ("raw", np.float32), ("child", np.int32)])
+CHILD_NONE, CHILD_DRAW, CHILD_WIN, CHILD_FILTERED = -1, -2, -3, -4
+NF_TERMINAL_PARENT = 1
 
 _LIBS = {}
 
@@ -106,6 +113,8 @@ def load_library(lib_path=None):
     L.gaz_engine_debug_fused_fault.argtypes = [H, C.c_int32]
     L.gaz_engine_read_positions.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32]
     L.gaz_engine_repack.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.gaz_engine_read_trees.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_int64, C.c_int64] + [C.c_void_p] * 4
+    L.gaz_engine_read_pv.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4
     L.gaz_engine_read_head_features.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.gaz_engine_dominant_kernel.argtypes = [H, C.c_char_p, C.c_int32, C.POINTER(C.c_double)]
     L.gaz_engine_timing_get.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -113,7 +122,7 @@ def load_library(lib_path=None):
     for f in ("create", "load_weights", "reset_games", "run_move", "get_root_stats", "apply_moves", "run_waves", "wave_begin",
               "wave_end", "batch_ptrs", "read_batch", "write_outputs", "batch_rows", "evaluate", "record_layout", "drain_finished", "sample_layout", "drain_samples", "get_stats",
               "synchronize", "timing_reset", "timing_get", "dominant_kernel", "set_position", "set_search_params", "start_search", "stop_search",
-              "set_hyperparams", "probe_rules", "read_head_features", "set_fused_wave", "debug_fused_fault", "read_positions", "repack"):
+              "set_hyperparams", "probe_rules", "read_head_features", "set_fused_wave", "debug_fused_fault", "read_positions", "repack", "read_trees", "read_pv"):
         getattr(L, "gaz_engine_" + f).restype = C.c_int
     _LIBS[path] = L
     return L
@@ -156,6 +165,36 @@ class SampleBatch:
         T, winner, r0 = int(self.games[i, 0]), int(self.games[i, 1]), int(self.games[i, 4]) - int(self.games[0, 4])
         v = np.broadcast_to(self.values[None, r0:r0 + T], (self.policies.shape[0], T, 1))
         return self.boards[:, r0:r0 + T], self.policies[:, r0:r0 + T], v, T, T, winner
+
+
+class SearchTree:
+    """One search tree as SelfPlayEngine.read_trees returns it (include/gaz_engine.h, gaz_engine_read_trees): `nodes` (TREE_NODE_DTYPE) in
+    breadth-first order from the root — index 0, parent -1 — and `edges` (TREE_EDGE_DTYPE), one per child slot of every node: node i owns
+    edges[edge0 : edge0 + n_actions].  An edge's `child` is the index of the child node, or CHILD_NONE / CHILD_DRAW / CHILD_WIN /
+    CHILD_FILTERED.  `slot` = the engine slot it was read from.  A slot without a tree gives empty arrays."""
+
+    def __init__(self, slot, nodes, edges):
+        self.slot, self.nodes, self.edges = int(slot), nodes, edges
+
+    def __len__(self):
+        return self.nodes.shape[0]
+
+    def edges_of(self, i):
+        """the edge records of node i, in slot order (a view)"""
+        n = self.nodes[i]
+        return self.edges[int(n["edge0"]):int(n["edge0"]) + int(n["n_actions"])]
+
+    def children(self, i):
+        """indices of node i's child nodes that are part of this export, in slot order"""
+        c = self.edges_of(i)["child"]
+        return [int(x) for x in c[c >= 0]]
+
+    def path_actions(self, i):
+        """action indices that lead from the root to node i"""
+        out = []
+        while self.nodes[i]["parent"] >= 0:
+            out.append(int(self.nodes[i]["action"])); i = int(self.nodes[i]["parent"])
+        return out[::-1]
 
 
 class SelfPlayEngine:
@@ -277,6 +316,36 @@ class SelfPlayEngine:
         n = np.zeros(self.cfg.n_games, np.int32); h = np.zeros((self.cfg.n_games, T), np.uint8)
         self._ck(self.L.gaz_engine_read_positions(self.h, n.ctypes.data, h.ctypes.data, T))
         return [h[g, :n[g]].astype(np.int32).tolist() for g in range(self.cfg.n_games)]
+
+    def read_trees(self, slots, tree=-1, max_depth=None, min_visits=0):
+        """The search trees of `slots` -> list of SearchTree, in that order.  tree = 0 / 1, or -1 = the tree running the slot's current move;
+        max_depth None = everything, else nodes deeper than that are left out; a child node is exported only if its edge has
+        N >= min_visits.  Legal at any time, also in the middle of a move (nodes["n_reserved"] then shows the leaves in flight)."""
+        s = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = int(s.size)
+        nf = np.zeros(n + 1, np.int64); ef = np.zeros(n + 1, np.int64)
+        depth = -1 if max_depth is None else int(max_depth)
+        if depth < 0 and max_depth is not None:
+            raise ValueError("max_depth must be None or >= 0")
+        self._ck(self.L.gaz_engine_read_trees(self.h, s.ctypes.data, n, int(tree), depth, int(min_visits), 0, 0, None, None, nf.ctypes.data, ef.ctypes.data))
+        nodes = np.zeros(max(int(nf[n]), 1), TREE_NODE_DTYPE); edges = np.zeros(max(int(ef[n]), 1), TREE_EDGE_DTYPE)
+        self._ck(self.L.gaz_engine_read_trees(self.h, s.ctypes.data, n, int(tree), depth, int(min_visits), int(nf[n]), int(ef[n]), nodes.ctypes.data,
+                                              edges.ctypes.data, nf.ctypes.data, ef.ctypes.data))
+        return [SearchTree(s[i], nodes[nf[i]:nf[i + 1]], edges[ef[i]:ef[i + 1]]) for i in range(n)]
+
+    def principal_variations(self, max_len, tree=-1, first_action=None):
+        """The most visited line below every slot's root (ties: the lowest slot) -> dict(actions uint8 [G, max_len], N uint32, W float32, len
+        int32 [G]); entries past len are 0.  first_action [G] (< 0 = most visited) names the first step: the move a finished search chose."""
+        G, m = self.n_games, int(max_len)
+        out = dict(actions=np.zeros((G, max(m, 0)), np.uint8), N=np.zeros((G, max(m, 0)), np.uint32), W=np.zeros((G, max(m, 0)), np.float32), len=np.zeros(G, np.int32))
+        fa = None
+        if first_action is not None:
+            fa = np.ascontiguousarray(first_action, np.int32).reshape(-1)
+            if fa.size != G:
+                raise ValueError("first_action needs one entry per game")
+        self._ck(self.L.gaz_engine_read_pv(self.h, int(tree), None if fa is None else fa.ctypes.data, m, out["actions"].ctypes.data, out["N"].ctypes.data,
+                                           out["W"].ctypes.data, out["len"].ctypes.data))
+        return out
 
     def start_search(self):
         self._ck(self.L.gaz_engine_start_search(self.h))

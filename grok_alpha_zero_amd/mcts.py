@@ -6,7 +6,9 @@ simulation with a batch of one, exactly where the reference calls it.  `MCTS(...
 roadmap's "Virtual Loss for Parallel MCTS") lets the tree keep up to K leaves in flight: `session.run` then gets the pending leaves
 of a wave stacked into one batch `[n_pending, H, W, C]` — a different, deterministic search (DESIGN.md "Leaf-batched PUCT search").
 `MCTS_Gumbel(..., gumbel_batch=K)` keeps up to K candidates of a sequential-halving phase in flight and stacks their requests the same
-way — the same search, bit for bit, in fewer `session.run` calls (DESIGN.md "Batched sequential halving").  `session=None` selects the synthetic evaluator
+way — the same search, bit for bit, in fewer `session.run` calls (DESIGN.md "Batched sequential halving").  `.root` is the reference's
+`MCTS.root` (Root / Node objects with `children`, `child_visits`, `child_values`, `child_prob_priors`, `is_terminal`, ...) read back from the
+engine on access, and `.pv(max_len)` the principal variation of the last `run()` (DESIGN.md "Reading search trees back").  `session=None` selects the synthetic evaluator
 (the reference's uniform-random dummy, MCTS.py:237-241, is not reproducible by construction).
 
 For throughput use `SelfPlayEngine` / `run_self_play` (thousands of games per launch); these classes exist so code written
@@ -19,7 +21,8 @@ from warnings import warn
 
 import numpy as np
 
-from .engine import EVAL_EXTERNAL, EVAL_HASH, PH_HALT, PH_IDLE, PH_WAIT_HOST, SEARCH_GUMBEL, SEARCH_PUCT, SelfPlayEngine
+from .engine import (CHILD_DRAW, CHILD_WIN, EVAL_EXTERNAL, EVAL_HASH, PH_HALT, PH_IDLE, PH_WAIT_HOST, SEARCH_GUMBEL, SEARCH_PUCT,
+                     SelfPlayEngine)
 
 _W = {"TicTacToe": 3, "Gomoku": 15}
 
@@ -41,9 +44,90 @@ def _to_action(name, idx):
     return np.array([idx % _W[name], idx // _W[name]], dtype=dt)
 
 
+class Node:
+    """A node of the search tree as the reference's Node shows it (MCTS.py:20-72; MCTS_Gumbel.py:19-50), read back from the engine: a
+    read-only snapshot made when MCTS.root was accessed.  `children`: the expanded children in slot order (MCTS), or one entry per legal
+    action with None where nothing was expanded (MCTS_Gumbel); a move that ends the game is a childless node with `is_terminal` set to
+    the winner or 0 (MCTS.py:403-426).  `child_prob_priors` are raw logits for MCTS_Gumbel (also `child_logit_priors`, with
+    `child_raw_values`).  `action_history` are the game's own actions; `board` is rebuilt from it on access."""
+    def __init__(self, name, base_board, base_len, action_history, current_player, child_id=0, parent=None, is_terminal=None):
+        self._name, self._base_board, self._base_len = name, base_board, base_len
+        self.action_history, self.current_player, self.child_id, self.parent, self.is_terminal = action_history, current_player, child_id, parent, is_terminal
+        self.children = []
+        self.child_visits = np.zeros(0, np.uint32); self.child_values = np.zeros(0, np.float32); self.child_prob_priors = np.zeros(0, np.float32)
+        self.child_actions = []
+
+    @property
+    def board(self):
+        from .games import GAMES
+        G = GAMES[self._name]
+        b = self._base_board.copy()
+        player = -self.current_player if (len(self.action_history) - self._base_len) % 2 else self.current_player   # who moved into the root
+        for a in self.action_history[self._base_len:]:
+            player = -player
+            G.do_action_MCTS(b, a, player)
+        return b
+
+
+class Root(Node):
+    visits = 0
+
+
+def _build_root(name, tree, root_visits, gumbel, base_board, history):
+    """SearchTree -> Root / Node objects"""
+    if len(tree) == 0:
+        return None
+    nodes, edges = tree.nodes, tree.edges
+    objs = [None] * len(tree)
+    for i in range(len(tree)):
+        n = nodes[i]
+        if i == 0:
+            o = Root(name, base_board, len(history), list(history), int(n["player"]))
+            o.visits = int(root_visits)
+        else:
+            par = objs[int(n["parent"])]
+            o = Node(name, base_board, len(history), par.action_history + [_to_action(name, int(n["action"]))], int(n["player"]), int(n["slot"]), par)
+        objs[i] = o
+        e = tree.edges_of(i)
+        o.child_visits = e["N"].copy(); o.child_values = e["W"].copy(); o.child_prob_priors = e["P"].copy()
+        o.child_actions = [_to_action(name, int(a)) for a in e["action"]]
+        if gumbel:
+            o.child_logit_priors = o.child_prob_priors; o.child_raw_values = e["raw"].copy()
+    for i in range(len(tree)):
+        o, kids = objs[i], []
+        for s, (c, a) in enumerate(zip(tree.edges_of(i)["child"], o.child_actions)):
+            if c >= 0:
+                kids.append(objs[int(c)])
+            elif c in (CHILD_WIN, CHILD_DRAW):     # the mover of a winning move is the player to move at o
+                kids.append(Node(name, base_board, len(history), o.action_history + [a], -o.current_player, s, o,
+                                 is_terminal=-o.current_player if c == CHILD_WIN else 0))
+            elif gumbel:
+                kids.append(None)
+        o.children = kids
+    return objs[0]
+
+
 class _EngineSearch:
+    @property
+    def root(self):
+        """MCTS.root (MCTS.py:20-72,132): the whole tree below the current root as Root / Node objects, read from the engine with one
+        read_trees call on every access; None before the first run() has built a root."""
+        tree = self._eng.read_trees([0])[0]
+        return _build_root(self._name, tree, self._root_visits, self._eng.cfg.search == SEARCH_GUMBEL, np.array(self.game.board, np.int8).copy(),
+                           [np.array(a) if np.ndim(a) else a for a in self.game.action_history])
+
+    def pv(self, max_len):
+        """The principal variation after the last run(): starts at the move run() returned, then the most visited child at every node
+        (ties: the lowest slot) -> list of (action, N, W), at most max_len long."""
+        if self._chosen is None:
+            raise RuntimeError("pv(): no finished run() for the current root (call run() first; prune_tree() moves the root)")
+        r = self._eng.principal_variations(max_len, first_action=[self._chosen])
+        return [(_to_action(self._name, int(r["actions"][0, k])), int(r["N"][0, k]), float(r["W"][0, k])) for k in range(int(r["len"][0]))]
+
     def _attach(self, game, session, seed, lib_path, **engine_kw):
         self.game, self.session = game, session
+        self._chosen = None                             # action index the last run() returned, for pv(); prune_tree clears it
+        self._root_visits, self._last_N = 0, None       # Root.visits: the last run()'s, carried over by prune_tree as MCTS.py:654 does
         self._name = _game_name(game)
         if seed is None:
             seed = int.from_bytes(os.urandom(8), "little")
@@ -98,6 +182,8 @@ class _EngineSearch:
 
     def prune_tree(self, action, create_new_root=False):
         """game.do_action(action) was already called by the user (Self_Play.py:142-150); replay it on the device and re-root."""
+        self._root_visits = 0 if (create_new_root or self._last_N is None) else int(self._last_N[_to_index(self._name, action)])
+        self._last_N = self._chosen = None
         if create_new_root:
             self._eng.set_position(0, [_to_index(self._name, a) for a in self.game.action_history])
         else:
@@ -166,6 +252,8 @@ class MCTS(_EngineSearch):
         self._pump(None if time_limit is None else time.time() + float(time_limit))
         st = self._eng.root_stats()
         N, Wv, P, rv = st["N"][0], st["W"][0], st["P"][0], int(st["root_visits"][0])
+        self._root_visits, self._last_N = rv, N.copy()
+        self._chosen = int(st["chosen"][0])
         idx = [a for a in np.argsort(-P, kind="stable") if N[a] > 0 or P[a] > 0]        # child order = descending prior
         total = float(N.sum())
         term = self._child_terminal(idx)
@@ -200,6 +288,8 @@ class MCTS_Gumbel(_EngineSearch):
         self._pump()
         st = self._eng.root_stats()
         N, Wv, P, pi, rv = st["N"][0], st["W"][0], st["P"][0], st["policy"][0], int(st["root_visits"][0])
+        self._root_visits, self._last_N = rv, None
+        self._chosen = int(st["chosen"][0])
         legal = [_to_index(self._name, a) for a in self.game.get_legal_actions()]
         term = self._child_terminal(legal)
         rows = [[_to_action(self._name, a), pi[a], (float(Wv[a]) / float(N[a])) if N[a] else pi[a], Wv[a], N[a], P[a], rv, term[a]]
@@ -209,4 +299,5 @@ class MCTS_Gumbel(_EngineSearch):
 
     def prune_tree(self, action, create_new_root=False):
         # the reference rebuilds the Gumbel tree every move (Self_Play.py:151-153); so does the engine
+        self._root_visits, self._chosen = 0, None
         self._eng.apply_moves([_to_index(self._name, action)])

@@ -37,6 +37,9 @@
  *                                  apart by a virtual loss — the first open item of the reference's roadmap, README.md:59)
  *   gaz_engine_config.gumbel_batch  (scheduling of MCTS_Gumbel.run's loop over the surviving root children, MCTS_Gumbel.py:625-645: the
  *                                  candidates of one halving phase in one evaluator batch, same results)
+ *   gaz_engine_read_trees      MCTS.root and everything below it: Node.children / child_visits / child_values /
+ *                              child_prob_priors / is_terminal of every node                                MCTS.py:20-72,403-426
+ *   gaz_engine_read_pv         (no reference counterpart: the most visited line below every root)
  */
 #ifndef GAZ_ENGINE_H
 #define GAZ_ENGINE_H
@@ -53,7 +56,7 @@ enum { GAZ_EVAL_HASH = 0,      /* synthetic bit-reproducible evaluator (parity t
        GAZ_EVAL_RESNET = 1,    /* the ResNet policy/value network, HIP MFMA kernels */
        GAZ_EVAL_EXTERNAL = 2   /* caller evaluates the batch between wave_begin / wave_end */ };
 
-#define GAZ_ENGINE_ABI_VERSION 7   /* bumped whenever gaz_engine_config / gaz_search_hyperparams / an entry point changes */
+#define GAZ_ENGINE_ABI_VERSION 8   /* bumped whenever gaz_engine_config / gaz_search_hyperparams / an entry point changes */
 
 typedef struct {
     uint32_t struct_size;         /* = sizeof(gaz_engine_config) of the header the caller was built against; gaz_engine_create
@@ -305,6 +308,61 @@ int gaz_engine_repack(gaz_engine* h, int32_t* n_active, int32_t* n_launch);
  * gaz_engine_set_position takes.  n_hist int32 [n_games] (0 for a halted slot), hist uint8 [n_games][stride] with stride >= the game's
  * max_T (gaz_record_layout.max_T): row g starts at hist + g * stride, and its bytes past the history are 0.  Synchronises the engine's stream.  bench.py draws its staggered start from it. */
 int gaz_engine_read_positions(gaz_engine* h, int32_t* n_hist, uint8_t* hist, int32_t stride);
+
+/* ---- reading search trees back (DESIGN.md "Reading search trees back") ----------------------------------------------------------------
+ * A CANONICAL export of the tree below a slot's current root: it depends on the tree alone, never on where the engine keeps its node
+ * records.  Nodes come in breadth-first order from the root — parents in export order, the children of a node in slot order — and every
+ * exported node contributes one edge record per child slot [0, n_actions), in slot order, nodes in export order.  Export index 0 is the
+ * root (parent = -1, slot = 0, depth = 0), whatever the engine's record says after a re-root.  Only what is reachable from the current
+ * root is exported.  Read-only: no search state changes. */
+typedef struct {                  /* 48 bytes */
+    int32_t parent;               /* export index of the parent, -1 for the root */
+    int32_t slot;                 /* child slot in the parent (child_id, MCTS.py:32); 0 for the root */
+    int32_t depth;                /* 0 for the root */
+    int32_t edge0;                /* index of the node's first edge within this tree's edge range; its edges are [edge0, edge0 + n_actions) */
+    int32_t n_actions;            /* len(child_visits) */
+    int32_t n_children;           /* PUCT: len(children), the expanded prefix of the slots.  Gumbel search: the count of a terminal parent, else 0
+                                     (children are expanded in any order there; an edge's `child` says whether it is) */
+    int32_t flags;                /* bit 0: terminal parent — every child ends the game (edge codes -2 / -3) */
+    int32_t n_reserved;           /* leaf_batch > 1: children reserved and not yet applied (leaves in flight), slots [n_children, n_children + n_reserved) */
+    int32_t player;               /* current_player: who moved into this position (-1 / 1) */
+    int32_t action;               /* action_history[-1] as an action index (0 at the empty board) */
+    int32_t n_hist;               /* len(action_history) */
+    int32_t reserved_;            /* 0 */
+} gaz_tree_node;
+typedef struct {                  /* 24 bytes */
+    int32_t action;               /* the slot's action index */
+    uint32_t N;                   /* child_visits (with leaf_batch > 1: virtual losses of leaves in flight included) */
+    float W;                      /* child_values */
+    float P;                      /* child_prob_priors; Gumbel search: the raw logit */
+    float raw;                    /* Gumbel search: child_raw_values (the evaluator's value of the expanded child); PUCT: 0 */
+    int32_t child;                /* >= 0: export index of the child node; -1 not expanded; -2 the move draws, -3 it wins (terminal children have no
+                                     node); -4: the child has a node that max_depth / min_visits left out of this export */
+} gaz_tree_edge;
+enum { GAZ_TREE_CHILD_NONE = -1, GAZ_TREE_CHILD_DRAW = -2, GAZ_TREE_CHILD_WIN = -3, GAZ_TREE_CHILD_FILTERED = -4 };
+
+/* The trees of `n_slots` slots (any order, repeats allowed) into the caller's arrays, tree after tree in the order of `slots`: tree i has the
+ * nodes [node_first[i], node_first[i + 1]) and the edges [edge_first[i], edge_first[i + 1]).  tree = 0 / 1: that tree of the game; -1: the
+ * tree running the game's current move (a single_tree or Gumbel engine has tree 0 only: tree = 1 is refused).  A tree without a root exports
+ * nothing.  max_depth < 0: no limit, else nodes deeper than max_depth are left out; a child node is exported only if its edge has
+ * N >= min_visits; the root always is.
+ * nodes == NULL and edges == NULL: only node_first / edge_first are filled (the counts) — the first call of the usual two.  Otherwise both
+ * arrays are required, and max_nodes / max_edges below the totals is an error: last_error names the needed counts, node_first / edge_first
+ * are filled and nothing is written to nodes / edges.
+ * A host synchronisation point like gaz_engine_get_root_stats, legal at any time: between the waves of continuous self-play, and in the
+ * middle of a leaf_batch / gumbel_batch move (n_reserved then shows the leaves in flight).  With game groups the slots are forwarded to their
+ * groups and the results come back in the caller's order; after gaz_engine_repack slots are physical. */
+int gaz_engine_read_trees(gaz_engine* h, const int32_t* slots, int32_t n_slots, int32_t tree, int32_t max_depth, uint32_t min_visits,
+                          int64_t max_nodes, int64_t max_edges, gaz_tree_node* nodes, gaz_tree_edge* edges,
+                          int64_t* node_first /* [n_slots + 1] */, int64_t* edge_first /* [n_slots + 1] */);
+/* The principal variation of every slot: from the root, follow the edge with the most visits (ties: the lowest slot).  first_action
+ * (NULL, or per game; < 0 = most visited) names the first step instead — the move a finished search chose: sequential halving ends with
+ * two equally visited candidates, so "most visited" is not always the move played.  Step k of game g: actions / N / W [g * max_len + k] =
+ * the edge's action, visits and value sum; entries from len[g] on are 0.  The line ends after an edge whose child is terminal, is not
+ * expanded or has N = 0, at max_len, and before a node without children; a first_action the root does not have gives len 0.
+ * Synchronisation and slot rules as for gaz_engine_read_trees. */
+int gaz_engine_read_pv(gaz_engine* h, int32_t tree, const int32_t* first_action /* [n_games] or NULL */, int32_t max_len,
+                       uint8_t* actions, uint32_t* N, float* W /* [n_games][max_len] each */, int32_t* len /* [n_games] */);
 
 /* measurement hooks (bench.py): HIP-event timing of the kernels launched on the engine's stream */
 int gaz_engine_timing_reset(gaz_engine* h, int32_t enable);
