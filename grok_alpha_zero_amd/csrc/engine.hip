@@ -148,7 +148,7 @@ template <class G> GAZ_KERNEL k_set_position(DevParams<G> E, int g, const int32_
         const int m = n < G::MAXT ? n : G::MAXT;
         uint32_t* q = reinterpret_cast<uint32_t*>(rec + RL::OFF_Q); uint32_t* rv = reinterpret_cast<uint32_t*>(rec + RL::OFF_RV);
         uint32_t* ev = reinterpret_cast<uint32_t*>(rec + RL::OFF_EV);
-        for (int i = lane_id(); i < m; i += WAVE) { q[i] = 0u; rv[i] = 0u; ev[i] = 0u; }
+        for (int i = lane_id(); i < m; i += WAVE) { q[i] = 0u; rv[i] = 0u; ev[i] = 0u; rec[RL::OFF_MK + i] = MK_NONE; }
         uint32_t* pol = reinterpret_cast<uint32_t*>(rec + RL::OFF_POL); uint32_t* nn = reinterpret_cast<uint32_t*>(rec + RL::OFF_N);
         uint32_t* w = reinterpret_cast<uint32_t*>(rec + RL::OFF_W); uint32_t* p = reinterpret_cast<uint32_t*>(rec + RL::OFF_P);
         for (int i = lane_id(); i < m * G::A; i += WAVE) { pol[i] = 0u; nn[i] = 0u; w[i] = 0u; p[i] = 0u; }
@@ -283,6 +283,7 @@ template <class G> GAZ_KERNEL k_release(DevParams<G> E, const int32_t* moves) {
     const int g = block_id();
     if (g >= E.n_games || lane_id() != 0) return;
     GameState<G>& gs = E.games[g];
+    if (gs.phase == PH_IDLE && moves && moves[g] >= 0 && gs.n_hist < G::MAXT) E.recs[(size_t)g * RecLayout<G>::SIZE + RecLayout<G>::OFF_MK + gs.n_hist] = MK_NONE;   // played without a search
     if (gs.phase == PH_WAIT_HOST || (gs.phase == PH_IDLE && moves && moves[g] >= 0)) { gs.host_move = moves ? moves[g] : -1; gs.phase = PH_APPLY; }
 }
 
@@ -346,7 +347,7 @@ struct gaz_engine {
     virtual int drain(void* out, int max_records, int32_t* n_out) = 0;
     virtual int sample_layout(gaz_sample_layout*) = 0;
     // gaz_engine_drain_samples for one ring: the caller's arrays start at this call's first game / row, their augmentation planes are `plane_rows`
-    // rows apart, games[i][4] = row_base + the row in this call.  *blocked_T = plies of the oldest game when it alone is more than max_rows (else 0).
+    // rows apart, games[i][4] = row_base + the row in this call.  *blocked_T = rows of the oldest game when it alone is more than max_rows (else 0).
     virtual int drain_samples(int max_games, int64_t max_rows, int64_t plane_rows, int64_t row_base, int32_t* games, int8_t* boards, float* policies,
                               float* values, int32_t* n_games, int64_t* n_rows, int32_t* blocked_T) = 0;
     virtual int get_stats(uint64_t out[16]) = 0;
@@ -474,6 +475,7 @@ template <class G> struct EngineT : gaz_engine {
         if (!(cfg.move_time_limit >= 0.0) || cfg.move_time_limit > 1e6) return fail("move_time_limit must be in [0, 1e6] seconds");
         if (cfg.move_time_limit > 0.0 && cfg.sync_moves) return fail("move_time_limit is for continuous self-play; the per-move API has gaz_engine_stop_search");
         E.move_time_ticks = cfg.move_time_limit > 0.0 ? (uint64_t)(cfg.move_time_limit * 1e8) + 1 : 0;
+        E.fast_iterations = cfg.fast_iterations; E.full_search_prob = cfg.full_search_prob;      // (checked by gaz_engine_create)
         if (cfg.games_budget < 0) return fail("games_budget must be >= 0");
         if (cfg.games_budget > 0 && cfg.sync_moves) return fail("games_budget needs continuous self-play (sync_moves = 0)");
         E.games_budget = cfg.games_budget;
@@ -1017,6 +1019,7 @@ template <class G> struct EngineT : gaz_engine {
         o->record_bytes = RL::SIZE; o->max_T = G::MAXT; o->A = G::A; o->t_pad = G::TPAD;
         o->off_hdr = RL::OFF_HDR; o->off_actions = RL::OFF_ACT; o->off_q = RL::OFF_Q; o->off_root_visits = RL::OFF_RV;
         o->off_evals = RL::OFF_EV; o->off_policy = RL::OFF_POL; o->off_N = RL::OFF_N; o->off_W = RL::OFF_W; o->off_P = RL::OFF_P;
+        o->off_move_kind = RL::OFF_MK;
         return 0;
     }
 
@@ -1042,7 +1045,7 @@ template <class G> struct EngineT : gaz_engine {
     // ---- gaz_engine_drain_samples (samples.hpp): one staging buffer on the device [boards | policies | values] and its pinned twin on the
     // host, both grown on demand; per call one header gather, one build launch and ONE device-to-host copy, then the augmentation planes
     // are copied apart into the caller's arrays
-    int32_t* dPlan = nullptr;                        // [ring_cap][4] gathered headers | [2][ring_cap] ring slots, row0
+    int32_t* dPlan = nullptr;                        // [ring_cap][SAMPLE_HDR_INTS] gathered headers + kept rows | [2][ring_cap] ring slots, row0
     uint8_t* dSamples = nullptr; uint8_t* hSamples = nullptr; size_t samples_cap = 0;
     static size_t al256(size_t n) { return (n + 255) / 256 * 256; }
     int sample_layout(gaz_sample_layout* o) override {
@@ -1065,7 +1068,7 @@ template <class G> struct EngineT : gaz_engine {
             HIP_OK(hipHostMalloc(&hp, want, 0));
             hSamples = (uint8_t*)hp; samples_cap = want;
         }
-        int32_t* d_plan = dPlan + (size_t)4 * E.ring_cap;
+        int32_t* d_plan = dPlan + (size_t)SAMPLE_HDR_INTS * E.ring_cap;
         HIP_OK(hipMemcpyAsync(d_plan, plan.data(), plan.size() * 4, hipMemcpyHostToDevice, stream));
 #ifdef GAZ_HOST_EMU
         const int threads = 1;
@@ -1096,25 +1099,26 @@ template <class G> struct EngineT : gaz_engine {
         if (avail > (uint32_t)E.ring_cap) avail = (uint32_t)E.ring_cap;
         if ((int64_t)avail > (int64_t)max_games) avail = (uint32_t)(max_games > 0 ? max_games : 0);
         if (!avail) return check_device_error();
-        if (!dPlan && dalloc(&dPlan, (size_t)6 * E.ring_cap)) return 1;
+        if (!dPlan && dalloc(&dPlan, (size_t)(SAMPLE_HDR_INTS + 2) * E.ring_cap)) return 1;
 #ifdef GAZ_HOST_EMU
         GAZ_LAUNCH(k_sample_headers<G>, (int)avail, 1, stream, (const uint8_t*)E.ring, E.ring_cap, ring_consumed, (int)avail, dPlan);
 #else
         GAZ_LAUNCH(k_sample_headers<G>, ((int)avail + SAMPLES_THREADS - 1) / SAMPLES_THREADS, SAMPLES_THREADS, stream, (const uint8_t*)E.ring, E.ring_cap, ring_consumed, (int)avail, dPlan);
 #endif
         HIP_OK(hipGetLastError());
-        std::vector<int32_t> hdr((size_t)4 * avail);
+        std::vector<int32_t> hdr((size_t)SAMPLE_HDR_INTS * avail);
         HIP_OK(hipMemcpyAsync(hdr.data(), dPlan, hdr.size() * 4, hipMemcpyDeviceToHost, stream));
         HIP_OK(hipStreamSynchronize(stream));
-        int n = 0; int64_t R = 0;                    // whole games, oldest first, while they fit
+        int n = 0; int64_t R = 0;                    // whole games, oldest first, while their rows (the plies that were not fast searches) fit
         std::vector<int32_t> plan;
         for (; n < (int)avail; ++n) {
-            const int T = sample_plies<G>(hdr[4 * n]);
-            if (R + T > max_rows) { if (n == 0) *blocked_T = T; break; }
+            const int32_t* h = &hdr[(size_t)SAMPLE_HDR_INTS * n];
+            const int T = sample_plies<G>(h[0]), rows = h[4] < 0 ? 0 : (h[4] > T ? T : h[4]);
+            if (R + rows > max_rows) { if (n == 0) *blocked_T = rows; break; }
             plan.push_back((int32_t)((ring_consumed + (uint32_t)n) % (uint32_t)E.ring_cap));
-            games[6 * n] = T; games[6 * n + 1] = hdr[4 * n + 1]; games[6 * n + 2] = hdr[4 * n + 2]; games[6 * n + 3] = hdr[4 * n + 3];
-            games[6 * n + 4] = (int32_t)(row_base + R); games[6 * n + 5] = 0;
-            R += T;
+            games[6 * n] = T; games[6 * n + 1] = h[1]; games[6 * n + 2] = h[2]; games[6 * n + 3] = h[3];
+            games[6 * n + 4] = (int32_t)(row_base + R); games[6 * n + 5] = T - rows;
+            R += rows;
         }
         if (!n) return check_device_error();
         if (row_base + R > 0x7fffffffLL) return fail("drain_samples: more than 2^31 rows in one call");
@@ -1668,6 +1672,18 @@ int gaz_engine_create(const gaz_engine_config* cfg, gaz_engine** out) {
         if (cfg->eval_cache_log2 > 0) { g_create_error = "leaf_batch > 1 cannot be combined with eval_cache_log2 > 0"; return 1; }
         if (cfg->game_groups > 1) { g_create_error = "leaf_batch > 1 cannot be combined with game_groups > 1"; return 1; }
     }
+    // playout cap randomisation: fast_iterations = 0 is off (and then takes no probability), else a fast limit in [1, run_iterations] and p in (0, 1]
+    if (cfg->fast_iterations < 0) { g_create_error = "fast_iterations must be >= 0 (0 = no playout cap), not " + std::to_string(cfg->fast_iterations); return 1; }
+    if (cfg->fast_iterations > cfg->run_iterations) {
+        g_create_error = "fast_iterations (" + std::to_string(cfg->fast_iterations) + ") must not exceed run_iterations (" + std::to_string(cfg->run_iterations) + ")";
+        return 1;
+    }
+    if (cfg->fast_iterations > 0 && !(cfg->full_search_prob > 0.0 && cfg->full_search_prob <= 1.0)) {
+        g_create_error = "full_search_prob must be in (0, 1] with fast_iterations > 0, not " + std::to_string(cfg->full_search_prob);
+        return 1;
+    }
+    if (cfg->fast_iterations == 0 && !(cfg->full_search_prob == 0.0)) { g_create_error = "full_search_prob must be 0 with fast_iterations = 0 (the playout cap is off)"; return 1; }
+    if (cfg->fast_iterations > 0 && cfg->move_time_limit > 0.0) { g_create_error = "fast_iterations > 0 cannot be combined with move_time_limit > 0 (a timed move has no iteration cap to randomise)"; return 1; }
     const int groups = choose_game_groups(*cfg);
     if (groups <= 1) {
         gaz_engine* h = make_single_engine(*cfg, &g_create_error);

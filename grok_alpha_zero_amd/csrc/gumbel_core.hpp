@@ -21,7 +21,7 @@ namespace gaz {
 
 template <class G> struct GumbelState {          // per game, lives across launches of one MCTS_Gumbel.run
     int32_t m_eff, phase, n_top, cand, stage, sims_left, vpc, cur_iter, pend_counts;
-    int32_t iter_limit, pad_;  // this move's iteration_limit: run_iterations, or 3 x legal moves under a time limit (DevParams::move_time_ticks)
+    int32_t iter_limit, pad_;  // this move's iteration_limit: run_iterations (a fast move: playout_cap_base), or 3 x legal moves under a time limit (DevParams::move_time_ticks)
     float top_logits[G::APAD];
     float top_mean[G::APAD];
     uint8_t top_ids[G::APAD];
@@ -484,6 +484,7 @@ template <class G> GAZ_DEV void g_move_end(const DevParams<G>& E, int g, GameSta
         reinterpret_cast<float*>(rec + RL::OFF_Q)[ply] = mean;
         reinterpret_cast<uint32_t*>(rec + RL::OFF_RV)[ply] = (uint32_t)ts.root_visits;
         reinterpret_cast<uint32_t*>(rec + RL::OFF_EV)[ply] = gs.move_evals;
+        rec[RL::OFF_MK + ply] = move_kind_of(gs);
     }
     wave_sync();
 }
@@ -631,11 +632,15 @@ template <class G, bool GB = false, class Fin> GAZ_DEV void g_game_step_body(con
             for (int c = tlane<G>(); c < G::BPAD; c += G::TEAM) gs.board[c] = 0;
             if (tlane<G>() == 0) {
                 gs.n_hist = 0; gs.next_player = -1; gs.roots_todo = 1; gs.phase = PH_ROOT; gs.winner = RUNNING; gs.host_move = -1;
-                gs.move_evals = 0; ts.root = -1; ts.event = 0; ts.n_nodes = 0; ts.root_visits = 0;
+                gs.move_evals = 0; gs.cap_state = 0; ts.root = -1; ts.event = 0; ts.n_nodes = 0; ts.root_visits = 0;
             }
             wave_sync();
         } else if (phase == PH_ROOT) {
-            if (tuni<G>(gs.roots_todo) == 0) { if (tlane<G>() == 0) gs.phase = PH_MOVE_BEGIN; wave_sync(); return false; }
+            if (tuni<G>(gs.roots_todo) == 0) {
+                if (tlane<G>() == 0) { playout_cap_limit<G>(E, gs); gs.phase = PH_MOVE_BEGIN; }   // the cap's draw, kept in gs.cap_state for PH_MOVE_BEGIN (puct_core.hpp)
+                wave_sync();
+                return false;
+            }
             if (tlane<G>() == 0) gs.move_evals = 0;
             if (g_root_pre<G>(E, g, gs, ts, S, row0)) {
                 const uint8_t* hit = E.cache ? cache_probe<G>(E, g) : nullptr;
@@ -668,7 +673,7 @@ template <class G, bool GB = false, class Fin> GAZ_DEV void g_game_step_body(con
             if (tlane<G>() == 0) {
                 if (!E.no_gumbel_noise) ts.event += 1;
                 gu.m_eff = E.gumbel_m < len_legal ? E.gumbel_m : len_legal; gu.phase = 0; gu.n_top = n; gu.cur_iter = 0;
-                gu.iter_limit = E.move_time_ticks ? 3 * len_legal : E.run_iterations;
+                gu.iter_limit = E.move_time_ticks ? 3 * len_legal : playout_cap_base<G>(E, gs);   // (drawn on the way out of PH_ROOT)
                 gu.cand = 0; gu.stage = 0; gu.sims_left = 0; gu.pend_counts = 0;
             }
             wave_sync();

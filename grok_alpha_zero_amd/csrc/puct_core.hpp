@@ -59,7 +59,9 @@ template <class G> struct DevParams {
     uint32_t first_game_seq;   // game_seq of every slot's first game (resume: games already in the replay file)
     long long games_budget;    // > 0: slot g plays its k-th game iff k * n_games + g < games_budget, then halts
     int32_t n_opening, opening_actions[8];   // train_config["opening_actions"] (Self_Play.py:130-140)
+    int32_t fast_iterations;   // playout cap randomisation (gaz_engine_config::fast_iterations): 0 = off, else the limit of a fast move
     double opening_weights[8];
+    double full_search_prob;   // probability that a move is searched at the full limit (the first searched move of a game always is)
     float one_minus_eps;
     uint32_t key0, key1, slot_offset;
     // state in HBM
@@ -172,6 +174,32 @@ template <class G> GAZ_DEV det::Event make_event(const DevParams<G>& E, int g, c
     e.event = ts.event; e.tree = (uint32_t)tree; e.purpose = purpose;
     return e;
 }
+
+// Playout cap randomisation (gaz_engine_config::fast_iterations, DESIGN.md "Playout cap randomisation"; no reference counterpart): the base
+// iteration limit of the move that begins at ply gs.n_hist.  A move is FULL (run_iterations) if the game has had no full move yet or
+// u < full_search_prob, else FAST (min(fast_iterations, run_iterations)); u is one uniform variate of the game-level stream (tree 2) keyed by
+// the ply, so no tree's event counter moves and a game's limits can be replayed from (seed, slot, game_seq) alone.  Off: nothing is drawn.
+// For the team's lane 0: it notes the outcome in gs.cap_state, from which move_end marks the ply in the record.  PUCT calls
+// playout_cap_limit in PH_MOVE_BEGIN.  The Gumbel kernels call it one step earlier, where PH_ROOT hands over to PH_MOVE_BEGIN — every move
+// passes there in the same launch, with the same n_hist, and next to nothing is live — for the side effect on gs.cap_state only, and
+// PH_MOVE_BEGIN takes the limit that goes with that draw from playout_cap_base: with the Philox rounds inside PH_MOVE_BEGIN the fused
+// Gumbel launch k_wave_trunk_gumbel<true, true, true> spills 9 VGPRs instead of 8 ("Registers").
+template <class G> GAZ_DEV int playout_cap_limit(const DevParams<G>& E, GameState<G>& gs) {
+    if (E.fast_iterations <= 0) return E.run_iterations;
+    bool full = !(gs.cap_state & CAP_HAD_FULL);
+    if (!full) {
+        det::Event e; e.key0 = E.key0; e.key1 = E.key1; e.slot = gs.slot_id; e.game_seq = gs.game_seq;
+        e.event = (uint32_t)gs.n_hist; e.tree = 2; e.purpose = det::P_PLAYOUT_CAP;
+        full = det::uniform(e) < E.full_search_prob;
+    }
+    gs.cap_state = full ? CAP_HAD_FULL : (CAP_HAD_FULL | CAP_FAST_NOW);
+    if (full) return E.run_iterations;
+    return E.fast_iterations < E.run_iterations ? E.fast_iterations : E.run_iterations;
+}
+template <class G> GAZ_DEV int playout_cap_base(const DevParams<G>& E, const GameState<G>& gs) {
+    return (gs.cap_state & CAP_FAST_NOW) && E.fast_iterations < E.run_iterations ? E.fast_iterations : E.run_iterations;
+}
+template <class G> GAZ_DEV uint8_t move_kind_of(const GameState<G>& gs) { return (gs.cap_state & CAP_FAST_NOW) ? MK_FAST : MK_FULL; }
 
 // ---------------------------------------------------------------------------------------------------
 // legal actions of a board in ascending action order -> S.legal; returns count.  Lanes test cells,
@@ -926,6 +954,7 @@ template <class G> GAZ_DEV void move_end(const DevParams<G>& E, int g, GameState
         reinterpret_cast<float*>(rec + RL::OFF_Q)[ply] = (float)((double)r.W()[chosen] / (double)r.N()[chosen]);   // Self_Play.py:117-125
         reinterpret_cast<uint32_t*>(rec + RL::OFF_RV)[ply] = (uint32_t)ts.root_visits;
         reinterpret_cast<uint32_t*>(rec + RL::OFF_EV)[ply] = gs.move_evals;
+        rec[RL::OFF_MK + ply] = move_kind_of(gs);
     }
     wave_sync();
 }
@@ -1018,7 +1047,7 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
             for (int c = tlane<G>(); c < G::BPAD; c += G::TEAM) gs.board[c] = 0;
             if (tlane<G>() == 0) {
                 gs.n_hist = 0; gs.next_player = -1; gs.roots_todo = E.single_tree ? 1 : 3; gs.phase = PH_ROOT; gs.winner = RUNNING;
-                gs.host_move = -1; gs.move_evals = 0;
+                gs.host_move = -1; gs.move_evals = 0; gs.cap_state = 0;
                 trees[0].root = -1; trees[0].event = 0; trees[0].n_nodes = 0; trees[0].root_visits = 0;
                 trees[1].root = -1; trees[1].event = 0; trees[1].n_nodes = 0; trees[1].root_visits = 0;
             }
@@ -1052,7 +1081,7 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
                 gs.tau_on[1] = ((num + 1) % 2 == 0 && (num + 1) / 2 < E.explore_second) ? 1 : 0;
                 if (E.tau >= 0.0) { gs.tau_on[0] = E.tau != 0.0; gs.tau_on[1] = gs.tau_on[0]; }
                 gs.runner = E.single_tree ? 0 : ((gs.next_player == -1) ? 0 : 1);
-                int lim = E.run_iterations;
+                int lim = playout_cap_limit<G>(E, gs);
                 if (len_legal == 1) lim = 1; else if (lim < len_legal) lim = len_legal * 3;
                 gs.iter_limit = lim; gs.sims_done = 0; gs.fully_visited = 0; gs.move_evals = 0;
                 if (E.move_time_ticks) gs.move_t0 = (uint64_t)wall_clock64();

@@ -10,6 +10,11 @@
 //     READ side (output cell -> source cell), so a game's rows of one augmentation are one contiguous range that is written as
 //     whole 16-byte vectors (single elements only at the ragged ends: a row is 18 / 168 / 450 bytes, a range starts anywhere).
 // One workgroup per game; fill table and action list in LDS.
+//
+// Playout cap randomisation (gaz_engine_config::fast_iterations): a ply whose search was a fast one (RecLayout::OFF_MK, MK_FAST) gives no row.
+// The workgroup compacts the plies it keeps into a table in LDS (kept row -> ply, a ballot / popcount scan) and every output element is
+// indexed through it: the rows of a game stay one contiguous range, and a kept row is what it is without the cap — its state shows every
+// move played before it, fast ones included.  With the cap off the table is the identity.
 #pragma once
 #include "tree.hpp"
 
@@ -90,7 +95,9 @@ template <class T, class F> GAZ_DEV void emit_range(T* dst, size_t start, int co
     for (int i = head + n_vec * VEC + t; i < count; i += nT) dst[start + i] = f(i);
 }
 
-// the [T, winner, slot, game_seq] headers of `n` ring slots from `first` on, dense: what the host needs to choose the games of a drain
+// the [T, winner, slot, game_seq] headers of `n` ring slots from `first` on and the rows each game gives (its plies that are not MK_FAST),
+// dense, SAMPLE_HDR_INTS per game: what the host needs to choose the games of a drain
+constexpr int SAMPLE_HDR_INTS = 5;
 template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_sample_headers(const uint8_t* ring, int ring_cap, uint32_t first, int n, int32_t* out) {
 #ifdef GAZ_HOST_EMU
     const int i = block_id();
@@ -98,11 +105,21 @@ template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_sample_headers(const uin
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
 #endif
     if (i >= n) return;
-    const int32_t* hdr = reinterpret_cast<const int32_t*>(ring + (size_t)((first + (uint32_t)i) % (uint32_t)ring_cap) * RecLayout<G>::SIZE + RecLayout<G>::OFF_HDR);
-    for (int j = 0; j < 4; ++j) out[4 * i + j] = hdr[j];
+    const uint8_t* rec = ring + (size_t)((first + (uint32_t)i) % (uint32_t)ring_cap) * RecLayout<G>::SIZE;
+    const int32_t* hdr = reinterpret_cast<const int32_t*>(rec + RecLayout<G>::OFF_HDR);
+    for (int j = 0; j < 4; ++j) out[SAMPLE_HDR_INTS * i + j] = hdr[j];
+    static_assert(RecLayout<G>::OFF_MK % 4 == 0 && G::TPAD % 4 == 0, "move_kind is read in 32-bit words");
+    const uint32_t* mk = reinterpret_cast<const uint32_t*>(rec + RecLayout<G>::OFF_MK);
+    const int T = sample_plies<G>(hdr[0]);
+    int fast = 0;
+    for (int w = 0; w * 4 < T; ++w) {
+        const uint32_t v = mk[w];
+        for (int j = 0; j < 4; ++j) fast += (w * 4 + j < T) && ((v >> (8 * j)) & 0xffu) == MK_FAST;
+    }
+    out[SAMPLE_HDR_INTS * i + 4] = T - fast;
 }
 
-// plan[i] = ring slot of the drain's i-th game, plan[n + i] = row0[i] = the exclusive prefix sum of the games' plies.  The drain has R rows;
+// plan[i] = ring slot of the drain's i-th game, plan[n + i] = row0[i] = the exclusive prefix sum of the games' kept rows.  The drain has R rows;
 // augmentation k of an output array starts k * R rows in.
 template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_build_samples(const uint8_t* ring, int ring_cap, const int32_t* plan, int n, long long R,
                                                                        int8_t* boards, float* policies, float* values) {
@@ -115,6 +132,9 @@ template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_build_samples(const uint
 #endif
     GAZ_SHARED int fill[G::HW];
     GAZ_SHARED uint8_t act[G::TPAD];
+    GAZ_SHARED uint8_t kept[G::TPAD];                                     // kept row -> ply (MAXT <= 255)
+    GAZ_SHARED int wave_kept[SAMPLES_THREADS / 64 + 1];
+    static_assert(G::MAXT <= 255, "plies are kept as bytes");
     if (b >= n) return;
     const int slot = plan[b];
     if (slot < 0 || slot >= ring_cap) return;
@@ -122,10 +142,27 @@ template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_build_samples(const uint
     const int32_t* hdr = reinterpret_cast<const int32_t*>(rec + RL::OFF_HDR);
     const int T = sample_plies<G>(hdr[0]), winner = hdr[1];
     const long long row0 = plan[n + b];
-    if (row0 < 0 || row0 + T > R) return;                                 // (the host built row0 from these very headers)
     for (int i = t; i < G::HW; i += nT) fill[i] = NEVER;
     for (int i = t; i < T; i += nT) act[i] = rec[RL::OFF_ACT + i];
-    group_sync();
+    // the plies that give a row, in order: per pass of nT plies every wavefront ballots its lanes, the wavefronts' counts meet in LDS, and a
+    // kept ply lands at (rows of earlier passes) + (rows of lower wavefronts) + (kept lanes below its own).  (The one-lane emulation: WAVE = 1,
+    // one "wavefront", one ply per pass.)
+    const int lane = t % WAVE, wv = t / WAVE, n_wv = (nT + WAVE - 1) / WAVE;
+    int K = 0;
+    for (int base = 0; base < T; base += nT) {
+        const int p = base + t;
+        const bool keep = p < T && rec[RL::OFF_MK + p] != MK_FAST;
+        const uint64_t m = ballot(keep);
+        if (lane == 0) wave_kept[wv] = popcll(m);
+        group_sync();
+        int below = 0, all = 0;
+        for (int w = 0; w < n_wv; ++w) { const int c = wave_kept[w]; below += w < wv ? c : 0; all += c; }
+        if (keep) kept[K + below + popcll(m & ((1ull << lane) - 1ull))] = (uint8_t)p;
+        K += all;
+        group_sync();
+    }
+    group_sync();                                                         // (T = 0: no pass ran)
+    if (row0 < 0 || row0 + K > R) return;                              // (the host built row0 from k_sample_headers' counts of these very records)
     if (G::ID == GAME_C4) {
         for (int p = t; p < T; p += nT) {                                 // row = 5 - the earlier moves in the same column
             const int a = act[p];
@@ -142,15 +179,16 @@ template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_build_samples(const uint
     // z as engine.py decode_record derives it: the mover of the ply (Self_Play.py:127), all signs turned when -1 won and made the last
     // move, zeros for a draw
     const bool flip = winner == -1 && T > 0 && ((T - 1) & 1) == 0;
-    for (int p = t; p < T; p += nT) {
+    for (int j = t; j < K; j += nT) {
+        const int p = kept[j];
         float z = (p & 1) ? 1.0f : -1.0f;
         if (flip) z = z * -1.0f; else if (winner == 0) z = 0.0f;
-        values[row0 + p] = 0.5f * (z + q[p]);
+        values[row0 + j] = 0.5f * (z + q[p]);
     }
     for (int k = 0; k < NA; ++k) {
         const size_t row = (size_t)k * (size_t)R + (size_t)row0;
-        emit_range<int8_t>(boards, row * SB, T * SB, t, nT, [&](int i) { return state_element<G>(fill, i / SB, k, i % SB); });
-        emit_range<float>(policies, row * G::A, T * G::A, t, nT, [&](int i) { return pol[(i / G::A) * G::A + policy_src_index<G>(k, i % G::A)]; });
+        emit_range<int8_t>(boards, row * SB, K * SB, t, nT, [&](int i) { return state_element<G>(fill, kept[i / SB], k, i % SB); });
+        emit_range<float>(policies, row * G::A, K * G::A, t, nT, [&](int i) { return pol[kept[i / G::A] * G::A + policy_src_index<G>(k, i % G::A)]; });
     }
 }
 

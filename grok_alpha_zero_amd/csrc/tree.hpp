@@ -93,7 +93,9 @@ template <class G> struct GameState {
     uint64_t n_hits;           // evaluations answered by the on-device evaluation cache (included in n_evals)
     uint64_t move_t0;          // wall clock at MOVE_BEGIN (DevParams::move_time_ticks)
     uint32_t slot_id;          // the game's GLOBAL slot (slot_offset + the physical slot it started in): RNG streams and the record
-    uint32_t pad_;             // header carry this, not the physical index, so gaz_engine_repack may move a running game
+                               // header carry this, not the physical index, so gaz_engine_repack may move a running game
+    uint32_t cap_state;        // playout cap randomisation (playout_cap_limit): CAP_HAD_FULL once a move of this game ran at the
+                               // full limit, CAP_FAST_NOW while the current move is a fast one
 };
 
 // per-game record of the game in progress (and of finished games in the ring); see engine.hip for the
@@ -109,7 +111,11 @@ template <class G> struct RecLayout {
     static constexpr int OFF_N = OFF_POL + 4 * T * G::A;    // u32 [T][A]
     static constexpr int OFF_W = OFF_N + 4 * T * G::A;      // f32 [T][A]
     static constexpr int OFF_P = OFF_W + 4 * T * G::A;      // f32 [T][A]
-    static constexpr int SIZE = (OFF_P + 4 * T * G::A + 15) / 16 * 16;
+    static constexpr int OFF_MK = OFF_P + 4 * T * G::A;     // u8 [TPAD] move_kind: MK_NONE / MK_FULL / MK_FAST
+    static constexpr int SIZE = (OFF_MK + G::TPAD + 15) / 16 * 16;
 };
+// how a ply of a record was searched (gaz_engine_config::fast_iterations): a fast ply gives no training sample (samples.hpp)
+enum : uint8_t { MK_NONE = 0, MK_FULL = 1, MK_FAST = 2 };
+enum : uint32_t { CAP_HAD_FULL = 1, CAP_FAST_NOW = 2 };
 
 }  // namespace gaz

@@ -19,7 +19,7 @@ EVAL_HASH, EVAL_RESNET, EVAL_EXTERNAL = 0, 1, 2
 PH_WAIT_HOST, PH_HALT, PH_IDLE = 5, 8, 9
 
 
-ABI_VERSION = 8               # GAZ_ENGINE_ABI_VERSION of include/gaz_engine.h this binding was written against
+ABI_VERSION = 9               # GAZ_ENGINE_ABI_VERSION of include/gaz_engine.h this binding was written against
 
 
 class EngineConfig(C.Structure):       # gaz_engine_config — tests/test_abi.py checks names, order and sizeof against the header
@@ -34,7 +34,7 @@ class EngineConfig(C.Structure):       # gaz_engine_config — tests/test_abi.py
                 ("single_tree", C.c_int32), ("n_opening", C.c_int32), ("opening_actions", C.c_int32 * 8),
                 ("opening_weights", C.c_double * 8), ("max_tree_sims_per_wave", C.c_int32), ("eval_cache_log2", C.c_int32), ("gumbel_stablemax", C.c_int32), ("fast_find_win", C.c_int32),
                 ("no_gumbel_noise", C.c_int32), ("first_game_seq", C.c_uint32), ("games_budget", C.c_int64), ("tau", C.c_double), ("move_time_limit", C.c_double), ("game_groups", C.c_int32),
-                ("leaf_batch", C.c_int32), ("gumbel_batch", C.c_int32)]
+                ("leaf_batch", C.c_int32), ("gumbel_batch", C.c_int32), ("fast_iterations", C.c_int32), ("full_search_prob", C.c_double)]
 
 
 class SearchHyperparams(C.Structure):  # gaz_search_hyperparams
@@ -49,7 +49,7 @@ class Tensor(C.Structure):
 
 class RecordLayout(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("record_bytes", "max_T", "A", "t_pad", "off_hdr", "off_actions", "off_q",
-                                         "off_root_visits", "off_evals", "off_policy", "off_N", "off_W", "off_P")]
+                                         "off_root_visits", "off_evals", "off_policy", "off_N", "off_W", "off_P", "off_move_kind")]
 
 
 class SampleLayout(C.Structure):        # gaz_sample_layout
@@ -134,8 +134,9 @@ class EngineError(RuntimeError):
 
 class SampleBatch:
     """The finished games of one SelfPlayEngine.drain_samples() call as training samples (include/gaz_engine.h, gaz_engine_drain_samples):
-    `games` int32 [n, 6] (T, winner, slot, game_seq, first row, 0), `boards` int8 [n_aug, R, H, W, C], `policies` f32 [n_aug, R, A],
-    `values` f32 [R, 1]; rows = the games in the order handed out, plies in order."""
+    `games` int32 [n, 6] (T, winner, slot, game_seq, first row, plies left out), `boards` int8 [n_aug, R, H, W, C], `policies` f32 [n_aug, R, A],
+    `values` f32 [R, 1]; rows = the games in the order handed out, plies in order.  With playout cap randomisation (fast_iterations) the
+    plies of fast searches give no row: game i has T - games[i, 5] rows."""
 
     def __init__(self, games, boards, policies, values):
         self.games, self.boards, self.policies, self.values = games, boards, policies, values
@@ -160,11 +161,13 @@ class SampleBatch:
         return SampleBatch(self.games.copy(), self.boards.copy(), self.policies.copy(), self.values.copy())
 
     def game(self, i):
-        """game i as ReplayStore.append_game takes it: (boards [n_aug, T, H, W, C], policies [n_aug, T, A], values [n_aug, T, 1],
-        game_length, n_positions, winner) — views, no copy"""
+        """game i as ReplayStore.append_game takes it: (boards [n_aug, n, H, W, C], policies [n_aug, n, A], values [n_aug, n, 1],
+        game_length, n_positions, winner) — views, no copy.  n = the game's rows (T minus the plies of fast searches); game_length and
+        n_positions stay T, the plies played"""
         T, winner, r0 = int(self.games[i, 0]), int(self.games[i, 1]), int(self.games[i, 4]) - int(self.games[0, 4])
-        v = np.broadcast_to(self.values[None, r0:r0 + T], (self.policies.shape[0], T, 1))
-        return self.boards[:, r0:r0 + T], self.policies[:, r0:r0 + T], v, T, T, winner
+        n = T - int(self.games[i, 5])
+        v = np.broadcast_to(self.values[None, r0:r0 + n], (self.policies.shape[0], n, 1))
+        return self.boards[:, r0:r0 + n], self.policies[:, r0:r0 + n], v, T, T, winner
 
 
 class SearchTree:
@@ -208,7 +211,7 @@ class SelfPlayEngine:
                  policy_is_logits=False, max_tree_sims_per_wave=0, gumbel_m=0, c_visit=50.0, c_scale=1.0,
                  compact_trees=0, single_tree=False, opening_actions=None, eval_cache_log2=0, gumbel_stablemax=False, fast_find_win=False,
                  use_gumbel_noise=True, first_game_seq=0, games_budget=0, tau=-1.0, move_time_limit=0.0, game_groups=0, leaf_batch=1, gumbel_batch=1,
-                 lib_path=None):
+                 fast_iterations=0, full_search_prob=0.0, lib_path=None):
         self.L = load_library(lib_path)
         self.game_id = GAME_IDS[game] if isinstance(game, str) else int(game)
         self.H, self.W, self.Cc, self.A = GAME_DIMS[self.game_id]
@@ -227,7 +230,9 @@ class SelfPlayEngine:
                                 gumbel_stablemax=int(gumbel_stablemax), fast_find_win=int(fast_find_win),
                                 no_gumbel_noise=int(not use_gumbel_noise), first_game_seq=int(first_game_seq), games_budget=int(games_budget),
                                 tau=float(tau), move_time_limit=float(move_time_limit or 0.0), game_groups=int(game_groups),
-                                leaf_batch=int(leaf_batch), gumbel_batch=int(gumbel_batch))
+                                leaf_batch=int(leaf_batch), gumbel_batch=int(gumbel_batch),
+                                # playout cap randomisation: a move runs run_iterations with probability full_search_prob, else fast_iterations
+                                fast_iterations=int(fast_iterations), full_search_prob=float(full_search_prob))
         for i, (a, w) in enumerate(opening_actions or []):       # [(action index, weight)] — train_config["opening_actions"]
             self.cfg.opening_actions[i] = int(a); self.cfg.opening_weights[i] = float(w); self.cfg.n_opening = i + 1
         self.h = C.c_void_p()
@@ -432,7 +437,7 @@ class SelfPlayEngine:
 
     def drain_finished(self, max_records=None):
         """Finished games as dicts: actions, policies [T,A], q, z, values (=0.5(z+q), Self_Play.py:165-172),
-        root_N/W/P [T,A], root_visits, evals, winner, slot, game_seq."""
+        root_N/W/P [T,A], root_visits, evals, move_kind (uint8 [T]: 0 no search, 1 full, 2 fast), winner, slot, game_seq."""
         lay = self.layout
         cap = max_records or max(self.cfg.ring_capacity, 1)
         buf = np.zeros((cap, lay.record_bytes), np.uint8)
@@ -445,7 +450,7 @@ class SelfPlayEngine:
     def drain_samples(self, max_games=None, max_rows=None):
         """Finished games as training samples, built on the device (gaz_engine_drain_samples): a SampleBatch of the games that have
         finished, oldest first; what the buffers (or `max_games` / `max_rows`) do not hold stays in the engine for the next call; a
-        `max_rows` below the oldest game's length is an EngineError.  May be mixed with drain_finished():
+        `max_rows` below the oldest game's rows is an EngineError.  May be mixed with drain_finished():
         a game is handed out once.  The host buffers are allocated once per engine and REUSED: the batch's arrays are views into them,
         valid until the next drain_samples() of this engine — a batch that goes to another thread, or is kept, is copied first
         (SampleBatch.copy(); run_self_play does that before it hands a batch to its writer thread)."""
@@ -490,7 +495,8 @@ class SelfPlayEngine:
                     root_N=arr(lay.off_N, np.uint32, (lay.max_T, A))[:T], root_W=arr(lay.off_W, np.float32, (lay.max_T, A))[:T],
                     root_P=arr(lay.off_P, np.float32, (lay.max_T, A))[:T],
                     root_visits=arr(lay.off_root_visits, np.uint32, (lay.max_T,))[:T],
-                    evals=arr(lay.off_evals, np.uint32, (lay.max_T,))[:T])
+                    evals=arr(lay.off_evals, np.uint32, (lay.max_T,))[:T],
+                    move_kind=arr(lay.off_move_kind, np.uint8, (lay.t_pad,))[:T])
 
     # ---- measurement ----------------------------------------------------------------------------------
     def repack(self):

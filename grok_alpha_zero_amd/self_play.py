@@ -302,7 +302,8 @@ def _fast_states(name, actions):
 
 def record_to_samples(game_class, rec):
     """Rebuild what Self_Play.play() collected for one finished game (Self_Play.py:80,114-127,159-175): input states by
-    replaying the moves through the Game plugin, improved policies, values = 0.5 (z + q), then augment_sample."""
+    replaying the moves through the Game plugin, improved policies, values = 0.5 (z + q), then augment_sample.  Plies whose search was
+    a fast one (rec["move_kind"] == 2, playout cap randomisation) give no row; the length returned stays the plies played."""
     game = game_class()
     from . import games as _builtin
     if game_class in (_builtin.Connect4, _builtin.Gomoku, _builtin.TicTacToe):
@@ -317,6 +318,10 @@ def record_to_samples(game_class, rec):
         n_plies = len(game.action_history)
     policies = np.asarray(rec["policies"], np.float32)
     values = np.asarray(rec["values"], np.float32).reshape(-1, 1)
+    kind = rec.get("move_kind")
+    if kind is not None and np.any(np.asarray(kind) == 2):
+        keep = np.asarray(kind) != 2
+        board_states, policies, values = board_states[keep], policies[keep], values[keep]
     aug_b, aug_p = game.augment_sample(board_states, policies)
     aug_b, aug_p = np.asarray(aug_b), np.asarray(aug_p)
     aug_v = np.repeat(values[None], aug_p.shape[0], axis=0)
@@ -406,6 +411,9 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
     `gumbel_batch`: gaz_engine_config.gumbel_batch; above 1 (use_gumbel only) every game keeps up to that many candidates of a halving
     phase in flight per wave — the same games byte for byte in fewer launches, for generations of few games; the evaluation cache
     and the repack of generation tails are off then.)
+    Playout cap randomisation: train_config["MCTS_fast_iteration_limit"] (absent or 0 = off) and train_config["full_search_prob"] — a
+    move is searched at the full limit with that probability (the first move of a game always), else at the fast limit, scaled like
+    the full one (int(1.5 x) for PUCT); only fully searched plies are written as samples, game_stats count every ply played.
     `configs` = (build_config, train_config[, optimizer_config]).  `weights` = dict from net.export_engine_weights()
     (generation > 0); generation 0 (folder name "0") plays with the synthetic evaluator like the reference's
     session=None dummy (Self_Play.py:40, MCTS.py:237-241).
@@ -449,6 +457,8 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
     gumbel = bool(train_config.get("use_gumbel"))
     # PUCT runs int(1.5 * limit) iterations per move (Self_Play.py:99), Gumbel runs `limit` (Self_Play.py:110-112)
     iters = int(train_config["MCTS_iteration_limit"]) if gumbel else int(train_config["MCTS_iteration_limit"] * 1.5)
+    fast = int(train_config.get("MCTS_fast_iteration_limit") or 0)
+    fast = fast if gumbel else int(fast * 1.5)
     eng = SelfPlayEngine(name, G, iters, train_config["max_actions"],
                          train_config.get("num_explore_actions_first", 0), train_config.get("num_explore_actions_second", 0),
                          train_config.get("c_puct_init", 0.0), train_config.get("dirichlet_alpha", 0.0), seed,
@@ -468,7 +478,8 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
                          # Self_Play.py:35,100-112: every MCTS.run gets time_limit = MCTS_time_limit next to its iteration limit; the engine keeps a
                          # wall clock per game and move (PUCT) / runs 3 x legal moves iterations per move (Gumbel, MCTS_Gumbel.py:576-578)
                          move_time_limit=float(train_config.get("MCTS_time_limit") or 0.0), game_groups=game_groups,
-                         leaf_batch=leaf_batch, gumbel_batch=gumbel_batch)
+                         leaf_batch=leaf_batch, gumbel_batch=gumbel_batch,
+                         fast_iterations=fast, full_search_prob=float(train_config.get("full_search_prob") or 0.0) if fast else 0.0)
     if train_config.get("MCTS_time_limit") and gumbel:
         logging.getLogger("grok_alpha_zero_amd").warning("Time limit isn't allowed for gumbel MCTS defaulting to use 3 * len_legal_actions")   # MCTS_Gumbel.py:578
     logging.getLogger("grok_alpha_zero_amd").info("run_self_play: generation %d, %d games on %d slots, evaluator = %s, game_seq from %d",

@@ -56,7 +56,7 @@ enum { GAZ_EVAL_HASH = 0,      /* synthetic bit-reproducible evaluator (parity t
        GAZ_EVAL_RESNET = 1,    /* the ResNet policy/value network, HIP MFMA kernels */
        GAZ_EVAL_EXTERNAL = 2   /* caller evaluates the batch between wave_begin / wave_end */ };
 
-#define GAZ_ENGINE_ABI_VERSION 8   /* bumped whenever gaz_engine_config / gaz_search_hyperparams / an entry point changes */
+#define GAZ_ENGINE_ABI_VERSION 9   /* bumped whenever gaz_engine_config / gaz_search_hyperparams / an entry point changes */
 
 typedef struct {
     uint32_t struct_size;         /* = sizeof(gaz_engine_config) of the header the caller was built against; gaz_engine_create
@@ -148,6 +148,14 @@ typedef struct {
                                      with gaz_engine_set_hyperparams is legal (more chunks).  Refused by gaz_engine_create with search = GAZ_SEARCH_PUCT,
                                      eval_cache_log2 > 0, game_groups > 1, leaf_batch > 1, or a value above 64; gaz_engine_repack and
                                      gaz_engine_debug_fused_fault are refused on such an engine */
+    int32_t fast_iterations;      /* playout cap randomisation (KataGo, Wu 2019; DESIGN.md "Playout cap randomisation"; no reference counterpart).  0 = off: every
+                                     move runs run_iterations.  F > 0: a move is a FULL search (run_iterations) with probability full_search_prob, else a
+                                     FAST one of min(F, run_iterations) iterations that only advances the game — its ply is left out of the training samples
+                                     (gaz_engine_drain_samples) and marked 2 in the record's move_kind.  Per move one uniform variate of the game-level stream
+                                     (tree 2, event = the ply, purpose 5) decides; the first searched move of every game is always full.  The PUCT rules
+                                     "one legal move: 1 iteration" and "limit below the legal moves: 3 x legal moves" apply to the chosen limit as before.
+                                     Refused by gaz_engine_create when negative, above run_iterations, or combined with move_time_limit > 0 */
+    double full_search_prob;      /* p in (0, 1] with fast_iterations > 0; must be 0 with fast_iterations = 0 */
 } gaz_engine_config;
 
 /* MCTS.update_hyperparams(**kwargs) (MCTS.py:134-168) / MCTS_Gumbel.update_hyperparams (MCTS_Gumbel.py:186-210): values take
@@ -172,6 +180,8 @@ typedef struct {
 typedef struct {
     int32_t record_bytes, max_T, A, t_pad;
     int32_t off_hdr, off_actions, off_q, off_root_visits, off_evals, off_policy, off_N, off_W, off_P;
+    int32_t off_move_kind;        /* u8 [t_pad] per ply: 0 = no search ran there (a gaz_engine_set_position prefix), 1 = full search, 2 = fast search
+                                     (gaz_engine_config.fast_iterations); always 1 for a searched ply with the cap off */
 } gaz_record_layout;
 
 int gaz_engine_abi_version(void);                   /* GAZ_ENGINE_ABI_VERSION of the library */
@@ -248,16 +258,19 @@ int gaz_engine_drain_finished(gaz_engine* h, void* out, int32_t max_records, int
 /* Finished games as TRAINING SAMPLES, built on the device from the same ring gaz_engine_drain_finished empties: the arrays
  * Self_Play.play() collects and augments for the replay file (Self_Play.py:159-175; augment_sample, Guide.py:255-283 —
  * Connect4.py:442-443 [identity, np.fliplr], Gomoku.py:265-303 / Tictactoe.py:321-358 the 8 symmetries in the reference's order).
- * For the R = sum of T rows of the games taken, row = games in the order handed out, plies in order:
+ * A ply whose search was a fast one (move_kind 2, gaz_engine_config.fast_iterations) gives no row; with the cap off every ply does.  For the
+ * R = sum of the KEPT rows of the games taken, row = games in the order handed out, kept plies in order (a kept row is what it would be
+ * without the cap: its state shows every move played before it, fast ones included):
  *   boards   int8 [n_aug][R][state_bytes]   get_input_state() before the move ([H][W][C]), augmented
  *   policies f32  [n_aug][R][A]             the improved policy of the ply, same augmentation
  *   values   f32  [R]                       0.5 * (z + q)  (the replay file repeats it per augmentation)
- *   games    int32 [n][6]                   T, winner, slot, game_seq, first row of the game, 0
+ *   games    int32 [n][6]                   T (every ply played), winner, slot, game_seq, first row of the game, plies left out (the game has
+ *                                           T - that many rows)
  * The augmentation planes of the caller's arrays are max_rows rows apart (plane k of boards starts at boards + k * max_rows *
  * state_bytes), so they are allocated once: boards n_aug * max_rows * state_bytes bytes, policies n_aug * max_rows * A floats, values
  * max_rows floats, games 6 * max_games ints.  Games leave the ring oldest first, as many WHOLE games as fit in max_games and max_rows;
- * the rest stays for the next call.  The call may be mixed with gaz_engine_drain_finished: a game is handed out once, by either.  An
- * oldest game longer than max_rows is an error (last_error says so); max_rows >= max_T always makes progress.  ring_capacity = 0:
+ * the rest stays for the next call (max_rows, *n_rows and the rule below count kept rows).  The call may be mixed with gaz_engine_drain_finished: a game is
+ * handed out once, by either.  An oldest game with more rows than max_rows is an error (last_error says so); max_rows >= max_T always makes progress.  ring_capacity = 0:
  * nothing to drain.  Rows of a gaz_engine_set_position prefix carry the zeros of their record (policy, q).  With game groups the groups'
  * rings are visited in turn, as drain_finished does.  A host synchronisation point like gaz_engine_drain_finished. */
 typedef struct { int32_t n_aug, state_bytes, A, max_T; } gaz_sample_layout;
