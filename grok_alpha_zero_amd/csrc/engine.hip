@@ -476,6 +476,7 @@ template <class G> struct EngineT : gaz_engine {
         if (cfg.move_time_limit > 0.0 && cfg.sync_moves) return fail("move_time_limit is for continuous self-play; the per-move API has gaz_engine_stop_search");
         E.move_time_ticks = cfg.move_time_limit > 0.0 ? (uint64_t)(cfg.move_time_limit * 1e8) + 1 : 0;
         E.fast_iterations = cfg.fast_iterations; E.full_search_prob = cfg.full_search_prob;      // (checked by gaz_engine_create)
+        E.forced_playouts_k = cfg.forced_playouts_k;                                              // (likewise)
         if (cfg.games_budget < 0) return fail("games_budget must be >= 0");
         if (cfg.games_budget > 0 && cfg.sync_moves) return fail("games_budget needs continuous self-play (sync_moves = 0)");
         E.games_budget = cfg.games_budget;
@@ -1684,6 +1685,14 @@ int gaz_engine_create(const gaz_engine_config* cfg, gaz_engine** out) {
     }
     if (cfg->fast_iterations == 0 && !(cfg->full_search_prob == 0.0)) { g_create_error = "full_search_prob must be 0 with fast_iterations = 0 (the playout cap is off)"; return 1; }
     if (cfg->fast_iterations > 0 && cfg->move_time_limit > 0.0) { g_create_error = "fast_iterations > 0 cannot be combined with move_time_limit > 0 (a timed move has no iteration cap to randomise)"; return 1; }
+    // forced playouts + policy target pruning: k = 0 is off, else a finite k > 0 on a PUCT root
+    if (cfg->forced_playouts_k != cfg->forced_playouts_k) { g_create_error = "forced_playouts_k must be a number (0 = no forced playouts), not NaN"; return 1; }
+    if (cfg->forced_playouts_k < 0.0) { g_create_error = "forced_playouts_k must be >= 0 (0 = no forced playouts), not " + std::to_string(cfg->forced_playouts_k); return 1; }
+    if (cfg->forced_playouts_k > 1.7976931348623157e308) { g_create_error = "forced_playouts_k must be finite (KataGo uses 2), not infinity"; return 1; }
+    if (cfg->forced_playouts_k > 0.0 && cfg->search == GAZ_SEARCH_GUMBEL) {
+        g_create_error = "forced_playouts_k > 0 cannot be combined with search = GAZ_SEARCH_GUMBEL (sequential halving has no PUCT root to force playouts at)";
+        return 1;
+    }
     const int groups = choose_game_groups(*cfg);
     if (groups <= 1) {
         gaz_engine* h = make_single_engine(*cfg, &g_create_error);

@@ -62,6 +62,7 @@ template <class G> struct DevParams {
     int32_t fast_iterations;   // playout cap randomisation (gaz_engine_config::fast_iterations): 0 = off, else the limit of a fast move
     double opening_weights[8];
     double full_search_prob;   // probability that a move is searched at the full limit (the first searched move of a game always is)
+    double forced_playouts_k;  // forced playouts + policy target pruning (gaz_engine_config::forced_playouts_k): 0 = off
     float one_minus_eps;
     uint32_t key0, key1, slot_offset;
     // state in HBM
@@ -499,10 +500,35 @@ template <class G> GAZ_DEV void root_post(const DevParams<G>& E, int g, GameStat
     wave_sync();
 }
 
+// Forced playouts (gaz_engine_config::forced_playouts_k = k > 0, DESIGN.md "Forced playouts and policy target pruning"; KataGo, Wu 2019,
+// section 3.2; no reference counterpart): on the staged record of a fully visited root, child slot i is OWED a visit iff N_i > 0 and
+// (double)N_i < sqrt((k * P_i) * root_visits) — this operation order, float64, the correctly rounded root.  Returns the LOWEST owed slot, or
+// -1 when nothing is owed (then PUCT's own choice stands).  One ballot per TEAM children on the record already in LDS; the statistics are
+// taken as they stand (leaf-batched search: virtual losses included) and reserved slots (>= n_children) are never owed.
+template <class G> GAZ_DEV int forced_slot(const NodeRef<G>& nd, int n_children, double k, double rv) {
+    for (int base = 0; base < n_children; base += G::TEAM) {
+        const int i = base + tlane<G>();
+        bool owed = false;
+        if (i < n_children) {
+            const uint32_t n = nd.N()[i];
+            owed = n > 0u && (double)n < dsqrt((k * (double)nd.P()[i]) * rv);
+        }
+        const uint64_t m = tballot<G>(owed);
+        if (m) return base + ffsll0(m);
+    }
+    return -1;
+}
+// forced playouts apply to this game's current move: the feature is on and the move is a FULL one (with the playout cap off every move is)
+template <class G> GAZ_DEV bool forced_playouts_on(const DevParams<G>& E, const GameState<G>& gs) {
+    return E.forced_playouts_k > 0.0 && !(tuni<G>(gs.cap_state) & CAP_FAST_NOW);
+}
+
 // K2: descend from the root.  Returns 0 = expand `node` (its next un-popped child), 1 = terminal leaf hit
 // (value in leaf_win).  S.path receives the edge list root..selected, depth its length.
 // LB (leaf-batched search): the statistics include the virtual losses of the leaves in flight, "next un-popped child" is slot
 // n_children + the node's reserved children, and 2 = the best child is one of those reserved ones (a collision: nothing was changed).
+// Forced playouts: at depth 0 the lowest owed child (forced_slot) replaces PUCT's choice; below it the descent is the ordinary one.  A root
+// that is a terminal parent never gets here.  No RNG event is consumed.
 template <class G, bool LB = false> GAZ_DEV int puct_select(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S,
                                            int& node, int& depth, bool& leaf_win) {
     node = ts.root; depth = 0;
@@ -558,7 +584,11 @@ template <class G, bool LB = false> GAZ_DEV int puct_select(const DevParams<G>& 
             wave_sync();
             return 1;
         }
-        const int best = best_puct_slot<G>(nd, n_actions, fs, fc);
+        int best = best_puct_slot<G>(nd, n_actions, fs, fc);
+        if (depth == 0 && forced_playouts_on<G>(E, gs)) {
+            const int owed = forced_slot<G>(nd, n_children, E.forced_playouts_k, (double)pv);
+            if (owed >= 0) best = owed;
+        }
         const int n_reserved = LB ? tuni<G>((int)h.pad[0]) : 0;
         if (best == n_children + n_reserved) { wave_sync(); return 0; }          // MCTS.py:217-218
         if (best > n_children + n_reserved) { set_error(E.error, ERR_BAD_SELECT); return -1; }
@@ -901,7 +931,82 @@ template <class G> GAZ_DEV bool prune(const DevParams<G>& E, int g, TreeState& t
 
 template <class G> GAZ_DEV uint8_t* rec_of(const DevParams<G>& E, int g) { return E.recs + (size_t)g * RecLayout<G>::SIZE; }
 
+// Policy target pruning (gaz_engine_config::forced_playouts_k = k > 0; KataGo, Wu 2019, section 3.2): the record's policy row of a full
+// move without the visits that forced_slot put there and PUCT would not have chosen.  With (s, c) = puct_factors(root_visits),
+// score(P, q, n) = q + (P * (s / (n + 1))) * c (best_puct_slot's expression) and q_i = f32(W_i / N_i):
+//   1. c* = the most visited child (lowest slot on ties), S* = score(P*, q*, N*);
+//   2. every other child with N_i > 0 gives back up to m_i = min(N_i, floor(sqrt((k * P_i) * root_visits))) visits, one at a time from
+//      n = N_i while score(P_i, q_i, n - 1) < S* (q_i held fixed); a child that ends at n = 1 having given some back ends at 0;
+//   3. pol[a_i] = f32(n_i / sum(n)); c* keeps N*.
+// One lane per child, the scan in registers, the sum by the team reduction; S.gam carries a lane's counts to the final division (Gomoku:
+// up to four children per lane).  With 16-lane teams the scan runs as ONE team-uniform loop — every lane steps while any lane of the team
+// still has visits to test, lanes that are done sit it out under a predicate — not as a loop per lane: a divergent inner loop made the
+// fused Connect4 launches (k_wave_trunk) spill 44 - 47 VGPRs instead of 17 - 23.  With whole-wave teams it is the other way round (the
+// uniform loop made k_wave<Gomoku> spill 202 VGPRs instead of 134), so there every lane loops on its own (DESIGN.md section 15,
+// "Registers").  The N / W / P rows, the move sample and q stay RAW: only `pol` is rewritten.
+template <class G> GAZ_DEV void prune_policy_target(const DevParams<G>& E, const NodeRef<G>& r, int n, uint64_t root_visits, Scratch<G>& S, float* pol) {
+    constexpr bool PER_LANE = G::TEAM >= 64 || G::A > G::TEAM;            // (the one-lane emulation build included: TEAM = 1)
+    double s, c;
+    puct_factors(root_visits, E.c_init, E.c_base, E.puct_table, s, c);
+    uint32_t bv = 0; int bi = 0x7fffffff;
+    for (int i = tlane<G>(); i < n; i += G::TEAM) { const uint32_t v = r.N()[i]; if (bi == 0x7fffffff || v > bv) { bv = v; bi = i; } }
+    team_argmax_u32<G>(bv, bi);
+    const int star = tuni<G>(bi);
+    const uint32_t n_star = r.N()[star];
+    if (n_star == 0u) return;   // no visits at all — unreachable at a fully visited root; team-uniform, nothing written yet, so no sync is owed: the row stays
+    const float q_star = (float)((double)r.W()[star] / (double)n_star);
+    const double s_star = (double)q_star + ((double)r.P()[star] * (s / (double)(n_star + 1u))) * c;
+    const double k = E.forced_playouts_k, rv = (double)root_visits;
+    uint64_t sum = 0;
+    if (PER_LANE) {                                                        // whole-wave teams: every lane scans its own children
+        for (int i = tlane<G>(); i < n; i += G::TEAM) {
+            const uint32_t n_i = r.N()[i];
+            uint32_t left = n_i;
+            if (i != star && n_i > 0u) {
+                const float p = r.P()[i];
+                const float q = (float)((double)r.W()[i] / (double)n_i);
+                const double t = dsqrt((k * (double)p) * rv);
+                const uint32_t m = t >= (double)n_i ? n_i : (uint32_t)t;  // min(N_i, floor(t)), t >= 0
+                for (uint32_t j = 0; j < m; ++j) {                         // (j < m <= N_i: the divisor is at least 1)
+                    const double sc = (double)q + ((double)p * (s / (double)left)) * c;   // score(P_i, q_i, left - 1)
+                    if (!(sc < s_star)) break;
+                    left -= 1u;
+                }
+                if (left == 1u && left < n_i) left = 0u;
+            }
+            S.gam[i] = (double)left;
+            sum += left;
+        }
+    } else {                                                               // 16-lane teams: n <= A <= TEAM, one child per lane, one uniform loop
+        const int i = tlane<G>();
+        const uint32_t n_i = i < n ? r.N()[i] : 0u;
+        uint32_t left = n_i, steps = 0u;                                   // steps: visits this child may still give back
+        float p = 0.0f, q = 0.0f;
+        if (i != star && n_i > 0u) {
+            p = r.P()[i];
+            q = (float)((double)r.W()[i] / (double)n_i);
+            const double t = dsqrt((k * (double)p) * rv);
+            steps = t >= (double)n_i ? n_i : (uint32_t)t;                  // min(N_i, floor(t)), t >= 0
+        }
+        while (tballot<G>(steps > 0u) != 0) {
+            if (steps > 0u) {                                              // (steps <= left: the divisor is at least 1)
+                const double sc = (double)q + ((double)p * (s / (double)left)) * c;   // score(P_i, q_i, left - 1)
+                if (sc < s_star) { left -= 1u; steps -= 1u; } else steps = 0u;
+            }
+        }
+        if (left == 1u && left < n_i) left = 0u;
+        if (i < n) S.gam[i] = (double)left;
+        sum = left;
+    }
+    sum = team_sum_u64<G>(sum);
+    wave_sync();
+    for (int i = tlane<G>(); i < n; i += G::TEAM) pol[r.act()[i]] = (float)(S.gam[i] / (double)sum);
+    wave_sync();
+}
+
 // end of MCTS.run (MCTS.py:591-613) + the bookkeeping of Self_Play.play (Self_Play.py:114-127)
+// Forced playouts (forced_playouts_k > 0, a full move, the root no terminal parent): the policy row is the pruned one
+// (prune_policy_target); everything else is what it is without them.
 template <class G> GAZ_DEV void move_end(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S) {
     using RL = RecLayout<G>;
     NodeRef<G> r = node_at(E, g, t, ts.root);
@@ -921,6 +1026,10 @@ template <class G> GAZ_DEV void move_end(const DevParams<G>& E, int g, GameState
         int a = r.act()[i];
         pol[a] = (float)((double)r.N()[i] / (double)sumv);           // prob = N / sum(N)  (MCTS.py:594, Connect4.py:421-424)
         rN[a] = r.N()[i]; rW[a] = r.W()[i]; rP[a] = r.P()[i];
+    }
+    if (forced_playouts_on<G>(E, gs) && !(tuni<G>((int)r.hdr()->flags) & NF_TERMINAL_PARENT)) {
+        wave_sync();
+        prune_policy_target<G>(E, r, n, ts.root_visits, S, pol);
     }
     // K10 move sampling
     int chosen;

@@ -19,7 +19,7 @@ EVAL_HASH, EVAL_RESNET, EVAL_EXTERNAL = 0, 1, 2
 PH_WAIT_HOST, PH_HALT, PH_IDLE = 5, 8, 9
 
 
-ABI_VERSION = 9               # GAZ_ENGINE_ABI_VERSION of include/gaz_engine.h this binding was written against
+ABI_VERSION = 10              # GAZ_ENGINE_ABI_VERSION of include/gaz_engine.h this binding was written against
 
 
 class EngineConfig(C.Structure):       # gaz_engine_config — tests/test_abi.py checks names, order and sizeof against the header
@@ -34,7 +34,8 @@ class EngineConfig(C.Structure):       # gaz_engine_config — tests/test_abi.py
                 ("single_tree", C.c_int32), ("n_opening", C.c_int32), ("opening_actions", C.c_int32 * 8),
                 ("opening_weights", C.c_double * 8), ("max_tree_sims_per_wave", C.c_int32), ("eval_cache_log2", C.c_int32), ("gumbel_stablemax", C.c_int32), ("fast_find_win", C.c_int32),
                 ("no_gumbel_noise", C.c_int32), ("first_game_seq", C.c_uint32), ("games_budget", C.c_int64), ("tau", C.c_double), ("move_time_limit", C.c_double), ("game_groups", C.c_int32),
-                ("leaf_batch", C.c_int32), ("gumbel_batch", C.c_int32), ("fast_iterations", C.c_int32), ("full_search_prob", C.c_double)]
+                ("leaf_batch", C.c_int32), ("gumbel_batch", C.c_int32), ("fast_iterations", C.c_int32), ("full_search_prob", C.c_double),
+                ("forced_playouts_k", C.c_double)]
 
 
 class SearchHyperparams(C.Structure):  # gaz_search_hyperparams
@@ -211,7 +212,7 @@ class SelfPlayEngine:
                  policy_is_logits=False, max_tree_sims_per_wave=0, gumbel_m=0, c_visit=50.0, c_scale=1.0,
                  compact_trees=0, single_tree=False, opening_actions=None, eval_cache_log2=0, gumbel_stablemax=False, fast_find_win=False,
                  use_gumbel_noise=True, first_game_seq=0, games_budget=0, tau=-1.0, move_time_limit=0.0, game_groups=0, leaf_batch=1, gumbel_batch=1,
-                 fast_iterations=0, full_search_prob=0.0, lib_path=None):
+                 fast_iterations=0, full_search_prob=0.0, forced_playouts_k=0.0, lib_path=None):
         self.L = load_library(lib_path)
         self.game_id = GAME_IDS[game] if isinstance(game, str) else int(game)
         self.H, self.W, self.Cc, self.A = GAME_DIMS[self.game_id]
@@ -232,7 +233,9 @@ class SelfPlayEngine:
                                 tau=float(tau), move_time_limit=float(move_time_limit or 0.0), game_groups=int(game_groups),
                                 leaf_batch=int(leaf_batch), gumbel_batch=int(gumbel_batch),
                                 # playout cap randomisation: a move runs run_iterations with probability full_search_prob, else fast_iterations
-                                fast_iterations=int(fast_iterations), full_search_prob=float(full_search_prob))
+                                fast_iterations=int(fast_iterations), full_search_prob=float(full_search_prob),
+                                # forced playouts + policy target pruning on full PUCT moves (KataGo: k = 2); 0 = off
+                                forced_playouts_k=float(forced_playouts_k or 0.0))
         for i, (a, w) in enumerate(opening_actions or []):       # [(action index, weight)] — train_config["opening_actions"]
             self.cfg.opening_actions[i] = int(a); self.cfg.opening_weights[i] = float(w); self.cfg.n_opening = i + 1
         self.h = C.c_void_p()
@@ -296,6 +299,8 @@ class SelfPlayEngine:
         return n.value
 
     def root_stats(self):
+        """gaz_engine_get_root_stats: the last search's root arrays per game.  `policy` is the record's policy row — with forced_playouts_k > 0
+        the pruned target of a full move — while N / W / P are the raw root statistics."""
         G, A = self.n_games, self.A
         out = dict(N=np.zeros((G, A), np.uint32), W=np.zeros((G, A), np.float32), P=np.zeros((G, A), np.float32),
                    policy=np.zeros((G, A), np.float32), root_visits=np.zeros(G, np.uint32), q=np.zeros(G, np.float32),
@@ -437,7 +442,8 @@ class SelfPlayEngine:
 
     def drain_finished(self, max_records=None):
         """Finished games as dicts: actions, policies [T,A], q, z, values (=0.5(z+q), Self_Play.py:165-172),
-        root_N/W/P [T,A], root_visits, evals, move_kind (uint8 [T]: 0 no search, 1 full, 2 fast), winner, slot, game_seq."""
+        root_N/W/P [T,A], root_visits, evals, move_kind (uint8 [T]: 0 no search, 1 full, 2 fast), winner, slot, game_seq.
+        With forced_playouts_k > 0 `policies` holds the pruned targets of the full moves; root_N / root_W / root_P stay raw."""
         lay = self.layout
         cap = max_records or max(self.cfg.ring_capacity, 1)
         buf = np.zeros((cap, lay.record_bytes), np.uint8)
@@ -450,7 +456,8 @@ class SelfPlayEngine:
     def drain_samples(self, max_games=None, max_rows=None):
         """Finished games as training samples, built on the device (gaz_engine_drain_samples): a SampleBatch of the games that have
         finished, oldest first; what the buffers (or `max_games` / `max_rows`) do not hold stays in the engine for the next call; a
-        `max_rows` below the oldest game's rows is an EngineError.  May be mixed with drain_finished():
+        `max_rows` below the oldest game's rows is an EngineError.  With forced_playouts_k > 0 the policies are the pruned targets (the
+        kernel reads the record's policy rows).  May be mixed with drain_finished():
         a game is handed out once.  The host buffers are allocated once per engine and REUSED: the batch's arrays are views into them,
         valid until the next drain_samples() of this engine — a batch that goes to another thread, or is kept, is copied first
         (SampleBatch.copy(); run_self_play does that before it hands a batch to its writer thread)."""

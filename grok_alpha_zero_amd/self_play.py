@@ -303,7 +303,8 @@ def _fast_states(name, actions):
 def record_to_samples(game_class, rec):
     """Rebuild what Self_Play.play() collected for one finished game (Self_Play.py:80,114-127,159-175): input states by
     replaying the moves through the Game plugin, improved policies, values = 0.5 (z + q), then augment_sample.  Plies whose search was
-    a fast one (rec["move_kind"] == 2, playout cap randomisation) give no row; the length returned stays the plies played."""
+    a fast one (rec["move_kind"] == 2, playout cap randomisation) give no row; the length returned stays the plies played.  With forced
+    playouts (forced_playouts_k > 0) rec["policies"] already holds the pruned targets: nothing is recomputed here."""
     game = game_class()
     from . import games as _builtin
     if game_class in (_builtin.Connect4, _builtin.Gomoku, _builtin.TicTacToe):
@@ -414,6 +415,8 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
     Playout cap randomisation: train_config["MCTS_fast_iteration_limit"] (absent or 0 = off) and train_config["full_search_prob"] — a
     move is searched at the full limit with that probability (the first move of a game always), else at the fast limit, scaled like
     the full one (int(1.5 x) for PUCT); only fully searched plies are written as samples, game_stats count every ply played.
+    Forced playouts and policy target pruning: train_config["forced_playouts_k"] (absent or 0 = off; KataGo uses 2; PUCT only) — every
+    visited root child of a full move gets at least sqrt(k * prior * root visits) visits, and the policy written is the pruned target.
     `configs` = (build_config, train_config[, optimizer_config]).  `weights` = dict from net.export_engine_weights()
     (generation > 0); generation 0 (folder name "0") plays with the synthetic evaluator like the reference's
     session=None dummy (Self_Play.py:40, MCTS.py:237-241).
@@ -479,7 +482,8 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
                          # wall clock per game and move (PUCT) / runs 3 x legal moves iterations per move (Gumbel, MCTS_Gumbel.py:576-578)
                          move_time_limit=float(train_config.get("MCTS_time_limit") or 0.0), game_groups=game_groups,
                          leaf_batch=leaf_batch, gumbel_batch=gumbel_batch,
-                         fast_iterations=fast, full_search_prob=float(train_config.get("full_search_prob") or 0.0) if fast else 0.0)
+                         fast_iterations=fast, full_search_prob=float(train_config.get("full_search_prob") or 0.0) if fast else 0.0,
+                         forced_playouts_k=float(train_config.get("forced_playouts_k") or 0.0))
     if train_config.get("MCTS_time_limit") and gumbel:
         logging.getLogger("grok_alpha_zero_amd").warning("Time limit isn't allowed for gumbel MCTS defaulting to use 3 * len_legal_actions")   # MCTS_Gumbel.py:578
     logging.getLogger("grok_alpha_zero_amd").info("run_self_play: generation %d, %d games on %d slots, evaluator = %s, game_seq from %d",

@@ -56,7 +56,7 @@ enum { GAZ_EVAL_HASH = 0,      /* synthetic bit-reproducible evaluator (parity t
        GAZ_EVAL_RESNET = 1,    /* the ResNet policy/value network, HIP MFMA kernels */
        GAZ_EVAL_EXTERNAL = 2   /* caller evaluates the batch between wave_begin / wave_end */ };
 
-#define GAZ_ENGINE_ABI_VERSION 9   /* bumped whenever gaz_engine_config / gaz_search_hyperparams / an entry point changes */
+#define GAZ_ENGINE_ABI_VERSION 10  /* bumped whenever gaz_engine_config / gaz_search_hyperparams / an entry point changes */
 
 typedef struct {
     uint32_t struct_size;         /* = sizeof(gaz_engine_config) of the header the caller was built against; gaz_engine_create
@@ -156,6 +156,15 @@ typedef struct {
                                      "one legal move: 1 iteration" and "limit below the legal moves: 3 x legal moves" apply to the chosen limit as before.
                                      Refused by gaz_engine_create when negative, above run_iterations, or combined with move_time_limit > 0 */
     double full_search_prob;      /* p in (0, 1] with fast_iterations > 0; must be 0 with fast_iterations = 0 */
+    double forced_playouts_k;     /* forced playouts and policy target pruning (KataGo, Wu 2019, section 3.2; DESIGN.md "Forced playouts and policy target
+                                     pruning"; no reference counterpart).  PUCT search only.  0 = off: every game is what it is without the field.  k > 0
+                                     (KataGo: 2), on every FULL move (with the playout cap off: every move) whose root is no terminal parent: at the fully
+                                     visited root a child with N > 0 and N < sqrt(k * P * root visits) is owed a visit, and the lowest owed slot is
+                                     selected instead of PUCT's choice (no RNG event is consumed); at the end of the move the record's POLICY row is written
+                                     without the forced visits that PUCT would not have chosen — the root's N / W / P rows, the move sample and q stay raw.
+                                     Composes with leaf_batch, single_tree, sync and continuous mode, the evaluation cache, game groups, fused launches,
+                                     gaz_engine_repack, move_time_limit and the playout cap.  Refused by gaz_engine_create when negative, NaN or infinite,
+                                     or when > 0 with search = GAZ_SEARCH_GUMBEL */
 } gaz_engine_config;
 
 /* MCTS.update_hyperparams(**kwargs) (MCTS.py:134-168) / MCTS_Gumbel.update_hyperparams (MCTS_Gumbel.py:186-210): values take
@@ -197,7 +206,8 @@ int gaz_engine_reset_games(gaz_engine* h, const int32_t* slots, int32_t n);   /*
 int gaz_engine_run_move(gaz_engine* h, int32_t* n_waiting);                    /* runs waves until every live game finished its MCTS.run */
 int gaz_engine_get_root_stats(gaz_engine* h, uint32_t* out_N, float* out_W, float* out_P, float* out_policy,
                               uint32_t* out_root_visits, float* out_q, int32_t* out_chosen, int32_t* out_phase);
-                              /* [n_games][A] x4, [n_games] x4; any pointer may be NULL */
+                              /* [n_games][A] x4, [n_games] x4; any pointer may be NULL.  out_policy is the record's policy row of the move: with
+                                 forced_playouts_k > 0 the PRUNED target of a full move, while out_N / out_W / out_P stay the raw root arrays */
 int gaz_engine_apply_moves(gaz_engine* h, const int32_t* moves);               /* moves NULL / entry < 0 = play the sampled move */
 
 /* continuous device-resident self-play (cfg.sync_moves = 0) */
@@ -253,6 +263,8 @@ int gaz_engine_evaluate(gaz_engine* h, const int8_t* inputs, int32_t n, float* p
 int gaz_engine_read_head_features(gaz_engine* h, int32_t n, float* p_feat, float* v_feat, int32_t* p_row_floats, int32_t* v_row_floats);
 
 int gaz_engine_record_layout(gaz_engine* h, gaz_record_layout* out);
+/* finished games as records (gaz_record_layout).  With forced_playouts_k > 0 the policy rows (off_policy) of full moves are the pruned
+ * targets; the root N / W / P rows (off_N / off_W / off_P), q and root_visits are the raw search statistics, forced visits included */
 int gaz_engine_drain_finished(gaz_engine* h, void* out, int32_t max_records, int32_t* n_out);
 
 /* Finished games as TRAINING SAMPLES, built on the device from the same ring gaz_engine_drain_finished empties: the arrays
@@ -272,7 +284,8 @@ int gaz_engine_drain_finished(gaz_engine* h, void* out, int32_t max_records, int
  * the rest stays for the next call (max_rows, *n_rows and the rule below count kept rows).  The call may be mixed with gaz_engine_drain_finished: a game is
  * handed out once, by either.  An oldest game with more rows than max_rows is an error (last_error says so); max_rows >= max_T always makes progress.  ring_capacity = 0:
  * nothing to drain.  Rows of a gaz_engine_set_position prefix carry the zeros of their record (policy, q).  With game groups the groups'
- * rings are visited in turn, as drain_finished does.  A host synchronisation point like gaz_engine_drain_finished. */
+ * rings are visited in turn, as drain_finished does.  A host synchronisation point like gaz_engine_drain_finished.
+ * With forced_playouts_k > 0 `policies` carries the pruned targets: the kernel reads the record's policy rows as move_end wrote them. */
 typedef struct { int32_t n_aug, state_bytes, A, max_T; } gaz_sample_layout;
 int gaz_engine_sample_layout(gaz_engine* h, gaz_sample_layout* out);
 int gaz_engine_drain_samples(gaz_engine* h, int32_t max_games, int64_t max_rows,
