@@ -353,11 +353,16 @@ template <class G> GAZ_DEV int best_puct_slot(const NodeRef<G>& nd, int n_action
 
 // K8 + K7 + K9: gather legal policy entries, renormalise (numpy pairwise float32 sum), mix Dirichlet noise,
 // sort descending (ties: higher original index first) into S.sact / S.spri.
+// Zero-mass rule (DESIGN.md "Oracle", documented divergence): a sum that is no positive finite number (0, NaN, +-inf) would make every
+// prior NaN — the rank sort below then gives every child rank 0 and the node keeps stale scratch — so such a node gets 1 / n_legal for
+// every legal action, before the Dirichlet mix.  The sum is team-uniform, and so is the branch.
 template <class G> GAZ_DEV void make_priors(const DevParams<G>& E, int g, const GameState<G>& gs, TreeState& ts, int tree,
                                             Scratch<G>& S, const float* policy, int n_legal) {
     for (int i = tlane<G>(); i < n_legal; i += G::TEAM) S.pri[i] = policy[S.legal[i]];
     wave_sync();
     const float sum = det::np_pairwise_sum<float>(S.pri, n_legal);   // uniform: every lane computes the same value
+    const bool flat = !(sum > 0.0f && sum <= 3.402823466e+38f);      // 0, negative, NaN, inf: the zero-mass rule
+    const float flat_p = 1.0f / (float)n_legal;
     wave_sync();
     if (E.use_dirichlet) {
         det::Event e = make_event(E, g, gs, ts, tree, det::P_DIRICHLET);
@@ -374,13 +379,13 @@ template <class G> GAZ_DEV void make_priors(const DevParams<G>& E, int g, const 
             for (int i = 0; i < n_legal; ++i) gs_sum = gs_sum + S.gam[i];
         }
         for (int i = tlane<G>(); i < n_legal; i += G::TEAM) {
-            float p = S.pri[i] / sum;
+            float p = flat ? flat_p : S.pri[i] / sum;
             float a = E.one_minus_eps * p;
             S.pri[i] = (float)((double)a + E.eps * (S.gam[i] / gs_sum));
         }
         if (tlane<G>() == 0) ts.event += 1;
     } else {
-        for (int i = tlane<G>(); i < n_legal; i += G::TEAM) S.pri[i] = S.pri[i] / sum;
+        for (int i = tlane<G>(); i < n_legal; i += G::TEAM) S.pri[i] = flat ? flat_p : S.pri[i] / sum;
     }
     wave_sync();
     if (n_legal <= 8) {                                   // rank sort, small node: the eight priors in registers first

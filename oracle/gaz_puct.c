@@ -12,10 +12,16 @@
  * sort).  The oracle, the fixture generator and the HIP engine all use
  * "stable ascending argsort, reversed": descending value, ties by HIGHER original
  * index first — what Numba's small-array insertion sort gives for MCTS.py:293.
+ *
+ * Zero-mass rule (documented divergence): when the numpy-order float32 sum of a node's legal policy
+ * entries is no positive finite number (0, NaN, +-inf), the reference divides by it and sorts NaN
+ * priors in an unspecified order.  The oracle, the test models and the HIP engine give such a node
+ * the prior 1 / n_legal for every legal action, before the Dirichlet mix (make_priors).
  */
 #include <stdlib.h>
 #include <stdio.h>
 #include <math.h>
+#include <float.h>
 #include "gaz_puct.h"
 
 #define MAXA 225
@@ -136,7 +142,8 @@ static void make_priors(gaz_puct* t, const float* policy, const int* legal, int 
     float p[MAXA];
     for (int i = 0; i < n_legal; ++i) p[i] = policy[gaz_policy_index(&t->g, legal[i])];
     float s = gaz_np_sum_f32(p, n_legal);
-    for (int i = 0; i < n_legal; ++i) p[i] = p[i] / s;
+    if (s > 0.0f && s <= FLT_MAX) { for (int i = 0; i < n_legal; ++i) p[i] = p[i] / s; }
+    else { for (int i = 0; i < n_legal; ++i) p[i] = 1.0f / (float)n_legal; }       /* the zero-mass rule (file header) */
     if (t->use_dirichlet) {
         double d[MAXA];
         gaz_event e = t->ev; e.purpose = GAZ_P_DIRICHLET; t->ev.event++;

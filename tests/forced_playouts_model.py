@@ -10,6 +10,9 @@ score(P, q, n) = q + (P * (s / (n + 1))) * c, the most visited child c* (lowest 
 gives back up to min(N_i, floor(sqrt((k * P_i) * root_visits))) visits one at a time while score(P_i, q_i, n - 1) < score of c*, and a
 child left with one visit after giving some back gets none.  The target is n / sum(n).
 
+Priors are leaf_batch_model.Tree._priors' (the zero-mass rule included: a node whose legal entries sum to no positive finite number gets
+1 / n_legal); this module builds none of its own.
+
 Arithmetic: Python floats (float64) and np.float32 in the stated order, the logarithm from the oracle library (gaz_api_log), the root
 from math.sqrt (correctly rounded).  restated_best() is the score's argmax; tests hold it against oracle.best_puct_index, which pins
 the restated score to the oracle's without touching the oracle."""

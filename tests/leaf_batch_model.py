@@ -94,9 +94,14 @@ class Tree:
         return wins[::-1] + draws[::-1], [1] * len(wins) + [0] * len(draws)
 
     def _priors(self, policy, legal):
-        """make_priors: legal entries / their numpy float32 sum, Dirichlet mix, descending (ties: higher index first)."""
+        """make_priors: legal entries / their numpy float32 sum — 1 / n_legal each when that sum is no positive finite number (the
+        zero-mass rule) —, Dirichlet mix, descending (ties: higher index first)."""
         p = np.asarray(policy, f32).reshape(-1)[legal].astype(f32)
-        p = (p / self.O.np_sum_f32(p)).astype(f32)
+        s = self.O.np_sum_f32(p)
+        if s > 0 and np.isfinite(s):
+            p = (p / s).astype(f32)
+        else:
+            p = np.full(len(legal), f32(1.0) / f32(len(legal)), f32)
         if self.use_dirichlet:
             d = self.O.dirichlet(self.seed, self.slot, self.seq, self.tree, self.event, self.alpha, len(legal)); self.event += 1
             a = (self.one_minus_eps * p).astype(f32)
@@ -195,14 +200,15 @@ class Tree:
 
     def run(self, iterations):
         """MCTS.run for the position the tree stands at -> dict: N / W / P [A] of the root by action, root_visits, evals (evaluator calls
-        of the search itself), launches (per kernel launch from the start of the search to the end of the move: the requested states)."""
+        of the search itself), launches (per kernel launch from the start of the search to the end of the move: the requested states),
+        collisions (launches that ended because the selection ran into a reserved child)."""
         launches = []
         if self.root_request is not None:
             launches.append([self.root_request]); self.root_request = None
         n_legal = len(self._legal(self.board))
         limit = 1 if n_legal == 1 else (3 * n_legal if iterations < n_legal else iterations)
         root, evals0 = self.root, self.n_evals
-        done, fully, flight = 0, False, []
+        done, fully, flight, collisions = 0, False, [], 0
         while True:
             for leaf in flight:
                 self._apply(leaf)
@@ -219,6 +225,7 @@ class Tree:
                     break
                 kind, node, path, win = self._select() if fully else (0, root, [], False)
                 if kind == 2:
+                    collisions += 1
                     break
                 if kind == 1:
                     self._backup(path, 1.0 if win else 0.0, 1); done += 1; tree_only += 1
@@ -238,7 +245,7 @@ class Tree:
         N = np.zeros(self.A, np.uint32); W = np.zeros(self.A, f32); P = np.zeros(self.A, f32)
         for i, a in enumerate(root.act):
             N[a], W[a], P[a] = root.N[i], root.W[i], root.P[i]
-        return dict(N=N, W=W, P=P, root_visits=self.root_visits, evals=self.n_evals - evals0, launches=launches)
+        return dict(N=N, W=W, P=P, root_visits=self.root_visits, evals=self.n_evals - evals0, launches=launches, collisions=collisions)
 
     def play(self, action):
         """game.do_action(action) + prune_tree(action): re-root at the child, or a new root where there is none (gaz_puct_prune)."""
