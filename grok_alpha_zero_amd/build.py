@@ -11,9 +11,9 @@ LIB = os.path.join(_PKG, "libgaz_engine.so")
 HEADER = os.path.join(os.path.dirname(_PKG), "include", "gaz_engine.h")
 # translation unit -> the headers it includes (rebuild trigger)
 UNITS = {
-    "engine.hip": ["rt.hpp", "wave.hpp", "det.hpp", "games.hpp", "tree.hpp", "puct_core.hpp", "gumbel_core.hpp", "evaluator.hpp", "samples.hpp", "tree_export.hpp"],
+    "engine.hip": ["rt.hpp", "wave.hpp", "det.hpp", "games.hpp", "tree.hpp", "resign.hpp", "puct_core.hpp", "gumbel_core.hpp", "evaluator.hpp", "samples.hpp", "tree_export.hpp"],
     "resnet.hip": ["rt.hpp", "wave.hpp", "evaluator.hpp", "netops.hpp", "conv3x3.hpp", "conv_wide.hpp", "resblock.hpp", "trunk.hpp", "tile_perm.hpp", "net_host.hpp",
-                   "det.hpp", "games.hpp", "tree.hpp", "puct_core.hpp", "gumbel_core.hpp"],          # the fused tree + trunk launch lives in resnet.hip
+                   "det.hpp", "games.hpp", "tree.hpp", "resign.hpp", "puct_core.hpp", "gumbel_core.hpp"],          # the fused tree + trunk launch lives in resnet.hip
 }
 # -ffp-contract=off: the injected-noise samplers and PUCT scores must not be FMA-contracted (bit parity)
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wno-unused-result", "-Wno-unused-value",

@@ -360,6 +360,8 @@ struct gaz_engine {
     virtual int stop_search(int) = 0;
     virtual int start_search() = 0;
     virtual int set_hyperparams(const gaz_search_hyperparams*) = 0;
+    virtual int set_resignation(const gaz_resign_params*) = 0;
+    virtual int get_resign_stats(uint64_t out[8]) = 0;
     virtual int read_head_features(int, float*, float*, int32_t*, int32_t*) = 0;
     virtual int set_fused_wave(int) = 0;
     virtual int debug_fused_fault(int) = 0;
@@ -532,7 +534,7 @@ template <class G> struct EngineT : gaz_engine {
             E.puct_table = tb;
             if (init_puct_table()) return 1;
         }
-        if (dalloc(&E.stats, 8)) return 1;
+        if (dalloc(&E.stats, RESIGN_STATS_OFFSET + (sizeof(ResignBlock) + 7) / 8)) return 1;      // zeroed: resignation off
         if (dalloc(&E.error, 4)) return 1;
         if (dalloc(&dN, (size_t)n * G::A) || dalloc(&dW, (size_t)n * G::A) || dalloc(&dP, (size_t)n * G::A) ||
             dalloc(&dPol, (size_t)n * G::A) || dalloc(&dRV, n) || dalloc(&dQ, n) || dalloc(&dChosen, n) ||
@@ -1328,6 +1330,26 @@ template <class G> struct EngineT : gaz_engine {
         if (table && E.puct_table) return init_puct_table();
         return 0;
     }
+    // resignation (resign.hpp): the parameters go to the block behind the game_stats counters, which PH_APPLY reads once per move, so the
+    // next wave sees them.  The block's counters live as long as the engine, through off and on again
+    ResignBlock* resign_block() { return reinterpret_cast<ResignBlock*>(E.stats + RESIGN_STATS_OFFSET); }
+    int set_resignation(const gaz_resign_params* p) override {
+        ResignBlock b{};                             // (threshold 0 = off: the other fields are then not looked at, on the device either)
+        if (p->threshold > 0.0) { b.threshold = p->threshold; b.no_resign_prob = p->no_resign_prob; b.consecutive = p->consecutive; b.min_ply = p->min_ply; }
+        HIP_OK(hipStreamSynchronize(stream));        // (no launch in flight reads the block while it changes)
+        if (pipeline_ready) { HIP_OK(hipStreamSynchronize(tstream)); HIP_OK(hipStreamSynchronize(hstream)); }
+        HIP_OK(hipMemcpy(resign_block(), &b, offsetof(ResignBlock, stats), hipMemcpyHostToDevice));
+        return 0;
+    }
+    int get_resign_stats(uint64_t out[8]) override {
+        for (int i = 0; i < 8; ++i) out[i] = 0;
+        HIP_OK(hipStreamSynchronize(stream));
+        if (pipeline_ready) { HIP_OK(hipStreamSynchronize(tstream)); HIP_OK(hipStreamSynchronize(hstream)); }
+        unsigned long long s[8];
+        HIP_OK(hipMemcpy(s, resign_block()->stats, sizeof(s), hipMemcpyDeviceToHost));
+        for (int i = 0; i < 7; ++i) out[i] = s[i];
+        return check_device_error();
+    }
     int8_t* pr_board = nullptr; uint8_t* pr_legal = nullptr; int32_t* pr_winner = nullptr; int8_t* pr_input = nullptr; int32_t* pr_term = nullptr;
     int32_t* pr_actions = nullptr; int32_t* pr_n = nullptr; float* pr_pin = nullptr; float* pr_pout = nullptr; int pr_cap = 0, pr_stride = 0;
     int probe_rules(const int32_t* actions, const int32_t* n_actions, int n_pos, int stride, int8_t* o_board, uint8_t* o_legal,
@@ -1564,6 +1586,11 @@ struct GroupEngine : gaz_engine {
     int stop_search(int s) override { return each([&](gaz_engine* k, int) { return k->stop_search(s); }); }
     int start_search() override { return each([](gaz_engine* k, int) { return k->start_search(); }); }
     int set_hyperparams(const gaz_search_hyperparams* hp) override { return each([&](gaz_engine* k, int) { return k->set_hyperparams(hp); }); }
+    int set_resignation(const gaz_resign_params* p) override { return each([&](gaz_engine* k, int) { return k->set_resignation(p); }); }
+    int get_resign_stats(uint64_t out[8]) override {
+        for (int i = 0; i < 8; ++i) out[i] = 0;
+        return each([&](gaz_engine* k, int) { uint64_t s[8]; if (k->get_resign_stats(s)) return 1; for (int i = 0; i < 8; ++i) out[i] += s[i]; return 0; });
+    }
     int read_head_features(int n, float* p, float* v, int32_t* p_row, int32_t* v_row) override {
         if (n < 0 || n > cfg.n_games) return fail("read_head_features: n must be in [0, n_games]");
         int32_t pr = 0, vr = 0;
@@ -1744,6 +1771,23 @@ int gaz_engine_set_search_params(gaz_engine* h, int32_t run_iterations, int32_t 
 int gaz_engine_stop_search(gaz_engine* h, int32_t stop) { return h->stop_search(stop); }
 int gaz_engine_start_search(gaz_engine* h) { return h->start_search(); }
 int gaz_engine_set_hyperparams(gaz_engine* h, const gaz_search_hyperparams* hp) { return h->set_hyperparams(hp); }
+// resignation: threshold = 0 is off (and then nothing else is looked at); else threshold in (0, 1), consecutive in [1, 8], min_ply >= 0, no_resign_prob in [0, 1]
+int gaz_engine_set_resignation(gaz_engine* h, const gaz_resign_params* p) {
+    if (!p) return h->fail("set_resignation: null argument");
+    if (p->struct_size != sizeof(gaz_resign_params))
+        return h->fail("set_resignation: struct_size is " + std::to_string(p->struct_size) + ", this library's gaz_resign_params has " + std::to_string(sizeof(gaz_resign_params)) + " bytes");
+    if (p->threshold != p->threshold) return h->fail("set_resignation: threshold must be a number (0 = no resignation), not NaN");
+    if (p->threshold > 1.7976931348623157e308 || p->threshold < -1.7976931348623157e308) return h->fail("set_resignation: threshold must be finite, not infinity");
+    if (p->threshold < 0.0) return h->fail("set_resignation: threshold must be >= 0 (0 = no resignation), not " + std::to_string(p->threshold));
+    if (p->threshold >= 1.0) return h->fail("set_resignation: threshold must be below 1 (q lies in [-1, 1], so no ply could trigger), not " + std::to_string(p->threshold));
+    if (p->threshold == 0.0) return h->set_resignation(p);
+    if (p->consecutive < 1 || p->consecutive > RESIGN_MAX_CONSECUTIVE)
+        return h->fail("set_resignation: consecutive must be in [1, " + std::to_string(RESIGN_MAX_CONSECUTIVE) + "], not " + std::to_string(p->consecutive));
+    if (p->min_ply < 0) return h->fail("set_resignation: min_ply must be >= 0, not " + std::to_string(p->min_ply));
+    if (!(p->no_resign_prob >= 0.0 && p->no_resign_prob <= 1.0)) return h->fail("set_resignation: no_resign_prob must be in [0, 1], not " + std::to_string(p->no_resign_prob));
+    return h->set_resignation(p);
+}
+int gaz_engine_get_resign_stats(gaz_engine* h, uint64_t out[8]) { return out ? h->get_resign_stats(out) : h->fail("get_resign_stats: null argument"); }
 int gaz_engine_set_fused_wave(gaz_engine* h, int32_t on) { return h->set_fused_wave(on); }
 int gaz_engine_debug_fused_fault(gaz_engine* h, int32_t mod) { return h->debug_fused_fault(mod); }
 int gaz_engine_read_positions(gaz_engine* h, int32_t* n_hist, uint8_t* hist, int32_t stride) { return h->read_positions(n_hist, hist, stride); }

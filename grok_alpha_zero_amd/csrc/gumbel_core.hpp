@@ -786,6 +786,11 @@ template <class G, bool GB = false, class Fin> GAZ_DEV void g_game_step_body(con
             wave_sync();
             bool ended = winner != RUNNING;
             if (ply + 1 == E.max_actions) { winner = 0; ended = true; }
+            {                                        // resignation (resign.hpp), as in puct_core.hpp: natural ends and the cap take precedence
+                int verdict = RESIGN_NONE;
+                if (tlane<G>() == 0) verdict = resign_after_ply(E.stats, E.key0, E.key1, gs.slot_id, gs.game_seq, reinterpret_cast<const float*>(rec + RL::OFF_Q), rec + RL::OFF_MK, ply, ended, winner);
+                if (tshfl<G>(verdict, 0) == RESIGN_NOW) { winner = -mover; ended = true; }
+            }
             if (!ended && tlane<G>() == 0) { gs.roots_todo = 1; gs.phase = (E.sync_moves && E.single_tree) ? PH_IDLE : PH_ROOT; }
             if (ended && tlane<G>() == 0) {
                 gs.winner = winner;

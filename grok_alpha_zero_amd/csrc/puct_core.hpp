@@ -31,6 +31,7 @@
 #pragma once
 #include "det.hpp"
 #include "tree.hpp"
+#include "resign.hpp"
 
 namespace gaz {
 
@@ -80,7 +81,7 @@ template <class G> struct DevParams {
     float* nn_value;           // [n_games]
     // evaluation cache (0 = off): direct-mapped, entry = [tag u32][pad u32][state row, 8-byte padded][policy f32 x A][value f32]
     uint8_t* cache; uint32_t* cache_lock; uint32_t cache_mask, cache_epoch; int32_t cache_stride;
-    unsigned long long* stats; // [8]: game_stats[0..5] (Self_Play.py:181-188), [6] waves, [7] spare
+    unsigned long long* stats; // [8]: game_stats[0..5] (Self_Play.py:181-188), [6] waves, [7] spare; behind them the ResignBlock (resign.hpp)
     const double* puct_table;  // [PUCT_TABLE_N][2]: sqrt(pv), c_init + ln((pv + c_base + 1) / c_base)
     unsigned long long* prof;  // diagnostic (GAZ_TREE_PROF=1): [n_games][8] shader-clock cycles per phase of the PUCT kernel, else null
     int32_t* error;            // first error code, 0 = none
@@ -1345,13 +1346,21 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
             }
             wave_sync();
             bool ended = winner != RUNNING;
+            // resignation (resign.hpp): natural ends and the max_actions cap take precedence; decided before prune, so that no tree is
+            // re-rooted for a game that is over
+            const bool capped = ply + 1 == E.max_actions;
+            {
+                int verdict = RESIGN_NONE;
+                if (tlane<G>() == 0) verdict = resign_after_ply(E.stats, E.key0, E.key1, gs.slot_id, gs.game_seq, reinterpret_cast<const float*>(rec + RL::OFF_Q), rec + RL::OFF_MK, ply, ended || capped, capped ? 0 : winner);
+                if (tshfl<G>(verdict, 0) == RESIGN_NOW) { winner = -mover; ended = true; }
+            }
             int todo = 0;
             if (!ended) {
                 if (prune<G>(E, g, trees[0], 0, action)) todo |= 1;   // both trees prune (Self_Play.py:149-150)
                 if (!E.single_tree && prune<G>(E, g, trees[1], 1, action)) todo |= 2;
             }
             // Self_Play.py:155-157: reaching max_actions forces winner = 0 — even when that last action won
-            if (ply + 1 == E.max_actions) { winner = 0; ended = true; }
+            if (capped) { winner = 0; ended = true; }
             if (!ended && tlane<G>() == 0) { gs.roots_todo = todo; gs.phase = (E.sync_moves && E.single_tree) ? PH_IDLE : PH_ROOT; }
             if (ended) {
                 if (tlane<G>() == 0) {

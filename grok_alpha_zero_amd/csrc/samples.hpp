@@ -114,7 +114,7 @@ template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_sample_headers(const uin
     int fast = 0;
     for (int w = 0; w * 4 < T; ++w) {
         const uint32_t v = mk[w];
-        for (int j = 0; j < 4; ++j) fast += (w * 4 + j < T) && ((v >> (8 * j)) & 0xffu) == MK_FAST;
+        for (int j = 0; j < 4; ++j) fast += (w * 4 + j < T) && ((v >> (8 * j)) & MK_KIND_MASK) == MK_FAST;   // (the kind: the bits above it mark resignation)
     }
     out[SAMPLE_HDR_INTS * i + 4] = T - fast;
 }
@@ -151,7 +151,7 @@ template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_build_samples(const uint
     int K = 0;
     for (int base = 0; base < T; base += nT) {
         const int p = base + t;
-        const bool keep = p < T && rec[RL::OFF_MK + p] != MK_FAST;
+        const bool keep = p < T && (rec[RL::OFF_MK + p] & MK_KIND_MASK) != MK_FAST;
         const uint64_t m = ballot(keep);
         if (lane == 0) wave_kept[wv] = popcll(m);
         group_sync();
@@ -176,13 +176,12 @@ template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_build_samples(const uint
     group_sync();
     const float* q = reinterpret_cast<const float*>(rec + RL::OFF_Q);
     const float* pol = reinterpret_cast<const float*>(rec + RL::OFF_POL);
-    // z as engine.py decode_record derives it: the mover of the ply (Self_Play.py:127), all signs turned when -1 won and made the last
-    // move, zeros for a draw
-    const bool flip = winner == -1 && T > 0 && ((T - 1) & 1) == 0;
+    // z as engine.py decode_record derives it: z[p] = mover(p) * winner, the mover of ply p being -1 on even plies (Self_Play.py:127).  Without
+    // resignation the winner is 0 or the LAST mover, and this is the reference's rule (mover signs, all turned when -1 won and moved last,
+    // zeros for a draw: Self_Play.py:165-172) value for value; a resigned game is won by the player who did not move last
     for (int j = t; j < K; j += nT) {
         const int p = kept[j];
-        float z = (p & 1) ? 1.0f : -1.0f;
-        if (flip) z = z * -1.0f; else if (winner == 0) z = 0.0f;
+        const float z = (float)(((p & 1) ? 1 : -1) * winner);
         values[row0 + j] = 0.5f * (z + q[p]);
     }
     for (int k = 0; k < NA; ++k) {

@@ -111,11 +111,14 @@ template <class G> struct RecLayout {
     static constexpr int OFF_N = OFF_POL + 4 * T * G::A;    // u32 [T][A]
     static constexpr int OFF_W = OFF_N + 4 * T * G::A;      // f32 [T][A]
     static constexpr int OFF_P = OFF_W + 4 * T * G::A;      // f32 [T][A]
-    static constexpr int OFF_MK = OFF_P + 4 * T * G::A;     // u8 [TPAD] move_kind: MK_NONE / MK_FULL / MK_FAST
+    static constexpr int OFF_MK = OFF_P + 4 * T * G::A;     // u8 [TPAD] move_kind: MK_NONE / MK_FULL / MK_FAST | MK_RESIGNED / MK_WOULD_RESIGN
     static constexpr int SIZE = (OFF_MK + G::TPAD + 15) / 16 * 16;
 };
 // how a ply of a record was searched (gaz_engine_config::fast_iterations): a fast ply gives no training sample (samples.hpp)
 enum : uint8_t { MK_NONE = 0, MK_FULL = 1, MK_FAST = 2 };
+// the kind is the low two bits of the byte; above them the marks of resignation (resign.hpp): the ply after which the game was resigned,
+// and in a game that is played out the plies at which it would have been
+enum : uint8_t { MK_KIND_MASK = 3, MK_RESIGNED = 0x10, MK_WOULD_RESIGN = 0x20 };
 enum : uint32_t { CAP_HAD_FULL = 1, CAP_FAST_NOW = 2 };
 
 }  // namespace gaz

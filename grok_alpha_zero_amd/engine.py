@@ -53,6 +53,14 @@ class RecordLayout(C.Structure):
                                          "off_root_visits", "off_evals", "off_policy", "off_N", "off_W", "off_P", "off_move_kind")]
 
 
+class ResignParams(C.Structure):        # gaz_resign_params
+    _fields_ = [("struct_size", C.c_uint32), ("consecutive", C.c_int32), ("min_ply", C.c_int32), ("reserved_", C.c_int32),
+                ("threshold", C.c_double), ("no_resign_prob", C.c_double)]
+
+
+MK_KIND_MASK, MK_RESIGNED, MK_WOULD_RESIGN = 3, 0x10, 0x20      # the bits of a record's raw move_kind byte (gaz_record_layout.off_move_kind)
+
+
 class SampleLayout(C.Structure):        # gaz_sample_layout
     _fields_ = [(n, C.c_int32) for n in ("n_aug", "state_bytes", "A", "max_T")]
 
@@ -109,6 +117,8 @@ def load_library(lib_path=None):
     L.gaz_engine_stop_search.argtypes = [H, C.c_int32]
     L.gaz_engine_start_search.argtypes = [H]
     L.gaz_engine_set_hyperparams.argtypes = [H, C.POINTER(SearchHyperparams)]
+    L.gaz_engine_set_resignation.argtypes = [H, C.POINTER(ResignParams)]
+    L.gaz_engine_get_resign_stats.argtypes = [H, C.POINTER(C.c_uint64)]
     L.gaz_engine_probe_rules.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7
     L.gaz_engine_set_fused_wave.argtypes = [H, C.c_int32]
     L.gaz_engine_debug_fused_fault.argtypes = [H, C.c_int32]
@@ -123,7 +133,7 @@ def load_library(lib_path=None):
     for f in ("create", "load_weights", "reset_games", "run_move", "get_root_stats", "apply_moves", "run_waves", "wave_begin",
               "wave_end", "batch_ptrs", "read_batch", "write_outputs", "batch_rows", "evaluate", "record_layout", "drain_finished", "sample_layout", "drain_samples", "get_stats",
               "synchronize", "timing_reset", "timing_get", "dominant_kernel", "set_position", "set_search_params", "start_search", "stop_search",
-              "set_hyperparams", "probe_rules", "read_head_features", "set_fused_wave", "debug_fused_fault", "read_positions", "repack", "read_trees", "read_pv"):
+              "set_hyperparams", "set_resignation", "get_resign_stats", "probe_rules", "read_head_features", "set_fused_wave", "debug_fused_fault", "read_positions", "repack", "read_trees", "read_pv"):
         getattr(L, "gaz_engine_" + f).restype = C.c_int
     _LIBS[path] = L
     return L
@@ -212,7 +222,8 @@ class SelfPlayEngine:
                  policy_is_logits=False, max_tree_sims_per_wave=0, gumbel_m=0, c_visit=50.0, c_scale=1.0,
                  compact_trees=0, single_tree=False, opening_actions=None, eval_cache_log2=0, gumbel_stablemax=False, fast_find_win=False,
                  use_gumbel_noise=True, first_game_seq=0, games_budget=0, tau=-1.0, move_time_limit=0.0, game_groups=0, leaf_batch=1, gumbel_batch=1,
-                 fast_iterations=0, full_search_prob=0.0, forced_playouts_k=0.0, lib_path=None):
+                 fast_iterations=0, full_search_prob=0.0, forced_playouts_k=0.0,
+                 resign_threshold=0.0, resign_consecutive=1, resign_min_ply=0, no_resign_prob=0.0, lib_path=None):
         self.L = load_library(lib_path)
         self.game_id = GAME_IDS[game] if isinstance(game, str) else int(game)
         self.H, self.W, self.Cc, self.A = GAME_DIMS[self.game_id]
@@ -250,6 +261,12 @@ class SelfPlayEngine:
             r = C.c_int32()
             self._ck(self.L.gaz_engine_batch_rows(self.h, C.byref(r)))
             self.batch_rows = int(r.value)
+        if resign_threshold:                         # (0 = off, the state of a new engine)
+            try:
+                self.set_resignation(resign_threshold, resign_consecutive, resign_min_ply, no_resign_prob)
+            except EngineError:
+                self.close()
+                raise
 
     def _ck(self, rc):
         if rc:
@@ -440,9 +457,30 @@ class SelfPlayEngine:
         s = [int(x) for x in out]
         return dict(game_stats=np.array(s[:6], np.uint64), evals=s[6], sims=s[7], plies=s[8], waves=s[9], cache_hits=s[10], pipeline_groups=s[11], fused_wave=s[12], fused_faults=s[13], game_groups=max(int(s[14]), 1), reserved_children=s[15])
 
+    def set_resignation(self, threshold, consecutive=1, min_ply=0, no_resign_prob=0.0):
+        """Resignation in self-play (gaz_engine_set_resignation), from the next launch on: a game ends after a ply — lost for its mover —
+        when the recorded q of the mover's last `consecutive` searched plies were all below -threshold and the ply is at least `min_ply`;
+        a game is instead played out with probability `no_resign_prob`, its would-be resign plies marked, so that resign_stats() can tell
+        the false positives.  threshold = 0 switches it off (the other arguments are then ignored)."""
+        p = ResignParams(struct_size=C.sizeof(ResignParams), consecutive=int(consecutive), min_ply=int(min_ply), reserved_=0,
+                         threshold=float(threshold), no_resign_prob=float(no_resign_prob))
+        self._ck(self.L.gaz_engine_set_resignation(self.h, C.byref(p)))
+
+    def resign_stats(self):
+        """gaz_engine_get_resign_stats as a dict: games `resigned` (`resigned_by_minus1` / `resigned_by_plus1`: the player who gave up),
+        `playout_games` finished, of them `would_resign`, of those `false_positives` (the would-be resigner drew or won), and
+        `resigned_plies`, the plies the resigned games were played for.  A synchronisation point like stats()."""
+        out = (C.c_uint64 * 8)()
+        self._ck(self.L.gaz_engine_get_resign_stats(self.h, out))
+        s = [int(x) for x in out]
+        return dict(resigned=s[0], resigned_by_minus1=s[1], resigned_by_plus1=s[2], playout_games=s[3], would_resign=s[4], false_positives=s[5],
+                    resigned_plies=s[6])
+
     def drain_finished(self, max_records=None):
         """Finished games as dicts: actions, policies [T,A], q, z, values (=0.5(z+q), Self_Play.py:165-172),
-        root_N/W/P [T,A], root_visits, evals, move_kind (uint8 [T]: 0 no search, 1 full, 2 fast), winner, slot, game_seq.
+        root_N/W/P [T,A], root_visits, evals, move_kind (uint8 [T]: 0 no search, 1 full, 2 fast), winner, slot, game_seq, and of
+        resignation (set_resignation) resigned (bool), resign_ply (the last ply of a resigned game, else -1) and would_resign_plies (the
+        plies at which a game that was played out would have been resigned).
         With forced_playouts_k > 0 `policies` holds the pruned targets of the full moves; root_N / root_W / root_P stay raw."""
         lay = self.layout
         cap = max_records or max(self.cfg.ring_capacity, 1)
@@ -490,12 +528,13 @@ class SelfPlayEngine:
             return raw[off:off + n].view(dt).reshape(shape).copy()
         actions = arr(lay.off_actions, np.uint8, (lay.t_pad,))[:T].astype(np.int32)
         q = arr(lay.off_q, np.float32, (lay.max_T,))[:T]
-        mover = np.where(np.arange(T) % 2 == 0, -1.0, 1.0).astype(np.float32)   # target_z.append(next_player), Self_Play.py:127
-        z = mover.copy()
-        if winner == -1 and T and z[-1] == -1.0:
-            z *= -1.0
-        elif winner == 0:
-            z[:] = 0.0
+        # z[p] = mover(p) * winner, the mover of ply p being -1 on even plies (target_z.append(next_player), Self_Play.py:127).  Without
+        # resignation the winner is 0 or the last mover, and this is the reference's rule (the mover signs, all turned when -1 won and moved
+        # last, zeros for a draw: Self_Play.py:165-172) value for value; a resigned game is won by the player who did NOT move last
+        mover = np.where(np.arange(T) % 2 == 0, -1, 1)
+        z = (mover * winner).astype(np.float32)
+        raw_kind = arr(lay.off_move_kind, np.uint8, (lay.t_pad,))[:T]
+        resigned_at = np.flatnonzero(raw_kind & MK_RESIGNED)
         return dict(T=T, winner=winner, slot=slot, game_seq=seq, actions=actions, q=q, z=z,
                     values=(np.float32(0.5) * (z + q)).astype(np.float32),
                     policies=arr(lay.off_policy, np.float32, (lay.max_T, A))[:T],
@@ -503,7 +542,9 @@ class SelfPlayEngine:
                     root_P=arr(lay.off_P, np.float32, (lay.max_T, A))[:T],
                     root_visits=arr(lay.off_root_visits, np.uint32, (lay.max_T,))[:T],
                     evals=arr(lay.off_evals, np.uint32, (lay.max_T,))[:T],
-                    move_kind=arr(lay.off_move_kind, np.uint8, (lay.t_pad,))[:T])
+                    move_kind=raw_kind & np.uint8(MK_KIND_MASK), resigned=bool(resigned_at.size),
+                    resign_ply=int(resigned_at[0]) if resigned_at.size else -1,
+                    would_resign_plies=np.flatnonzero(raw_kind & MK_WOULD_RESIGN).astype(np.int32))
 
     # ---- measurement ----------------------------------------------------------------------------------
     def repack(self):

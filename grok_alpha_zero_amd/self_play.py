@@ -329,6 +329,41 @@ def record_to_samples(game_class, rec):
     return aug_b, aug_p, aug_v, n_plies
 
 
+def resign_trigger_plies(q, move_kind, threshold, consecutive=1, min_ply=0):
+    """The plies of one game at which the resign rule of SelfPlayEngine.set_resignation triggers, from the record's q and move_kind:
+    ply p < T - 1 (the game went on after it) with p >= min_ply, p >= 2 (consecutive - 1) and, for i in 0 .. consecutive-1, ply p - 2i
+    searched (move_kind != 0) and q[p - 2i] < -threshold (the float32 widened to double, strict)."""
+    T = len(q)
+    out = []
+    for p in range(max(int(min_ply), 2 * (int(consecutive) - 1)), T - 1):
+        if all((int(move_kind[p - 2 * i]) & 3) != 0 and float(q[p - 2 * i]) < -float(threshold) for i in range(int(consecutive))):
+            out.append(p)
+    return out
+
+
+def resign_curve(records, thresholds, consecutive=1, min_ply=0):
+    """What resignation would have done to games that were played out (records of SelfPlayEngine.drain_finished(), e.g. a generation
+    with no_resign_prob = 1), per threshold: a list of dicts with `threshold`, `games`, `would_resign` (games in which the rule
+    triggers), `false_positives` (of those, games the player who would have resigned first went on to draw or win), `plies_saved`
+    (plies after the first trigger, summed) and `plies` (all plies played).  The threshold to use is the lowest one whose
+    false_positives / would_resign is acceptable (AlphaGo Zero: under 5 %)."""
+    rows = []
+    for thr in thresholds:
+        would = false_pos = saved = plies = 0
+        for r in records:
+            plies += int(r["T"])
+            hit = resign_trigger_plies(r["q"], r["move_kind"], thr, consecutive, min_ply)
+            if not hit:
+                continue
+            f = hit[0]
+            would += 1
+            saved += int(r["T"]) - (f + 1)
+            resigner = 1 if f % 2 else -1            # the mover of ply f: -1 moves first
+            false_pos += int(r["winner"]) != -resigner
+        rows.append(dict(threshold=float(thr), games=len(records), would_resign=would, false_positives=false_pos, plies_saved=saved, plies=plies))
+    return rows
+
+
 class _ReplayWriter:
     """The generation's writer thread: the only user of the ReplayStore while it lives, inside one `writing()` session.  The loop that
     queues the waves hands it work with put(); work is a SampleBatch (every game of it is appended, in order) or one game's
@@ -417,6 +452,13 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
     the full one (int(1.5 x) for PUCT); only fully searched plies are written as samples, game_stats count every ply played.
     Forced playouts and policy target pruning: train_config["forced_playouts_k"] (absent or 0 = off; KataGo uses 2; PUCT only) — every
     visited root child of a full move gets at least sqrt(k * prior * root visits) visits, and the policy written is the pruned target.
+    Resignation: train_config["resign_threshold"] (absent or 0 = off), ["resign_consecutive"] (default 1), ["resign_min_ply"] (default 0)
+    and ["no_resign_prob"] (default 0) — SelfPlayEngine.set_resignation: a game is resigned after a ply when the recorded q of its
+    mover's last `resign_consecutive` searched plies were all below -resign_threshold; with probability no_resign_prob a game is played
+    out instead and its would-be resign plies are marked.  The file format does not change: a resigned game has fewer rows, its winner
+    is the player who did not resign, and game_stats count it like any other game.  `engine_stats["resign"]` receives
+    SelfPlayEngine.resign_stats() (the false positives among the games played out); resign_curve() picks a threshold from the records
+    of a generation played with no_resign_prob = 1.
     `configs` = (build_config, train_config[, optimizer_config]).  `weights` = dict from net.export_engine_weights()
     (generation > 0); generation 0 (folder name "0") plays with the synthetic evaluator like the reference's
     session=None dummy (Self_Play.py:40, MCTS.py:237-241).
@@ -483,7 +525,9 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
                          move_time_limit=float(train_config.get("MCTS_time_limit") or 0.0), game_groups=game_groups,
                          leaf_batch=leaf_batch, gumbel_batch=gumbel_batch,
                          fast_iterations=fast, full_search_prob=float(train_config.get("full_search_prob") or 0.0) if fast else 0.0,
-                         forced_playouts_k=float(train_config.get("forced_playouts_k") or 0.0))
+                         forced_playouts_k=float(train_config.get("forced_playouts_k") or 0.0),
+                         resign_threshold=float(train_config.get("resign_threshold") or 0.0), resign_consecutive=int(train_config.get("resign_consecutive") or 1),
+                         resign_min_ply=int(train_config.get("resign_min_ply") or 0), no_resign_prob=float(train_config.get("no_resign_prob") or 0.0))
     if train_config.get("MCTS_time_limit") and gumbel:
         logging.getLogger("grok_alpha_zero_amd").warning("Time limit isn't allowed for gumbel MCTS defaulting to use 3 * len_legal_actions")   # MCTS_Gumbel.py:578
     logging.getLogger("grok_alpha_zero_amd").info("run_self_play: generation %d, %d games on %d slots, evaluator = %s, game_seq from %d",
@@ -537,6 +581,7 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
         w.close()                                   # everything queued is in the file; a failure of the writer surfaces here
         if engine_stats is not None:
             engine_stats.update({k: v for k, v in eng.stats().items() if k != "game_stats"})
+            engine_stats["resign"] = eng.resign_stats()
             engine_stats.update(gpu_wait_seconds=t_wait, sample_seconds=t_samples, queue_wait_seconds=w.wait_seconds, writer_seconds=w.write_seconds)
     finally:
         if writer is not None:                      # an error above: what was queued is still written, the thread is joined, the error stays the caller's

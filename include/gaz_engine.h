@@ -40,6 +40,9 @@
  *   gaz_engine_read_trees      MCTS.root and everything below it: Node.children / child_visits / child_values /
  *                              child_prob_priors / is_terminal of every node                                MCTS.py:20-72,403-426
  *   gaz_engine_read_pv         (no reference counterpart: the most visited line below every root)
+ *   gaz_engine_set_resignation / gaz_engine_get_resign_stats  (no reference counterpart: Self_Play.play() plays every game to its end;
+ *                              resignation with a share of games played out to measure its false positives is AlphaGo Zero's, Silver 2017)
+ *   the 0x10 / 0x20 bits of a record's move_kind  (no reference counterpart: the marks that rule leaves in the record)
  */
 #ifndef GAZ_ENGINE_H
 #define GAZ_ENGINE_H
@@ -56,7 +59,10 @@ enum { GAZ_EVAL_HASH = 0,      /* synthetic bit-reproducible evaluator (parity t
        GAZ_EVAL_RESNET = 1,    /* the ResNet policy/value network, HIP MFMA kernels */
        GAZ_EVAL_EXTERNAL = 2   /* caller evaluates the batch between wave_begin / wave_end */ };
 
-#define GAZ_ENGINE_ABI_VERSION 10  /* bumped whenever gaz_engine_config / gaz_search_hyperparams / an entry point changes */
+#define GAZ_ENGINE_ABI_VERSION 10  /* bumped whenever something EXISTING changes: a field of gaz_engine_config / gaz_search_hyperparams / a layout
+                                      struct, or the signature or meaning of an entry point.  A new entry point or a new struct next to
+                                      unchanged ones does not bump it: a caller detects such a feature by its symbol (dlsym), as with
+                                      gaz_engine_set_resignation */
 
 typedef struct {
     uint32_t struct_size;         /* = sizeof(gaz_engine_config) of the header the caller was built against; gaz_engine_create
@@ -190,7 +196,10 @@ typedef struct {
     int32_t record_bytes, max_T, A, t_pad;
     int32_t off_hdr, off_actions, off_q, off_root_visits, off_evals, off_policy, off_N, off_W, off_P;
     int32_t off_move_kind;        /* u8 [t_pad] per ply: 0 = no search ran there (a gaz_engine_set_position prefix), 1 = full search, 2 = fast search
-                                     (gaz_engine_config.fast_iterations); always 1 for a searched ply with the cap off */
+                                     (gaz_engine_config.fast_iterations); always 1 for a searched ply with the cap off.  That kind is the byte's
+                                     low two bits (& 3).  With resignation on (gaz_engine_set_resignation) two more bits may be set: 0x10 on the last
+                                     ply of a game that was resigned after it, 0x20 on every ply of a game played out with resignation
+                                     disabled at which it would have been resigned; all other bits are 0 */
 } gaz_record_layout;
 
 int gaz_engine_abi_version(void);                   /* GAZ_ENGINE_ABI_VERSION of the library */
@@ -236,6 +245,35 @@ int gaz_engine_set_position(gaz_engine* h, int32_t slot, const int32_t* actions,
 int gaz_engine_set_search_params(gaz_engine* h, int32_t run_iterations, int32_t tau_mode);
 /* MCTS.update_hyperparams / MCTS_Gumbel.update_hyperparams for every tree of the engine (see gaz_search_hyperparams) */
 int gaz_engine_set_hyperparams(gaz_engine* h, const gaz_search_hyperparams* hp);
+/* Resignation in self-play, with games played out to calibrate it (no reference counterpart).  Legal on any engine
+ * and at any time; takes effect at the next launch, like gaz_engine_set_hyperparams.  threshold = 0 = off, the state of a new engine (the
+ * other fields are then ignored).  With threshold in (0, 1): after ply p (0-based) of a game that goes on — natural ends and the
+ * max_actions cap take precedence — the rule triggers iff p >= min_ply, p >= 2 (consecutive - 1) and for i in 0 .. consecutive-1 ply
+ * p - 2i was searched ((move_kind & 3) != 0) and its recorded q, the float widened to double, is < -threshold: the mover's last
+ * `consecutive` searched plies all saw the game as lost.  A ply without a search (a gaz_engine_set_position prefix, a host move on an idle
+ * slot) breaks a run; fast plies of the playout cap count like full ones.  A game is a PLAY-OUT game iff the uniform variate (tree 2,
+ * event 0, purpose 6) of its (seed, slot, game_seq) is < no_resign_prob; no other variate is drawn and no search changes, so a game's
+ * record with resignation on is a prefix of its record with it off.
+ *   trigger, not a play-out game: the game ends after ply p, the move played and recorded: hdr = [p + 1, -mover, slot, game_seq],
+ *                                 move_kind[p] |= 0x10, game_stats count it like any other game
+ *   trigger, play-out game:       move_kind[p] |= 0x20 and the game goes on
+ * The value target of a record is z[p] = mover(p) * winner (the winner of a resigned game is not its last mover).
+ * Refused (last_error): a struct_size other than sizeof(gaz_resign_params); threshold NaN, infinite, negative or >= 1; consecutive outside
+ * [1, 8]; min_ply < 0; no_resign_prob NaN or outside [0, 1]. */
+typedef struct {
+    uint32_t struct_size;         /* = sizeof(gaz_resign_params) */
+    int32_t consecutive;          /* 1 .. 8 */
+    int32_t min_ply;              /* >= 0 */
+    int32_t reserved_;
+    double threshold;             /* 0 = off, else in (0, 1) */
+    double no_resign_prob;        /* in [0, 1]: the share of games played out (AlphaGo Zero: 0.1, false positives kept under 5 %) */
+} gaz_resign_params;
+int gaz_engine_set_resignation(gaz_engine* h, const gaz_resign_params* p);
+/* counters over the engine's life, summed over the game groups; a host synchronisation point like gaz_engine_get_stats:
+ * [0] games ended by resignation, [1] of them resigned by player -1, [2] by player 1, [3] play-out games finished, [4] of those with a
+ * would-have-resigned ply, [5] of those false positives (the would-be resigner of the FIRST such ply drew or won), [6] plies of the
+ * resigned games (sum of T), [7] 0 */
+int gaz_engine_get_resign_stats(gaz_engine* h, uint64_t out[8]);
 /* MCTS.run(time_limit=...) (MCTS.py:528-563): stop != 0 makes every running search finish its move at the next launch, as the
  * reference's `time.time() - start_time < time_limit` test does between iterations; stop = 0 re-arms.  The host owns the clock. */
 int gaz_engine_stop_search(gaz_engine* h, int32_t stop);
