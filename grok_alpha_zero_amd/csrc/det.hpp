@@ -13,7 +13,8 @@
 namespace gaz {
 namespace det {
 
-enum : uint32_t { P_DIRICHLET = 0, P_TERMINAL_PICK = 1, P_MOVE = 2, P_GUMBEL = 3, P_OPENING = 4, P_PLAYOUT_CAP = 5, P_RESIGN = 6 };   // three bits in draw()
+enum : uint32_t { P_DIRICHLET = 0, P_TERMINAL_PICK = 1, P_MOVE = 2, P_GUMBEL = 3, P_OPENING = 4, P_PLAYOUT_CAP = 5, P_RESIGN = 6,
+                  P_EVAL_SYMMETRY = 7 };   // three bits in draw(): 7 is the last free value
 
 struct Event {
     uint32_t key0, key1;  // 64-bit seed

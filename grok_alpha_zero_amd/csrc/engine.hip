@@ -261,6 +261,7 @@ template <class G> GAZ_KERNEL_WIDE k_move_slots(DevParams<G> E, const int32_t* m
     copy1(E.nn_in + (size_t)dst * (G::HW * G::C), E.nn_in + (size_t)src * (G::HW * G::C), G::HW * G::C);
     copy1(E.nn_policy + (size_t)dst * G::A, E.nn_policy + (size_t)src * G::A, 4 * G::A);
     copy1(E.nn_value + dst, E.nn_value + src, 4);
+    copy1(E.row_sym() + dst, E.row_sym() + src, 1);                      // the symmetry the row was encoded under answers with it
     if (E.eval_done) copy1(E.eval_done + dst, E.eval_done + src, 4);
     // swap the two GameStates word by word (each thread its own words: no staging needed)
     uint32_t* ga = reinterpret_cast<uint32_t*>(&E.games[src]); uint32_t* gb = reinterpret_cast<uint32_t*>(&E.games[dst]);
@@ -362,6 +363,9 @@ struct gaz_engine {
     virtual int set_hyperparams(const gaz_search_hyperparams*) = 0;
     virtual int set_resignation(const gaz_resign_params*) = 0;
     virtual int get_resign_stats(uint64_t out[8]) = 0;
+    virtual int set_eval_symmetry(int32_t mode) = 0;
+    virtual int get_eval_symmetry(int32_t* mode) = 0;
+    virtual int read_batch_symmetry(uint8_t* sym) = 0;
     virtual int read_head_features(int, float*, float*, int32_t*, int32_t*) = 0;
     virtual int set_fused_wave(int) = 0;
     virtual int debug_fused_fault(int) = 0;
@@ -519,7 +523,9 @@ template <class G> struct EngineT : gaz_engine {
         if (dalloc(&E.ring_head, 4)) return 1;
         if (dalloc(&E.nn_in, rows * G::HW * G::C + 64)) return 1;
         if (dalloc(&E.nn_policy, rows * G::A + 64)) return 1;
-        if (dalloc(&E.nn_value, rows + 64)) return 1;
+        // behind the value rows, in the same allocation: one symmetry byte per batch row (DevParams::row_sym()), zeroed = the identity
+        E.row_sym_off = (uint32_t)((rows + 64) * sizeof(float));
+        if (dalloc(&E.nn_value, rows + 64 + (rows + 64 + 3) / 4)) return 1;
         if (cfg.eval_cache_log2 < 0 || cfg.eval_cache_log2 > 28) return fail("eval_cache_log2 out of range (0 = off, at most 28)");
         if (cfg.eval_cache_log2 > 0) {
             const size_t slots = (size_t)1 << cfg.eval_cache_log2;
@@ -595,9 +601,12 @@ template <class G> struct EngineT : gaz_engine {
     bool prev_marked = false;                        // the wave before this one wrote eval_done
     DevParams<G> wave_params() { DevParams<G> P = E; P.wave_epoch = ++fuse_epoch; P.eval_done = prev_marked ? d_evaldone : nullptr; return P; }
     void launch_wave(hipStream_t st, int g0, int g1) { const DevParams<G> P = wave_params(); prev_marked = false; launch_wave(st, g0, g1, P); }   // (callers follow with a full evaluator pass)
-    void launch_wave(hipStream_t st, int g0, int g1, const DevParams<G>& E) {
+    void launch_wave(hipStream_t st, int g0, int g1, const DevParams<G>& E) { if (E.eval_symmetry) launch_wave_v<true>(st, g0, g1, E); else launch_wave_v<false>(st, g0, g1, E); }
+    // SYM: the instantiations with the code of the random evaluation symmetry (games.hpp WithSym; same layouts, so the parameters are reinterpreted)
+    template <bool SYM> void launch_wave_v(hipStream_t st, int g0, int g1, const DevParams<G>& E) {
         // the small boards run four games per wavefront (PuctVariant: same records, 16-lane teams); GAZ_TREE_TEAMS=0 -> one per wave
-        typedef typename PuctVariant<G>::type GP;
+        typedef typename SymSel<SYM, typename PuctVariant<G>::type>::type GP;
+        typedef typename SymSel<SYM, G>::type GS;
         if (gbk > 1) {                                // (Gumbel only, no evaluation cache: gaz_engine_create refuses the rest; the register budget of k_wave_lb)
             constexpr int PER = WAVE / GP::TEAM;
             GAZ_LAUNCH(k_wave_gb<GP>, (g1 - g0 + PER - 1) / PER, WAVE, st, *reinterpret_cast<const DevParams<GP>*>(&E), GB, g0, g1);
@@ -616,7 +625,7 @@ template <class G> struct EngineT : gaz_engine {
             // measured (8192 Connect4 games, n = 32, m = 7): the team build is bit-exact but SLOWER, 225 vs 185 us per launch (sequential
             // halving keeps the four games of a wave in different phases) — opt-in only (GAZ_TREE_TEAMS=1)
             if (GPER > 1 && gteams_env == 1) GAZ_LAUNCH(k_wave_gumbel_teams<GP>, (g1 - g0 + GPER - 1) / GPER, WAVE, st, *reinterpret_cast<const DevParams<GP>*>(&E), g0, g1);
-            else GAZ_LAUNCH(k_wave_gumbel<G>, g1 - g0, WAVE, st, E, g0, g1);
+            else GAZ_LAUNCH(k_wave_gumbel<GS>, g1 - g0, WAVE, st, *reinterpret_cast<const DevParams<GS>*>(&E), g0, g1);
             return;
         }
         // measured (4096 Connect4 games): 66 vs 71 us per launch; with the evaluation cache (up to 8 evaluation-free simulations per
@@ -625,7 +634,7 @@ template <class G> struct EngineT : gaz_engine {
         const bool teams = teams_env >= 0 ? teams_env != 0 : E.cache == nullptr;
         constexpr int PER = WAVE / GP::TEAM;
         if (PER > 1 && teams) GAZ_LAUNCH(k_wave_teams<GP>, (g1 - g0 + PER - 1) / PER, WAVE, st, *reinterpret_cast<const DevParams<GP>*>(&E), g0, g1);
-        else GAZ_LAUNCH(k_wave<G>, g1 - g0, WAVE, st, E, g0, g1);
+        else GAZ_LAUNCH(k_wave<GS>, g1 - g0, WAVE, st, *reinterpret_cast<const DevParams<GS>*>(&E), g0, g1);
     }
     void launch_wave() { launch_wave(stream, 0, n_eff); }
 
@@ -977,6 +986,11 @@ template <class G> struct EngineT : gaz_engine {
             else GAZ_LAUNCH(k_gather_root<G>, E.n_games, WAVE, stream, E, dN, dW, dP, dPol, dRV, dQ, dChosen, dPhase, dPending);
             HIP_OK(hipMemcpyAsync(pending, dPending, rows * 4, hipMemcpyDeviceToHost, stream));
         }
+        HIP_OK(hipStreamSynchronize(stream));
+        return check_device_error();
+    }
+    int read_batch_symmetry(uint8_t* sym) override {
+        HIP_OK(hipMemcpyAsync(sym, E.row_sym(), rows, hipMemcpyDeviceToHost, stream));
         HIP_OK(hipStreamSynchronize(stream));
         return check_device_error();
     }
@@ -1350,6 +1364,13 @@ template <class G> struct EngineT : gaz_engine {
         for (int i = 0; i < 7; ++i) out[i] = s[i];
         return check_device_error();
     }
+    // random board symmetry per evaluator request (puct_core.hpp eval_sym_draw): kernels take DevParams by value per launch, so rows encoded
+    // from the next launch on follow the mode; rows in flight are answered under the byte they were encoded with (DevParams::row_sym)
+    // The kernels with the symmetry code (games.hpp WithSym) are launched from the first time the mode is 1, and from then on for good: rows encoded
+    // under a symmetry may be in flight when the mode goes back to 0, and only those kernels read a row's byte
+    // (DevParams::eval_symmetry: bit 0 = the mode, bit 1 = those kernels are in use)
+    int set_eval_symmetry(int32_t mode) override { E.eval_symmetry = (mode ? 1 : 0) | ((mode || E.eval_symmetry) ? 2 : 0); return 0; }
+    int get_eval_symmetry(int32_t* mode) override { *mode = E.eval_symmetry & 1; return 0; }
     int8_t* pr_board = nullptr; uint8_t* pr_legal = nullptr; int32_t* pr_winner = nullptr; int8_t* pr_input = nullptr; int32_t* pr_term = nullptr;
     int32_t* pr_actions = nullptr; int32_t* pr_n = nullptr; float* pr_pin = nullptr; float* pr_pout = nullptr; int pr_cap = 0, pr_stride = 0;
     int probe_rules(const int32_t* actions, const int32_t* n_actions, int n_pos, int stride, int8_t* o_board, uint8_t* o_legal,
@@ -1501,6 +1522,7 @@ struct GroupEngine : gaz_engine {
     int wave_end() override { return no_batch(); }
     int batch_ptrs(void**, void**, void**) override { return no_batch(); }
     int read_batch(int8_t*, int32_t*) override { return no_batch(); }
+    int read_batch_symmetry(uint8_t*) override { return fail("read_batch_symmetry: game groups hold one evaluator batch each, like read_batch it needs game_groups = 1"); }
     int batch_rows(int32_t*) override { return no_batch(); }
     int write_outputs(const float*, const float*) override { return no_batch(); }
     // rows [first[c], first[c + 1]) go through group c's evaluator (and stay in ITS head-feature buffers: read_head_features below); ms: the sum
@@ -1587,6 +1609,8 @@ struct GroupEngine : gaz_engine {
     int start_search() override { return each([](gaz_engine* k, int) { return k->start_search(); }); }
     int set_hyperparams(const gaz_search_hyperparams* hp) override { return each([&](gaz_engine* k, int) { return k->set_hyperparams(hp); }); }
     int set_resignation(const gaz_resign_params* p) override { return each([&](gaz_engine* k, int) { return k->set_resignation(p); }); }
+    int set_eval_symmetry(int32_t mode) override { return each([&](gaz_engine* k, int) { return k->set_eval_symmetry(mode); }); }
+    int get_eval_symmetry(int32_t* mode) override { return up(kid[0], kid[0]->get_eval_symmetry(mode)); }
     int get_resign_stats(uint64_t out[8]) override {
         for (int i = 0; i < 8; ++i) out[i] = 0;
         return each([&](gaz_engine* k, int) { uint64_t s[8]; if (k->get_resign_stats(s)) return 1; for (int i = 0; i < 8; ++i) out[i] += s[i]; return 0; });
@@ -1788,6 +1812,13 @@ int gaz_engine_set_resignation(gaz_engine* h, const gaz_resign_params* p) {
     return h->set_resignation(p);
 }
 int gaz_engine_get_resign_stats(gaz_engine* h, uint64_t out[8]) { return out ? h->get_resign_stats(out) : h->fail("get_resign_stats: null argument"); }
+// random board symmetry per evaluator request: 0 = off (a new engine), 1 = on
+int gaz_engine_set_eval_symmetry(gaz_engine* h, int32_t mode) {
+    if (mode != 0 && mode != 1) return h->fail("set_eval_symmetry: mode must be 0 (off) or 1 (a random board symmetry per evaluator request), not " + std::to_string(mode));
+    return h->set_eval_symmetry(mode);
+}
+int gaz_engine_get_eval_symmetry(gaz_engine* h, int32_t* mode) { return mode ? h->get_eval_symmetry(mode) : h->fail("get_eval_symmetry: null argument"); }
+int gaz_engine_read_batch_symmetry(gaz_engine* h, uint8_t* sym) { return sym ? h->read_batch_symmetry(sym) : h->fail("read_batch_symmetry: null argument"); }
 int gaz_engine_set_fused_wave(gaz_engine* h, int32_t on) { return h->set_fused_wave(on); }
 int gaz_engine_debug_fused_fault(gaz_engine* h, int32_t mod) { return h->debug_fused_fault(mod); }
 int gaz_engine_read_positions(gaz_engine* h, int32_t* n_hist, uint8_t* hist, int32_t stride) { return h->read_positions(n_hist, hist, stride); }

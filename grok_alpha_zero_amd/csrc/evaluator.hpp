@@ -90,6 +90,8 @@ struct HashEvaluator : Evaluator {
 Evaluator* make_resnet_evaluator(const gaz_engine_config& cfg, int H, int W, int C, int A, std::string* err);
 // resnet.hip k_wave_trunk: ONE launch = the PUCT tree step of Connect4 games [g0, g1) (16-lane teams) + the trunk kernel of their leaf rows.
 // dev_params: DevParams<TeamGame<GAME_C4>> by value; plan: what Evaluator::trunk_plan returned.  false = not launched.
+// (all three) a non-zero DevParams::eval_symmetry selects the instantiation whose tree role carries the code of the random evaluation symmetry
+// (games.hpp WithSym)
 bool launch_wave_trunk_c4(hipStream_t s, const void* dev_params, int g0, int g1, const void* plan);
 // the same for the Gumbel search (MCTS_Gumbel.py:562-679) of Connect4: one wavefront per game, four games per tree block.  dev_params: DevParams<Game<GAME_C4>>
 bool launch_wave_trunk_c4_gumbel(hipStream_t s, const void* dev_params, int g0, int g1, const void* plan);

@@ -22,19 +22,30 @@ template <> struct Game<GAME_TTT> {
     static constexpr int APAD = 16, BPAD = 16, MAXT = 9, TPAD = 16;
     static constexpr bool DRAWS = true;
     static constexpr int TEAM = GAZ_TEAM(64);       // lanes that own one game (wave.hpp "Teams")
+    static constexpr bool SYM = false;              // see WithSym below
 };
 template <> struct Game<GAME_C4> {
     static constexpr int ID = GAME_C4, H = 6, W = 7, HW = 42, C = 4, A = 7, K = 4;
     static constexpr int APAD = 8, BPAD = 48, MAXT = 42, TPAD = 48;
     static constexpr bool DRAWS = true;
     static constexpr int TEAM = GAZ_TEAM(64);
+    static constexpr bool SYM = false;
 };
 template <> struct Game<GAME_GMK> {
     static constexpr int ID = GAME_GMK, H = 15, W = 15, HW = 225, C = 2, A = 225, K = 5;
     static constexpr int APAD = 232, BPAD = 240, MAXT = 225, TPAD = 232;
     static constexpr bool DRAWS = false;   // check_win_MCTS never reports a draw (Gomoku.py:249-255)
     static constexpr int TEAM = GAZ_TEAM(64);
+    static constexpr bool SYM = false;
 };
+
+// The same game with the code of the search's random evaluation symmetry compiled in (puct_core.hpp eval_sym_draw; gaz_engine_set_eval_symmetry):
+// every tree kernel exists twice, and an engine launches the WithSym instantiations from the first time the symmetry is switched on.  Until then it
+// runs the kernels without that code — the fused tree + trunk launches sit at their register cap, and the hash and the Philox rounds of the draw
+// cost them spilled VGPRs even on the path that never executes them.  Identical rules and layouts: HBM state is shared between the two.
+template <class B> struct WithSym : B { static constexpr bool SYM = true; };
+template <bool S, class B> struct SymSel { typedef B type; };
+template <class B> struct SymSel<true, B> { typedef WithSym<B> type; };
 
 // The same game stepped by a 16-lane team: FOUR games per wavefront (PUCT tree kernel of the small boards).  Identical rules and
 // record layouts — only the lane mapping differs, so HBM state written by one variant is read by the other.
@@ -45,6 +56,25 @@ template <int ID> struct TeamGame : Game<ID> { static constexpr int TEAM = GAZ_T
 template <class G> struct PuctVariant { typedef G type; };
 template <> struct PuctVariant<Game<GAME_TTT>> { typedef TeamGame<GAME_TTT> type; };
 template <> struct PuctVariant<Game<GAME_C4>> { typedef TeamGame<GAME_C4> type; };
+
+// cell (y, x) of symmetry k of a square board of side W -> the cell of the original board it shows.  The order is that of
+// games._GridGame.augment_sample: id, flipud, fliplr, rot90, flipud(rot90), fliplr(rot90), rot180, rot270 (np.rot90: counter-clockwise,
+// rot90(m)[y][x] = m[x][n-1-y]).  Shared by the training samples (samples.hpp) and the search's random evaluation symmetry (puct_core.hpp).
+GAZ_DEV int square_src_cell(int k, int y, int x, int W) {
+    const int n = W - 1;
+    int sy = y, sx = x;
+    switch (k) {
+        case 1: sy = n - y; break;
+        case 2: sx = n - x; break;
+        case 3: sy = x; sx = n - y; break;
+        case 4: sy = x; sx = y; break;
+        case 5: sy = n - x; sx = n - y; break;
+        case 6: sy = n - y; sx = n - x; break;
+        case 7: sy = n - x; sx = y; break;
+        default: break;
+    }
+    return sy * W + sx;
+}
 
 // is action a legal on this board?  (get_legal_actions_MCTS: Connect4.py:271-276 column not full —
 // pieces stack from row 5 upward so "sum |col| < 6" == top cell empty; Gomoku.py:114-119 /

@@ -366,19 +366,23 @@ template <class G> GAZ_DEV bool g_root_pre(const DevParams<G>& E, int g, GameSta
         wave_sync();
         return false;
     }
-    encode_input<G>(S.board, -gs.next_player, h3, gs.n_hist, E.nn_in + (size_t)row * (G::HW * G::C), E.done_flag != nullptr);
+    encode_request<G>(E, gs, S.board, -gs.next_player, h3, gs.n_hist, (size_t)row, E.done_flag != nullptr);
     wave_sync();
     return true;
 }
 
 // children of a freshly evaluated node: raw logits of the legal actions in legal order (normalize=False), all unexpanded
 // `fresh`: S.board already is this node's board (same launch as g_expand_pre / g_root_pre: evaluation-cache hit)
+// `row`: the batch row the request was encoded in — `policy` is in the network's frame under that row's symmetry (puct_core.hpp
+// eval_sym_policy_index), the children are by the position's own actions
 template <class G> GAZ_DEV void g_write_children(const DevParams<G>& E, int g, const NodeRef<G>& nd, Scratch<G>& S, const float* policy,
-                                                 bool fresh = false) {
+                                                 int row, bool fresh = false) {
     if (!fresh) { copy_board<G>(S.board, nd.board()); wave_sync(); }
     const int n_legal = build_legal<G>(S.board, S.legal);
+    const int sym = row_sym_of<G>(E, (size_t)row);
     for (int i = tlane<G>(); i < n_legal; i += G::TEAM) {
-        nd.N()[i] = 0u; nd.W()[i] = 0.0f; node_raw<G>(nd)[i] = 0.0f; nd.P()[i] = policy[S.legal[i]];
+        const int a = S.legal[i];
+        nd.N()[i] = 0u; nd.W()[i] = 0.0f; node_raw<G>(nd)[i] = 0.0f; nd.P()[i] = policy[sym ? eval_sym_policy_index<G>(sym, a) : a];
         nd.child()[i] = CHILD_NONE; nd.act()[i] = S.legal[i];
     }
     if (tlane<G>() == 0) { nd.hdr()->n_actions = (uint8_t)n_legal; nd.hdr()->n_children = 0; }
@@ -430,7 +434,7 @@ template <class G> GAZ_DEV bool g_expand_pre(const DevParams<G>& E, int g, GameS
         return false;
     }
     uint8_t h3[3] = {(uint8_t)action, ph.hist3[0], ph.hist3[1]};
-    encode_input<G>(S.board, mover, h3, (int)ph.n_hist + 1, E.nn_in + (size_t)row * (G::HW * G::C), E.done_flag != nullptr);
+    encode_request<G>(E, gs, S.board, mover, h3, (int)ph.n_hist + 1, (size_t)row, E.done_flag != nullptr);
     PathEnt* gp = E.paths + (size_t)row * PathCap<G>::V;
     for (int d = tlane<G>(); d <= depth; d += G::TEAM) gp[d] = S.path[d];
     if (tlane<G>() == 0) {
@@ -445,7 +449,7 @@ template <class G> GAZ_DEV void g_expand_post(const DevParams<G>& E, int g, Game
                                               const float* policy, const float* value_p, int row, bool fresh = false) {
     const int node = gs.pend_parent, index = gs.pend_slot, idx = gs.pend_node, depth = gs.pend_depth;
     NodeRef<G> nd = node_at(E, g, 0, idx);
-    g_write_children<G>(E, g, nd, S, policy, fresh);
+    g_write_children<G>(E, g, nd, S, policy, row, fresh);
     NodeRef<G> pn = node_at(E, g, 0, node);
     const float value = *value_p;
     if (tlane<G>() == 0) { pn.child()[index] = idx; node_raw<G>(pn)[index] = value; }       // MCTS_Gumbel.py:516-517
@@ -593,7 +597,7 @@ template <class G, bool GB = false, class Fin> GAZ_DEV void g_game_step_body(con
     const long long tp0 = GAZ_PROF_NOW();
     if (E.prof && tlane<G>() == 0) E.prof[(size_t)g * 8 + 7] += 1;
     if (tuni<G>(gs.pend_kind) == PEND_ROOT) {
-        g_write_children<G>(E, g, node_at(E, g, 0, ts.root), S, E.nn_policy + (size_t)row0 * G::A);
+        g_write_children<G>(E, g, node_at(E, g, 0, ts.root), S, E.nn_policy + (size_t)row0 * G::A, row0);
         if (tlane<G>() == 0) { gs.pend_kind = PEND_NONE; gs.roots_todo = 0; gs.n_evals += 1; }
         wave_sync();
     } else if (tuni<G>(gs.pend_kind) == PEND_EXPAND) {
@@ -645,7 +649,7 @@ template <class G, bool GB = false, class Fin> GAZ_DEV void g_game_step_body(con
             if (g_root_pre<G>(E, g, gs, ts, S, row0)) {
                 const uint8_t* hit = E.cache ? cache_probe<G>(E, g) : nullptr;
                 if (hit) {                                                     // evaluation cache hit
-                    g_write_children<G>(E, g, node_at(E, g, 0, ts.root), S, reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_POL), true);
+                    g_write_children<G>(E, g, node_at(E, g, 0, ts.root), S, reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_POL), row0, true);
                     if (tlane<G>() == 0) { gs.roots_todo = 0; gs.n_evals += 1; gs.n_hits += 1; }
                     wave_sync();
                     return false;

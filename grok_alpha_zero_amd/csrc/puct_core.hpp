@@ -44,6 +44,8 @@ template <class G> struct DevParams {
     // configuration
     int32_t n_games, run_iterations, max_actions, explore_first, explore_second;
     int32_t create_new_root, sync_moves, nodes_per_tree, ring_cap, use_dirichlet, max_tree_sims;
+    int32_t eval_symmetry;     // random board symmetry per evaluator request (gaz_engine_set_eval_symmetry): bit 0 = the mode (1 = on), bit 1 = it has been on,
+                               // so the host launches the kernels that carry its code (games.hpp WithSym); 0 = a new engine
     double c_init, c_base, alpha, eps;
     double c_visit, c_scale;   // Gumbel (MCTS_Gumbel.py:160-161)
     int32_t gumbel_m, node_bytes, compact;
@@ -54,6 +56,7 @@ template <class G> struct DevParams {
     uint64_t move_time_ticks;
     int32_t fast_find_win;     // MCTS(fast_find_win=True): keep only the first winning move of a position (MCTS.py:282-283)
     int32_t g_stablemax;       // Gumbel: activation_fn = "stablemax" in deterministic_selection (Self_Play.py:69)
+    uint32_t row_sym_off;      // the symmetry bytes of the batch rows live behind the value rows, in nn_value's allocation: this many bytes from nn_value (row_sym())
     int32_t single_tree;       // 1: one tree searches for both players (MCTS used on its own, e.g. Connect4/play.py, Game_Tester.py:480-513)
     double tau;                // < 0: Self_Play's exploration schedule (tau 1 / 0); >= 0: tau fixed by the caller (MCTS(tau=...), update_hyperparams)
     int32_t no_gumbel_noise;   // MCTS_Gumbel(use_gumbel_noise=False)
@@ -95,6 +98,10 @@ template <class G> struct DevParams {
     // never computed.  A game only loses a wave: its results cannot change.  (Marking success, not failure: a workgroup of THIS launch may give
     // up before this game's team has even started, and must not be able to disturb what the team reads about the previous launch.)
     uint32_t* eval_done;       // [n_games] or null
+    // random board symmetry per evaluator request: row_sym()[row] = the symmetry k the row was encoded under (0 while
+    // eval_symmetry is off).  The launch that consumes a row un-permutes its policy with THIS byte, never with the mode.  (No pointer of its own,
+    // and the two words above sit in what was padding: the struct — which the fused launches copy to their stack — keeps its size.)
+    GAZ_HD uint8_t* row_sym() const { return reinterpret_cast<uint8_t*>(nn_value) + row_sym_off; }
     // completion queue of the fused launch (round 3; trunk.hpp TrunkArgs::queue): instead of a flag per game, a finished game's team appends the
     // game to a queue and the trunk workgroups take ENTRIES, not fixed boards — the first tiles get whichever games finished first, and no
     // workgroup sits on a slot waiting for one slow game (rows of an evaluator batch are independent bit for bit, so which tile evaluates a
@@ -278,11 +285,57 @@ template <class G> GAZ_DEV int terminal_probe(const int8_t* board, const uint8_t
     return nt;
 }
 
+GAZ_DEV uint64_t mix64(uint64_t x) {
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+    return x;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Random board symmetry per evaluator request (DevParams::eval_symmetry; AlphaGo Zero, KataGo; no reference
+// counterpart — the reference only augments its training samples, Guide.py:255-283).  The network sees T_k(state), k drawn per POSITION of a
+// game: the key is a hash of the int8 board (cells in canonical order; each lane mixes the cells it owns and the team adds, as row_hash
+// does), the variate one uniform of the game-level stream (tree 2) with that key as its event and a purpose of its own.  No tree's event
+// counter moves, both trees of a game (and the evaluation cache) see the same k for the same position, and k can be replayed from (seed,
+// slot, game_seq, board) alone — whatever the launch shape, the batch row or the cache did.  Square boards: the 8 transforms of
+// games._GridGame.augment_sample, in its order; Connect4: the identity and the COLUMN mirror (not the row reversal its augment_sample
+// applies to the states of the samples).
+template <class G> struct EvalSym { static constexpr int N = G::ID == GAME_C4 ? 2 : 8; };
+
+// batch-row cell c under symmetry k -> the cell of the position it shows: row[c] = state[eval_sym_src_cell(k, c)]
+template <class G> GAZ_DEV int eval_sym_src_cell(int k, int c) {
+    if (G::ID == GAME_C4) { const int x = c % G::W; return k ? c - x + (G::W - 1 - x) : c; }
+    return square_src_cell(k, c / G::W, c % G::W, G::W);
+}
+// action a of the position -> its index in the network's policy row.  That is the inverse permutation, i.e. the source map of the inverse
+// transform, [0, 1, 2, 7, 4, 5, 6, 3]: the two quarter turns swap, every other transform is its own inverse
+template <class G> GAZ_DEV int eval_sym_policy_index(int k, int a) {
+    if (G::ID == GAME_C4) return k ? G::A - 1 - a : a;
+    return square_src_cell(k == 3 ? 7 : (k == 7 ? 3 : k), a / G::W, a % G::W, G::W);
+}
+// the symmetry of the request for `board` (team-uniform; 0 when the feature is off: nothing is hashed or drawn)
+template <class G> GAZ_DEV int eval_sym_draw(const DevParams<G>& E, const GameState<G>& gs, const int8_t* board) {
+    if (!(E.eval_symmetry & 1)) return 0;
+    uint64_t h = 0;
+    for (int c = tlane<G>(); c < G::HW; c += G::TEAM) h += mix64(((uint64_t)(c + 1) << 32) | (uint64_t)(uint8_t)board[c]);
+    h = team_sum_u64<G>(h);
+    det::Event e; e.key0 = E.key0; e.key1 = E.key1; e.slot = gs.slot_id; e.game_seq = gs.game_seq;
+    e.event = (uint32_t)(mix64(h) >> 32); e.tree = 2; e.purpose = det::P_EVAL_SYMMETRY;
+    int k = (int)(det::uniform(e) * (double)EvalSym<G>::N);
+    if (k > EvalSym<G>::N - 1) k = EvalSym<G>::N - 1;
+    return tuni<G>(k);
+}
+// the symmetry batch row `row` was encoded under (team-uniform)
+template <class G> GAZ_DEV int row_sym_of(const DevParams<G>& E, size_t row) {
+    if constexpr (G::SYM) return tuni<G>((int)E.row_sym()[row]);
+    else return 0;
+}
+
 // get_input_state_MCTS -> int8 [HW][C] row of the evaluator batch.
 // Connect4.py:329-346 (incl. the plane-0 overwrite once >= 4 moves were played), Gomoku.py:175-177,
 // Tictactoe.py:231-235.  hist3 = last three actions newest first, n_hist = len(action_history).
+// sym: the row shows the state under that board symmetry: output cell c takes all its planes from cell sc = eval_sym_src_cell(sym, c)
 template <class G> GAZ_DEV void encode_input(const int8_t* board, int current_player, const uint8_t* hist3, int n_hist,
-                                             int8_t* out, bool coherent = false) {
+                                             int8_t* out, bool coherent = false, int sym = 0) {
     if (G::ID == GAME_C4) {
         int max_length = n_hist - 1; if (max_length > 3) max_length = 3; if (max_length < 0) max_length = 0;
         int rem[3] = {-1, -1, -1};
@@ -303,10 +356,11 @@ template <class G> GAZ_DEV void encode_input(const int8_t* board, int current_pl
             rem[i] = y * 7 + x;
         }
         for (int c = tlane<G>(); c < G::HW; c += G::TEAM) {
-            int8_t b = board[c];
-            int8_t p2 = (c == rem[0]) ? 0 : b;
-            int8_t p1 = (c == rem[0] || c == rem[1]) ? 0 : b;
-            int8_t p0 = (max_length >= 3) ? ((c == rem[0] || c == rem[1] || c == rem[2]) ? (int8_t)0 : b)
+            const int sc = sym ? eval_sym_src_cell<G>(sym, c) : c;
+            int8_t b = board[sc];
+            int8_t p2 = (sc == rem[0]) ? 0 : b;
+            int8_t p1 = (sc == rem[0] || sc == rem[1]) ? 0 : b;
+            int8_t p0 = (max_length >= 3) ? ((sc == rem[0] || sc == rem[1] || sc == rem[2]) ? (int8_t)0 : b)
                                           : (int8_t)current_player;
             if (max_length < 1) p2 = 0;
             if (max_length < 2) p1 = 0;
@@ -317,8 +371,20 @@ template <class G> GAZ_DEV void encode_input(const int8_t* board, int current_pl
     } else {
         for (int c = tlane<G>(); c < G::HW; c += G::TEAM) {
             out[c * 2] = (int8_t)(-current_player);
-            out[c * 2 + 1] = board[c];
+            out[c * 2 + 1] = board[sym ? eval_sym_src_cell<G>(sym, c) : c];
         }
+    }
+}
+
+// one evaluator request: draw the position's symmetry, write the (permuted) row and the row's symmetry byte
+template <class G> GAZ_DEV void encode_request(const DevParams<G>& E, const GameState<G>& gs, const int8_t* board, int current_player,
+                                               const uint8_t* hist3, int n_hist, size_t row, bool coherent) {
+    if constexpr (G::SYM) {
+        const int k = eval_sym_draw<G>(E, gs, board);
+        encode_input<G>(board, current_player, hist3, n_hist, E.nn_in + row * (G::HW * G::C), coherent, k);
+        if (tlane<G>() == 0) E.row_sym()[row] = (uint8_t)k;
+    } else {                                         // (an engine that never switched the symmetry on: every byte of row_sym is 0)
+        encode_input<G>(board, current_player, hist3, n_hist, E.nn_in + row * (G::HW * G::C), coherent);
     }
 }
 
@@ -358,8 +424,9 @@ template <class G> GAZ_DEV int best_puct_slot(const NodeRef<G>& nd, int n_action
 // prior NaN — the rank sort below then gives every child rank 0 and the node keeps stale scratch — so such a node gets 1 / n_legal for
 // every legal action, before the Dirichlet mix.  The sum is team-uniform, and so is the branch.
 template <class G> GAZ_DEV void make_priors(const DevParams<G>& E, int g, const GameState<G>& gs, TreeState& ts, int tree,
-                                            Scratch<G>& S, const float* policy, int n_legal) {
-    for (int i = tlane<G>(); i < n_legal; i += G::TEAM) S.pri[i] = policy[S.legal[i]];
+                                            Scratch<G>& S, const float* policy, int n_legal, int sym = 0) {
+    // `policy` is in the network's frame: under symmetry `sym` the entry of action a sits at eval_sym_policy_index(sym, a)
+    for (int i = tlane<G>(); i < n_legal; i += G::TEAM) { const int a = S.legal[i]; S.pri[i] = policy[sym ? eval_sym_policy_index<G>(sym, a) : a]; }
     wave_sync();
     const float sum = det::np_pairwise_sum<float>(S.pri, n_legal);   // uniform: every lane computes the same value
     const bool flat = !(sum > 0.0f && sum <= 3.402823466e+38f);      // 0, negative, NaN, inf: the zero-mass rule
@@ -487,20 +554,20 @@ template <class G> GAZ_DEV bool root_pre(const DevParams<G>& E, int g, GameState
         wave_sync();
         return false;
     }
-    encode_input<G>(S.board, -gs.next_player, h3, gs.n_hist, E.nn_in + (size_t)row * (G::HW * G::C), E.done_flag != nullptr);
+    encode_request<G>(E, gs, S.board, -gs.next_player, h3, gs.n_hist, (size_t)row, E.done_flag != nullptr);
     wave_sync();
     return true;
 }
 
 // K12 second half: the evaluator's policy row -> root priors (the value is discarded, MCTS.py:346-365)
-// `policy`: row g of the evaluator output, or the policy block of an evaluation-cache entry
+// `policy`: row g of the evaluator output, or the policy block of an evaluation-cache entry; `row`: the batch row the request was encoded in
 template <class G> GAZ_DEV void root_post(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S,
-                                          const float* policy) {
+                                          const float* policy, int row) {
     NodeRef<G> nd = node_at(E, g, t, ts.root);
     copy_board<G>(S.board, nd.board());
     wave_sync();
     const int n_legal = build_legal<G>(S.board, S.legal);
-    make_priors<G>(E, g, gs, ts, t, S, policy, n_legal);
+    make_priors<G>(E, g, gs, ts, t, S, policy, n_legal, row_sym_of<G>(E, (size_t)row));
     write_children_from_scratch<G>(nd, S, n_legal);
     if (tlane<G>() == 0) { nd.hdr()->n_actions = (uint8_t)n_legal; nd.hdr()->n_children = 0; }
     wave_sync();
@@ -617,11 +684,6 @@ template <class G> struct CacheLayout {
     static constexpr int OFF_KEY = 8, OFF_POL = OFF_KEY + KEYB, OFF_VAL = OFF_POL + 4 * G::A, SIZE = (OFF_VAL + 4 + 63) / 64 * 64;
 };
 
-GAZ_DEV uint64_t mix64(uint64_t x) {
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-    return x;
-}
-
 // The row is handled in units of one board cell (C bytes: a dword for Connect4, 16 bits otherwise), one load per unit.
 template <int C> struct CellUnitC { typedef uint16_t type; };
 template <> struct CellUnitC<4> { typedef uint32_t type; };
@@ -719,7 +781,7 @@ template <class G> GAZ_DEV bool expand_pre(const DevParams<G>& E, int g, GameSta
     }
     copy_board<G>(nd.board(), S.board);
     uint8_t h3[3] = {(uint8_t)action, ph.hist3[0], ph.hist3[1]};
-    encode_input<G>(S.board, mover, h3, (int)ph.n_hist + 1, E.nn_in + (size_t)g * (G::HW * G::C), E.done_flag != nullptr);
+    encode_request<G>(E, gs, S.board, mover, h3, (int)ph.n_hist + 1, (size_t)g, E.done_flag != nullptr);
     // park the path for expand_post
     PathEnt* gp = E.paths + (size_t)g * PathCap<G>::V;
     for (int d = tlane<G>(); d <= depth; d += G::TEAM) gp[d] = S.path[d];
@@ -758,7 +820,7 @@ template <class G> GAZ_DEV void expand_post(const DevParams<G>& E, int g, GameSt
     }
     wave_sync();
     const int n_legal = build_legal<G>(S.board, S.legal);
-    make_priors<G>(E, g, gs, ts, t, S, S.aux, n_legal);                 // the policy row, staged in LDS
+    make_priors<G>(E, g, gs, ts, t, S, S.aux, n_legal, row_sym_of<G>(E, (size_t)g));   // the policy row, staged in LDS
     write_children_from_scratch<G>(nd, S, n_legal);
     NodeRef<G> pn = node_at(E, g, t, node);
     if (tlane<G>() == 0) {
@@ -776,7 +838,7 @@ template <class G> GAZ_DEV void expand_post(const DevParams<G>& E, int g, GameSt
 // created and backed up, as expand_pre does), 2 = deferred: the child would be a terminal parent while earlier children of the node are
 // still reserved — linking it now would break "children [0, n_children) are linked, the next n reserved" — so nothing is written and
 // the game yields; the same descent succeeds once those leaves have been applied.  -1 = error.
-template <class G> GAZ_DEV int lb_reserve(const DevParams<G>& E, const LeafBatch& B, int g, int j, TreeState& ts, int t, Scratch<G>& S,
+template <class G> GAZ_DEV int lb_reserve(const DevParams<G>& E, const LeafBatch& B, int g, int j, const GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S,
                                           int node, int depth, bool staged) {
     NodeRef<G> pn = node_at(E, g, t, node);
     const NodeRef<G> ps = staged ? NodeRef<G>{reinterpret_cast<uint8_t*>(S.node)} : pn;
@@ -817,7 +879,7 @@ template <class G> GAZ_DEV int lb_reserve(const DevParams<G>& E, const LeafBatch
     const size_t row = (size_t)g * B.K + j;
     copy_board<G>(nd.board(), S.board);
     uint8_t h3[3] = {(uint8_t)action, ph.hist3[0], ph.hist3[1]};
-    encode_input<G>(S.board, mover, h3, (int)ph.n_hist + 1, E.nn_in + row * (G::HW * G::C));
+    encode_request<G>(E, gs, S.board, mover, h3, (int)ph.n_hist + 1, row, false);
     PathEnt* gp = E.paths + row * PathCap<G>::V;
     for (int d = tlane<G>(); d <= depth; d += G::TEAM) gp[d] = S.path[d];
     if (tlane<G>() == 0) {
@@ -852,7 +914,7 @@ template <class G> GAZ_DEV void lb_apply(const DevParams<G>& E, const LeafBatch&
     copy_board<G>(S.board, nd.board());
     wave_sync();
     const int n_legal = build_legal<G>(S.board, S.legal);
-    make_priors<G>(E, g, gs, ts, t, S, S.aux, n_legal);
+    make_priors<G>(E, g, gs, ts, t, S, S.aux, n_legal, row_sym_of<G>(E, row));
     write_children_from_scratch<G>(nd, S, n_legal);
     NodeRef<G> pn = node_at(E, g, t, node);
     if (tlane<G>() == 0) {
@@ -1136,7 +1198,7 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
     if (E.prof && tlane<G>() == 0) E.prof[(size_t)g * 8 + 7] += 1;
     if (tuni<G>(gs.pend_kind) == PEND_ROOT) {
         const int t = tuni<G>(gs.pend_tree);
-        root_post<G>(E, g, gs, trees[t], t, S, E.nn_policy + (size_t)row0 * G::A);
+        root_post<G>(E, g, gs, trees[t], t, S, E.nn_policy + (size_t)row0 * G::A, row0);
         if (tlane<G>() == 0) { gs.pend_kind = PEND_NONE; gs.roots_todo &= ~(1 << t); gs.n_evals += 1; }
         wave_sync();
     } else if (LB && tuni<G>(gs.pend_kind) == PEND_EXPAND) {           // the leaves reserved by the previous launch, in reservation order
@@ -1174,7 +1236,7 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
             if (root_pre<G>(E, g, gs, trees[t], t, S, row0)) {
                 const uint8_t* hit = E.cache ? cache_probe<G>(E, g) : nullptr;
                 if (hit) {                                             // evaluation cache hit: the root is complete in this launch
-                    root_post<G>(E, g, gs, trees[t], t, S, reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_POL));
+                    root_post<G>(E, g, gs, trees[t], t, S, reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_POL), row0);
                     if (tlane<G>() == 0) { gs.roots_todo &= ~(1 << t); gs.n_evals += 1; gs.n_hits += 1; }
                     wave_sync();
                     return false;
@@ -1282,7 +1344,7 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
             if (LB && kind == 2) return true;                               // collision with a leaf in flight: collecting ends for this launch
             if (LB && kind == 0) {
                 const int fl = tuni<G>(gs.pend_depth);
-                const int r = lb_reserve<G>(E, B, g, fl, ts, t, S, node, depth, tuni<G>(gs.fully_visited) != 0);
+                const int r = lb_reserve<G>(E, B, g, fl, gs, ts, t, S, node, depth, tuni<G>(gs.fully_visited) != 0);
                 if (r < 0 || r == 2) return true;
                 if (tlane<G>() == 0) {
                     if (r == 1) { gs.sims_done += 1; gs.n_sims += 1; }

@@ -1295,8 +1295,10 @@ __device__ __forceinline__ void wave_trunk_body(const DevParams<GP>& E, int g0, 
     else trunk_tile<2, 2, 8, true, true, false, true, 4, false, SKIP ? 1 : 0>(a, (long)bid * a.tile_rows, a.tile_rows, SKIP ? a.perm : nullptr, a.boff);
 }
 
-template <bool MIX, bool SKIP> __global__ __launch_bounds__(TR_THREADS, 2) void k_wave_trunk(DevParams<GP4> E, int g0, int g1, int n_tree_blocks, TrunkArgs a) {
-    wave_trunk_body<MIX, SKIP, GP4, PuctLocal<GP4>, false>(E, g0, g1, n_tree_blocks, a);
+// SYM (here and below): the tree role with the code of the random evaluation symmetry (games.hpp WithSym), launched once an engine has switched it on
+template <bool MIX, bool SKIP, bool SYM = false> __global__ __launch_bounds__(TR_THREADS, 2) void k_wave_trunk(DevParams<typename SymSel<SYM, GP4>::type> E, int g0, int g1, int n_tree_blocks, TrunkArgs a) {
+    typedef typename SymSel<SYM, GP4>::type GP;
+    wave_trunk_body<MIX, SKIP, GP, PuctLocal<GP>, false>(E, g0, g1, n_tree_blocks, a);
 }
 
 // Gomoku (BASELINE configs[3]): one game per wavefront, eight per 512-thread tree block and round; the trunk role is the 8-wave launch with block 0
@@ -1306,11 +1308,12 @@ template <bool MIX, bool SKIP> __global__ __launch_bounds__(TR_THREADS, 2) void 
 // DevParams::handoff_release) and then writes its queue entry; the workgroup's polling lane acquires before the barrier, the planes are
 // read with plain loads behind it.  A tree step here is hundreds of microseconds, the two fences a few.
 typedef Game<GAME_GMK> GGMK;
-__global__ __launch_bounds__(512, 1) void k_wave_trunk_gmk(DevParams<GGMK> E, int g0, int g1, int n_tree_blocks, TrunkArgs a) {
+template <bool SYM> __global__ __launch_bounds__(512, 1) void k_wave_trunk_gmk(DevParams<typename SymSel<SYM, GGMK>::type> E, int g0, int g1, int n_tree_blocks, TrunkArgs a) {
+    typedef typename SymSel<SYM, GGMK>::type GP;
     if ((int)blockIdx.x < n_tree_blocks) {
         extern __shared__ uint4 lds[];
         if (a.stamps && (threadIdx.x & 63) == 0) a.stamps[(size_t)blockIdx.x * 128 + (threadIdx.x >> 6)] = wall_clock64();
-        tree_role<GGMK, PuctLocal<GGMK>, false, 512, trunk_lds_bytes_s0()>(E, g0, g1, lds);
+        tree_role<GP, PuctLocal<GP>, false, 512, trunk_lds_bytes_s0()>(E, g0, g1, lds);
         if (a.stamps && (threadIdx.x & 63) == 0) a.stamps[(size_t)blockIdx.x * 128 + 8 + (threadIdx.x >> 6)] = wall_clock64();
         return;
     }
@@ -1331,29 +1334,43 @@ template <class GP> static bool wave_trunk_launch(void (*kernel)(DevParams<GP>, 
 }
 
 bool launch_wave_trunk_gmk(hipStream_t s, const void* dev_params, int g0, int g1, const void* plan) {
+    const bool sym = dev_params && static_cast<const DevParams<GGMK>*>(dev_params)->eval_symmetry != 0;
     static bool attr = false;
-    if (!attr) { hipFuncSetAttribute((const void*)k_wave_trunk_gmk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes_s0()); attr = true; }
-    return wave_trunk_launch<GGMK>(k_wave_trunk_gmk, 512, 8, s, dev_params, g0, g1, plan);
+    if (!attr) {
+        hipFuncSetAttribute((const void*)k_wave_trunk_gmk<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes_s0());
+        hipFuncSetAttribute((const void*)k_wave_trunk_gmk<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes_s0());
+        attr = true;
+    }
+    if (sym) return wave_trunk_launch<WithSym<GGMK>>(k_wave_trunk_gmk<true>, 512, 8, s, dev_params, g0, g1, plan);
+    return wave_trunk_launch<GGMK>(k_wave_trunk_gmk<false>, 512, 8, s, dev_params, g0, g1, plan);
 }
 
 // The Gumbel search (MCTS_Gumbel.py:562-679) in the same launch shape.  TEAMS: four games per wavefront (16 games per tree block, as the PUCT
 // launch) or one game per wavefront (4 per tree block: less lock-step, but four times the tree blocks ahead of the trunk workgroups).
-template <bool MIX, bool SKIP, bool TEAMS> __global__ __launch_bounds__(TR_THREADS, 2) void k_wave_trunk_gumbel(DevParams<Game<GAME_C4>> E, int g0, int g1, int n_tree_blocks, TrunkArgs a) {
-    if constexpr (TEAMS) wave_trunk_body<MIX, SKIP, GP4, GumbelLocal<GP4>, true>(*reinterpret_cast<const DevParams<GP4>*>(&E), g0, g1, n_tree_blocks, a);
-    else wave_trunk_body<MIX, SKIP, Game<GAME_C4>, GumbelLocal<Game<GAME_C4>>, true>(E, g0, g1, n_tree_blocks, a);
+template <bool MIX, bool SKIP, bool TEAMS, bool SYM = false> __global__ __launch_bounds__(TR_THREADS, 2) void k_wave_trunk_gumbel(DevParams<typename SymSel<SYM, Game<GAME_C4>>::type> E, int g0, int g1, int n_tree_blocks, TrunkArgs a) {
+    typedef typename SymSel<SYM, GP4>::type GT;
+    typedef typename SymSel<SYM, Game<GAME_C4>>::type GW;
+    if constexpr (TEAMS) wave_trunk_body<MIX, SKIP, GT, GumbelLocal<GT>, true>(*reinterpret_cast<const DevParams<GT>*>(&E), g0, g1, n_tree_blocks, a);
+    else wave_trunk_body<MIX, SKIP, GW, GumbelLocal<GW>, true>(E, g0, g1, n_tree_blocks, a);
 }
 
 bool launch_wave_trunk_c4_gumbel(hipStream_t s, const void* dev_params, int g0, int g1, const void* plan) {
+    const bool sym = dev_params && static_cast<const DevParams<GP4>*>(dev_params)->eval_symmetry != 0;
     static const bool teams = env_on("GAZ_FUSE_GUMBEL_TEAMS", true);
     const TrunkLaunchPlan* P = static_cast<const TrunkLaunchPlan*>(plan);
     if (!P || !P->mix || !(P->args.perm && P->args.perm_small)) return false;      // only the headline trunk variant is built for this launch
+    if (sym) return wave_trunk_launch<WithSym<Game<GAME_C4>>>(teams ? k_wave_trunk_gumbel<true, true, true, true> : k_wave_trunk_gumbel<true, true, false, true>, TR_THREADS,
+                                                              (TR_THREADS / WAVE) * (teams ? WAVE / GP4::TEAM : 1), s, dev_params, g0, g1, plan);
     return wave_trunk_launch<Game<GAME_C4>>(teams ? k_wave_trunk_gumbel<true, true, true> : k_wave_trunk_gumbel<true, true, false>, TR_THREADS,
                                             (TR_THREADS / WAVE) * (teams ? WAVE / GP4::TEAM : 1), s, dev_params, g0, g1, plan);
 }
 
 bool launch_wave_trunk_c4(hipStream_t s, const void* dev_params, int g0, int g1, const void* plan) {
+    const bool sym = dev_params && static_cast<const DevParams<GP4>*>(dev_params)->eval_symmetry != 0;
     const TrunkLaunchPlan* P = static_cast<const TrunkLaunchPlan*>(plan);
     const bool mix = P && P->mix, skip = P && P->args.perm && P->args.perm_small;      // skip: both tile shapes carry an edge-tile permutation (checked by the evaluator)
+    if (sym) return wave_trunk_launch<WithSym<GP4>>(mix && skip ? k_wave_trunk<true, true, true> : mix ? k_wave_trunk<true, false, true> : k_wave_trunk<false, false, true>, TR_THREADS,
+                                                    (TR_THREADS / WAVE) * (WAVE / GP4::TEAM), s, dev_params, g0, g1, plan);
     return wave_trunk_launch<GP4>(mix && skip ? k_wave_trunk<true, true> : mix ? k_wave_trunk<true, false> : k_wave_trunk<false, false>, TR_THREADS,
                                   (TR_THREADS / WAVE) * (WAVE / GP4::TEAM), s, dev_params, g0, g1, plan);
 }

@@ -36,23 +36,11 @@ template <> struct SampleAug<Game<GAME_C4>> { static constexpr int N = 2; };  //
 template <class G> GAZ_HD int sample_plies(int T) { return T < 0 ? 0 : (T > G::MAXT ? G::MAXT : T); }
 
 // output cell (y, x) of augmentation k -> the cell of the un-augmented board it shows.
-// games._GridGame.augment_sample: id, flipud, fliplr, rot90, flipud(rot90), fliplr(rot90), rot180, rot270 (np.rot90: counter-clockwise,
-// rot90(m)[y][x] = m[x][n-1-y]).  games.Connect4.augment_sample: np.fliplr of the [T,6,7,4] states reverses axis 1 = the board ROWS.
+// Square boards: games.hpp square_src_cell (the order of games._GridGame.augment_sample).  games.Connect4.augment_sample: np.fliplr of the
+// [T,6,7,4] states reverses axis 1 = the board ROWS.
 template <class G> GAZ_DEV int board_src_cell(int k, int y, int x) {
     if (G::ID == GAME_C4) return (k ? G::H - 1 - y : y) * G::W + x;
-    const int n = G::W - 1;
-    int sy = y, sx = x;
-    switch (k) {
-        case 1: sy = n - y; break;
-        case 2: sx = n - x; break;
-        case 3: sy = x; sx = n - y; break;
-        case 4: sy = x; sx = y; break;
-        case 5: sy = n - x; sx = n - y; break;
-        case 6: sy = n - y; sx = n - x; break;
-        case 7: sy = n - x; sx = y; break;
-        default: break;
-    }
-    return sy * G::W + sx;
+    return square_src_cell(k, y, x, G::W);
 }
 // the same for a policy index; Connect4's [T,7] policy is mirrored along the COLUMNS (Connect4.py:442-443: kept as the reference has it)
 template <class G> GAZ_DEV int policy_src_index(int k, int a) {

@@ -119,6 +119,9 @@ def load_library(lib_path=None):
     L.gaz_engine_set_hyperparams.argtypes = [H, C.POINTER(SearchHyperparams)]
     L.gaz_engine_set_resignation.argtypes = [H, C.POINTER(ResignParams)]
     L.gaz_engine_get_resign_stats.argtypes = [H, C.POINTER(C.c_uint64)]
+    L.gaz_engine_set_eval_symmetry.argtypes = [H, C.c_int32]
+    L.gaz_engine_get_eval_symmetry.argtypes = [H, C.POINTER(C.c_int32)]
+    L.gaz_engine_read_batch_symmetry.argtypes = [H, C.c_void_p]
     L.gaz_engine_probe_rules.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7
     L.gaz_engine_set_fused_wave.argtypes = [H, C.c_int32]
     L.gaz_engine_debug_fused_fault.argtypes = [H, C.c_int32]
@@ -133,7 +136,7 @@ def load_library(lib_path=None):
     for f in ("create", "load_weights", "reset_games", "run_move", "get_root_stats", "apply_moves", "run_waves", "wave_begin",
               "wave_end", "batch_ptrs", "read_batch", "write_outputs", "batch_rows", "evaluate", "record_layout", "drain_finished", "sample_layout", "drain_samples", "get_stats",
               "synchronize", "timing_reset", "timing_get", "dominant_kernel", "set_position", "set_search_params", "start_search", "stop_search",
-              "set_hyperparams", "set_resignation", "get_resign_stats", "probe_rules", "read_head_features", "set_fused_wave", "debug_fused_fault", "read_positions", "repack", "read_trees", "read_pv"):
+              "set_hyperparams", "set_resignation", "get_resign_stats", "set_eval_symmetry", "get_eval_symmetry", "read_batch_symmetry", "probe_rules", "read_head_features", "set_fused_wave", "debug_fused_fault", "read_positions", "repack", "read_trees", "read_pv"):
         getattr(L, "gaz_engine_" + f).restype = C.c_int
     _LIBS[path] = L
     return L
@@ -223,7 +226,7 @@ class SelfPlayEngine:
                  compact_trees=0, single_tree=False, opening_actions=None, eval_cache_log2=0, gumbel_stablemax=False, fast_find_win=False,
                  use_gumbel_noise=True, first_game_seq=0, games_budget=0, tau=-1.0, move_time_limit=0.0, game_groups=0, leaf_batch=1, gumbel_batch=1,
                  fast_iterations=0, full_search_prob=0.0, forced_playouts_k=0.0,
-                 resign_threshold=0.0, resign_consecutive=1, resign_min_ply=0, no_resign_prob=0.0, lib_path=None):
+                 resign_threshold=0.0, resign_consecutive=1, resign_min_ply=0, no_resign_prob=0.0, eval_symmetry=False, lib_path=None):
         self.L = load_library(lib_path)
         self.game_id = GAME_IDS[game] if isinstance(game, str) else int(game)
         self.H, self.W, self.Cc, self.A = GAME_DIMS[self.game_id]
@@ -267,6 +270,8 @@ class SelfPlayEngine:
             except EngineError:
                 self.close()
                 raise
+        if eval_symmetry:                            # (off = the state of a new engine)
+            self.set_eval_symmetry(True)
 
     def _ck(self, rc):
         if rc:
@@ -444,6 +449,26 @@ class SelfPlayEngine:
         p = np.ascontiguousarray(policy, np.float32); v = np.ascontiguousarray(value, np.float32)
         assert p.shape == (self.batch_rows, self.A) and v.size == self.batch_rows
         self._ck(self.L.gaz_engine_write_outputs(self.h, p.ctypes.data, v.ctypes.data))
+
+    def set_eval_symmetry(self, on=True):
+        """Evaluate every search position under a random board symmetry (gaz_engine_set_eval_symmetry), for the rows encoded from the next
+        launch on: the network sees T_k(state) — the 8 transforms of a square board in the order of games.augment_sample, Connect4's column
+        mirror — with k drawn per (seed, slot, game_seq, position), and the search uses the policy mapped back.  Records, samples, root
+        statistics and trees stay in the board's own frame; an external evaluator sees the permuted rows and answers in their frame."""
+        self._ck(self.L.gaz_engine_set_eval_symmetry(self.h, int(on)))
+
+    @property
+    def eval_symmetry(self):
+        m = C.c_int32()
+        self._ck(self.L.gaz_engine_get_eval_symmetry(self.h, C.byref(m)))
+        return bool(m.value)
+
+    def read_batch_symmetry(self):
+        """uint8 [batch_rows]: the symmetry k every row of the evaluator batch was encoded under (meaningful where read_batch's
+        pending is set; 0 while eval_symmetry is off)"""
+        k = np.zeros(self.batch_rows, np.uint8)
+        self._ck(self.L.gaz_engine_read_batch_symmetry(self.h, k.ctypes.data))
+        return k
 
     def batch_ptrs(self):
         a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()

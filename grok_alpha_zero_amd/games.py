@@ -90,6 +90,29 @@ class _GridGame:
             return [a, a[:, ::-1], a[:, :, ::-1], r1, r1[:, ::-1], r1[:, :, ::-1], np.rot90(a, 2, axes=(1, 2)), np.rot90(a, 3, axes=(1, 2))]
         return (np.stack(sym(st)).astype(self.board.dtype), np.stack(sym(pol)).reshape(8, T, -1).astype(np.float32))
 
+    # ---- the search's random evaluation symmetry (SelfPlayEngine.set_eval_symmetry), for callers that serve session.run themselves
+    N_SYMMETRIES = 8
+    _SYM_INVERSE = (0, 1, 2, 7, 4, 5, 6, 3)          # the two quarter turns undo each other, every other transform undoes itself
+
+    @staticmethod
+    def _sym(a, k):
+        """transform k of augment_sample's list on axes (0, 1) of `a`"""
+        if not 0 <= k < 8:
+            raise ValueError(f"symmetry {k} is not in [0, 8)")
+        r1 = np.rot90(a, 1, axes=(0, 1))
+        return (a, a[::-1], a[:, ::-1], r1, r1[::-1], r1[:, ::-1], np.rot90(a, 2, axes=(0, 1)), np.rot90(a, 3, axes=(0, 1)))[k]
+
+    @classmethod
+    def symmetry_transform(cls, state, k):
+        """T_k of an [H, W, C] input state: what the engine writes into the evaluator batch for a request under symmetry k"""
+        return np.ascontiguousarray(cls._sym(np.asarray(state), int(k)))
+
+    @classmethod
+    def symmetry_untransform_policy(cls, policy, k):
+        """T_k^-1 of a policy the network gave for symmetry_transform(state, k): the policy by the state's own actions"""
+        p = np.asarray(policy).reshape(cls.H, cls.W)
+        return np.ascontiguousarray(cls._sym(p, cls._SYM_INVERSE[int(k)])).reshape(-1)
+
 
 class TicTacToe(_GridGame):
     H = W = 3
@@ -234,6 +257,24 @@ class Connect4(_GridGame):
         """[identity, np.fliplr] on BOTH arrays, as the reference does: on the [T,6,7,4] states np.fliplr reverses
         axis 1 = board ROWS, while the [T,7] policy is mirrored along columns (Connect4.py:442-443) — kept as is."""
         return np.stack((board, np.fliplr(board))), np.stack((policy, np.fliplr(policy)))
+
+    # the search's evaluation symmetry is the COLUMN mirror of the board, on all four planes — not the row reversal augment_sample above
+    # applies to the states of the samples (that quirk of the reference stays where it is)
+    N_SYMMETRIES = 2
+
+    @classmethod
+    def symmetry_transform(cls, state, k):
+        if k not in (0, 1):
+            raise ValueError(f"symmetry {k} is not in [0, 2)")
+        s = np.asarray(state)
+        return np.ascontiguousarray(s[:, ::-1] if k else s)
+
+    @classmethod
+    def symmetry_untransform_policy(cls, policy, k):
+        if k not in (0, 1):
+            raise ValueError(f"symmetry {k} is not in [0, 2)")
+        p = np.asarray(policy).reshape(-1)
+        return np.ascontiguousarray(p[::-1] if k else p)
 
 
 GAMES = {"TicTacToe": TicTacToe, "Connect4": Connect4, "Gomoku": Gomoku}

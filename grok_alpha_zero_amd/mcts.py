@@ -198,14 +198,16 @@ class MCTS(_EngineSearch):
 
     def __init__(self, game, session=None, use_njit=None, c_puct_init=2.5, c_puct_base=19_652, use_dirichlet=True,
                  dirichlet_alpha=1.11, dirichlet_epsilon=0.25, tau=1.0, fast_find_win=False, *, seed=None, hash_salt=0,
-                 max_actions=None, leaf_batch=1, lib_path=None):
+                 max_actions=None, leaf_batch=1, eval_symmetry=False, lib_path=None):
+        # eval_symmetry: SelfPlayEngine.set_eval_symmetry — the session is shown every position under a random board symmetry and answers
+        # in that frame; the engine maps the policy back, so run()'s rows, root and pv() stay in the board's own frame
         self.c_puct_init, self.c_puct_base = c_puct_init, c_puct_base
         self.use_dirichlet, self.dirichlet_alpha, self.dirichlet_epsilon = use_dirichlet, dirichlet_alpha, dirichlet_epsilon
         self.tau = 0.0 if (tau != 0.0 and tau < 5e-3) else tau                          # MCTS.py:116-120
         self._attach(game, session, seed, lib_path, max_actions=max_actions or int(np.prod(game.board.shape)),
                      c_puct_init=c_puct_init, c_puct_base=c_puct_base, dirichlet_alpha=dirichlet_alpha,
                      dirichlet_epsilon=dirichlet_epsilon, use_dirichlet=use_dirichlet, hash_salt=hash_salt, search=SEARCH_PUCT,
-                     fast_find_win=bool(fast_find_win), leaf_batch=int(leaf_batch))
+                     fast_find_win=bool(fast_find_win), leaf_batch=int(leaf_batch), eval_symmetry=bool(eval_symmetry))
 
     def update_hyperparams(self, **kwargs):
         """MCTS.py:134-168: invalid values are ignored with a warning, valid ones take effect at the next simulation."""
@@ -265,13 +267,14 @@ class MCTS(_EngineSearch):
 class MCTS_Gumbel(_EngineSearch):
     def __init__(self, game, session, use_gumbel_noise=False, use_njit=None, m=16, c_visit=50.0, c_scale=0.1,
                  activation_fn="softmax", fast_find_win=False, *, seed=None, hash_salt=0, max_actions=None, gumbel_batch=1,
-                 lib_path=None):
+                 eval_symmetry=False, lib_path=None):
         if activation_fn not in ("softmax", "stablemax"):
             raise ValueError("activation_fn must be 'softmax' or 'stablemax'")
         self.m, self.c_visit, self.c_scale, self.use_gumbel_noise = m, c_visit, c_scale, use_gumbel_noise
         self._attach(game, session, seed, lib_path, max_actions=max_actions or int(np.prod(game.board.shape)), hash_salt=hash_salt,
                      search=SEARCH_GUMBEL, gumbel_m=m, c_visit=c_visit, c_scale=c_scale, gumbel_stablemax=activation_fn == "stablemax",
-                     fast_find_win=bool(fast_find_win), use_gumbel_noise=bool(use_gumbel_noise), gumbel_batch=int(gumbel_batch))
+                     fast_find_win=bool(fast_find_win), use_gumbel_noise=bool(use_gumbel_noise), gumbel_batch=int(gumbel_batch),
+                     eval_symmetry=bool(eval_symmetry))
 
     def update_hyperparams(self, *args, **kwargs):                                       # MCTS_Gumbel.py:186-210
         upd = {k: kwargs[k] for k in ("m", "c_visit", "c_scale") if kwargs.get(k) is not None}

@@ -459,6 +459,9 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
     is the player who did not resign, and game_stats count it like any other game.  `engine_stats["resign"]` receives
     SelfPlayEngine.resign_stats() (the false positives among the games played out); resign_curve() picks a threshold from the records
     of a generation played with no_resign_prob = 1.
+    Random evaluation symmetry: train_config["eval_symmetry"] (absent or False = off, and then no call is made) —
+    SelfPlayEngine.set_eval_symmetry: the network sees every search position under a board symmetry drawn per game and position, and the
+    search uses the policy mapped back.  Records and samples stay in the board's own frame; the file format does not change.
     `configs` = (build_config, train_config[, optimizer_config]).  `weights` = dict from net.export_engine_weights()
     (generation > 0); generation 0 (folder name "0") plays with the synthetic evaluator like the reference's
     session=None dummy (Self_Play.py:40, MCTS.py:237-241).
@@ -534,6 +537,8 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
                                                   generation, games_left, G, "ResNet (HIP)" if use_net else "synthetic hash evaluator", first_game_seq)
     if use_net:
         eng.load_weights(weights)
+    if train_config.get("eval_symmetry"):
+        eng.set_eval_symmetry(True)
     written = 0
     launch = G                                          # slots the launches cover (shrinks in the generation's tail, see repack)
     clock = time.perf_counter

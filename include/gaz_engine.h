@@ -43,6 +43,9 @@
  *   gaz_engine_set_resignation / gaz_engine_get_resign_stats  (no reference counterpart: Self_Play.play() plays every game to its end;
  *                              resignation with a share of games played out to measure its false positives is AlphaGo Zero's, Silver 2017)
  *   the 0x10 / 0x20 bits of a record's move_kind  (no reference counterpart: the marks that rule leaves in the record)
+ *   gaz_engine_set_eval_symmetry / gaz_engine_get_eval_symmetry / gaz_engine_read_batch_symmetry  (no reference counterpart: the reference
+ *                              augments its training samples with the board symmetries, Guide.py:255-283, but always shows the search's
+ *                              network one orientation; a random symmetry per evaluation is AlphaGo Zero's and KataGo's)
  */
 #ifndef GAZ_ENGINE_H
 #define GAZ_ENGINE_H
@@ -233,6 +236,29 @@ int gaz_engine_write_outputs(gaz_engine* h, const float* policy, const float* va
  * gaz_engine_evaluate takes up to that many rows.  Rows nobody requested are evaluated and ignored.  The same with gumbel_batch = K > 1:
  * n_games * K rows, and pending[] is per row — the rows of a game that carry a request need not be its first ones. */
 int gaz_engine_batch_rows(gaz_engine* h, int32_t* rows);
+
+/* Random board symmetry per evaluator request.  mode 0 = off (the state of a new engine), 1 = on; any other value is refused.  Legal on any
+ * engine at any time; it takes effect for the rows encoded from the next launch on, and a request already in flight is answered under the
+ * symmetry it was encoded with.  No struct changes and GAZ_ENGINE_ABI_VERSION stays 10: the feature is detected by its symbols.
+ * With the mode on, every request the searches encode (root creations and leaf expansions; PUCT, leaf_batch, Gumbel, gumbel_batch) shows the
+ * network T_k(state), and the search uses T_k^-1 of the policy row it gets back; the value is used as it is.  k is drawn per POSITION of a game:
+ *   h = sum over the cells c = y * W + x of mix64(((uint64)(c + 1) << 32) | (uint8)board[c])  (mod 2^64; board = the int8 board, -1 -> 0xff),
+ *   mix64(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31,
+ *   u = the uniform variate of (seed, slot, game_seq, tree 2, event = (uint32)(mix64(h) >> 32), purpose 7),  k = min(NSYM - 1, (int)(u * NSYM)).
+ * No tree's event counter moves and no other variate changes; both trees of a game, every launch shape and the evaluation cache see the same k
+ * for the same position of the same game.  Square boards (NSYM = 8): the transforms of the training samples in their order — identity, flipud,
+ * fliplr, rot90, flipud(rot90), fliplr(rot90), rot180, rot270 (counter-clockwise) — applied to the [H][W][C] state over its first two axes; the
+ * inverses are k' = [0, 1, 2, 7, 4, 5, 6, 3].  Connect4 (NSYM = 2): k = 1 mirrors the COLUMNS (x -> 6 - x) of all four planes, and the policy
+ * likewise (this is not the row reversal its sample augmentation applies to states).
+ * Everything else stays in the board's own frame: records, gaz_engine_drain_samples, gaz_engine_get_root_stats, gaz_engine_read_trees / read_pv,
+ * gaz_engine_probe_rules, gaz_engine_evaluate.  A GAZ_EVAL_EXTERNAL caller sees the PERMUTED rows in gaz_engine_read_batch / batch_ptrs and
+ * answers in that frame — a network needs nothing else; gaz_engine_read_batch_symmetry tells which k a row was written under. */
+int gaz_engine_set_eval_symmetry(gaz_engine* h, int32_t mode);
+int gaz_engine_get_eval_symmetry(gaz_engine* h, int32_t* mode);
+/* sym[rows] (gaz_engine_batch_rows): the k of every row of the evaluator batch — meaningful where gaz_engine_read_batch's pending is set; a row
+ * without a request keeps the k of the last request written there (0 if none, and 0 everywhere while the mode has never been on).  Available and
+ * refused where gaz_engine_read_batch is (game groups: refused). */
+int gaz_engine_read_batch_symmetry(gaz_engine* h, uint8_t* sym);
 
 /* place one slot at the position reached by `n` actions from the empty board (new roots are built there).  The game keeps its
  * game_seq, the next player follows from the parity of n, both trees start fresh (event counter 0), and the tau schedule, the
