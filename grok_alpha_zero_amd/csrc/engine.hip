@@ -288,6 +288,34 @@ template <class G> GAZ_KERNEL k_release(DevParams<G> E, const int32_t* moves) {
     if (gs.phase == PH_WAIT_HOST || (gs.phase == PH_IDLE && moves && moves[g] >= 0)) { gs.host_move = moves ? moves[g] : -1; gs.phase = PH_APPLY; }
 }
 
+// gaz_engine_set_solver(1): tag the edges into the terminal parents that were made while the solver was off (their status is derived from their
+// record, puct_core.hpp rule 1), in every record the trees have allocated.  One wavefront per game, a lane per node record; the stream is idle.
+template <class G> GAZ_KERNEL k_solver_retag(DevParams<G> E) {
+    const int g = block_id();
+    if (g >= E.n_games) return;
+    for (int t = 0; t < 2; ++t) {
+        const TreeState& ts = E.trees[(size_t)g * 2 + t];
+        if (ts.root < 0) continue;
+        const int n = (int)(ts.n_nodes < (uint32_t)E.nodes_per_tree ? ts.n_nodes : (uint32_t)E.nodes_per_tree);
+        for (int i = lane_id(); i < n; i += WAVE) {
+            const NodeRef<G> nd = node_at(E, g, t, i);
+            if (nd.hdr()->flags & NF_TERMINAL_PARENT) continue;
+            int nc = nd.hdr()->n_children;
+            if (nc > G::A) nc = G::A;
+            for (int s = 0; s < nc; ++s) {
+                const int32_t w = nd.child()[s];
+                if (w < 0 || child_tag(w) != ST_UNKNOWN || w >= E.nodes_per_tree) continue;
+                const NodeRef<G> x = node_at(E, g, t, w);
+                if (!(x.hdr()->flags & NF_TERMINAL_PARENT)) continue;
+                int xn = x.hdr()->n_children, st = ST_DRAW;
+                if (xn > G::A) xn = G::A;
+                for (int k = 0; k < xn; ++k) if (x.child()[k] == CHILD_LEAF_WIN) st = ST_WIN;
+                nd.child()[s] = w | (st << CHILD_TAG_SHIFT);
+            }
+        }
+    }
+}
+
 // dense copies of the last MCTS.run result of every game (engine_get_root_stats)
 template <class G> GAZ_KERNEL k_gather_root(DevParams<G> E, uint32_t* oN, float* oW, float* oP, float* oPol, uint32_t* oRV,
                                              float* oQ, int32_t* oChosen, int32_t* oPhase, int32_t* oPending) {
@@ -366,6 +394,9 @@ struct gaz_engine {
     virtual int set_eval_symmetry(int32_t mode) = 0;
     virtual int get_eval_symmetry(int32_t* mode) = 0;
     virtual int read_batch_symmetry(uint8_t* sym) = 0;
+    virtual int set_solver(int32_t mode) = 0;
+    virtual int get_solver(int32_t* mode) = 0;
+    virtual int get_solver_stats(uint64_t out[8]) = 0;
     virtual int read_head_features(int, float*, float*, int32_t*, int32_t*) = 0;
     virtual int set_fused_wave(int) = 0;
     virtual int debug_fused_fault(int) = 0;
@@ -601,12 +632,17 @@ template <class G> struct EngineT : gaz_engine {
     bool prev_marked = false;                        // the wave before this one wrote eval_done
     DevParams<G> wave_params() { DevParams<G> P = E; P.wave_epoch = ++fuse_epoch; P.eval_done = prev_marked ? d_evaldone : nullptr; return P; }
     void launch_wave(hipStream_t st, int g0, int g1) { const DevParams<G> P = wave_params(); prev_marked = false; launch_wave(st, g0, g1, P); }   // (callers follow with a full evaluator pass)
-    void launch_wave(hipStream_t st, int g0, int g1, const DevParams<G>& E) { if (E.eval_symmetry) launch_wave_v<true>(st, g0, g1, E); else launch_wave_v<false>(st, g0, g1, E); }
+    void launch_wave(hipStream_t st, int g0, int g1, const DevParams<G>& E) {
+        if (E.solver) { if (E.eval_symmetry) launch_wave_v<true, true>(st, g0, g1, E); else launch_wave_v<false, true>(st, g0, g1, E); return; }
+        if (E.eval_symmetry) launch_wave_v<true>(st, g0, g1, E); else launch_wave_v<false>(st, g0, g1, E);
+    }
     // SYM: the instantiations with the code of the random evaluation symmetry (games.hpp WithSym; same layouts, so the parameters are reinterpreted)
-    template <bool SYM> void launch_wave_v(hipStream_t st, int g0, int g1, const DevParams<G>& E) {
+    // SOLVE: those with the solver's code (games.hpp WithSolve) — the plain PUCT step only: set_solver refuses every other search
+    template <bool SYM, bool SOLVE = false> void launch_wave_v(hipStream_t st, int g0, int g1, const DevParams<G>& E) {
         // the small boards run four games per wavefront (PuctVariant: same records, 16-lane teams); GAZ_TREE_TEAMS=0 -> one per wave
-        typedef typename SymSel<SYM, typename PuctVariant<G>::type>::type GP;
-        typedef typename SymSel<SYM, G>::type GS;
+        typedef typename SolveSel<SOLVE, typename SymSel<SYM, typename PuctVariant<G>::type>::type>::type GP;
+        typedef typename SolveSel<SOLVE, typename SymSel<SYM, G>::type>::type GS;
+        if constexpr (!SOLVE) {
         if (gbk > 1) {                                // (Gumbel only, no evaluation cache: gaz_engine_create refuses the rest; the register budget of k_wave_lb)
             constexpr int PER = WAVE / GP::TEAM;
             GAZ_LAUNCH(k_wave_gb<GP>, (g1 - g0 + PER - 1) / PER, WAVE, st, *reinterpret_cast<const DevParams<GP>*>(&E), GB, g0, g1);
@@ -627,6 +663,7 @@ template <class G> struct EngineT : gaz_engine {
             if (GPER > 1 && gteams_env == 1) GAZ_LAUNCH(k_wave_gumbel_teams<GP>, (g1 - g0 + GPER - 1) / GPER, WAVE, st, *reinterpret_cast<const DevParams<GP>*>(&E), g0, g1);
             else GAZ_LAUNCH(k_wave_gumbel<GS>, g1 - g0, WAVE, st, *reinterpret_cast<const DevParams<GS>*>(&E), g0, g1);
             return;
+        }
         }
         // measured (4096 Connect4 games): 66 vs 71 us per launch; with the evaluation cache (up to 8 evaluation-free simulations per
         // game and launch, and a wave is as slow as its slowest team) one game per wave stays faster: 60.1 k vs 56.2 k positions/s
@@ -1371,6 +1408,42 @@ template <class G> struct EngineT : gaz_engine {
     // (DevParams::eval_symmetry: bit 0 = the mode, bit 1 = those kernels are in use)
     int set_eval_symmetry(int32_t mode) override { E.eval_symmetry = (mode ? 1 : 0) | ((mode || E.eval_symmetry) ? 2 : 0); return 0; }
     int get_eval_symmetry(int32_t* mode) override { *mode = E.eval_symmetry & 1; return 0; }
+    // solver (puct_core.hpp "MCTS-Solver"): like the symmetry, the kernels with its code (games.hpp WithSolve) are launched from the first time the
+    // mode is 1 and from then on for good — the tag bits they wrote into child words stay in the trees, and only those kernels take an index through
+    // child_index().  (DevParams::solver: bit 0 = the mode, bit 1 = those kernels are in use.)  Switching on tags the edges into the terminal parents
+    // made while it was off (k_solver_retag): a terminal parent's status is derived from its record, whenever it was made.
+    unsigned long long* d_solver_ctr = nullptr;
+    int set_solver(int32_t mode) override {
+        if (cfg.search == GAZ_SEARCH_GUMBEL && gbk > 1) return fail("set_solver: not with gumbel_batch > 1 (the solver proves in the PUCT tree; the Gumbel search is the follow-up)");
+        if (cfg.search == GAZ_SEARCH_GUMBEL) return fail("set_solver: not with the Gumbel search (the solver proves in the PUCT tree)");
+        if (lbk > 1) return fail("set_solver: not with leaf_batch > 1 (a proof may not stand on leaves in flight)");
+        if (E.nodes_per_tree > CHILD_INDEX_MASK) return fail("set_solver: nodes_per_tree must be below 2^29 (two bits of a child word carry the proof)");
+        if (mode && !(E.solver & 1)) {
+            HIP_OK(hipStreamSynchronize(stream));
+            if (pipeline_ready) { HIP_OK(hipStreamSynchronize(tstream)); HIP_OK(hipStreamSynchronize(hstream)); }
+            if (!d_solver_ctr) {
+                if (dalloc(&d_solver_ctr, 8)) return 1;
+                E.solver_ctr_lo = (uint32_t)(uintptr_t)d_solver_ctr; E.solver_ctr_hi = (uint32_t)((uint64_t)(uintptr_t)d_solver_ctr >> 32);
+            }
+            GAZ_LAUNCH(k_solver_retag<G>, E.n_games, WAVE, stream, E);
+            HIP_OK(hipGetLastError());
+            HIP_OK(hipStreamSynchronize(stream));
+        }
+        E.solver = (mode ? 1 : 0) | ((mode || E.solver) ? 2 : 0);
+        return 0;
+    }
+    int get_solver(int32_t* mode) override { *mode = E.solver & 1; return 0; }
+    int get_solver_stats(uint64_t out[8]) override {
+        for (int i = 0; i < 8; ++i) out[i] = 0;
+        HIP_OK(hipStreamSynchronize(stream));
+        if (pipeline_ready) { HIP_OK(hipStreamSynchronize(tstream)); HIP_OK(hipStreamSynchronize(hstream)); }
+        if (d_solver_ctr) {
+            unsigned long long s[8];
+            HIP_OK(hipMemcpy(s, d_solver_ctr, sizeof(s), hipMemcpyDeviceToHost));
+            for (int i = 0; i < 8; ++i) out[i] = s[i];
+        }
+        return check_device_error();
+    }
     int8_t* pr_board = nullptr; uint8_t* pr_legal = nullptr; int32_t* pr_winner = nullptr; int8_t* pr_input = nullptr; int32_t* pr_term = nullptr;
     int32_t* pr_actions = nullptr; int32_t* pr_n = nullptr; float* pr_pin = nullptr; float* pr_pout = nullptr; int pr_cap = 0, pr_stride = 0;
     int probe_rules(const int32_t* actions, const int32_t* n_actions, int n_pos, int stride, int8_t* o_board, uint8_t* o_legal,
@@ -1611,6 +1684,12 @@ struct GroupEngine : gaz_engine {
     int set_resignation(const gaz_resign_params* p) override { return each([&](gaz_engine* k, int) { return k->set_resignation(p); }); }
     int set_eval_symmetry(int32_t mode) override { return each([&](gaz_engine* k, int) { return k->set_eval_symmetry(mode); }); }
     int get_eval_symmetry(int32_t* mode) override { return up(kid[0], kid[0]->get_eval_symmetry(mode)); }
+    int set_solver(int32_t mode) override { return each([&](gaz_engine* k, int) { return k->set_solver(mode); }); }
+    int get_solver(int32_t* mode) override { return up(kid[0], kid[0]->get_solver(mode)); }
+    int get_solver_stats(uint64_t out[8]) override {
+        for (int i = 0; i < 8; ++i) out[i] = 0;
+        return each([&](gaz_engine* k, int) { uint64_t s[8]; if (k->get_solver_stats(s)) return 1; for (int i = 0; i < 8; ++i) out[i] += s[i]; return 0; });
+    }
     int get_resign_stats(uint64_t out[8]) override {
         for (int i = 0; i < 8; ++i) out[i] = 0;
         return each([&](gaz_engine* k, int) { uint64_t s[8]; if (k->get_resign_stats(s)) return 1; for (int i = 0; i < 8; ++i) out[i] += s[i]; return 0; });
@@ -1817,6 +1896,12 @@ int gaz_engine_set_eval_symmetry(gaz_engine* h, int32_t mode) {
     if (mode != 0 && mode != 1) return h->fail("set_eval_symmetry: mode must be 0 (off) or 1 (a random board symmetry per evaluator request), not " + std::to_string(mode));
     return h->set_eval_symmetry(mode);
 }
+int gaz_engine_set_solver(gaz_engine* h, int32_t mode) {
+    if (mode != 0 && mode != 1) return h->fail("set_solver: mode must be 0 (off) or 1 (prove wins, draws and losses in the PUCT tree), not " + std::to_string(mode));
+    return h->set_solver(mode);
+}
+int gaz_engine_get_solver(gaz_engine* h, int32_t* mode) { return mode ? h->get_solver(mode) : h->fail("get_solver: null argument"); }
+int gaz_engine_get_solver_stats(gaz_engine* h, uint64_t out[8]) { return out ? h->get_solver_stats(out) : h->fail("get_solver_stats: null argument"); }
 int gaz_engine_get_eval_symmetry(gaz_engine* h, int32_t* mode) { return mode ? h->get_eval_symmetry(mode) : h->fail("get_eval_symmetry: null argument"); }
 int gaz_engine_read_batch_symmetry(gaz_engine* h, uint8_t* sym) { return sym ? h->read_batch_symmetry(sym) : h->fail("read_batch_symmetry: null argument"); }
 int gaz_engine_set_fused_wave(gaz_engine* h, int32_t on) { return h->set_fused_wave(on); }

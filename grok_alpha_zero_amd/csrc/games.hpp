@@ -23,6 +23,7 @@ template <> struct Game<GAME_TTT> {
     static constexpr bool DRAWS = true;
     static constexpr int TEAM = GAZ_TEAM(64);       // lanes that own one game (wave.hpp "Teams")
     static constexpr bool SYM = false;              // see WithSym below
+    static constexpr bool SOLVE = false;            // see WithSolve below
 };
 template <> struct Game<GAME_C4> {
     static constexpr int ID = GAME_C4, H = 6, W = 7, HW = 42, C = 4, A = 7, K = 4;
@@ -30,6 +31,7 @@ template <> struct Game<GAME_C4> {
     static constexpr bool DRAWS = true;
     static constexpr int TEAM = GAZ_TEAM(64);
     static constexpr bool SYM = false;
+    static constexpr bool SOLVE = false;
 };
 template <> struct Game<GAME_GMK> {
     static constexpr int ID = GAME_GMK, H = 15, W = 15, HW = 225, C = 2, A = 225, K = 5;
@@ -37,6 +39,7 @@ template <> struct Game<GAME_GMK> {
     static constexpr bool DRAWS = false;   // check_win_MCTS never reports a draw (Gomoku.py:249-255)
     static constexpr int TEAM = GAZ_TEAM(64);
     static constexpr bool SYM = false;
+    static constexpr bool SOLVE = false;
 };
 
 // The same game with the code of the search's random evaluation symmetry compiled in (puct_core.hpp eval_sym_draw; gaz_engine_set_eval_symmetry):
@@ -46,6 +49,13 @@ template <> struct Game<GAME_GMK> {
 template <class B> struct WithSym : B { static constexpr bool SYM = true; };
 template <bool S, class B> struct SymSel { typedef B type; };
 template <class B> struct SymSel<true, B> { typedef WithSym<B> type; };
+
+// The same game with the code of the solver compiled in (puct_core.hpp "MCTS-Solver"; gaz_engine_set_solver): proven wins, draws and losses in
+// the PUCT tree.  As with WithSym, the PUCT tree kernels exist once more per game, and an engine launches the WithSolve instantiations from the
+// first time the solver is switched on; until then it runs kernels without a trace of it.  Identical rules and layouts: HBM state is shared.
+template <class B> struct WithSolve : B { static constexpr bool SOLVE = true; };
+template <bool S, class B> struct SolveSel { typedef B type; };
+template <class B> struct SolveSel<true, B> { typedef WithSolve<B> type; };
 
 // The same game stepped by a 16-lane team: FOUR games per wavefront (PUCT tree kernel of the small boards).  Identical rules and
 // record layouts — only the lane mapping differs, so HBM state written by one variant is read by the other.

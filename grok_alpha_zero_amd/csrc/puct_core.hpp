@@ -84,6 +84,9 @@ template <class G> struct DevParams {
     float* nn_value;           // [n_games]
     // evaluation cache (0 = off): direct-mapped, entry = [tag u32][pad u32][state row, 8-byte padded][policy f32 x A][value f32]
     uint8_t* cache; uint32_t* cache_lock; uint32_t cache_mask, cache_epoch; int32_t cache_stride;
+    int32_t solver;            // proven wins / draws / losses in the PUCT tree (gaz_engine_set_solver, "MCTS-Solver" below): bit 0 = the mode (1 = on), bit 1 = it
+                               // has been on, so the host launches the kernels that carry its code (games.hpp WithSolve); 0 = a new engine.  (This word and the
+                               // two halves of solver_ctr() sit in what was padding: the struct — which the fused launches copy to their stack — keeps its size.)
     unsigned long long* stats; // [8]: game_stats[0..5] (Self_Play.py:181-188), [6] waves, [7] spare; behind them the ResignBlock (resign.hpp)
     const double* puct_table;  // [PUCT_TABLE_N][2]: sqrt(pv), c_init + ln((pv + c_base + 1) / c_base)
     unsigned long long* prof;  // diagnostic (GAZ_TREE_PROF=1): [n_games][8] shader-clock cycles per phase of the PUCT kernel, else null
@@ -107,9 +110,13 @@ template <class G> struct DevParams {
     // workgroup sits on a slot waiting for one slow game (rows of an evaluator batch are independent bit for bit, so which tile evaluates a
     // game cannot change its outputs).  No global atomics: a tree block ranks its own games by a counter in LDS, and entry (rank r, block j)
     // sits at r * n_full + min(r, rem) + j — rank-major, so the entries of every block's fastest game come first.  Entry = epoch << 32 | game.
+    uint32_t solver_ctr_lo;            // the solver's counters (gaz_engine_get_solver_stats) live in memory of their own, allocated at the first switch-on: the low
+                                       // and (below) the high half of their address, see solver_ctr()
     int32_t handoff_release;           // 1: the leaf row was written with plain stores -> agent-scope release before the flag / entry (Gomoku: rows not dword-aligned)
     unsigned long long* done_queue;    // [n_games] or null (then done_flag is used)
     int32_t queue_gpb, queue_nfull, queue_rem;   // games per tree block; blocks with that many games; games of the last, partial block
+    uint32_t solver_ctr_hi;
+    GAZ_HD unsigned long long* solver_ctr() const { return reinterpret_cast<unsigned long long*>(((uint64_t)solver_ctr_hi << 32) | (uint64_t)solver_ctr_lo); }
 };
 
 // leaf-batched search: what the K > 1 kernels get next to DevParams (whose nn_in / nn_policy / nn_value then hold n_games * K rows and paths
@@ -388,6 +395,61 @@ template <class G> GAZ_DEV void encode_request(const DevParams<G>& E, const Game
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// MCTS-Solver (gaz_engine_set_solver; Winands, Bjornsson, Saito 2008; no reference counterpart): proven wins, draws and
+// losses in the PUCT tree.  Only the kernels instantiated for a game type with G::SOLVE (games.hpp WithSolve) carry this code, and they use and
+// write statuses only while bit 0 of DevParams::solver is set.  Storage: tree.hpp (NodeHdr::flags bits 1-2, the tag bits of a child word).
+//   1. sources: a terminal parent is a WIN if one of its children is CHILD_LEAF_WIN, else a DRAW (a drawing move exists only when it is the only
+//      legal move, terminal_probe: nothing legal was dropped) — derived from the record, never stored;
+//   2. propagation (solver_propagate) starts when expand_pre has just created a terminal parent, after that creation's ordinary backup;
+//   3. selection leaves out -1 edges and stops at a known edge (puct_select);
+//   4. a move also ends as soon as the root has a status and every root child has a visit (PH_SIMS);
+//   5. move_end restricts the policy row and the move to the candidate slots and records the exact q.
+template <class G> GAZ_DEV void solver_count(const DevParams<G>& E, int k, unsigned long long v = 1ull) {
+    if (tlane<G>() == 0) atomic_add(E.solver_ctr() + k, v);
+}
+// status of a node for its mover (team-uniform): stored bits, or rule 1 for a terminal parent
+template <class G> GAZ_DEV int node_status(const NodeRef<G>& nd) {
+    const int fl = tuni<G>((int)nd.hdr()->flags);
+    if (!(fl & NF_TERMINAL_PARENT)) return (fl & NF_STATUS_MASK) >> NF_STATUS_SHIFT;
+    const int n = tuni<G>((int)nd.hdr()->n_children);
+    uint64_t win = 0;
+    for (int base = 0; base < n; base += G::TEAM) { const int i = base + tlane<G>(); win |= tballot<G>(i < n && nd.child()[i] == CHILD_LEAF_WIN); }
+    return win ? ST_WIN : ST_DRAW;
+}
+// Rule 2.  path[0 .. deep] is the simulation's own path, path[deep] the edge under which the terminal parent `made` (status st_made) was just
+// linked.  The new edge is tagged; then, from the deepest node up to the root, a node Y without a status is a WIN if some edge is +1, else — every
+// one of its n_actions edges known (so n_children == n_actions) — a DRAW if some edge is 0, else a LOSS; otherwise the walk stops.  A newly proven
+// Y is written (its flags, and the tag in its parent's child word) and the walk goes on to that parent.  One lane per child, three ballots per
+// TEAM children; rare (once per terminal parent created): it sits behind the branch of expand_pre that returns without an evaluation.
+template <class G> GAZ_DEV void solver_propagate(const DevParams<G>& E, int g, int t, const PathEnt* path, int deep, int st_made) {
+    if (tlane<G>() == 0) {
+        int32_t* w = node_at(E, g, t, path[deep].node).child() + path[deep].slot;
+        *w = child_index(*w) | (st_made << CHILD_TAG_SHIFT);
+    }
+    wave_sync();
+    for (int d = deep; d >= 0; --d) {
+        const NodeRef<G> nd = node_at(E, g, t, path[d].node);
+        const int fl = tuni<G>((int)nd.hdr()->flags);
+        if (fl & (NF_STATUS_MASK | NF_TERMINAL_PARENT)) break;
+        const int na = tuni<G>((int)nd.hdr()->n_actions);
+        uint64_t win = 0, unknown = 0, draw = 0;
+        for (int base = 0; base < na; base += G::TEAM) {
+            const int i = base + tlane<G>();
+            const int es = i < na ? edge_status(nd.child()[i]) : -1;          // (a slot not expanded yet holds CHILD_NONE: unknown)
+            win |= tballot<G>(es == ST_WIN); unknown |= tballot<G>(es == ST_UNKNOWN); draw |= tballot<G>(es == ST_DRAW);
+        }
+        const int st = win ? ST_WIN : (unknown ? ST_UNKNOWN : (draw ? ST_DRAW : ST_LOSS));
+        if (st == ST_UNKNOWN) break;
+        if (tlane<G>() == 0) {
+            nd.hdr()->flags = (uint8_t)(fl | (st << NF_STATUS_SHIFT));
+            if (d > 0) { int32_t* w = node_at(E, g, t, path[d - 1].node).child() + path[d - 1].slot; *w = child_index(*w) | (st << CHILD_TAG_SHIFT); }
+        }
+        solver_count<G>(E, 0);
+        wave_sync();
+    }
+}
+
 // K1: argmax_i  Q_i + U_i over the node's n_actions children (expanded and not), float64 like numpy:
 //   U_i = (P_i * (sqrt(Np) / (N_i + 1))) * (c_init + ln((Np + c_base + 1) / c_base));  Q_i = f32(W_i / N_i) or W_i
 // The two factors that depend only on the parent's visit count come from a table filled at engine creation by the same code
@@ -403,10 +465,14 @@ GAZ_DEV void puct_factors(uint64_t parent_visits, double c_init, double c_base, 
     else { const double pv = (double)parent_visits; s = dsqrt(pv); c = puct_c_of(pv, c_init, c_base); }
 }
 
-template <class G> GAZ_DEV int best_puct_slot(const NodeRef<G>& nd, int n_actions, double s, double c) {
+// Solver (`masked`, kernels with the solver's code only): slots whose edge value is -1 — the child is proven a win for its mover — are left out
+// of the argmax; `any_left_out` reports whether the team left one out.  Everything else of the score is unchanged.
+template <class G> GAZ_DEV int best_puct_slot(const NodeRef<G>& nd, int n_actions, double s, double c, bool masked = false, bool* any_left_out = nullptr) {
     const uint32_t* N = nd.N(); const float* Wv = nd.W(); const float* P = nd.P();
     double best = 0.0; int bi = 0x7fffffff;
+    bool left_out = false;
     for (int i = tlane<G>(); i < n_actions; i += G::TEAM) {
+        if constexpr (G::SOLVE) { if (masked && edge_status(nd.child()[i]) == ST_LOSS) { left_out = true; continue; } }
         uint32_t n = N[i]; float w = Wv[i];
         double u = ((double)P[i] * (s / (double)(n + 1u))) * c;
         float q = w;
@@ -415,6 +481,7 @@ template <class G> GAZ_DEV int best_puct_slot(const NodeRef<G>& nd, int n_action
         if (bi == 0x7fffffff || sc > best) { best = sc; bi = i; }
     }
     team_argmax<G>(best, bi);
+    if constexpr (G::SOLVE) { if (masked && any_left_out) *any_left_out = tballot<G>(left_out) != 0; }
     return tuni<G>(bi);
 }
 
@@ -578,13 +645,14 @@ template <class G> GAZ_DEV void root_post(const DevParams<G>& E, int g, GameStat
 // (double)N_i < sqrt((k * P_i) * root_visits) — this operation order, float64, the correctly rounded root.  Returns the LOWEST owed slot, or
 // -1 when nothing is owed (then PUCT's own choice stands).  One ballot per TEAM children on the record already in LDS; the statistics are
 // taken as they stand (leaf-batched search: virtual losses included) and reserved slots (>= n_children) are never owed.
-template <class G> GAZ_DEV int forced_slot(const NodeRef<G>& nd, int n_children, double k, double rv) {
+template <class G> GAZ_DEV int forced_slot(const NodeRef<G>& nd, int n_children, double k, double rv, bool masked = false) {
     for (int base = 0; base < n_children; base += G::TEAM) {
         const int i = base + tlane<G>();
         bool owed = false;
         if (i < n_children) {
             const uint32_t n = nd.N()[i];
             owed = n > 0u && (double)n < dsqrt((k * (double)nd.P()[i]) * rv);
+            if constexpr (G::SOLVE) { if (masked && edge_status(nd.child()[i]) == ST_LOSS) owed = false; }     // solver: a -1 slot is never owed
         }
         const uint64_t m = tballot<G>(owed);
         if (m) return base + ffsll0(m);
@@ -602,6 +670,9 @@ template <class G> GAZ_DEV bool forced_playouts_on(const DevParams<G>& E, const 
 // n_children + the node's reserved children, and 2 = the best child is one of those reserved ones (a collision: nothing was changed).
 // Forced playouts: at depth 0 the lowest owed child (forced_slot) replaces PUCT's choice; below it the descent is the ordinary one.  A root
 // that is a terminal parent never gets here.  No RNG event is consumed.
+// Solver on (rule 3 of "MCTS-Solver" below): slots with edge value -1 are left out of the argmax (a node whose slots are ALL left out can only come
+// from terminal parents made while the solver was off; slot 0 then stands), and a chosen slot whose edge value is known ends the simulation there as
+// a PROVEN HIT: 3 = edge value 0, 4 = +1, 5 = -1 (the last two only in such leftover nodes), the path includes the edge.  No RNG event is consumed.
 template <class G, bool LB = false> GAZ_DEV int puct_select(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S,
                                            int& node, int& depth, bool& leaf_win) {
     node = ts.root; depth = 0;
@@ -657,10 +728,30 @@ template <class G, bool LB = false> GAZ_DEV int puct_select(const DevParams<G>& 
             wave_sync();
             return 1;
         }
-        int best = best_puct_slot<G>(nd, n_actions, fs, fc);
+        int best;
+        if constexpr (G::SOLVE) {
+            const bool on = (E.solver & 1) != 0;
+            bool left_out = false;
+            best = best_puct_slot<G>(nd, n_actions, fs, fc, on, &left_out);
+            if (on && left_out) { if (best == 0x7fffffff) best = 0; solver_count<G>(E, 7); }
+            if (depth == 0 && forced_playouts_on<G>(E, gs)) {
+                const int owed = forced_slot<G>(nd, n_children, E.forced_playouts_k, (double)pv, on);
+                if (owed >= 0) best = owed;
+            }
+            if (on && best < n_children) {
+                const int es = tuni<G>(edge_status(nd.child()[best]));
+                if (es != ST_UNKNOWN) {                                  // proven hit
+                    S.path[depth].node = node; S.path[depth].slot = best; depth++;
+                    wave_sync();
+                    return es == ST_DRAW ? 3 : (es == ST_WIN ? 4 : 5);
+                }
+            }
+        } else {
+        best = best_puct_slot<G>(nd, n_actions, fs, fc);
         if (depth == 0 && forced_playouts_on<G>(E, gs)) {
             const int owed = forced_slot<G>(nd, n_children, E.forced_playouts_k, (double)pv);
             if (owed >= 0) best = owed;
+        }
         }
         const int n_reserved = LB ? tuni<G>((int)h.pad[0]) : 0;
         if (best == n_children + n_reserved) { wave_sync(); return 0; }          // MCTS.py:217-218
@@ -668,7 +759,7 @@ template <class G, bool LB = false> GAZ_DEV int puct_select(const DevParams<G>& 
         if (LB && best >= n_children) { wave_sync(); return 2; }
         S.path[depth].node = node; S.path[depth].slot = best; depth++;
         pv = tuni<G>(nd.N()[best]);
-        node = tuni<G>(nd.child()[best]);
+        node = tuni<G>(G::SOLVE ? child_index(nd.child()[best]) : nd.child()[best]);
     }
 }
 
@@ -777,6 +868,7 @@ template <class G> GAZ_DEV bool expand_pre(const DevParams<G>& E, int g, GameSta
         wave_sync();
         // value = -(len(terminal_mask)) if any win else 0; visits = len(terminal_mask)  (MCTS.py:373-380, 428)
         backup<G>(E, g, t, ts, S.path, depth + 1, any_win ? -(float)nt : 0.0f, (uint32_t)nt);
+        if constexpr (G::SOLVE) { if (E.solver & 1) solver_propagate<G>(E, g, t, S.path, depth, any_win ? ST_WIN : ST_DRAW); }
         return false;
     }
     copy_board<G>(nd.board(), S.board);
@@ -957,12 +1049,13 @@ template <class G> GAZ_DEV int compact_subtree(const DevParams<G>& E, int g, int
         if (tuni<G>((int)nd.hdr()->flags) & NF_TERMINAL_PARENT) continue;          // children are leaf codes, no records
         const int nch = tuni<G>((int)nd.hdr()->n_children);
         for (int s = 0; s < nch; ++s) {
-            const int c = tuni<G>(nd.child()[s]);
-            if (c < 0) continue;
+            const int cw = tuni<G>(nd.child()[s]);
+            if (cw < 0) continue;
+            const int c = G::SOLVE ? child_index(cw) : cw;                        // (solver: the word's tag bits travel with it)
             if (n_new >= E.nodes_per_tree) { set_error(E.error, ERR_ARENA_FULL); return -1; }
             copy_rec(n_new, c);
             wave_sync();
-            if (tlane<G>() == 0) { nd.child()[s] = n_new; reinterpret_cast<NodeHdr*>(base_n + (size_t)n_new * nb)->parent = i; }
+            if (tlane<G>() == 0) { nd.child()[s] = G::SOLVE ? (n_new | (cw & ~CHILD_INDEX_MASK)) : n_new; reinterpret_cast<NodeHdr*>(base_n + (size_t)n_new * nb)->parent = i; }
             n_new++;
         }
     }
@@ -985,7 +1078,7 @@ template <class G> GAZ_DEV bool prune(const DevParams<G>& E, int g, TreeState& t
         if (m) { found = base + ffsll0(m); break; }
     }
     if (found < 0) return true;
-    const int c = tuni<G>(r.child()[found]);
+    const int c = tuni<G>(G::SOLVE ? child_index(r.child()[found]) : r.child()[found]);
     if (c < 0) return true;                                           // (terminal leaf: never pruned on a live game)
     const uint32_t v = tuni<G>(r.N()[found]);
     wave_sync();
@@ -1095,17 +1188,45 @@ template <class G> GAZ_DEV void move_end(const DevParams<G>& E, int g, GameState
         pol[a] = (float)((double)r.N()[i] / (double)sumv);           // prob = N / sum(N)  (MCTS.py:594, Connect4.py:421-424)
         rN[a] = r.N()[i]; rW[a] = r.W()[i]; rP[a] = r.P()[i];
     }
-    if (forced_playouts_on<G>(E, gs) && !(tuni<G>((int)r.hdr()->flags) & NF_TERMINAL_PARENT)) {
+    const bool pruned = forced_playouts_on<G>(E, gs) && !(tuni<G>((int)r.hdr()->flags) & NF_TERMINAL_PARENT);
+    if (pruned) {
         wave_sync();
         prune_policy_target<G>(E, r, n, ts.root_visits, S, pol);
     }
-    // K10 move sampling
+    // Solver, rule 5: the candidate slots C by the root's status — WIN: edges +1, DRAW: edges 0, LOSS: all, unknown: edges that are not -1 and
+    // have a visit (all slots if there are none).  The policy row is the counts it would be without the solver — N, or the pruned counts that
+    // prune_policy_target left in S.gam — restricted to C: f32(n_i / sum over C) on C, 0 elsewhere (left as it was if that sum is 0).
+    int root_st = ST_UNKNOWN; bool solve = false;
+    if constexpr (G::SOLVE) {
+        solve = (E.solver & 1) != 0;
+        if (solve) {
+            root_st = node_status<G>(r);
+            uint64_t any = 0;
+            for (int base = 0; base < n; base += G::TEAM) { const int i = base + tlane<G>(); any |= tballot<G>(i < n && edge_status(r.child()[i]) != ST_LOSS && r.N()[i] > 0u); }
+            uint64_t csum = 0;
+            for (int i = tlane<G>(); i < n; i += G::TEAM) {
+                const int es = edge_status(r.child()[i]);
+                const bool in = root_st == ST_WIN ? es == ST_WIN : root_st == ST_DRAW ? es == ST_DRAW : root_st == ST_LOSS ? true : (!any || (es != ST_LOSS && r.N()[i] > 0u));
+                const double cnt = pruned ? S.gam[i] : (double)r.N()[i];
+                S.aux[i] = in ? 1.0f : 0.0f;                            // membership, for the move below
+                if (in) csum += (uint64_t)cnt;
+            }
+            csum = team_sum_u64<G>(csum);
+            wave_sync();
+            if (csum) for (int i = tlane<G>(); i < n; i += G::TEAM) {
+                const double cnt = pruned ? S.gam[i] : (double)r.N()[i];
+                pol[r.act()[i]] = S.aux[i] != 0.0f ? (float)(cnt / (double)csum) : 0.0f;
+            }
+            wave_sync();
+        }
+    }
+    // K10 move sampling (solver: slots outside C weigh 0; a root proven WIN or DRAW plays its most visited candidate whatever tau says)
     int chosen;
     det::Event e = make_event(E, g, gs, ts, t, det::P_MOVE);
     const double u = det::uniform(e);
-    if (!gs.tau_on[t]) {                                               // tau == 0: one-hot at first argmax N (MCTS.py:602-604)
+    if (!gs.tau_on[t] || root_st == ST_WIN || root_st == ST_DRAW) {     // tau == 0: one-hot at first argmax N (MCTS.py:602-604)
         uint32_t bv = 0; int bi = 0x7fffffff;
-        for (int i = tlane<G>(); i < n; i += G::TEAM) { uint32_t v = r.N()[i]; if (bi == 0x7fffffff || v > bv) { bv = v; bi = i; } }
+        for (int i = tlane<G>(); i < n; i += G::TEAM) { uint32_t v = r.N()[i]; if (solve && S.aux[i] == 0.0f) v = 0u; if (bi == 0x7fffffff || v > bv) { bv = v; bi = i; } }
         team_argmax_u32<G>(bv, bi);
         chosen = tuni<G>(bi);
     } else {                                                           // tau > 0 (MCTS.py:606-612), float64: N^(1/tau) / visits^(1/tau)
@@ -1113,9 +1234,10 @@ template <class G> GAZ_DEV void move_end(const DevParams<G>& E, int g, GameState
         if (ex == 1.0) {                                               // x ** 1.0 == x exactly
             const double den = (double)ts.root_visits;
             for (int i = tlane<G>(); i < n; i += G::TEAM) S.gam[i] = (double)r.N()[i] / den;
+            if (solve) { for (int i = tlane<G>(); i < n; i += G::TEAM) if (S.aux[i] == 0.0f) S.gam[i] = 0.0; }
         } else {                                                       // det::dpow stands in for libm pow (< 1e-14 relative: the sampled
             const double den = det::dpow((double)ts.root_visits, ex);  // move differs only if u lands within that of a cdf step)
-            for (int i = tlane<G>(); i < n; i += G::TEAM) S.gam[i] = det::dpow((double)r.N()[i], ex) / den;
+            for (int i = tlane<G>(); i < n; i += G::TEAM) S.gam[i] = (solve && S.aux[i] == 0.0f) ? 0.0 : det::dpow((double)r.N()[i], ex) / den;
         }
         wave_sync();
         const double s = det::np_pairwise_sum<double>(S.gam, n);
@@ -1132,6 +1254,14 @@ template <class G> GAZ_DEV void move_end(const DevParams<G>& E, int g, GameState
         reinterpret_cast<uint32_t*>(rec + RL::OFF_RV)[ply] = (uint32_t)ts.root_visits;
         reinterpret_cast<uint32_t*>(rec + RL::OFF_EV)[ply] = gs.move_evals;
         rec[RL::OFF_MK + ply] = move_kind_of(gs);
+        if (root_st != ST_UNKNOWN) {                                   // solver: the exact value, the mark of a proven ply, the counters
+            reinterpret_cast<float*>(rec + RL::OFF_Q)[ply] = root_st == ST_WIN ? 1.0f : (root_st == ST_DRAW ? 0.0f : -1.0f);
+            rec[RL::OFF_MK + ply] = (uint8_t)(move_kind_of(gs) | MK_PROVEN);
+            unsigned long long* ctr = E.solver_ctr();
+            atomic_add(ctr + 2, 1ull);
+            if (gs.iter_limit > gs.sims_done) atomic_add(ctr + 3, (unsigned long long)(gs.iter_limit - gs.sims_done));
+            atomic_add(ctr + 3 + root_st, 1ull);
+        }
     }
     wave_sync();
 }
@@ -1291,6 +1421,13 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
                 for (int base = 0; base < na; base += G::TEAM) { int i = base + tlane<G>(); zero |= tballot<G>(i < na && r.N()[i] == 0u); }
                 if (!zero) { if (tlane<G>() == 0) gs.fully_visited = 1; wave_sync(); }
             }
+            if constexpr (G::SOLVE) {                                       // solver, rule 4: a root with a status, every child visited -> the move ends
+                if ((E.solver & 1) && tuni<G>(gs.fully_visited) && node_status<G>(r) != ST_UNKNOWN) {
+                    if (tlane<G>() == 0) gs.phase = PH_MOVE_END;
+                    wave_sync();
+                    return false;
+                }
+            }
             if (tuni<G>(gs.fully_visited) && (tuni<G>((int)r.hdr()->flags) & NF_TERMINAL_PARENT)) {
                 // Root with a terminal move available (MCTS.py:200-208 at depth 0): every remaining simulation is
                 // "pick a terminal child, back up 1 (win) or 0 (draw)" and touches only the root's arrays, so up to 64
@@ -1355,7 +1492,12 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
                 return false;
             }
             if (LB) tree_only++;
-            if (kind == 1) {                                           // terminal leaf: value 1 / 0, visits 1 (MCTS.py:573-575)
+            if (G::SOLVE && kind >= 3) {                               // solver: proven hit, the edge value in the sign convention of a terminal leaf
+                backup<G>(E, g, t, ts, S.path, depth, kind == 3 ? 0.0f : (kind == 4 ? 1.0f : -1.0f), 1u);
+                if (tlane<G>() == 0) { gs.sims_done += 1; gs.n_sims += 1; }
+                solver_count<G>(E, 1);
+                wave_sync();
+            } else if (kind == 1) {                                    // terminal leaf: value 1 / 0, visits 1 (MCTS.py:573-575)
                 const long long tb0 = GAZ_PROF_NOW();
                 backup<G>(E, g, t, ts, S.path, depth, leaf_win ? 1.0f : 0.0f, 1u);
                 if (tlane<G>() == 0) { gs.sims_done += 1; gs.n_sims += 1; }

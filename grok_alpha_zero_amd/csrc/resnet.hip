@@ -1296,8 +1296,9 @@ __device__ __forceinline__ void wave_trunk_body(const DevParams<GP>& E, int g0, 
 }
 
 // SYM (here and below): the tree role with the code of the random evaluation symmetry (games.hpp WithSym), launched once an engine has switched it on
-template <bool MIX, bool SKIP, bool SYM = false> __global__ __launch_bounds__(TR_THREADS, 2) void k_wave_trunk(DevParams<typename SymSel<SYM, GP4>::type> E, int g0, int g1, int n_tree_blocks, TrunkArgs a) {
-    typedef typename SymSel<SYM, GP4>::type GP;
+// SOLVE: likewise, the tree role with the solver's code (games.hpp WithSolve)
+template <bool MIX, bool SKIP, bool SYM = false, bool SOLVE = false> __global__ __launch_bounds__(TR_THREADS, 2) void k_wave_trunk(DevParams<typename SolveSel<SOLVE, typename SymSel<SYM, GP4>::type>::type> E, int g0, int g1, int n_tree_blocks, TrunkArgs a) {
+    typedef typename SolveSel<SOLVE, typename SymSel<SYM, GP4>::type>::type GP;
     wave_trunk_body<MIX, SKIP, GP, PuctLocal<GP>, false>(E, g0, g1, n_tree_blocks, a);
 }
 
@@ -1308,8 +1309,8 @@ template <bool MIX, bool SKIP, bool SYM = false> __global__ __launch_bounds__(TR
 // DevParams::handoff_release) and then writes its queue entry; the workgroup's polling lane acquires before the barrier, the planes are
 // read with plain loads behind it.  A tree step here is hundreds of microseconds, the two fences a few.
 typedef Game<GAME_GMK> GGMK;
-template <bool SYM> __global__ __launch_bounds__(512, 1) void k_wave_trunk_gmk(DevParams<typename SymSel<SYM, GGMK>::type> E, int g0, int g1, int n_tree_blocks, TrunkArgs a) {
-    typedef typename SymSel<SYM, GGMK>::type GP;
+template <bool SYM, bool SOLVE = false> __global__ __launch_bounds__(512, 1) void k_wave_trunk_gmk(DevParams<typename SolveSel<SOLVE, typename SymSel<SYM, GGMK>::type>::type> E, int g0, int g1, int n_tree_blocks, TrunkArgs a) {
+    typedef typename SolveSel<SOLVE, typename SymSel<SYM, GGMK>::type>::type GP;
     if ((int)blockIdx.x < n_tree_blocks) {
         extern __shared__ uint4 lds[];
         if (a.stamps && (threadIdx.x & 63) == 0) a.stamps[(size_t)blockIdx.x * 128 + (threadIdx.x >> 6)] = wall_clock64();
@@ -1335,12 +1336,17 @@ template <class GP> static bool wave_trunk_launch(void (*kernel)(DevParams<GP>, 
 
 bool launch_wave_trunk_gmk(hipStream_t s, const void* dev_params, int g0, int g1, const void* plan) {
     const bool sym = dev_params && static_cast<const DevParams<GGMK>*>(dev_params)->eval_symmetry != 0;
+    const bool solve = dev_params && static_cast<const DevParams<GGMK>*>(dev_params)->solver != 0;
     static bool attr = false;
     if (!attr) {
         hipFuncSetAttribute((const void*)k_wave_trunk_gmk<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes_s0());
         hipFuncSetAttribute((const void*)k_wave_trunk_gmk<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes_s0());
+        hipFuncSetAttribute((const void*)k_wave_trunk_gmk<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes_s0());
+        hipFuncSetAttribute((const void*)k_wave_trunk_gmk<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes_s0());
         attr = true;
     }
+    if (solve && sym) return wave_trunk_launch<WithSolve<WithSym<GGMK>>>(k_wave_trunk_gmk<true, true>, 512, 8, s, dev_params, g0, g1, plan);
+    if (solve) return wave_trunk_launch<WithSolve<GGMK>>(k_wave_trunk_gmk<false, true>, 512, 8, s, dev_params, g0, g1, plan);
     if (sym) return wave_trunk_launch<WithSym<GGMK>>(k_wave_trunk_gmk<true>, 512, 8, s, dev_params, g0, g1, plan);
     return wave_trunk_launch<GGMK>(k_wave_trunk_gmk<false>, 512, 8, s, dev_params, g0, g1, plan);
 }
@@ -1369,6 +1375,11 @@ bool launch_wave_trunk_c4(hipStream_t s, const void* dev_params, int g0, int g1,
     const bool sym = dev_params && static_cast<const DevParams<GP4>*>(dev_params)->eval_symmetry != 0;
     const TrunkLaunchPlan* P = static_cast<const TrunkLaunchPlan*>(plan);
     const bool mix = P && P->mix, skip = P && P->args.perm && P->args.perm_small;      // skip: both tile shapes carry an edge-tile permutation (checked by the evaluator)
+    const bool solve = dev_params && static_cast<const DevParams<GP4>*>(dev_params)->solver != 0;
+    if (solve && sym) return wave_trunk_launch<WithSolve<WithSym<GP4>>>(mix && skip ? k_wave_trunk<true, true, true, true> : mix ? k_wave_trunk<true, false, true, true> : k_wave_trunk<false, false, true, true>,
+                                                                       TR_THREADS, (TR_THREADS / WAVE) * (WAVE / GP4::TEAM), s, dev_params, g0, g1, plan);
+    if (solve) return wave_trunk_launch<WithSolve<GP4>>(mix && skip ? k_wave_trunk<true, true, false, true> : mix ? k_wave_trunk<true, false, false, true> : k_wave_trunk<false, false, false, true>,
+                                                        TR_THREADS, (TR_THREADS / WAVE) * (WAVE / GP4::TEAM), s, dev_params, g0, g1, plan);
     if (sym) return wave_trunk_launch<WithSym<GP4>>(mix && skip ? k_wave_trunk<true, true, true> : mix ? k_wave_trunk<true, false, true> : k_wave_trunk<false, false, true>, TR_THREADS,
                                                     (TR_THREADS / WAVE) * (WAVE / GP4::TEAM), s, dev_params, g0, g1, plan);
     return wave_trunk_launch<GP4>(mix && skip ? k_wave_trunk<true, true> : mix ? k_wave_trunk<true, false> : k_wave_trunk<false, false>, TR_THREADS,

@@ -18,6 +18,21 @@ namespace gaz {
 
 enum : int32_t { CHILD_NONE = -1, CHILD_LEAF_DRAW = -2, CHILD_LEAF_WIN = -3 };
 enum : uint8_t { NF_TERMINAL_PARENT = 1 };
+// Solver (puct_core.hpp "MCTS-Solver"): a node's proven status for the player to move there is bits 1-2 of NodeHdr::flags — 0 unknown, 1 win,
+// 2 draw, 3 loss.  (A terminal parent's status is never stored: bit 0 and its child codes say it.)  So that a descent sees the edge values of
+// all children in the record it has staged, the status of an expanded child is repeated in bits 29-30 of the parent's child[] word; only the
+// kernels with the solver's code (games.hpp WithSolve) write such a word, and they — and the read-outs — take the index through child_index().
+enum : int32_t { ST_UNKNOWN = 0, ST_WIN = 1, ST_DRAW = 2, ST_LOSS = 3, NF_STATUS_SHIFT = 1, NF_STATUS_MASK = 6 };
+enum : int32_t { CHILD_TAG_SHIFT = 29, CHILD_INDEX_MASK = (1 << 29) - 1 };
+GAZ_HD int32_t child_index(int32_t w) { return w < 0 ? w : (w & CHILD_INDEX_MASK); }
+GAZ_HD int32_t child_tag(int32_t w) { return w < 0 ? 0 : (w >> CHILD_TAG_SHIFT); }
+// edge value of a child word from the parent mover's view, as a status of the PARENT's side of the edge: ST_WIN = +1, ST_DRAW = 0, ST_LOSS = -1
+GAZ_HD int32_t edge_status(int32_t w) {
+    if (w == CHILD_LEAF_WIN) return ST_WIN;
+    if (w == CHILD_LEAF_DRAW) return ST_DRAW;
+    const int32_t t = child_tag(w);                  // the child's own status: its win is this side's loss
+    return t == ST_WIN ? ST_LOSS : (t == ST_LOSS ? ST_WIN : t);
+}
 
 struct NodeHdr {          // 32 bytes
     int32_t parent;       // node index in this tree's arena, -1 for a root created by create_expand_root
@@ -119,6 +134,8 @@ enum : uint8_t { MK_NONE = 0, MK_FULL = 1, MK_FAST = 2 };
 // the kind is the low two bits of the byte; above them the marks of resignation (resign.hpp): the ply after which the game was resigned,
 // and in a game that is played out the plies at which it would have been
 enum : uint8_t { MK_KIND_MASK = 3, MK_RESIGNED = 0x10, MK_WOULD_RESIGN = 0x20 };
+// and the mark of the solver (puct_core.hpp move_end): the ply ended with a proven root (its q is the exact +1 / 0 / -1)
+enum : uint8_t { MK_PROVEN = 0x40 };
 enum : uint32_t { CAP_HAD_FULL = 1, CAP_FAST_NOW = 2 };
 
 }  // namespace gaz

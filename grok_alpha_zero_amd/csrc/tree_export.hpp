@@ -88,7 +88,7 @@ template <class G, bool WRITE> GAZ_DEV void export_tree(const DevParams<G>& E, c
             for (int base = 0; base < na; base += G::TEAM) {
                 const int s = base + tlane<G>();
                 const bool in = s < na;
-                const int c = in ? nd.child()[s] : CHILD_NONE;
+                const int c = in ? child_index(nd.child()[s]) : CHILD_NONE;       // (solver: a child word may carry tag bits, tree.hpp)
                 const uint32_t n = in ? nd.N()[s] : 0u;
                 const bool has = in && c >= 0;
                 const bool take = has && deeper && n >= X.min_visits && c < E.nodes_per_tree;
@@ -151,7 +151,7 @@ template <class G> GAZ_KERNEL_TEAMS k_tree_pv(DevParams<G> E, int tree, const in
             pick = tuni<G>(bi);
         }
         const uint32_t pn = tuni<G>(nd.N()[pick]);
-        const int c = tuni<G>(nd.child()[pick]);
+        const int c = tuni<G>(child_index(nd.child()[pick]));
         if (tlane<G>() == 0) {
             const size_t o = (size_t)g * (size_t)max_len + (size_t)len;
             o_act[o] = nd.act()[pick]; o_N[o] = pn; o_W[o] = nd.W()[pick];

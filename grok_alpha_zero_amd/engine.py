@@ -59,6 +59,8 @@ class ResignParams(C.Structure):        # gaz_resign_params
 
 
 MK_KIND_MASK, MK_RESIGNED, MK_WOULD_RESIGN = 3, 0x10, 0x20      # the bits of a record's raw move_kind byte (gaz_record_layout.off_move_kind)
+MK_PROVEN = 0x40                                                 # solver (set_solver): the ply ended with a proven root
+PROVEN_UNKNOWN, PROVEN_WIN, PROVEN_DRAW, PROVEN_LOSS = 0, 1, 2, 3   # a node's status for the player to move there (SearchTree.proven)
 
 
 class SampleLayout(C.Structure):        # gaz_sample_layout
@@ -122,6 +124,9 @@ def load_library(lib_path=None):
     L.gaz_engine_set_eval_symmetry.argtypes = [H, C.c_int32]
     L.gaz_engine_get_eval_symmetry.argtypes = [H, C.POINTER(C.c_int32)]
     L.gaz_engine_read_batch_symmetry.argtypes = [H, C.c_void_p]
+    L.gaz_engine_set_solver.argtypes = [H, C.c_int32]
+    L.gaz_engine_get_solver.argtypes = [H, C.POINTER(C.c_int32)]
+    L.gaz_engine_get_solver_stats.argtypes = [H, C.POINTER(C.c_uint64)]
     L.gaz_engine_probe_rules.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7
     L.gaz_engine_set_fused_wave.argtypes = [H, C.c_int32]
     L.gaz_engine_debug_fused_fault.argtypes = [H, C.c_int32]
@@ -136,7 +141,7 @@ def load_library(lib_path=None):
     for f in ("create", "load_weights", "reset_games", "run_move", "get_root_stats", "apply_moves", "run_waves", "wave_begin",
               "wave_end", "batch_ptrs", "read_batch", "write_outputs", "batch_rows", "evaluate", "record_layout", "drain_finished", "sample_layout", "drain_samples", "get_stats",
               "synchronize", "timing_reset", "timing_get", "dominant_kernel", "set_position", "set_search_params", "start_search", "stop_search",
-              "set_hyperparams", "set_resignation", "get_resign_stats", "set_eval_symmetry", "get_eval_symmetry", "read_batch_symmetry", "probe_rules", "read_head_features", "set_fused_wave", "debug_fused_fault", "read_positions", "repack", "read_trees", "read_pv"):
+              "set_hyperparams", "set_resignation", "get_resign_stats", "set_eval_symmetry", "get_eval_symmetry", "read_batch_symmetry", "set_solver", "get_solver", "get_solver_stats", "probe_rules", "read_head_features", "set_fused_wave", "debug_fused_fault", "read_positions", "repack", "read_trees", "read_pv"):
         getattr(L, "gaz_engine_" + f).restype = C.c_int
     _LIBS[path] = L
     return L
@@ -206,6 +211,16 @@ class SearchTree:
         c = self.edges_of(i)["child"]
         return [int(x) for x in c[c >= 0]]
 
+    @property
+    def proven(self):
+        """int32 [len(self)]: what the solver (SelfPlayEngine.set_solver) proved for the player to move at every node — PROVEN_UNKNOWN (0),
+        PROVEN_WIN (1), PROVEN_DRAW (2), PROVEN_LOSS (3): bits 1-2 of the node's flags, and for a terminal parent (whose status is not
+        stored) a win if one of its moves wins, else a draw"""
+        out = ((self.nodes["flags"] >> 1) & 3).astype(np.int32)
+        for i in np.flatnonzero(self.nodes["flags"] & NF_TERMINAL_PARENT):
+            out[i] = PROVEN_WIN if np.any(self.edges_of(i)["child"] == CHILD_WIN) else PROVEN_DRAW
+        return out
+
     def path_actions(self, i):
         """action indices that lead from the root to node i"""
         out = []
@@ -226,7 +241,7 @@ class SelfPlayEngine:
                  compact_trees=0, single_tree=False, opening_actions=None, eval_cache_log2=0, gumbel_stablemax=False, fast_find_win=False,
                  use_gumbel_noise=True, first_game_seq=0, games_budget=0, tau=-1.0, move_time_limit=0.0, game_groups=0, leaf_batch=1, gumbel_batch=1,
                  fast_iterations=0, full_search_prob=0.0, forced_playouts_k=0.0,
-                 resign_threshold=0.0, resign_consecutive=1, resign_min_ply=0, no_resign_prob=0.0, eval_symmetry=False, lib_path=None):
+                 resign_threshold=0.0, resign_consecutive=1, resign_min_ply=0, no_resign_prob=0.0, eval_symmetry=False, solver=False, lib_path=None):
         self.L = load_library(lib_path)
         self.game_id = GAME_IDS[game] if isinstance(game, str) else int(game)
         self.H, self.W, self.Cc, self.A = GAME_DIMS[self.game_id]
@@ -272,6 +287,12 @@ class SelfPlayEngine:
                 raise
         if eval_symmetry:                            # (off = the state of a new engine)
             self.set_eval_symmetry(True)
+        if solver:                                   # (likewise)
+            try:
+                self.set_solver(True)
+            except EngineError:
+                self.close()
+                raise
 
     def _ck(self, rc):
         if rc:
@@ -463,6 +484,30 @@ class SelfPlayEngine:
         self._ck(self.L.gaz_engine_get_eval_symmetry(self.h, C.byref(m)))
         return bool(m.value)
 
+    def set_solver(self, on=True):
+        """Prove wins, draws and losses in the PUCT search (gaz_engine_set_solver; MCTS-Solver), from the next launch on: moves that are
+        proven lost are no longer searched, a move ends as soon as its root is proven, the policy row and the move are restricted to the
+        moves that keep the proven result, and the recorded q of such a ply is the exact +1 / 0 / -1 (its `proven` flag is set).  Refused
+        with the Gumbel search, leaf_batch > 1 and gumbel_batch > 1."""
+        self._ck(self.L.gaz_engine_set_solver(self.h, int(bool(on))))
+
+    @property
+    def solver(self):
+        m = C.c_int32()
+        self._ck(self.L.gaz_engine_get_solver(self.h, C.byref(m)))
+        return bool(m.value)
+
+    def solver_stats(self):
+        """gaz_engine_get_solver_stats as a dict, over the engine's life: `proven_nodes` (by propagation; terminal parents not counted),
+        `proven_hits` (simulations that ended at a proven edge), `proven_moves` (moves that ended with a proven root: `root_win` +
+        `root_draw` + `root_loss`), `saved_sims` (simulations those moves did not run) and `masked_levels` (descent levels at which a
+        proven-lost move was left out).  A synchronisation point like stats()."""
+        out = (C.c_uint64 * 8)()
+        self._ck(self.L.gaz_engine_get_solver_stats(self.h, out))
+        s = [int(x) for x in out]
+        return dict(proven_nodes=s[0], proven_hits=s[1], proven_moves=s[2], saved_sims=s[3], root_win=s[4], root_draw=s[5], root_loss=s[6],
+                    masked_levels=s[7])
+
     def read_batch_symmetry(self):
         """uint8 [batch_rows]: the symmetry k every row of the evaluator batch was encoded under (meaningful where read_batch's
         pending is set; 0 while eval_symmetry is off)"""
@@ -503,7 +548,8 @@ class SelfPlayEngine:
 
     def drain_finished(self, max_records=None):
         """Finished games as dicts: actions, policies [T,A], q, z, values (=0.5(z+q), Self_Play.py:165-172),
-        root_N/W/P [T,A], root_visits, evals, move_kind (uint8 [T]: 0 no search, 1 full, 2 fast), winner, slot, game_seq, and of
+        root_N/W/P [T,A], root_visits, evals, move_kind (uint8 [T]: 0 no search, 1 full, 2 fast), proven (bool [T]: the ply ended with a root
+        the solver had proven, set_solver; its q is exact), winner, slot, game_seq, and of
         resignation (set_resignation) resigned (bool), resign_ply (the last ply of a resigned game, else -1) and would_resign_plies (the
         plies at which a game that was played out would have been resigned).
         With forced_playouts_k > 0 `policies` holds the pruned targets of the full moves; root_N / root_W / root_P stay raw."""
@@ -567,7 +613,7 @@ class SelfPlayEngine:
                     root_P=arr(lay.off_P, np.float32, (lay.max_T, A))[:T],
                     root_visits=arr(lay.off_root_visits, np.uint32, (lay.max_T,))[:T],
                     evals=arr(lay.off_evals, np.uint32, (lay.max_T,))[:T],
-                    move_kind=raw_kind & np.uint8(MK_KIND_MASK), resigned=bool(resigned_at.size),
+                    move_kind=raw_kind & np.uint8(MK_KIND_MASK), proven=(raw_kind & np.uint8(MK_PROVEN)) != 0, resigned=bool(resigned_at.size),
                     resign_ply=int(resigned_at[0]) if resigned_at.size else -1,
                     would_resign_plies=np.flatnonzero(raw_kind & MK_WOULD_RESIGN).astype(np.int32))
 

@@ -54,6 +54,7 @@ class Node:
         self._name, self._base_board, self._base_len = name, base_board, base_len
         self.action_history, self.current_player, self.child_id, self.parent, self.is_terminal = action_history, current_player, child_id, parent, is_terminal
         self.children = []
+        self.proven = 0                                  # solver: 0 unknown, 1 win, 2 draw, 3 loss for the player to move here
         self.child_visits = np.zeros(0, np.uint32); self.child_values = np.zeros(0, np.float32); self.child_prob_priors = np.zeros(0, np.float32)
         self.child_actions = []
 
@@ -78,6 +79,7 @@ def _build_root(name, tree, root_visits, gumbel, base_board, history):
     if len(tree) == 0:
         return None
     nodes, edges = tree.nodes, tree.edges
+    proven = tree.proven
     objs = [None] * len(tree)
     for i in range(len(tree)):
         n = nodes[i]
@@ -88,6 +90,7 @@ def _build_root(name, tree, root_visits, gumbel, base_board, history):
             par = objs[int(n["parent"])]
             o = Node(name, base_board, len(history), par.action_history + [_to_action(name, int(n["action"]))], int(n["player"]), int(n["slot"]), par)
         objs[i] = o
+        o.proven = int(proven[i])
         e = tree.edges_of(i)
         o.child_visits = e["N"].copy(); o.child_values = e["W"].copy(); o.child_prob_priors = e["P"].copy()
         o.child_actions = [_to_action(name, int(a)) for a in e["action"]]
@@ -198,7 +201,9 @@ class MCTS(_EngineSearch):
 
     def __init__(self, game, session=None, use_njit=None, c_puct_init=2.5, c_puct_base=19_652, use_dirichlet=True,
                  dirichlet_alpha=1.11, dirichlet_epsilon=0.25, tau=1.0, fast_find_win=False, *, seed=None, hash_salt=0,
-                 max_actions=None, leaf_batch=1, eval_symmetry=False, lib_path=None):
+                 max_actions=None, leaf_batch=1, eval_symmetry=False, solver=False, lib_path=None):
+        # solver: SelfPlayEngine.set_solver — proven wins, draws and losses; the nodes of `root` then carry `.proven` (0 unknown, 1 win, 2 draw,
+        # 3 loss for the player to move there)
         # eval_symmetry: SelfPlayEngine.set_eval_symmetry — the session is shown every position under a random board symmetry and answers
         # in that frame; the engine maps the policy back, so run()'s rows, root and pv() stay in the board's own frame
         self.c_puct_init, self.c_puct_base = c_puct_init, c_puct_base
@@ -207,7 +212,7 @@ class MCTS(_EngineSearch):
         self._attach(game, session, seed, lib_path, max_actions=max_actions or int(np.prod(game.board.shape)),
                      c_puct_init=c_puct_init, c_puct_base=c_puct_base, dirichlet_alpha=dirichlet_alpha,
                      dirichlet_epsilon=dirichlet_epsilon, use_dirichlet=use_dirichlet, hash_salt=hash_salt, search=SEARCH_PUCT,
-                     fast_find_win=bool(fast_find_win), leaf_batch=int(leaf_batch), eval_symmetry=bool(eval_symmetry))
+                     fast_find_win=bool(fast_find_win), leaf_batch=int(leaf_batch), eval_symmetry=bool(eval_symmetry), solver=bool(solver))
 
     def update_hyperparams(self, **kwargs):
         """MCTS.py:134-168: invalid values are ignored with a warning, valid ones take effect at the next simulation."""

@@ -459,6 +459,8 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
     is the player who did not resign, and game_stats count it like any other game.  `engine_stats["resign"]` receives
     SelfPlayEngine.resign_stats() (the false positives among the games played out); resign_curve() picks a threshold from the records
     of a generation played with no_resign_prob = 1.
+    Solver: train_config["solver"] (absent or False = off, and then no call is made) — SelfPlayEngine.set_solver: the PUCT search proves
+    wins, draws and losses; proven plies end early, and their value targets use the exact q.  PUCT with leaf_batch 1 only (else an EngineError).
     Random evaluation symmetry: train_config["eval_symmetry"] (absent or False = off, and then no call is made) —
     SelfPlayEngine.set_eval_symmetry: the network sees every search position under a board symmetry drawn per game and position, and the
     search uses the policy mapped back.  Records and samples stay in the board's own frame; the file format does not change.
@@ -539,6 +541,8 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
         eng.load_weights(weights)
     if train_config.get("eval_symmetry"):
         eng.set_eval_symmetry(True)
+    if train_config.get("solver"):
+        eng.set_solver(True)
     written = 0
     launch = G                                          # slots the launches cover (shrinks in the generation's tail, see repack)
     clock = time.perf_counter

@@ -43,6 +43,8 @@
  *   gaz_engine_set_resignation / gaz_engine_get_resign_stats  (no reference counterpart: Self_Play.play() plays every game to its end;
  *                              resignation with a share of games played out to measure its false positives is AlphaGo Zero's, Silver 2017)
  *   the 0x10 / 0x20 bits of a record's move_kind  (no reference counterpart: the marks that rule leaves in the record)
+ *   gaz_engine_set_solver / gaz_engine_get_solver / gaz_engine_get_solver_stats  (no reference counterpart: proven wins, draws and losses in
+ *     the PUCT tree), bits 1-2 of gaz_tree_node.flags and the 0x40 bit of a record's move_kind
  *   gaz_engine_set_eval_symmetry / gaz_engine_get_eval_symmetry / gaz_engine_read_batch_symmetry  (no reference counterpart: the reference
  *                              augments its training samples with the board symmetries, Guide.py:255-283, but always shows the search's
  *                              network one orientation; a random symmetry per evaluation is AlphaGo Zero's and KataGo's)
@@ -202,7 +204,8 @@ typedef struct {
                                      (gaz_engine_config.fast_iterations); always 1 for a searched ply with the cap off.  That kind is the byte's
                                      low two bits (& 3).  With resignation on (gaz_engine_set_resignation) two more bits may be set: 0x10 on the last
                                      ply of a game that was resigned after it, 0x20 on every ply of a game played out with resignation
-                                     disabled at which it would have been resigned; all other bits are 0 */
+                                     disabled at which it would have been resigned.  With the solver on (gaz_engine_set_solver) 0x40 marks a ply
+                                     that ended with a proven root (its q is the exact +1 / 0 / -1); all other bits are 0 */
 } gaz_record_layout;
 
 int gaz_engine_abi_version(void);                   /* GAZ_ENGINE_ABI_VERSION of the library */
@@ -259,6 +262,46 @@ int gaz_engine_get_eval_symmetry(gaz_engine* h, int32_t* mode);
  * without a request keeps the k of the last request written there (0 if none, and 0 everywhere while the mode has never been on).  Available and
  * refused where gaz_engine_read_batch is (game groups: refused). */
 int gaz_engine_read_batch_symmetry(gaz_engine* h, uint8_t* sym);
+
+/* Solver (MCTS-Solver): proven wins, draws and losses in the PUCT search.  mode 0 = off (the state of a new engine), 1 = on; any other value
+ * is refused.  It takes effect at the next launch; statuses are written and used only while it is on.  Refused — each with its own last_error
+ * text — on engines with the Gumbel search, with leaf_batch > 1 and with gumbel_batch > 1.  No struct changes and GAZ_ENGINE_ABI_VERSION stays
+ * 10: the feature is detected by its symbols.  With the mode on the search is a different, deterministic one; while it has never been on, every
+ * launched kernel is the one of an engine without the feature.
+ * A node may carry a STATUS for the player to move there: WIN (+1), DRAW (0), LOSS (-1), or none.  The EDGE VALUE e(Y, s) of child slot s of
+ * node Y, for Y's mover: +1 for a winning terminal move (edge code -3), 0 for a drawing one (-2), -status(X) for an expanded child X with a
+ * status, unknown otherwise.
+ *   1. Sources.  A terminal parent (root or not) is a WIN if one of its children is a winning move, else a DRAW — in these games a drawing move
+ *      exists only when it is the only legal move, so nothing legal was dropped.  That status is derived from the record, never stored: it holds
+ *      for terminal parents made while the solver was off.
+ *   2. Propagation starts only when an expansion has just created a terminal parent below (Y, s), after that creation's ordinary backup: along
+ *      the simulation's own path from its deepest node up to the root, a node Y without a status becomes a WIN if some edge is +1; else, if all
+ *      its n_actions children are expanded and every edge value is known, a DRAW if some edge is 0, else a LOSS; otherwise the walk stops.  A newly
+ *      proven Y is written and the walk goes on to its parent.
+ *   3. Selection leaves slots whose edge value is -1 out of the PUCT argmax (the score is unchanged, the first un-popped slot still wins among
+ *      the un-popped ones).  If the chosen slot has a known edge value the simulation ends there as a PROVEN HIT: the path includes that edge, the
+ *      edge value is backed up with one visit in the sign convention of a terminal-leaf hit, no random variate is drawn, and it counts as an
+ *      evaluation-free simulation.  A non-root terminal parent is thus never entered.  With forced playouts a -1 slot is never owed.  (Only edge
+ *      value 0 can be met this way in a tree searched with the solver on throughout.  Under terminal parents made while it was off a known +1 or -1
+ *      edge can be chosen as well — it is backed up the same way —, and a node all of whose slots are left out takes slot 0.)
+ *   4. A move also ends as soon as the root has a status and every root child has a visit; that may hold when the move begins (a re-rooted
+ *      proven subtree, a terminal-parent root): the move then runs 0 simulations.
+ *   5. Move and policy row.  Candidate slots C: root WIN — the slots with e = +1; DRAW — those with e = 0; LOSS — all; no status — those with
+ *      e != -1 and N > 0 (all slots if there are none).  The policy row is the counts it would be without the solver (N, or the pruned counts of
+ *      a forced-playouts move) restricted to C: f32(n_i / sum over C) on C, 0 elsewhere; left as it was if that sum is 0.  Root WIN or DRAW: the
+ *      move is the slot of C with the most visits, lowest slot on ties, whatever tau says; otherwise the tau-0 argmax / tau sampling runs with the
+ *      weights of slots outside C set to 0.  The move variate is drawn and the event counter advances as without the solver.  q is the exact
+ *      +1 / 0 / -1 as f32 when the root has a status, else W / N of the chosen child.  Root N / W / P rows, root_visits and evals stay raw
+ *      (gaz_engine_get_root_stats' out_policy and out_q follow this rule).  Such a ply's move_kind has 0x40 set.
+ *   6. Proofs are about the game's rules; max_actions is no part of them.  Statuses live in the tree: they survive re-rooting and compaction and
+ *      die with create_new_root; the two trees of a game prove independently.
+ * Follow-up, refused today: the Gumbel search, leaf_batch > 1, gumbel_batch > 1. */
+int gaz_engine_set_solver(gaz_engine* h, int32_t mode);
+int gaz_engine_get_solver(gaz_engine* h, int32_t* mode);
+/* a host synchronisation point; summed over game groups, over the engine's life: [0] nodes proven by propagation (terminal parents not counted),
+ * [1] proven hits, [2] moves that ended with a proven root, [3] simulations those moves did not run (iteration limit - simulations done),
+ * [4] / [5] / [6] of [2]: root WIN / DRAW / LOSS, [7] descent levels at which at least one slot was left out.  All 0 while never switched on. */
+int gaz_engine_get_solver_stats(gaz_engine* h, uint64_t out[8]);
 
 /* place one slot at the position reached by `n` actions from the empty board (new roots are built there).  The game keeps its
  * game_seq, the next player follows from the parity of n, both trees start fresh (event counter 0), and the tau schedule, the
@@ -413,7 +456,9 @@ typedef struct {                  /* 48 bytes */
     int32_t n_actions;            /* len(child_visits) */
     int32_t n_children;           /* PUCT: len(children), the expanded prefix of the slots.  Gumbel search: the count of a terminal parent, else 0
                                      (children are expanded in any order there; an edge's `child` says whether it is) */
-    int32_t flags;                /* bit 0: terminal parent — every child ends the game (edge codes -2 / -3) */
+    int32_t flags;                /* bit 0: terminal parent — every child ends the game (edge codes -2 / -3); bits 1-2: the status the solver proved
+                                     for the player to move here (gaz_engine_set_solver): 0 unknown, 1 win, 2 draw, 3 loss.  A terminal parent's
+                                     status is not stored: it is a win if one of its edges is -3, else a draw */
     int32_t n_reserved;           /* leaf_batch > 1: children reserved and not yet applied (leaves in flight), slots [n_children, n_children + n_reserved) */
     int32_t player;               /* current_player: who moved into this position (-1 / 1) */
     int32_t action;               /* action_history[-1] as an action index (0 at the empty board) */
