@@ -202,12 +202,14 @@ def test_evaluation_cache_changes_nothing_but_the_wave_count(game, search, iters
     eng_a.close(); eng_b.close()
 
 
-def _repack_run(lib_path, oracle, game, G, budget, iters, max_actions, search_kw, oracle_fn):
+def _repack_run(lib_path, oracle, game, G, budget, iters, max_actions, search_kw, oracle_fn, prepare=None):
     """continuous self-play with a games_budget; whenever half of the covered slots have halted the live games are moved together
-    (gaz_engine_repack) — every admitted game must still come out equal to the oracle's"""
+    (gaz_engine_repack) — every admitted game must still come out equal to the oracle's.  prepare(engine): called before the first launch"""
     from grok_alpha_zero_amd.engine import SelfPlayEngine
     eng = SelfPlayEngine(game, G, iters, max_actions, 4, 3, 2.5, 0.5, seed=13, hash_salt=6, slot_offset=200, ring_capacity=4 * G,
                          games_budget=budget, lib_path=lib_path, **search_kw)
+    if prepare:
+        prepare(eng)
     recs, launch, repacks = [], G, 0
     for _ in range(100000):
         eng.run_waves(16)
