@@ -107,11 +107,11 @@ template <class G> GAZ_KERNEL k_cache_insert(DevParams<G> E, int g0, int g1) {
 // sqrt(pv) and the exploration factor of every parent visit count below PUCT_TABLE_N, computed by the code the kernel would run
 template <int UNUSED> GAZ_KERNEL_WIDE k_init_puct_table(double* table, double c_init, double c_base, int n) {
 #ifdef GAZ_HOST_EMU
-    for (int i = 0; i < n; ++i) { table[2 * i] = dsqrt((double)i); table[2 * i + 1] = puct_c_of((double)i, c_init, c_base); }
+    const int i = block_id();
 #else
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { table[2 * i] = dsqrt((double)i); table[2 * i + 1] = puct_c_of((double)i, c_init, c_base); }
 #endif
+    if (i < n) { table[2 * i] = dsqrt((double)i); table[2 * i + 1] = puct_c_of((double)i, c_init, c_base); }
 }
 
 template <class G> GAZ_KERNEL k_init_games(DevParams<G> E, int first_seq) {
@@ -423,6 +423,68 @@ struct CallScratch {
     template <class T> T* get(size_t n) { void* q = nullptr; if (hipMalloc(&q, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr; p.push_back(q); return (T*)q; }
 };
 
+// ------------------------------------------------------------------------------------------ config
+// why k game groups cannot be made of this config (nullptr: they can)
+static const char* group_fault(const gaz_engine_config& c, int k) {
+    if (k < 2 || k > c.n_games) return "game_groups must be in [1, n_games]";
+    if (c.sync_moves || c.evaluator == GAZ_EVAL_EXTERNAL) return "game_groups > 1 needs continuous self-play (sync_moves = 0) with a built-in evaluator";
+    if (c.games_budget > 0 && c.games_budget < c.n_games) return "game_groups > 1 with a games_budget below n_games: a group could be left without a game (use game_groups = 1)";
+    return nullptr;
+}
+
+// every refusal of a config that needs no device state, first fault first ("" = none), for an engine of `groups` game groups: one group is the
+// engine itself; a GroupEngine checks what it needs to split the games, and each group's own config is checked when that group is made
+static std::string config_fault(const gaz_engine_config& c, int groups) {
+    if (c.game_groups < 0) return "game_groups must be >= 0";
+    if (c.gumbel_batch < 0 || c.gumbel_batch > 64) return "gumbel_batch must be in [0, 64] (0 and 1 = one candidate of sequential halving per game and wave)";
+    if (c.gumbel_batch > 1) {                     // the chunk step exists for the Gumbel search with one batch and no evaluation cache
+        if (c.leaf_batch > 1) return "gumbel_batch > 1 cannot be combined with leaf_batch > 1";
+        if (c.search != GAZ_SEARCH_GUMBEL) return "gumbel_batch > 1 needs search = GAZ_SEARCH_GUMBEL (the PUCT search has leaf_batch)";
+        if (c.eval_cache_log2 > 0) return "gumbel_batch > 1 cannot be combined with eval_cache_log2 > 0";
+        if (c.game_groups > 1) return "gumbel_batch > 1 cannot be combined with game_groups > 1";
+    }
+    if (c.leaf_batch < 0 || c.leaf_batch > 64) return "leaf_batch must be in [0, 64] (0 and 1 = one leaf per game and wave)";
+    if (c.leaf_batch > 1) {                       // the K-leaf step exists for the PUCT search with one batch and no evaluation cache
+        if (c.search == GAZ_SEARCH_GUMBEL) return "leaf_batch > 1 needs search = GAZ_SEARCH_PUCT (the Gumbel search plans its simulations itself)";
+        if (c.eval_cache_log2 > 0) return "leaf_batch > 1 cannot be combined with eval_cache_log2 > 0";
+        if (c.game_groups > 1) return "leaf_batch > 1 cannot be combined with game_groups > 1";
+    }
+    // playout cap randomisation: fast_iterations = 0 is off (and then takes no probability), else a fast limit in [1, run_iterations] and p in (0, 1]
+    if (c.fast_iterations < 0) return "fast_iterations must be >= 0 (0 = no playout cap), not " + std::to_string(c.fast_iterations);
+    if (c.fast_iterations > c.run_iterations) return "fast_iterations (" + std::to_string(c.fast_iterations) + ") must not exceed run_iterations (" + std::to_string(c.run_iterations) + ")";
+    if (c.fast_iterations > 0 && !(c.full_search_prob > 0.0 && c.full_search_prob <= 1.0)) return "full_search_prob must be in (0, 1] with fast_iterations > 0, not " + std::to_string(c.full_search_prob);
+    if (c.fast_iterations == 0 && !(c.full_search_prob == 0.0)) return "full_search_prob must be 0 with fast_iterations = 0 (the playout cap is off)";
+    if (c.fast_iterations > 0 && c.move_time_limit > 0.0) return "fast_iterations > 0 cannot be combined with move_time_limit > 0 (a timed move has no iteration cap to randomise)";
+    // forced playouts + policy target pruning: k = 0 is off, else a finite k > 0 on a PUCT root
+    if (c.forced_playouts_k != c.forced_playouts_k) return "forced_playouts_k must be a number (0 = no forced playouts), not NaN";
+    if (c.forced_playouts_k < 0.0) return "forced_playouts_k must be >= 0 (0 = no forced playouts), not " + std::to_string(c.forced_playouts_k);
+    if (c.forced_playouts_k > 1.7976931348623157e308) return "forced_playouts_k must be finite (KataGo uses 2), not infinity";
+    if (c.forced_playouts_k > 0.0 && c.search == GAZ_SEARCH_GUMBEL) return "forced_playouts_k > 0 cannot be combined with search = GAZ_SEARCH_GUMBEL (sequential halving has no PUCT root to force playouts at)";
+    if (groups > 1) { const char* g = group_fault(c, groups); return g ? g : ""; }
+    int max_t = 0, n_act = 0;
+    switch (c.game) {
+        case GAZ_GAME_TICTACTOE: max_t = Game<GAME_TTT>::MAXT; n_act = Game<GAME_TTT>::A; break;
+        case GAZ_GAME_CONNECT4: max_t = Game<GAME_C4>::MAXT; n_act = Game<GAME_C4>::A; break;
+        case GAZ_GAME_GOMOKU: max_t = Game<GAME_GMK>::MAXT; n_act = Game<GAME_GMK>::A; break;
+        default: return "unknown game id";
+    }
+    if (c.n_games <= 0) return "n_games must be positive";
+    if (c.search != GAZ_SEARCH_PUCT && c.search != GAZ_SEARCH_GUMBEL) return "unknown search id";
+    if (c.search == GAZ_SEARCH_GUMBEL && (c.gumbel_m < 2 || c.run_iterations < 1)) return "Gumbel search needs m >= 2 and run_iterations >= 1";
+    if (c.max_actions > max_t || c.max_actions <= 0) return "max_actions out of range for this game";
+    if (!(c.move_time_limit >= 0.0) || c.move_time_limit > 1e6) return "move_time_limit must be in [0, 1e6] seconds";
+    if (c.move_time_limit > 0.0 && c.sync_moves) return "move_time_limit is for continuous self-play; the per-move API has gaz_engine_stop_search";
+    if (c.games_budget < 0) return "games_budget must be >= 0";
+    if (c.games_budget > 0 && c.sync_moves) return "games_budget needs continuous self-play (sync_moves = 0)";
+    if (c.n_opening < 0 || c.n_opening > 8) return "at most 8 opening_actions";
+    for (int i = 0; i < c.n_opening; ++i) if (c.opening_actions[i] < 0 || c.opening_actions[i] >= n_act) return "opening action out of range";
+    if (c.eval_cache_log2 < 0 || c.eval_cache_log2 > 28) return "eval_cache_log2 out of range (0 = off, at most 28)";
+    return "";
+}
+
+// an event that lives for one call (gaz_engine_evaluate), whichever way the call returns
+struct CallEvent { hipEvent_t e = 0; bool ok; CallEvent() : ok(hipEventCreate(&e) == hipSuccess) {} ~CallEvent() { if (ok) hipEventDestroy(e); } };
+
 template <class G> struct EngineT : gaz_engine {
     using RL = RecLayout<G>;
     DevParams<G> E;
@@ -476,53 +538,44 @@ template <class G> struct EngineT : gaz_engine {
         hipStreamDestroy(stream);
     }
 
+    // nodes per tree that `it` iterations per move (and Gumbel's m) need when nodes_per_tree is left to the engine: what init() sizes the arena
+    // from, and what set_hyperparams() holds later values against
+    long long nodes_needed(int it, int m) const {
+        const long long its = it < 3 * G::A ? 3 * G::A : it;
+        if (cfg.search == GAZ_SEARCH_GUMBEL) return 2LL * (it + m) + 3 * G::A + 64;      // fresh tree every move
+        if (E.compact) return 4 * its + 3 * G::A + 64;      // per half: kept subtree + one run; generous bound, ERR_ARENA_FULL if a game exceeds it
+        return (long long)((cfg.max_actions + 1) / 2 + 1) * (its + 2) + 64;      // a tree lives for the whole game and gains <= 1 record per simulation of its own moves
+    }
+
     int init() override {
         HIP_OK(hipSetDevice(cfg.device));
         HIP_OK(hipStreamCreate(&stream));
         memset(&E, 0, sizeof(E));
-        const int n = cfg.n_games;
-        if (n <= 0) return fail("n_games must be positive");
+        const int n = cfg.n_games;               // (the config has passed config_fault)
         const bool gumbel = cfg.search == GAZ_SEARCH_GUMBEL;
-        if (cfg.search != GAZ_SEARCH_PUCT && !gumbel) return fail("unknown search id");
         E.c_visit = cfg.c_visit; E.c_scale = cfg.c_scale; E.gumbel_m = cfg.gumbel_m; E.g_stablemax = cfg.gumbel_stablemax; E.fast_find_win = cfg.fast_find_win;
-        if (gumbel && (cfg.gumbel_m < 2 || cfg.run_iterations < 1)) return fail("Gumbel search needs m >= 2 and run_iterations >= 1");
         E.node_bytes = gumbel ? gumbel_node_bytes<G>() : NodeLayout<G>::SIZE;
         // re-root compaction: needed where a whole-game arena does not fit (Gomoku: 4.2 KB records); 0 = auto
         E.compact = gumbel ? 0 : (cfg.compact_trees == 0 ? (G::ID == GAME_GMK ? 1 : 0) : (cfg.compact_trees > 0 ? 1 : 0));
         gbk = gumbel && cfg.gumbel_batch > 1 ? cfg.gumbel_batch : 1;
         lbk = gbk > 1 ? gbk : (cfg.leaf_batch > 1 ? cfg.leaf_batch : 1); rows = (size_t)n * lbk;
         E.n_games = n; n_eff = n; E.run_iterations = cfg.run_iterations; E.max_actions = cfg.max_actions;
-        if (cfg.max_actions > G::MAXT || cfg.max_actions <= 0) return fail("max_actions out of range for this game");
         E.explore_first = cfg.num_explore_actions_first; E.explore_second = cfg.num_explore_actions_second;
         E.create_new_root = cfg.create_new_root; E.sync_moves = cfg.sync_moves; E.use_dirichlet = cfg.use_dirichlet;
         int npt = cfg.nodes_per_tree;
-        if (npt <= 0 && gumbel) npt = 2 * ((cfg.move_time_limit > 0.0 && 3 * G::A > cfg.run_iterations ? 3 * G::A : cfg.run_iterations) + cfg.gumbel_m) + 3 * G::A + 64;   // fresh tree every move
-        if (npt <= 0 && E.compact) {   // per half: kept subtree + one run; generous bound, ERR_ARENA_FULL if a game exceeds it
-            const int its = cfg.run_iterations < 3 * G::A ? 3 * G::A : cfg.run_iterations;
-            npt = 4 * its + 3 * G::A + 64 + (lbk > 1 ? lbk : 0);
-        }
-        if (npt <= 0) {   // a tree lives for the whole game and gains <= 1 record per simulation of its own moves
-            const int own_moves = (cfg.max_actions + 1) / 2 + 1;
-            int its = cfg.run_iterations < 3 * G::A ? 3 * G::A : cfg.run_iterations;
-            npt = own_moves * (its + 2) + 64 + (lbk > 1 ? lbk : 0);
+        if (npt <= 0) {   // on top of nodes_needed: a timed Gumbel move may run 3 A iterations; the K leaves a PUCT tree holds in flight
+            const bool timed = gumbel && cfg.move_time_limit > 0.0 && 3 * G::A > cfg.run_iterations;
+            npt = (int)nodes_needed(timed ? 3 * G::A : cfg.run_iterations, cfg.gumbel_m) + (!gumbel && lbk > 1 ? lbk : 0);
         }
         E.nodes_per_tree = npt;
         E.ring_cap = cfg.ring_capacity; E.single_tree = cfg.single_tree;
         E.tau = norm_tau(cfg.tau); E.no_gumbel_noise = cfg.no_gumbel_noise; E.first_game_seq = cfg.first_game_seq;
-        if (!(cfg.move_time_limit >= 0.0) || cfg.move_time_limit > 1e6) return fail("move_time_limit must be in [0, 1e6] seconds");
-        if (cfg.move_time_limit > 0.0 && cfg.sync_moves) return fail("move_time_limit is for continuous self-play; the per-move API has gaz_engine_stop_search");
         E.move_time_ticks = cfg.move_time_limit > 0.0 ? (uint64_t)(cfg.move_time_limit * 1e8) + 1 : 0;
-        E.fast_iterations = cfg.fast_iterations; E.full_search_prob = cfg.full_search_prob;      // (checked by gaz_engine_create)
-        E.forced_playouts_k = cfg.forced_playouts_k;                                              // (likewise)
-        if (cfg.games_budget < 0) return fail("games_budget must be >= 0");
-        if (cfg.games_budget > 0 && cfg.sync_moves) return fail("games_budget needs continuous self-play (sync_moves = 0)");
+        E.fast_iterations = cfg.fast_iterations; E.full_search_prob = cfg.full_search_prob;
+        E.forced_playouts_k = cfg.forced_playouts_k;
         E.games_budget = cfg.games_budget;
-        if (cfg.n_opening < 0 || cfg.n_opening > 8) return fail("at most 8 opening_actions");
         E.n_opening = cfg.n_opening;
-        for (int i = 0; i < cfg.n_opening; ++i) {
-            if (cfg.opening_actions[i] < 0 || cfg.opening_actions[i] >= G::A) return fail("opening action out of range");
-            E.opening_actions[i] = cfg.opening_actions[i]; E.opening_weights[i] = cfg.opening_weights[i];
-        }
+        for (int i = 0; i < cfg.n_opening; ++i) { E.opening_actions[i] = cfg.opening_actions[i]; E.opening_weights[i] = cfg.opening_weights[i]; }
         // measured: 32 -> 4 cuts the kernel tail 0.167 -> 0.067 ms; with the evaluation cache a hit is such a simulation too and 8 pays
         // (small boards; a Gomoku simulation is ten times as long and 8 only stretches the launch)
         // (round 2) with the fused tree + trunk launch the tail of the tree step hides behind the trunk: 12 pays there (69.6 k vs 67.9 k)
@@ -557,14 +610,13 @@ template <class G> struct EngineT : gaz_engine {
         // behind the value rows, in the same allocation: one symmetry byte per batch row (DevParams::row_sym()), zeroed = the identity
         E.row_sym_off = (uint32_t)((rows + 64) * sizeof(float));
         if (dalloc(&E.nn_value, rows + 64 + (rows + 64 + 3) / 4)) return 1;
-        if (cfg.eval_cache_log2 < 0 || cfg.eval_cache_log2 > 28) return fail("eval_cache_log2 out of range (0 = off, at most 28)");
         if (cfg.eval_cache_log2 > 0) {
             const size_t slots = (size_t)1 << cfg.eval_cache_log2;
             E.cache_stride = CacheLayout<G>::SIZE; E.cache_mask = (uint32_t)(slots - 1); E.cache_epoch = 1;
             if (dalloc(&E.cache, slots * (size_t)E.cache_stride)) return 1;      // zeroed: tag 0 never matches (tags are odd)
             if (dalloc(&E.cache_lock, slots)) return 1;
         }
-        if (getenv("GAZ_TREE_PROF") && atoi(getenv("GAZ_TREE_PROF"))) { if (dalloc(&E.prof, (size_t)n * 8)) return 1; }
+        if (env_on("GAZ_TREE_PROF", false)) { if (dalloc(&E.prof, (size_t)n * 8)) return 1; }
         if (!gumbel) {
             double* tb = nullptr;
             if (dalloc(&tb, (size_t)2 * PUCT_TABLE_N)) return 1;
@@ -624,7 +676,7 @@ template <class G> struct EngineT : gaz_engine {
         return 0;
     }
 
-    hipEvent_t new_event() { hipEvent_t e; hipEventCreate(&e); ev.push_back(e); return e; }
+    int new_event(hipEvent_t* e) { HIP_OK(hipEventCreate(e)); ev.push_back(*e); return 0; }
     static constexpr size_t MAX_TIMING_EVENTS = 1 << 16;            // a timed run of any length holds at most this many events
 
     // every tree launch carries the wave's epoch, and the marks of the previous wave's evaluator pass if that pass made any (a fused launch, or
@@ -656,7 +708,7 @@ template <class G> struct EngineT : gaz_engine {
             return;
         }
         if (cfg.search == GAZ_SEARCH_GUMBEL) {
-            static const int gteams_env = getenv("GAZ_TREE_TEAMS") ? atoi(getenv("GAZ_TREE_TEAMS")) : -1;
+            static const int gteams_env = env_int("GAZ_TREE_TEAMS", -1);
             constexpr int GPER = WAVE / GP::TEAM;
             // measured (8192 Connect4 games, n = 32, m = 7): the team build is bit-exact but SLOWER, 225 vs 185 us per launch (sequential
             // halving keeps the four games of a wave in different phases) — opt-in only (GAZ_TREE_TEAMS=1)
@@ -667,7 +719,7 @@ template <class G> struct EngineT : gaz_engine {
         }
         // measured (4096 Connect4 games): 66 vs 71 us per launch; with the evaluation cache (up to 8 evaluation-free simulations per
         // game and launch, and a wave is as slow as its slowest team) one game per wave stays faster: 60.1 k vs 56.2 k positions/s
-        static const int teams_env = getenv("GAZ_TREE_TEAMS") ? atoi(getenv("GAZ_TREE_TEAMS")) : -1;
+        static const int teams_env = env_int("GAZ_TREE_TEAMS", -1);
         const bool teams = teams_env >= 0 ? teams_env != 0 : E.cache == nullptr;
         constexpr int PER = WAVE / GP::TEAM;
         if (PER > 1 && teams) GAZ_LAUNCH(k_wave_teams<GP>, (g1 - g0 + PER - 1) / PER, WAVE, st, *reinterpret_cast<const DevParams<GP>*>(&E), g0, g1);
@@ -710,21 +762,21 @@ template <class G> struct EngineT : gaz_engine {
         if (fuse_state >= 0) return fuse_state == 1;
         fuse_state = 0;
         if (lbk > 1) return false;                   // K rows per game: the one-launch form hands over one row per game
-        static const bool off = getenv("GAZ_FUSE_WAVE") && atoi(getenv("GAZ_FUSE_WAVE")) == 0;
+        static const bool off = !env_on("GAZ_FUSE_WAVE", true);
         typedef typename PuctVariant<G>::type GP;
         // with the evaluation cache too (measured 67.5 k vs 64.3 k positions/s): a team's probe reads its OWN row, and the table is
         // written by k_cache_insert between launches as before.  GAZ_FUSE_CACHE=0 -> separate launches when the cache is on
-        static const bool with_cache = !(getenv("GAZ_FUSE_CACHE") && atoi(getenv("GAZ_FUSE_CACHE")) == 0);
+        static const bool with_cache = env_on("GAZ_FUSE_CACHE", true);
         const bool gumbel = cfg.search == GAZ_SEARCH_GUMBEL;
         // round 3: Gomoku's PUCT search as well (one game per wavefront; compacting trees are fine: a game's state lives in HBM either way).  GAZ_FUSE_GOMOKU=0 -> separate
-        const bool gmk = G::ID == GAME_GMK && !gumbel && !E.cache && !(getenv("GAZ_FUSE_GOMOKU") && atoi(getenv("GAZ_FUSE_GOMOKU")) == 0);
+        const bool gmk = G::ID == GAME_GMK && !gumbel && !E.cache && env_on("GAZ_FUSE_GOMOKU", true);
         const bool c4 = G::ID == GAME_C4 && WAVE / GP::TEAM >= 4 && !E.compact && !(E.cache && !with_cache);
         if (off || !(c4 || gmk) || !eval || !eval->supports_split()) return false;
         // round 3: the Gumbel search too (BASELINE configs[4]; its tree step is 17 % of a wave when launched separately).  GAZ_FUSE_GUMBEL=0 -> separate
-        if (gumbel && ((getenv("GAZ_FUSE_GUMBEL") && atoi(getenv("GAZ_FUSE_GUMBEL")) == 0) || E.cache)) return false;
-        if (!gumbel && getenv("GAZ_TREE_TEAMS") && atoi(getenv("GAZ_TREE_TEAMS")) == 0) return false;
+        if (gumbel && (!env_on("GAZ_FUSE_GUMBEL", true) || E.cache)) return false;
+        if (!gumbel && !env_on("GAZ_TREE_TEAMS", true)) return false;
         if (dalloc(&d_done, (size_t)E.n_games) || !ensure_skip_buffers()) return false;
-        if (!(getenv("GAZ_FUSE_QUEUE") && atoi(getenv("GAZ_FUSE_QUEUE")) == 0) && dalloc(&d_queue, (size_t)E.n_games + 64)) return false;
+        if (env_on("GAZ_FUSE_QUEUE", true) && dalloc(&d_queue, (size_t)E.n_games + 64)) return false;
         fuse_state = 1;
         return true;
     }
@@ -754,8 +806,7 @@ template <class G> struct EngineT : gaz_engine {
         if (E.sync_moves) return fail("repack needs continuous self-play (sync_moves = 0)");
         if (gbk > 1) return fail("repack: not with gumbel_batch > 1 (a game owns gumbel_batch rows of the batch)");
         if (lbk > 1) return fail("repack: not with leaf_batch > 1 (a game owns leaf_batch rows of the batch)");
-        HIP_OK(hipStreamSynchronize(stream));
-        if (pipeline_ready) { HIP_OK(hipStreamSynchronize(tstream)); HIP_OK(hipStreamSynchronize(hstream)); }
+        if (quiesce()) return 1;
         GAZ_LAUNCH(k_gather_root<G>, E.n_games, WAVE, stream, E, dN, dW, dP, dPol, dRV, dQ, dChosen, dPhase, dPending);
         std::vector<int32_t> ph(E.n_games);
         HIP_OK(hipMemcpyAsync(ph.data(), dPhase, (size_t)E.n_games * 4, hipMemcpyDeviceToHost, stream));
@@ -778,13 +829,8 @@ template <class G> struct EngineT : gaz_engine {
             HIP_OK(hipMemcpyAsync(dMoveList, mv.data(), mv.size() * 4, hipMemcpyHostToDevice, stream));
             const size_t slot_bytes = (size_t)2 * (E.compact ? 2 : 1) * (size_t)E.nodes_per_tree * (size_t)E.node_bytes;
             const size_t gbytes = cfg.search == GAZ_SEARCH_GUMBEL ? sizeof(GumbelState<G>) : 0;
-#ifdef GAZ_HOST_EMU
             DevParams<G> Em = E; Em.eval_done = d_evaldone;              // a game's "evaluated last wave" mark travels with it
-            GAZ_LAUNCH(k_move_slots<G>, (int)(mv.size() / 2), 1, stream, Em, (const int32_t*)dMoveList, (int)(mv.size() / 2), slot_bytes, gbytes);
-#else
-            DevParams<G> Em = E; Em.eval_done = d_evaldone;              // a game's "evaluated last wave" mark travels with it
-            GAZ_LAUNCH(k_move_slots<G>, (int)(mv.size() / 2), 256, stream, Em, (const int32_t*)dMoveList, (int)(mv.size() / 2), slot_bytes, gbytes);
-#endif
+            GAZ_LAUNCH(k_move_slots<G>, (int)(mv.size() / 2), 256, stream, Em, (const int32_t*)dMoveList, (int)(mv.size() / 2), slot_bytes, gbytes);   // one block per move
             HIP_OK(hipGetLastError());
             HIP_OK(hipStreamSynchronize(stream));
         }
@@ -793,66 +839,64 @@ template <class G> struct EngineT : gaz_engine {
         return 0;
     }
 
+    // the wave as ONE launch, tree blocks and trunk workgroups together; -1: not this wave (no plan or no kernel for this trunk variant), nothing was launched
+    int fused_wave(bool timing, hipEvent_t e0, hipEvent_t e1, hipEvent_t e2) {
+        // diagnostic: GAZ_FUSED_STAMPS=<file>[:n] -> wall-clock stamps of every block of the n-th fused launch (tools/fused_timeline.py)
+        static const char* stamp_spec = getenv("GAZ_FUSED_STAMPS");
+        static const long stamp_at = stamp_spec && strchr(stamp_spec, ':') ? atol(strchr(stamp_spec, ':') + 1) : 3000;
+        unsigned long long* d_stamps = nullptr;
+        const size_t stamp_blocks = (size_t)n_eff + 4096;              // >= tree blocks + trunk workgroups
+        if (stamp_spec && n_waves_total == stamp_at && hipMalloc((void**)&d_stamps, stamp_blocks * 128 * 8) == hipSuccess) hipMemsetAsync(d_stamps, 0, stamp_blocks * 128 * 8, stream);
+        const FuseHandoff ho{d_done, fuse_epoch + 1, d_evaldone, d_fault, SPIN_TICKS, debug_fault_mod, d_stamps, d_queue};
+        const void* plan = eval->trunk_plan(E.nn_in, n_eff, 0, ho);
+        if (!plan) return -1;
+        if (timing) hipEventRecord(e0, stream);
+        DevParams<G> Ef = wave_params(); Ef.done_flag = d_done;
+        if (eval->plan_uses_queue(plan)) {   // the trunk workgroups take queue entries: the tree blocks rank their games as they finish
+            typedef typename PuctVariant<G>::type GPq;
+            static const bool gumbel_teams = env_on("GAZ_FUSE_GUMBEL_TEAMS", true);
+            // games per tree block = rounds x (4 waves x games per wavefront); rounds: measured, see DESIGN (GAZ_FUSE_TREE_ROUNDS overrides)
+            static const int rounds_env = env_int("GAZ_FUSE_TREE_ROUNDS", 0);
+            // measured on one box (tools/sweep_rounds.sh): PUCT 1 round 56.6 k positions/s, 2 rounds 54.6 k, 4: 53.8 k; Gumbel (8192 games: every slot
+            // starts as a tree block) 1: 314 k, 2: 319 k, 4: 321 k, 8: 317 k
+            // Gomoku as one of two game groups (tools/sweep_groups5.sh): 2: 2372, 3: 2372, 4: 2384, 6: 2357, 8: 2330 positions/s
+            // Gumbel as one of two game groups of 4096 (tools/sweep_groups6.sh, sweep_groups7.sh, one box): 1: 341.3 k, 2: 344.2 k, 4: 321.4 k, 8: 247.5 k (one batch: 323.9 k)
+            const int rounds = rounds_env > 0 ? rounds_env : (G::ID == GAME_GMK ? (this->grouped > 1 ? 4 : 8) : (cfg.search == GAZ_SEARCH_GUMBEL ? (this->grouped > 1 ? 2 : 4) : 1));
+            const int gpb = G::ID == GAME_GMK ? rounds * 8 : rounds * 4 * ((cfg.search == GAZ_SEARCH_GUMBEL && !gumbel_teams) ? 1 : WAVE / GPq::TEAM);
+            Ef.done_queue = d_queue; Ef.queue_gpb = gpb; Ef.queue_nfull = n_eff / gpb; Ef.queue_rem = n_eff % gpb;
+        }
+        Ef.handoff_release = G::ID == GAME_GMK;
+        const bool launched = G::ID == GAME_GMK ? launch_wave_trunk_gmk(stream, &Ef, 0, n_eff, plan)
+                            : cfg.search == GAZ_SEARCH_GUMBEL ? launch_wave_trunk_c4_gumbel(stream, &Ef, 0, n_eff, plan) : launch_wave_trunk_c4(stream, &Ef, 0, n_eff, plan);
+        if (!launched) { fuse_state = 0; --fuse_epoch; return -1; }      // no fused kernel for this trunk variant: separate launches, for good
+        prev_marked = true;                  // the trunk workgroups of this launch mark the boards they evaluate
+        if (d_stamps) {
+            std::vector<unsigned long long> hst(stamp_blocks * 128);
+            hipStreamSynchronize(stream);
+            hipMemcpy(hst.data(), d_stamps, hst.size() * 8, hipMemcpyDeviceToHost); hipFree(d_stamps);
+            std::string path(stamp_spec); if (path.find(':') != std::string::npos) path = path.substr(0, path.find(':'));
+            if (FILE* f = fopen(path.c_str(), "wb")) { fwrite(hst.data(), 8, hst.size(), f); fclose(f); }
+        }
+        if (timing) hipEventRecord(e1, stream);
+        eval->forward_heads(stream, E.nn_policy, E.nn_value, n_eff, 0);
+        if (E.cache) { Ef.eval_done = d_evaldone; GAZ_LAUNCH(k_cache_insert<G>, n_eff, WAVE, stream, Ef, 0, n_eff); E.cache_epoch++; }
+        if (timing) {       // the fused kernel is booked as evaluator time; tree time is what it hides
+            hipEventRecord(e2, stream); ev_eval.push_back({e0, e2}); n_waves_timed++;
+            ev_fused.push_back({e0, e1});
+        }
+        n_waves_total++;
+        return 0;
+    }
+
     int one_wave(bool with_eval) {
         ++waves_launched;
-        if (with_eval && eval && fuse_enabled && can_fuse()) {
-            const bool timing = this->timing && n_waves_total % TIMING_STRIDE == 0 && ev.size() + 4 <= MAX_TIMING_EVENTS;
-            // diagnostic: GAZ_FUSED_STAMPS=<file>[:n] -> wall-clock stamps of every block of the n-th fused launch (tools/fused_timeline.py)
-            static const char* stamp_spec = getenv("GAZ_FUSED_STAMPS");
-            static const long stamp_at = stamp_spec && strchr(stamp_spec, ':') ? atol(strchr(stamp_spec, ':') + 1) : 3000;
-            unsigned long long* d_stamps = nullptr;
-            const size_t stamp_blocks = (size_t)n_eff + 4096;              // >= tree blocks + trunk workgroups
-            if (stamp_spec && n_waves_total == stamp_at && hipMalloc((void**)&d_stamps, stamp_blocks * 128 * 8) == hipSuccess) hipMemsetAsync(d_stamps, 0, stamp_blocks * 128 * 8, stream);
-            const FuseHandoff ho{d_done, fuse_epoch + 1, d_evaldone, d_fault, SPIN_TICKS, debug_fault_mod, d_stamps, d_queue};
-            const void* plan = eval->trunk_plan(E.nn_in, n_eff, 0, ho);
-            if (plan) {
-                hipEvent_t e0 = 0, e1 = 0, e2 = 0;
-                if (timing) { e0 = new_event(); e1 = new_event(); e2 = new_event(); hipEventRecord(e0, stream); }
-                DevParams<G> Ef = wave_params(); Ef.done_flag = d_done;
-                if (eval->plan_uses_queue(plan)) {   // the trunk workgroups take queue entries: the tree blocks rank their games as they finish
-                    typedef typename PuctVariant<G>::type GPq;
-                    static const bool gumbel_teams = !(getenv("GAZ_FUSE_GUMBEL_TEAMS") && atoi(getenv("GAZ_FUSE_GUMBEL_TEAMS")) == 0);
-                    // games per tree block = rounds x (4 waves x games per wavefront); rounds: measured, see DESIGN (GAZ_FUSE_TREE_ROUNDS overrides)
-                    static const int rounds_env = getenv("GAZ_FUSE_TREE_ROUNDS") ? atoi(getenv("GAZ_FUSE_TREE_ROUNDS")) : 0;
-                    // measured on one box (tools/sweep_rounds.sh): PUCT 1 round 56.6 k positions/s, 2 rounds 54.6 k, 4: 53.8 k; Gumbel (8192 games: every slot
-                    // starts as a tree block) 1: 314 k, 2: 319 k, 4: 321 k, 8: 317 k
-                    // Gomoku as one of two game groups (tools/sweep_groups5.sh): 2: 2372, 3: 2372, 4: 2384, 6: 2357, 8: 2330 positions/s
-                    // Gumbel as one of two game groups of 4096 (tools/sweep_groups6.sh, sweep_groups7.sh, one box): 1: 341.3 k, 2: 344.2 k, 4: 321.4 k, 8: 247.5 k (one batch: 323.9 k)
-                    const int rounds = rounds_env > 0 ? rounds_env : (G::ID == GAME_GMK ? (this->grouped > 1 ? 4 : 8) : (cfg.search == GAZ_SEARCH_GUMBEL ? (this->grouped > 1 ? 2 : 4) : 1));
-                    const int gpb = G::ID == GAME_GMK ? rounds * 8 : rounds * 4 * ((cfg.search == GAZ_SEARCH_GUMBEL && !gumbel_teams) ? 1 : WAVE / GPq::TEAM);
-                    Ef.done_queue = d_queue; Ef.queue_gpb = gpb; Ef.queue_nfull = n_eff / gpb; Ef.queue_rem = n_eff % gpb;
-                }
-                Ef.handoff_release = G::ID == GAME_GMK;
-                const bool launched = G::ID == GAME_GMK ? launch_wave_trunk_gmk(stream, &Ef, 0, n_eff, plan)
-                                    : cfg.search == GAZ_SEARCH_GUMBEL ? launch_wave_trunk_c4_gumbel(stream, &Ef, 0, n_eff, plan) : launch_wave_trunk_c4(stream, &Ef, 0, n_eff, plan);
-                if (!launched) {                     // no fused kernel for this trunk variant: separate launches, for good
-                    fuse_state = 0; --fuse_epoch;
-                    return one_wave(with_eval);
-                }
-                prev_marked = true;                  // the trunk workgroups of this launch mark the boards they evaluate
-                if (d_stamps) {
-                    std::vector<unsigned long long> hst(stamp_blocks * 128);
-                    hipStreamSynchronize(stream);
-                    hipMemcpy(hst.data(), d_stamps, hst.size() * 8, hipMemcpyDeviceToHost); hipFree(d_stamps);
-                    std::string path(stamp_spec); if (path.find(':') != std::string::npos) path = path.substr(0, path.find(':'));
-                    if (FILE* f = fopen(path.c_str(), "wb")) { fwrite(hst.data(), 8, hst.size(), f); fclose(f); }
-                }
-                if (timing) hipEventRecord(e1, stream);
-                eval->forward_heads(stream, E.nn_policy, E.nn_value, n_eff, 0);
-                if (E.cache) { Ef.eval_done = d_evaldone; GAZ_LAUNCH(k_cache_insert<G>, n_eff, WAVE, stream, Ef, 0, n_eff); E.cache_epoch++; }
-                if (timing) {       // the fused kernel is booked as evaluator time; tree time is what it hides
-                    hipEventRecord(e2, stream); ev_eval.push_back({e0, e2}); n_waves_timed++;
-                    ev_fused.push_back({e0, e1});
-                }
-                n_waves_total++;
-                return 0;
-            }
-        }
         // timing brackets on every TIMING_STRIDE-th wave only: an event record is a barrier packet of its own (~5 us between two
         // kernels; five of them per wave were 4 % of the wave they measured)
         const bool timing = this->timing && n_waves_total % TIMING_STRIDE == 0 && ev.size() + 4 <= MAX_TIMING_EVENTS;
         hipEvent_t e0 = 0, e1 = 0, e2 = 0;
-        if (timing) { e0 = new_event(); e1 = new_event(); e2 = new_event(); hipEventRecord(e0, stream); }
+        if (timing && (new_event(&e0) || new_event(&e1) || new_event(&e2))) return 1;
+        if (with_eval && eval && fuse_enabled && can_fuse()) { const int rc = fused_wave(timing, e0, e1, e2); if (rc >= 0) return rc; }
+        if (timing) hipEventRecord(e0, stream);
         DevParams<G> P = wave_params();
         launch_wave(stream, 0, n_eff, P);
         prev_marked = false;                         // the separately launched evaluator pass covers every row
@@ -880,6 +924,8 @@ template <class G> struct EngineT : gaz_engine {
     int n_grp = 0, grp0[MAXGRP + 1] = {};
     hipEvent_t ev_tree_done[2][MAXGRP] = {}, ev_trunk_done[2][MAXGRP] = {}, ev_heads_done[2][MAXGRP] = {}, ev_join = 0;
     bool pipeline_ready = false;
+    // nothing of this engine is running or queued when this returns 0
+    int quiesce() { HIP_OK(hipStreamSynchronize(stream)); if (pipeline_ready) { HIP_OK(hipStreamSynchronize(tstream)); HIP_OK(hipStreamSynchronize(hstream)); } return 0; }
     bool can_pipeline() {
         static const char* spec = getenv("GAZ_PIPELINE");
         if (!spec || !*spec || atoi(spec) == 0) return false;
@@ -920,7 +966,7 @@ template <class G> struct EngineT : gaz_engine {
                 const int g0 = grp0[g], g1 = grp0[g + 1];
                 if (k > 0) hipStreamWaitEvent(tstream, ev_heads_done[prev][g], 0);      // this group's previous evaluation
                 hipEvent_t t0 = 0, t1 = 0;
-                if (timed) { t0 = new_event(); t1 = new_event(); hipEventRecord(t0, tstream); }
+                if (timed) { if (new_event(&t0) || new_event(&t1)) return 1; hipEventRecord(t0, tstream); }
                 launch_wave(tstream, g0, g1, P);
                 if (timed) { hipEventRecord(t1, tstream); ev_tree.push_back({t0, t1}); }
                 hipEventRecord(ev_tree_done[cur][g], tstream);
@@ -959,7 +1005,7 @@ template <class G> struct EngineT : gaz_engine {
         int32_t c[10];
         const int poll = lbk > 1 ? 4 : 16;           // a K-leaf move is a few dozen launches: look more often, every launch evaluates all rows
         for (int w = 0; w < max_waves + 16; w += poll) {
-            for (int i = 0; i < poll; ++i) one_wave(true);
+            for (int i = 0; i < poll; ++i) if (one_wave(true)) return 1;
             if (counts(c)) return 1;
             if (check_device_error()) return 1;
             if (c[0] == 0) break;
@@ -1003,12 +1049,12 @@ template <class G> struct EngineT : gaz_engine {
         if (!eval) return fail("run_waves needs a built-in evaluator");
         if (!eval->ready()) return fail("run_waves: evaluator weights not loaded (gaz_engine_load_weights)");
         if (can_pipeline()) return run_waves_pipelined(n);
-        for (int i = 0; i < n; ++i) one_wave(true);
+        for (int i = 0; i < n; ++i) if (one_wave(true)) return 1;
         HIP_OK(hipGetLastError());
         return 0;
     }
 
-    int wave_begin() override { one_wave(false); HIP_OK(hipGetLastError()); return 0; }
+    int wave_begin() override { if (one_wave(false)) return 1; HIP_OK(hipGetLastError()); return 0; }
     int wave_end() override { return 0; }   // the next wave_begin consumes the outputs; nothing to do here
 
     int batch_ptrs(void** a, void** b, void** c) override {
@@ -1044,15 +1090,16 @@ template <class G> struct EngineT : gaz_engine {
         if (!eval->ready()) return fail("evaluate: evaluator weights not loaded");
         if (n <= 0 || (size_t)n > rows) return fail("evaluate: n must be in [1, " + std::to_string(rows) + "] (the rows of the evaluator batch: n_games, or n_games * leaf_batch / gumbel_batch)");
         HIP_OK(hipMemcpyAsync(E.nn_in, in, (size_t)n * G::HW * G::C, hipMemcpyHostToDevice, stream));
-        hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+        CallEvent e0, e1;
+        if (!e0.ok || !e1.ok) return fail("evaluate: hipEventCreate failed");
         eval->forward(stream, E.nn_in, E.nn_policy, E.nn_value, n, false);      // warm-up / the measured result
-        hipEventRecord(e0, stream);
+        hipEventRecord(e0.e, stream);
         for (int r = 0; r < repeats; ++r) eval->forward(stream, E.nn_in, E.nn_policy, E.nn_value, n, false);
-        hipEventRecord(e1, stream);
+        hipEventRecord(e1.e, stream);
         HIP_OK(hipMemcpyAsync(pol, E.nn_policy, (size_t)n * G::A * 4, hipMemcpyDeviceToHost, stream));
         HIP_OK(hipMemcpyAsync(val, E.nn_value, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
         HIP_OK(hipStreamSynchronize(stream));
-        float t = 0; hipEventElapsedTime(&t, e0, e1); hipEventDestroy(e0); hipEventDestroy(e1);
+        float t = 0; hipEventElapsedTime(&t, e0.e, e1.e);
         if (ms) *ms = repeats > 0 ? (double)t / repeats : 0.0;
         HIP_OK(hipGetLastError());
         return 0;
@@ -1077,21 +1124,27 @@ template <class G> struct EngineT : gaz_engine {
         return 0;
     }
 
-    int drain(void* out, int max_records, int32_t* n_out) override {
-        *n_out = 0;
-        if (E.ring_cap <= 0) return 0;
+    // the two ends of a drain: the finished games waiting in the ring (the caller clamps the number to what it takes), then the n taken
+    int ring_begin(uint32_t* avail) {
         HIP_OK(hipStreamSynchronize(stream));
         if (poll_fuse_fault()) return 1;            // a host synchronisation point like the others: a caller that only ever drains must still get the fallback
         uint32_t head[2];
         HIP_OK(hipMemcpy(head, E.ring_head, sizeof(head), hipMemcpyDeviceToHost));
-        uint32_t avail = head[0] - ring_consumed;
+        *avail = head[0] - ring_consumed;
+        return 0;
+    }
+    int ring_commit(uint32_t n) { ring_consumed += n; HIP_OK(hipMemcpy(E.ring_head + 1, &ring_consumed, sizeof(uint32_t), hipMemcpyHostToDevice)); return 0; }
+    int drain(void* out, int max_records, int32_t* n_out) override {
+        *n_out = 0;
+        if (E.ring_cap <= 0) return 0;
+        uint32_t avail = 0;
+        if (ring_begin(&avail)) return 1;
         if ((int)avail > max_records) avail = (uint32_t)max_records;
         for (uint32_t i = 0; i < avail; ++i) {
             const uint32_t slot = (ring_consumed + i) % (uint32_t)E.ring_cap;
             HIP_OK(hipMemcpy((uint8_t*)out + (size_t)i * RL::SIZE, E.ring + (size_t)slot * RL::SIZE, RL::SIZE, hipMemcpyDeviceToHost));
         }
-        ring_consumed += avail;
-        HIP_OK(hipMemcpy(E.ring_head + 1, &ring_consumed, sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (ring_commit(avail)) return 1;
         *n_out = (int32_t)avail;
         return check_device_error();
     }
@@ -1124,12 +1177,7 @@ template <class G> struct EngineT : gaz_engine {
         }
         int32_t* d_plan = dPlan + (size_t)SAMPLE_HDR_INTS * E.ring_cap;
         HIP_OK(hipMemcpyAsync(d_plan, plan.data(), plan.size() * 4, hipMemcpyHostToDevice, stream));
-#ifdef GAZ_HOST_EMU
-        const int threads = 1;
-#else
-        const int threads = SAMPLES_THREADS;
-#endif
-        GAZ_LAUNCH(k_build_samples<G>, n, threads, stream, (const uint8_t*)E.ring, E.ring_cap, (const int32_t*)d_plan, n, (long long)R,
+        GAZ_LAUNCH(k_build_samples<G>, n, SAMPLES_THREADS, stream, (const uint8_t*)E.ring, E.ring_cap, (const int32_t*)d_plan, n, (long long)R,
                    reinterpret_cast<int8_t*>(dSamples), reinterpret_cast<float*>(dSamples + off_p), reinterpret_cast<float*>(dSamples + off_v));
         HIP_OK(hipGetLastError());
         HIP_OK(hipMemcpyAsync(hSamples, dSamples, off_v + (size_t)R * 4, hipMemcpyDeviceToHost, stream));
@@ -1145,20 +1193,13 @@ template <class G> struct EngineT : gaz_engine {
                       float* values, int32_t* n_games, int64_t* n_rows, int32_t* blocked_T) override {
         *n_games = 0; *n_rows = 0; *blocked_T = 0;
         if (E.ring_cap <= 0) return 0;
-        HIP_OK(hipStreamSynchronize(stream));
-        if (poll_fuse_fault()) return 1;            // a host synchronisation point, as drain()
-        uint32_t head[2];
-        HIP_OK(hipMemcpy(head, E.ring_head, sizeof(head), hipMemcpyDeviceToHost));
-        uint32_t avail = head[0] - ring_consumed;
+        uint32_t avail = 0;
+        if (ring_begin(&avail)) return 1;
         if (avail > (uint32_t)E.ring_cap) avail = (uint32_t)E.ring_cap;
         if ((int64_t)avail > (int64_t)max_games) avail = (uint32_t)(max_games > 0 ? max_games : 0);
         if (!avail) return check_device_error();
         if (!dPlan && dalloc(&dPlan, (size_t)(SAMPLE_HDR_INTS + 2) * E.ring_cap)) return 1;
-#ifdef GAZ_HOST_EMU
-        GAZ_LAUNCH(k_sample_headers<G>, (int)avail, 1, stream, (const uint8_t*)E.ring, E.ring_cap, ring_consumed, (int)avail, dPlan);
-#else
-        GAZ_LAUNCH(k_sample_headers<G>, ((int)avail + SAMPLES_THREADS - 1) / SAMPLES_THREADS, SAMPLES_THREADS, stream, (const uint8_t*)E.ring, E.ring_cap, ring_consumed, (int)avail, dPlan);
-#endif
+        GAZ_LAUNCH_FLAT(k_sample_headers<G>, (int)avail, SAMPLES_THREADS, stream, (const uint8_t*)E.ring, E.ring_cap, ring_consumed, (int)avail, dPlan);
         HIP_OK(hipGetLastError());
         std::vector<int32_t> hdr((size_t)SAMPLE_HDR_INTS * avail);
         HIP_OK(hipMemcpyAsync(hdr.data(), dPlan, hdr.size() * 4, hipMemcpyDeviceToHost, stream));
@@ -1178,8 +1219,7 @@ template <class G> struct EngineT : gaz_engine {
         if (row_base + R > 0x7fffffffLL) return fail("drain_samples: more than 2^31 rows in one call");
         for (int i = 0; i < n; ++i) plan.push_back(games[6 * i + 4] - (int32_t)row_base);
         if (R > 0 && build_samples(plan, n, R, plane_rows, boards, policies, values)) return 1;
-        ring_consumed += (uint32_t)n;
-        HIP_OK(hipMemcpy(E.ring_head + 1, &ring_consumed, sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (ring_commit((uint32_t)n)) return 1;
         *n_games = n; *n_rows = R;
         return check_device_error();
     }
@@ -1264,11 +1304,7 @@ template <class G> struct EngineT : gaz_engine {
         long long* d_qfirst = cs.get<long long>((size_t)n + 1); long long* d_counts = cs.get<long long>((size_t)2 * n);
         if (!d_slots || !d_cap || !d_qfirst || !d_counts) return fail("read_trees: out of device memory");
         HIP_OK(hipMemcpyAsync(d_slots, slots, sizeof(int32_t) * n, hipMemcpyHostToDevice, stream));
-#ifdef GAZ_HOST_EMU
-        GAZ_LAUNCH(k_tree_caps<G>, n, 1, stream, E, (const int32_t*)d_slots, n, tree, d_cap);
-#else
-        GAZ_LAUNCH(k_tree_caps<G>, (n + 255) / 256, 256, stream, E, (const int32_t*)d_slots, n, tree, d_cap);
-#endif
+        GAZ_LAUNCH_FLAT(k_tree_caps<G>, n, 256, stream, E, (const int32_t*)d_slots, n, tree, d_cap);
         HIP_OK(hipGetLastError());
         std::vector<int32_t> cap(n);
         HIP_OK(hipMemcpyAsync(cap.data(), d_cap, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
@@ -1337,11 +1373,7 @@ template <class G> struct EngineT : gaz_engine {
     }
     int init_puct_table() {
         double* tb = const_cast<double*>(E.puct_table);
-#ifdef GAZ_HOST_EMU
-        GAZ_LAUNCH(k_init_puct_table<0>, 1, 1, stream, tb, E.c_init, E.c_base, PUCT_TABLE_N);
-#else
-        GAZ_LAUNCH(k_init_puct_table<0>, (PUCT_TABLE_N + 255) / 256, 256, stream, tb, E.c_init, E.c_base, PUCT_TABLE_N);
-#endif
+        GAZ_LAUNCH_FLAT(k_init_puct_table<0>, PUCT_TABLE_N, 256, stream, tb, E.c_init, E.c_base, PUCT_TABLE_N);
         HIP_OK(hipGetLastError());
         return 0;
     }
@@ -1359,10 +1391,7 @@ template <class G> struct EngineT : gaz_engine {
         // the middle of a search, so it is refused here with the remedy
         if (cfg.nodes_per_tree <= 0) {
             const int it = hp->run_iterations > 0 ? hp->run_iterations : E.run_iterations, m = hp->gumbel_m >= 0 ? hp->gumbel_m : E.gumbel_m;
-            long long need = 0;
-            if (cfg.search == GAZ_SEARCH_GUMBEL) need = 2LL * (it + m) + 3 * G::A + 64;
-            else if (E.compact) need = 4LL * (it < 3 * G::A ? 3 * G::A : it) + 3 * G::A + 64;
-            else need = (long long)((cfg.max_actions + 1) / 2 + 1) * ((it < 3 * G::A ? 3 * G::A : it) + 2) + 64;
+            const long long need = nodes_needed(it, m);
             if (need > E.nodes_per_tree)
                 return fail("set_hyperparams: run_iterations / gumbel_m beyond what the tree arena was sized for at create time (" + std::to_string(E.nodes_per_tree) +
                             " nodes per tree, " + std::to_string(need) + " needed): create the engine with the largest values, or give nodes_per_tree");
@@ -1387,15 +1416,13 @@ template <class G> struct EngineT : gaz_engine {
     int set_resignation(const gaz_resign_params* p) override {
         ResignBlock b{};                             // (threshold 0 = off: the other fields are then not looked at, on the device either)
         if (p->threshold > 0.0) { b.threshold = p->threshold; b.no_resign_prob = p->no_resign_prob; b.consecutive = p->consecutive; b.min_ply = p->min_ply; }
-        HIP_OK(hipStreamSynchronize(stream));        // (no launch in flight reads the block while it changes)
-        if (pipeline_ready) { HIP_OK(hipStreamSynchronize(tstream)); HIP_OK(hipStreamSynchronize(hstream)); }
+        if (quiesce()) return 1;                     // (no launch in flight reads the block while it changes)
         HIP_OK(hipMemcpy(resign_block(), &b, offsetof(ResignBlock, stats), hipMemcpyHostToDevice));
         return 0;
     }
     int get_resign_stats(uint64_t out[8]) override {
         for (int i = 0; i < 8; ++i) out[i] = 0;
-        HIP_OK(hipStreamSynchronize(stream));
-        if (pipeline_ready) { HIP_OK(hipStreamSynchronize(tstream)); HIP_OK(hipStreamSynchronize(hstream)); }
+        if (quiesce()) return 1;
         unsigned long long s[8];
         HIP_OK(hipMemcpy(s, resign_block()->stats, sizeof(s), hipMemcpyDeviceToHost));
         for (int i = 0; i < 7; ++i) out[i] = s[i];
@@ -1419,8 +1446,7 @@ template <class G> struct EngineT : gaz_engine {
         if (lbk > 1) return fail("set_solver: not with leaf_batch > 1 (a proof may not stand on leaves in flight)");
         if (E.nodes_per_tree > CHILD_INDEX_MASK) return fail("set_solver: nodes_per_tree must be below 2^29 (two bits of a child word carry the proof)");
         if (mode && !(E.solver & 1)) {
-            HIP_OK(hipStreamSynchronize(stream));
-            if (pipeline_ready) { HIP_OK(hipStreamSynchronize(tstream)); HIP_OK(hipStreamSynchronize(hstream)); }
+            if (quiesce()) return 1;
             if (!d_solver_ctr) {
                 if (dalloc(&d_solver_ctr, 8)) return 1;
                 E.solver_ctr_lo = (uint32_t)(uintptr_t)d_solver_ctr; E.solver_ctr_hi = (uint32_t)((uint64_t)(uintptr_t)d_solver_ctr >> 32);
@@ -1435,8 +1461,7 @@ template <class G> struct EngineT : gaz_engine {
     int get_solver(int32_t* mode) override { *mode = E.solver & 1; return 0; }
     int get_solver_stats(uint64_t out[8]) override {
         for (int i = 0; i < 8; ++i) out[i] = 0;
-        HIP_OK(hipStreamSynchronize(stream));
-        if (pipeline_ready) { HIP_OK(hipStreamSynchronize(tstream)); HIP_OK(hipStreamSynchronize(hstream)); }
+        if (quiesce()) return 1;
         if (d_solver_ctr) {
             unsigned long long s[8];
             HIP_OK(hipMemcpy(s, d_solver_ctr, sizeof(s), hipMemcpyDeviceToHost));
@@ -1516,12 +1541,12 @@ template <class G> struct EngineT : gaz_engine {
 // Gumbel 8192 -> 2 x 4096 with two tree rounds per block: +6 %.  auto = 2 for Connect4 PUCT + ResNet from 3072 games, Gomoku PUCT + ResNet from
 // 2048 games, Connect4 Gumbel + ResNet from 6144 games.
 static gaz_engine* make_single_engine(const gaz_engine_config& cfg, std::string* err) {
+    if (*err = config_fault(cfg, 1); !err->empty()) return nullptr;
     gaz_engine* h = nullptr;
     switch (cfg.game) {
         case GAZ_GAME_TICTACTOE: h = new EngineT<Game<GAME_TTT>>(); break;
         case GAZ_GAME_CONNECT4: h = new EngineT<Game<GAME_C4>>(); break;
-        case GAZ_GAME_GOMOKU: h = new EngineT<Game<GAME_GMK>>(); break;
-        default: *err = "unknown game id"; return nullptr;
+        default: h = new EngineT<Game<GAME_GMK>>(); break;
     }
     h->cfg = cfg; h->cfg.game_groups = 1;
     if (h->init()) { *err = h->err; delete h; return nullptr; }
@@ -1532,19 +1557,26 @@ struct GroupEngine : gaz_engine {
     std::vector<gaz_engine*> kid;
     std::vector<int> first;                          // first[c] = first slot of group c, first[K] = n_games
     gaz_record_layout lay{};
+    gaz_sample_layout slay{};
     int drain_from = 0;
     ~GroupEngine() override { for (gaz_engine* k : kid) delete k; }
     int K() const { return (int)kid.size(); }
     int size_of(int c) const { return first[c + 1] - first[c]; }
+    int rows_of(int c, int n) const { return n - first[c] < 0 ? 0 : (n - first[c] > size_of(c) ? size_of(c) : n - first[c]); }      // of the first n rows, group c's
     int up(gaz_engine* k, int rc) { if (rc) err = k->err; return rc; }
     template <class F> int each(F f) { for (int c = 0; c < K(); ++c) if (up(kid[c], f(kid[c], c))) return 1; return 0; }
+    // the three plain ways a call reaches the groups: the same call on every group, on the first only (what all groups share), eight counters summed
+    template <class... P, class... A> int all(int (gaz_engine::*f)(P...), A... a) { return each([&](gaz_engine* k, int) { return (k->*f)(a...); }); }
+    template <class... P, class... A> int lead(int (gaz_engine::*f)(P...), A... a) { return up(kid[0], (kid[0]->*f)(a...)); }
+    int sum8(int (gaz_engine::*f)(uint64_t*), uint64_t out[8]) {
+        for (int i = 0; i < 8; ++i) out[i] = 0;
+        return each([&](gaz_engine* k, int) { uint64_t s[8]; if ((k->*f)(s)) return 1; for (int i = 0; i < 8; ++i) out[i] += s[i]; return 0; });
+    }
     int group_of(int slot) const { int c = 0; while (c + 1 < K() && slot >= first[c + 1]) ++c; return c; }
 
     int init() override {
         const int n = cfg.n_games, k = cfg.game_groups;
-        if (k < 2 || k > n) return fail("game_groups must be in [1, n_games]");
-        if (cfg.sync_moves || cfg.evaluator == GAZ_EVAL_EXTERNAL) return fail("game_groups > 1 needs continuous self-play (sync_moves = 0) with a built-in evaluator");
-        if (cfg.games_budget > 0 && cfg.games_budget < n) return fail("game_groups > 1 with a games_budget below n_games: a group could be left without a game (use game_groups = 1)");
+        if (const std::string fault = config_fault(cfg, k); !fault.empty()) return fail(fault);
         first.assign(1, 0);
         for (int c = 0; c < k; ++c) first.push_back(first.back() + n / k + (c < n % k ? 1 : 0));
         for (int c = 0; c < k; ++c) {
@@ -1566,11 +1598,11 @@ struct GroupEngine : gaz_engine {
             h->grouped = k; h->note_grouped();
             kid.push_back(h);
         }
-        return kid[0]->record_layout(&lay);
+        return lead(&gaz_engine::record_layout, &lay) || lead(&gaz_engine::sample_layout, &slay);
     }
-    int load_weights(const gaz_tensor* t, int n) override { return each([&](gaz_engine* k, int) { return k->load_weights(t, n); }); }
+    int load_weights(const gaz_tensor* t, int n) override { return all(&gaz_engine::load_weights, t, n); }
     int reset_games(const int32_t* slots, int n) override {
-        if (!slots) return each([&](gaz_engine* k, int) { return k->reset_games(nullptr, 0); });
+        if (!slots) return all(&gaz_engine::reset_games, nullptr, 0);
         std::vector<std::vector<int32_t>> per(K());
         for (int i = 0; i < n; ++i) {
             if (slots[i] < 0 || slots[i] >= cfg.n_games) return fail("reset_games: slot out of range");
@@ -1578,8 +1610,8 @@ struct GroupEngine : gaz_engine {
         }
         return each([&](gaz_engine* k, int c) { return per[c].empty() ? 0 : k->reset_games(per[c].data(), (int)per[c].size()); });
     }
-    int run_move(int32_t* w) override { return up(kid[0], kid[0]->run_move(w)); }             // (sync_moves = 0: the group's own refusal)
-    int apply_moves(const int32_t* m) override { return up(kid[0], kid[0]->apply_moves(m)); }
+    int run_move(int32_t* w) override { return lead(&gaz_engine::run_move, w); }             // (sync_moves = 0: the group's own refusal)
+    int apply_moves(const int32_t* m) override { return lead(&gaz_engine::apply_moves, m); }
     int get_root_stats(uint32_t* N, float* W, float* P, float* pol, uint32_t* rv, float* q, int32_t* chosen, int32_t* phase) override {
         return each([&](gaz_engine* k, int c) {
             const size_t a = (size_t)first[c] * lay.A, g = (size_t)first[c];
@@ -1587,7 +1619,7 @@ struct GroupEngine : gaz_engine {
         });
     }
     int run_waves(int n) override {                  // wave by wave, group by group: every group's stream always holds work
-        for (int i = 0; i < n; ++i) if (each([&](gaz_engine* k, int) { return k->run_waves(1); })) return 1;
+        for (int i = 0; i < n; ++i) if (all(&gaz_engine::run_waves, 1)) return 1;
         return 0;
     }
     int no_batch() { return fail("game groups hold one evaluator batch each: the wave_begin / batch API needs game_groups = 1"); }
@@ -1601,10 +1633,10 @@ struct GroupEngine : gaz_engine {
     // rows [first[c], first[c + 1]) go through group c's evaluator (and stay in ITS head-feature buffers: read_head_features below); ms: the sum
     int evaluate(const int8_t* in, int n, float* p, float* v, int rep, double* ms) override {
         if (n < 1 || n > cfg.n_games) return fail("evaluate: n must be in [1, n_games]");
-        const size_t row = cfg.game == GAZ_GAME_TICTACTOE ? Game<GAME_TTT>::HW * Game<GAME_TTT>::C : (cfg.game == GAZ_GAME_CONNECT4 ? Game<GAME_C4>::HW * Game<GAME_C4>::C : Game<GAME_GMK>::HW * Game<GAME_GMK>::C);
+        const size_t row = (size_t)slay.state_bytes;
         double total = 0;
         if (each([&](gaz_engine* k, int c) {
-                const int nc = n - first[c] < 0 ? 0 : (n - first[c] > size_of(c) ? size_of(c) : n - first[c]);
+                const int nc = rows_of(c, n);
                 double m = 0;
                 if (nc && k->evaluate(in + (size_t)first[c] * row, nc, p ? p + (size_t)first[c] * lay.A : p, v ? v + first[c] : v, rep, &m)) return 1;
                 total += m; return 0;
@@ -1625,11 +1657,10 @@ struct GroupEngine : gaz_engine {
         *n_out = total;
         return 0;
     }
-    int sample_layout(gaz_sample_layout* o) override { return up(kid[0], kid[0]->sample_layout(o)); }
+    int sample_layout(gaz_sample_layout* o) override { *o = slay; return 0; }
     int drain_samples(int max_games, int64_t max_rows, int64_t plane_rows, int64_t row_base, int32_t* games, int8_t* boards, float* policies,
                       float* values, int32_t* n_games, int64_t* n_rows, int32_t* blocked_T) override {
-        gaz_sample_layout sl;
-        if (sample_layout(&sl)) return 1;
+        const gaz_sample_layout& sl = slay;
         int total = 0, blocked = 0; int64_t rows = 0;
         for (int i = 0; i < K() && total < max_games; ++i) {         // children append at the running game / row offset
             gaz_engine* k = kid[(drain_from + i) % K()];
@@ -1658,8 +1689,8 @@ struct GroupEngine : gaz_engine {
         out[14] = (uint64_t)K();
         return 0;
     }
-    int synchronize() override { return each([](gaz_engine* k, int) { return k->synchronize(); }); }
-    int timing_reset(int en) override { return each([&](gaz_engine* k, int) { return k->timing_reset(en); }); }
+    int synchronize() override { return all(&gaz_engine::synchronize); }
+    int timing_reset(int en) override { return all(&gaz_engine::timing_reset, en); }
     // sums over the groups: per wave (of all groups) the kernel time of every group's launches — they overlap in time, so the sum is NOT wall clock
     int timing_get(double* ms_tree, double* ms_eval, double* ms_dom, int64_t* n_dom, int64_t* n_waves) override {
         double t = 0, e = 0, d = 0; int64_t nd = 0, nw = 0;
@@ -1671,41 +1702,35 @@ struct GroupEngine : gaz_engine {
         if (ms_tree) *ms_tree = t; if (ms_eval) *ms_eval = e; if (ms_dom) *ms_dom = d; if (n_dom) *n_dom = nd; if (n_waves) *n_waves = nw;
         return 0;
     }
-    int dominant(char* name, int cap, double* flops) override { return up(kid[0], kid[0]->dominant(name, cap, flops)); }      // per launch of one group
+    int dominant(char* name, int cap, double* flops) override { return lead(&gaz_engine::dominant, name, cap, flops); }      // per launch of one group
     int set_position(int slot, const int32_t* a, int n) override {
         if (slot < 0 || slot >= cfg.n_games) return fail("set_position: bad slot / history length");
         const int c = group_of(slot);
         return up(kid[c], kid[c]->set_position(slot - first[c], a, n));
     }
-    int set_search_params(int it, int tau) override { return each([&](gaz_engine* k, int) { return k->set_search_params(it, tau); }); }
-    int stop_search(int s) override { return each([&](gaz_engine* k, int) { return k->stop_search(s); }); }
-    int start_search() override { return each([](gaz_engine* k, int) { return k->start_search(); }); }
-    int set_hyperparams(const gaz_search_hyperparams* hp) override { return each([&](gaz_engine* k, int) { return k->set_hyperparams(hp); }); }
-    int set_resignation(const gaz_resign_params* p) override { return each([&](gaz_engine* k, int) { return k->set_resignation(p); }); }
-    int set_eval_symmetry(int32_t mode) override { return each([&](gaz_engine* k, int) { return k->set_eval_symmetry(mode); }); }
-    int get_eval_symmetry(int32_t* mode) override { return up(kid[0], kid[0]->get_eval_symmetry(mode)); }
-    int set_solver(int32_t mode) override { return each([&](gaz_engine* k, int) { return k->set_solver(mode); }); }
-    int get_solver(int32_t* mode) override { return up(kid[0], kid[0]->get_solver(mode)); }
-    int get_solver_stats(uint64_t out[8]) override {
-        for (int i = 0; i < 8; ++i) out[i] = 0;
-        return each([&](gaz_engine* k, int) { uint64_t s[8]; if (k->get_solver_stats(s)) return 1; for (int i = 0; i < 8; ++i) out[i] += s[i]; return 0; });
-    }
-    int get_resign_stats(uint64_t out[8]) override {
-        for (int i = 0; i < 8; ++i) out[i] = 0;
-        return each([&](gaz_engine* k, int) { uint64_t s[8]; if (k->get_resign_stats(s)) return 1; for (int i = 0; i < 8; ++i) out[i] += s[i]; return 0; });
-    }
+    int set_search_params(int it, int tau) override { return all(&gaz_engine::set_search_params, it, tau); }
+    int stop_search(int s) override { return all(&gaz_engine::stop_search, s); }
+    int start_search() override { return all(&gaz_engine::start_search); }
+    int set_hyperparams(const gaz_search_hyperparams* hp) override { return all(&gaz_engine::set_hyperparams, hp); }
+    int set_resignation(const gaz_resign_params* p) override { return all(&gaz_engine::set_resignation, p); }
+    int set_eval_symmetry(int32_t mode) override { return all(&gaz_engine::set_eval_symmetry, mode); }
+    int get_eval_symmetry(int32_t* mode) override { return lead(&gaz_engine::get_eval_symmetry, mode); }
+    int set_solver(int32_t mode) override { return all(&gaz_engine::set_solver, mode); }
+    int get_solver(int32_t* mode) override { return lead(&gaz_engine::get_solver, mode); }
+    int get_solver_stats(uint64_t out[8]) override { return sum8(&gaz_engine::get_solver_stats, out); }
+    int get_resign_stats(uint64_t out[8]) override { return sum8(&gaz_engine::get_resign_stats, out); }
     int read_head_features(int n, float* p, float* v, int32_t* p_row, int32_t* v_row) override {
         if (n < 0 || n > cfg.n_games) return fail("read_head_features: n must be in [0, n_games]");
         int32_t pr = 0, vr = 0;
-        if (up(kid[0], kid[0]->read_head_features(0, nullptr, nullptr, &pr, &vr))) return 1;
+        if (lead(&gaz_engine::read_head_features, 0, nullptr, nullptr, &pr, &vr)) return 1;
         if (p_row) *p_row = pr; if (v_row) *v_row = vr;
         return each([&](gaz_engine* k, int c) {
-            const int nc = n - first[c] < 0 ? 0 : (n - first[c] > size_of(c) ? size_of(c) : n - first[c]);
+            const int nc = rows_of(c, n);
             return nc ? k->read_head_features(nc, p ? p + (size_t)first[c] * pr : p, v ? v + (size_t)first[c] * vr : v, nullptr, nullptr) : 0;
         });
     }
-    int set_fused_wave(int on) override { return each([&](gaz_engine* k, int) { return k->set_fused_wave(on); }); }
-    int debug_fused_fault(int mod) override { return each([&](gaz_engine* k, int) { return k->debug_fused_fault(mod); }); }
+    int set_fused_wave(int on) override { return all(&gaz_engine::set_fused_wave, on); }
+    int debug_fused_fault(int mod) override { return all(&gaz_engine::debug_fused_fault, mod); }
     int read_positions(int32_t* n_hist, uint8_t* hist, int stride) override {
         if (!n_hist || !hist || stride < lay.max_T) return fail("read_positions: hist must hold at least max_T actions per slot");
         return each([&](gaz_engine* k, int c) { return k->read_positions(n_hist + first[c], hist + (size_t)first[c] * stride, stride); });
@@ -1753,16 +1778,15 @@ struct GroupEngine : gaz_engine {
         return 0;
     }
     int probe_rules(const int32_t* actions, const int32_t* n_actions, int n_pos, int stride, int8_t* b, uint8_t* l, int32_t* w, int8_t* in, int32_t* t,
-                    const float* pin, float* pout) override { return up(kid[0], kid[0]->probe_rules(actions, n_actions, n_pos, stride, b, l, w, in, t, pin, pout)); }
+                    const float* pin, float* pout) override { return lead(&gaz_engine::probe_rules, actions, n_actions, n_pos, stride, b, l, w, in, t, pin, pout); }
 };
 
 // auto (game_groups = 0): two groups where that was measured to pay (see above; measured at num_filters = 128 only, so other widths run one group); GAZ_GAME_GROUPS overrides the automatic choice only
 static int choose_game_groups(const gaz_engine_config& c) {
     if (c.game_groups != 0) return c.game_groups;
     if (c.leaf_batch > 1 || c.gumbel_batch > 1) return 1;   // K rows per game: one batch
-    static const int env = getenv("GAZ_GAME_GROUPS") ? atoi(getenv("GAZ_GAME_GROUPS")) : 0;
-    const bool able = !c.sync_moves && c.evaluator != GAZ_EVAL_EXTERNAL && !(c.games_budget > 0 && c.games_budget < c.n_games);
-    if (env > 0) return (able && env <= c.n_games) ? env : 1;
+    static const int env = env_int("GAZ_GAME_GROUPS", 0);
+    if (env > 0) return group_fault(c, env) ? 1 : env;
     // (with the evaluation cache every group has a table of its own — nothing is shared between groups: 108.2 k -> 110.2 k positions/s)
     const bool pays = c.game == GAZ_GAME_CONNECT4 && c.search == GAZ_SEARCH_PUCT && c.evaluator == GAZ_EVAL_RESNET && c.net_blocks > 0 && c.net_filters == 128 && c.n_games >= 3072;
     // Gomoku (2048 games, 10 blocks; the one-launch wave needs the cache off): 2195 -> 2330 positions/s, 2384 with four tree rounds per block
@@ -1771,7 +1795,7 @@ static int choose_game_groups(const gaz_engine_config& c) {
     const bool pays_gmk = c.game == GAZ_GAME_GOMOKU && c.search == GAZ_SEARCH_PUCT && c.evaluator == GAZ_EVAL_RESNET && c.net_blocks > 0 && c.net_filters == 128 && c.eval_cache_log2 == 0 && c.n_games >= 2048;
     // Gumbel (8192 games -> 2 x 4096, two tree rounds per block instead of four): 323.9 k -> 344.1 k positions/s same box (with four rounds: -1 %)
     const bool pays_gumbel = c.game == GAZ_GAME_CONNECT4 && c.search == GAZ_SEARCH_GUMBEL && c.evaluator == GAZ_EVAL_RESNET && c.net_blocks > 0 && c.net_filters == 128 && c.eval_cache_log2 == 0 && c.n_games >= 6144;
-    return able && (pays || pays_gmk || pays_gumbel) ? 2 : 1;
+    return (pays || pays_gmk || pays_gumbel) && !group_fault(c, 2) ? 2 : 1;
 }
 
 // ------------------------------------------------------------------------------------------ C ABI
@@ -1787,40 +1811,6 @@ int gaz_engine_create(const gaz_engine_config* cfg, gaz_engine** out) {
         g_create_error = "gaz_engine_config.struct_size is " + std::to_string(cfg->struct_size) + ", this library's gaz_engine_config has " +
                          std::to_string(sizeof(gaz_engine_config)) + " bytes (ABI version " + std::to_string(GAZ_ENGINE_ABI_VERSION) +
                          "): rebuild the binding from include/gaz_engine.h";
-        return 1;
-    }
-    if (cfg->game_groups < 0) { g_create_error = "game_groups must be >= 0"; return 1; }
-    if (cfg->gumbel_batch < 0 || cfg->gumbel_batch > 64) { g_create_error = "gumbel_batch must be in [0, 64] (0 and 1 = one candidate of sequential halving per game and wave)"; return 1; }
-    if (cfg->gumbel_batch > 1) {                     // the chunk step exists for the Gumbel search with one batch and no evaluation cache
-        if (cfg->leaf_batch > 1) { g_create_error = "gumbel_batch > 1 cannot be combined with leaf_batch > 1"; return 1; }
-        if (cfg->search != GAZ_SEARCH_GUMBEL) { g_create_error = "gumbel_batch > 1 needs search = GAZ_SEARCH_GUMBEL (the PUCT search has leaf_batch)"; return 1; }
-        if (cfg->eval_cache_log2 > 0) { g_create_error = "gumbel_batch > 1 cannot be combined with eval_cache_log2 > 0"; return 1; }
-        if (cfg->game_groups > 1) { g_create_error = "gumbel_batch > 1 cannot be combined with game_groups > 1"; return 1; }
-    }
-    if (cfg->leaf_batch < 0 || cfg->leaf_batch > 64) { g_create_error = "leaf_batch must be in [0, 64] (0 and 1 = one leaf per game and wave)"; return 1; }
-    if (cfg->leaf_batch > 1) {                       // the K-leaf step exists for the PUCT search with one batch and no evaluation cache
-        if (cfg->search == GAZ_SEARCH_GUMBEL) { g_create_error = "leaf_batch > 1 needs search = GAZ_SEARCH_PUCT (the Gumbel search plans its simulations itself)"; return 1; }
-        if (cfg->eval_cache_log2 > 0) { g_create_error = "leaf_batch > 1 cannot be combined with eval_cache_log2 > 0"; return 1; }
-        if (cfg->game_groups > 1) { g_create_error = "leaf_batch > 1 cannot be combined with game_groups > 1"; return 1; }
-    }
-    // playout cap randomisation: fast_iterations = 0 is off (and then takes no probability), else a fast limit in [1, run_iterations] and p in (0, 1]
-    if (cfg->fast_iterations < 0) { g_create_error = "fast_iterations must be >= 0 (0 = no playout cap), not " + std::to_string(cfg->fast_iterations); return 1; }
-    if (cfg->fast_iterations > cfg->run_iterations) {
-        g_create_error = "fast_iterations (" + std::to_string(cfg->fast_iterations) + ") must not exceed run_iterations (" + std::to_string(cfg->run_iterations) + ")";
-        return 1;
-    }
-    if (cfg->fast_iterations > 0 && !(cfg->full_search_prob > 0.0 && cfg->full_search_prob <= 1.0)) {
-        g_create_error = "full_search_prob must be in (0, 1] with fast_iterations > 0, not " + std::to_string(cfg->full_search_prob);
-        return 1;
-    }
-    if (cfg->fast_iterations == 0 && !(cfg->full_search_prob == 0.0)) { g_create_error = "full_search_prob must be 0 with fast_iterations = 0 (the playout cap is off)"; return 1; }
-    if (cfg->fast_iterations > 0 && cfg->move_time_limit > 0.0) { g_create_error = "fast_iterations > 0 cannot be combined with move_time_limit > 0 (a timed move has no iteration cap to randomise)"; return 1; }
-    // forced playouts + policy target pruning: k = 0 is off, else a finite k > 0 on a PUCT root
-    if (cfg->forced_playouts_k != cfg->forced_playouts_k) { g_create_error = "forced_playouts_k must be a number (0 = no forced playouts), not NaN"; return 1; }
-    if (cfg->forced_playouts_k < 0.0) { g_create_error = "forced_playouts_k must be >= 0 (0 = no forced playouts), not " + std::to_string(cfg->forced_playouts_k); return 1; }
-    if (cfg->forced_playouts_k > 1.7976931348623157e308) { g_create_error = "forced_playouts_k must be finite (KataGo uses 2), not infinity"; return 1; }
-    if (cfg->forced_playouts_k > 0.0 && cfg->search == GAZ_SEARCH_GUMBEL) {
-        g_create_error = "forced_playouts_k > 0 cannot be combined with search = GAZ_SEARCH_GUMBEL (sequential halving has no PUCT root to force playouts at)";
         return 1;
     }
     const int groups = choose_game_groups(*cfg);

@@ -1,5 +1,5 @@
 // net_host.hpp — host side shared by the two network evaluators of resnet.hip (ResNetEvaluator: Connect4; GenericEvaluator: Gomoku /
-// TicTacToe): environment switches, the device tensor store, the timing bracket around the trunk, the stamp dump, the k_stem_mfma launch,
+// TicTacToe): the device tensor store, the timing bracket around the trunk, the stamp dump, the k_stem_mfma launch,
 // the width dispatch and the k_conv_wide trunk.  No device code lives here: every kernel is declared by the headers included below.
 #pragma once
 #include <map>
@@ -13,11 +13,6 @@
 #include "trunk.hpp"
 
 namespace gaz {
-
-// ---- environment switches.  A switch keeps the moment at which it is read: at create / load time where the tests flip it between engines
-// of one process, once per process behind a `static const`.
-inline bool env_on(const char* name, bool dflt) { const char* v = getenv(name); return v ? atoi(v) != 0 : dflt; }
-inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 
 inline bf16_t f2bf_host(float f) { unsigned u; memcpy(&u, &f, 4); return (bf16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); }    // round to nearest even
 

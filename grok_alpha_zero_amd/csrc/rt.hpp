@@ -41,8 +41,17 @@ inline hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return 0; }
 #define GAZ_LAUNCH(kernel, grid, block, stream, ...)                          \
     do { for (int _b = 0; _b < (int)(grid); ++_b) { gaz::emu_block_id = _b; kernel(__VA_ARGS__); } } while (0)
-#define GAZ_EMU_THREADS 1
+// one thread per item (the kernel takes its item from block_id() here, from blockIdx.x * blockDim.x + threadIdx.x on the product build)
+#define GAZ_LAUNCH_FLAT(kernel, n, threads, stream, ...) GAZ_LAUNCH(kernel, n, 1, stream, __VA_ARGS__)
 #else
 #include <hip/hip_runtime.h>
 #define GAZ_LAUNCH(kernel, grid, block, stream, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)
+#define GAZ_LAUNCH_FLAT(kernel, n, threads, stream, ...) GAZ_LAUNCH(kernel, ((n) + (threads) - 1) / (threads), threads, stream, __VA_ARGS__)
 #endif
+
+namespace gaz {
+// ---- environment switches (every GAZ_* switch of the engine and the evaluators).  A switch keeps the moment at which it is read: at create /
+// load time where the tests flip it between engines of one process, once per process behind a `static const`.
+inline bool env_on(const char* name, bool dflt) { const char* v = getenv(name); return v ? atoi(v) != 0 : dflt; }
+inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+}  // namespace gaz
