@@ -403,6 +403,21 @@ struct TailArgs {
     const float* v_w2; const float* v_b2; const float* v_w3; const float* v_b3;
     float* policy; float* value; int B, A, logits;
 };
+// policy entry o of one position from its nout logits (LDS): logits == 1 as they are, 2 Stablemax, else softmax
+__device__ __forceinline__ float policy_entry(const float* lg, int nout, int o, int logits) {
+    if (logits == 1) return lg[o];
+    if (logits == 2) {                              // Stablemax layer (Net/Stablemax.py:8-12): s(x) = x + 1 | 1 / (1 - x), normalised
+        float sum = 0.f;
+        for (int k = 0; k < nout; ++k) { const float x = lg[k]; sum += x >= 0.0f ? x + 1.0f : 1.0f / (1.0f - x); }
+        const float x = lg[o];
+        return (x >= 0.0f ? x + 1.0f : 1.0f / (1.0f - x)) / sum;
+    }
+    float mx = lg[0];
+    for (int k = 1; k < nout; ++k) mx = fmaxf(mx, lg[k]);
+    float sum = 0.f;
+    for (int k = 0; k < nout; ++k) sum += expf(lg[k] - mx);
+    return expf(lg[o] - mx) / sum;
+}
 // 16 positions per block (8 threads each), blockIdx.y = head; Dense(128 -> 64) weights staged in LDS once per block.
 // Summation order per output is k ascending starting from the bias, independent of the batch composition.
 __global__ __launch_bounds__(128) void k_tail(TailArgs a) {
@@ -457,23 +472,154 @@ __global__ __launch_bounds__(128) void k_tail(TailArgs a) {
     if (b0 + p >= a.B) return;
     const int b = b0 + p;
     if (head == 0) {
-        for (int o = q; o < nout; o += 8) {
-            if (a.logits == 1) a.policy[(size_t)b * a.A + o] = lg[p][o];
-            else if (a.logits == 2) {               // Stablemax layer (Net/Stablemax.py:8-12): s(x) = x + 1 | 1 / (1 - x), normalised
-                float sum = 0.f;
-                for (int k = 0; k < nout; ++k) { const float x = lg[p][k]; sum += x >= 0.0f ? x + 1.0f : 1.0f / (1.0f - x); }
-                const float x = lg[p][o];
-                a.policy[(size_t)b * a.A + o] = (x >= 0.0f ? x + 1.0f : 1.0f / (1.0f - x)) / sum;
-            } else {
-                float mx = lg[p][0];
-                for (int k = 1; k < nout; ++k) mx = fmaxf(mx, lg[p][k]);
-                float sum = 0.f;
-                for (int k = 0; k < nout; ++k) sum += expf(lg[p][k] - mx);
-                a.policy[(size_t)b * a.A + o] = expf(lg[p][o] - mx) / sum;
-            }
-        }
+        for (int o = q; o < nout; o += 8) a.policy[(size_t)b * a.A + o] = policy_entry(lg[p], nout, o, a.logits);
     } else if (q == 0) {
         a.value[b] = tanhf(lg[p][0]);
+    }
+}
+
+// ---- both kernels above in ONE launch for the Connect4 network (GAZ_HEADS_ONE=0: the two launches): Dense(F -> 128) + folded BN + ReLU ->
+// Dense(128 -> 64) -> Dense(64 -> A | 1) -> softmax | logits | Stablemax | tanh.  An item = 32 positions of one head; a workgroup of 256
+// threads takes items blockIdx.x, blockIdx.x + gridDim.x, ...  The Dense-1 output stays in LDS, so the pd1 / vd1 round trip through HBM and
+// the second launch are gone.  62 KB of LDS and one wave per SIMD: the workgroup fits the slot a finished trunk workgroup frees, beside the
+// CU's other trunk workgroup (74.8 KB).  Next to another game group's trunk tiles a heads launch lasts as long as its workgroups wait for
+// such slots, so what counts there is how FEW workgroups it needs (forward_heads: the grid).
+// Results are bit for bit the two kernels': Dense-1 on v_mfma_f32_16x16x4_f32 (a sequential fmaf chain over ascending k like the 32x32x2 shape,
+// tools/probes/mfma_f32_order.hip) with k_dense1_mfma's two partial sums — k-groups [0, NGH) in waves 0-1, [NGH, NG) in waves 2-3, out =
+// relu((first + second) * s + t) — and the tail in k_tail's order (bias first, k ascending) with its expressions.  Needs F % 16 == 0
+// (no zero-padded k-group), F <= 384 and A <= 8 (forward_heads checks).
+struct HeadsC4Args {
+    const float* feat[2]; const float* w1[2]; const float* s1[2]; const float* t1[2];          // [head]: features [B][F], Dense-1 [F][128] + BN
+    const float* w2[2]; const float* b2[2]; const float* w3[2]; const float* b3[2];
+    float* policy; float* value; int B, F, A, logits;
+};
+constexpr int HC4_THREADS = 256, HC4_POS = 32, HC4_XP = 132;        // XP: row pitch of the Dense-1 output (the rows a wave reads at once on different banks)
+constexpr int HC4_FCH = 6, HC4_TAIL = 128 * 64 + HC4_POS * 64 + HC4_POS * 8;        // 16-byte feature loads per thread and round; floats of w2l + hl + lg
+static size_t heads_c4_lds_bytes(int F) { return (size_t)(std::max(HC4_POS * (F + 1), HC4_TAIL) + HC4_POS * HC4_XP + 64 * 8) * 4; }
+__global__ __launch_bounds__(HC4_THREADS) void k_heads_c4(HeadsC4Args a) {
+    typedef __attribute__((ext_vector_type(4))) float f32x4;
+    extern __shared__ float fl[];                  // [32][FP] features, FP = F + 1; after Dense-1 the same floats hold w2l [128][64], hl [32][64], lg [32][8]
+    constexpr int D = 12;                          // twelve-deep register ring of weight k-steps (4 k x 4 columns per lane each)
+    const int tid = threadIdx.x, F = a.F, FP = F + 1, F4 = F >> 2;
+    float* const w2l = fl; float* const hl = fl + 128 * 64; float* const lg = hl + HC4_POS * 64;
+    float* const xl = fl + max(HC4_POS * FP, HC4_TAIL);       // [32][XP]: the second half's partial sums, then the Dense-1 output
+    float* const w3l = xl + HC4_POS * HC4_XP;                 // [64][nout]
+    // Dense-1: A[i = c][k + kq] of both 16-position tiles, B[k + kq][j = c] of column tile t = column n0 + t (a lane's four tiles are ONE 16-byte
+    // weight load per k-step); D[tile][reg r] = position 16 tile + 4 kq + r.  Wave = (k half, 64 columns).
+    const int lane = tid & 63, wave = tid >> 6, c = lane & 15, kq = lane >> 4, half = wave >> 1, n0 = (wave & 1) * 64 + c * 4;
+    const int NG = F >> 4, NGH = (NG + 1) / 2, sA = half ? NGH * 4 : 0, sB = half ? NG * 4 : NGH * 4;       // this wave's k-steps [sA, sB)
+    const int p = tid >> 3, q = tid & 7;           // tail: 8 threads per position, eight Dense(128 -> 64) outputs each
+    const int items = 2 * ((a.B + HC4_POS - 1) / HC4_POS);
+    for (int item = blockIdx.x; item < items; item += gridDim.x) {
+        const int head = item & 1, b0 = (item >> 1) * HC4_POS, nout = head == 0 ? a.A : 1;
+        const float* feat = a.feat[head]; const float* w1 = a.w1[head]; const float* w3 = a.w3[head];
+        // the weights come from L2 (~1 us away under load): the first eleven k-steps are requested BEFORE anything is staged, as in k_dense1_mfma
+        float4 bq[D]; f32x4 wv[8];             // (wv as a native vector: an array of float4 classes held across Dense-1 ends up in scratch)
+        auto ldw = [&](int s) { return *reinterpret_cast<const float4*>(w1 + (size_t)min(4 * s + kq, F - 1) * 128 + n0); };
+#pragma unroll
+        for (int d = 0; d < D - 1; ++d) bq[d] = ldw(sA + d);
+        {   // features and Dense(64 -> nout) weights -> LDS in two rounds of six 16-byte loads per thread, each round's loads issued before its first
+            // LDS store (one round of twelve costs 46 more VGPRs than the kernel has); then the Dense(128 -> 64) weights -> registers: their
+            // LDS is the features' until Dense-1 is done, and they arrive while it runs
+            float w3v[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) w3v[i] = w3[min(tid + HC4_THREADS * i, 64 * nout - 1)];
+#pragma unroll 1
+            for (int e0 = tid; e0 < HC4_POS * F4; e0 += HC4_THREADS * HC4_FCH) {
+                float4 fv[HC4_FCH];
+#pragma unroll
+                for (int i = 0; i < HC4_FCH; ++i) {
+                    const int e = min(e0 + HC4_THREADS * i, HC4_POS * F4 - 1), r = e / F4;
+                    fv[i] = reinterpret_cast<const float4*>(feat + (size_t)min(b0 + r, a.B - 1) * F)[e - r * F4];
+                }
+#pragma unroll
+                for (int i = 0; i < HC4_FCH; ++i) {
+                    const int e = e0 + HC4_THREADS * i, r = e / F4, k = (e - r * F4) * 4;
+                    if (e < HC4_POS * F4) {
+                        const bool rok = b0 + r < a.B;
+                        float* dst = fl + r * FP + k;
+                        dst[0] = rok ? fv[i].x : 0.0f; dst[1] = rok ? fv[i].y : 0.0f; dst[2] = rok ? fv[i].z : 0.0f; dst[3] = rok ? fv[i].w : 0.0f;
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i) w3l[tid + HC4_THREADS * i] = w3v[i];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) wv[i] = reinterpret_cast<const f32x4*>(a.w2[head])[tid + HC4_THREADS * i];
+        }
+        __syncthreads();
+        f32x4 acc[2][4];
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[m][t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int s0 = sA; s0 < sB; s0 += D) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                const int s = s0 + d;
+                if (s + D - 1 < sB) bq[(d + D - 1) % D] = ldw(s + D - 1);      // wave-uniform, as is the next
+                if (s < sB) {
+#pragma unroll
+                    for (int m = 0; m < 2; ++m) {
+                        const float av = fl[(16 * m + c) * FP + 4 * s + kq];
+                        acc[m][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bq[d].x, acc[m][0], 0, 0, 0);
+                        acc[m][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bq[d].y, acc[m][1], 0, 0, 0);
+                        acc[m][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bq[d].z, acc[m][2], 0, 0, 0);
+                        acc[m][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bq[d].w, acc[m][3], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        if (half) {
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    *reinterpret_cast<float4*>(&xl[(16 * m + 4 * kq + r) * HC4_XP + n0]) = make_float4(acc[m][0][r], acc[m][1][r], acc[m][2][r], acc[m][3][r]);
+        }
+        __syncthreads();                           // the features are read: w2l / hl / lg overwrite them from here on
+        if (!half) {
+            const float4 s = *reinterpret_cast<const float4*>(a.s1[head] + n0), t = *reinterpret_cast<const float4*>(a.t1[head] + n0);
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float4* x = reinterpret_cast<float4*>(&xl[(16 * m + 4 * kq + r) * HC4_XP + n0]);
+                    const float4 pv = *x;
+                    *x = make_float4(fmaxf((acc[m][0][r] + pv.x) * s.x + t.x, 0.0f), fmaxf((acc[m][1][r] + pv.y) * s.y + t.y, 0.0f),
+                                     fmaxf((acc[m][2][r] + pv.z) * s.z + t.z, 0.0f), fmaxf((acc[m][3][r] + pv.w) * s.w + t.w, 0.0f));
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) reinterpret_cast<f32x4*>(w2l)[tid + HC4_THREADS * i] = wv[i];
+        __syncthreads();
+        {
+            const float* b2 = a.b2[head];
+            float h[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) h[j] = b2[q * 8 + j];
+            for (int k = 0; k < 128; ++k) {
+                const float xv = xl[p * HC4_XP + k];
+                const float4 wa = *reinterpret_cast<const float4*>(&w2l[k * 64 + q * 8]), wb = *reinterpret_cast<const float4*>(&w2l[k * 64 + q * 8 + 4]);
+                h[0] += xv * wa.x; h[1] += xv * wa.y; h[2] += xv * wa.z; h[3] += xv * wa.w;
+                h[4] += xv * wb.x; h[5] += xv * wb.y; h[6] += xv * wb.z; h[7] += xv * wb.w;
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) hl[p * 64 + q * 8 + j] = h[j];
+        }
+        __syncthreads();
+        for (int o = q; o < nout; o += 8) {
+            float z = a.b3[head][o];
+            for (int k = 0; k < 64; ++k) z += hl[p * 64 + k] * w3l[k * nout + o];
+            lg[p * 8 + o] = z;
+        }
+        __syncthreads();
+        const int b = b0 + p;
+        if (b < a.B) {
+            if (head == 0) { for (int o = q; o < nout; o += 8) a.policy[(size_t)b * a.A + o] = policy_entry(lg + p * 8, nout, o, a.logits); }
+            else if (q == 0) a.value[b] = tanhf(lg[p * 8]);
+        }
+        __syncthreads();                           // lg is read: the next item's features may overwrite it
     }
 }
 
@@ -496,6 +642,9 @@ struct ResNetEvaluator : Evaluator {
     bool trunk_mix = true;                          // ... with the last partial round in cheaper 96-row tiles (k_trunk_mix); GAZ_TRUNK_MIX=0 -> one tile shape
     bool trunk_whole = true;                        // ... including the stem and the heads' first convolution; GAZ_TRUNK_WHOLE=0 -> k_stem_mfma / k_conv_heads
     bool trunk = true;                              // k_trunk: every block in one kernel (trunk.hpp); GAZ_TRUNK=0 -> one k_resblock3 per block
+    bool heads_one = true;                          // k_heads_c4: both heads' dense layers in one launch (128 filters); GAZ_HEADS_ONE=0 -> k_dense1_mfma + k_tail
+    int heads_wgs = 128;                            // ... of at most this many workgroups when game groups share the chip (GAZ_HEADS_WGS)
+    int heads_one_rows = 2048;                      // ... for a game group's launches of up to this many rows (GAZ_HEADS_ONE_ROWS)
     bf16_t* trunk_w = nullptr; float* trunk_prm = nullptr;
     std::string dom_label;
     uint8_t *perm_big = nullptr, *perm_small = nullptr;    // TrunkArgs::perm for the 128-row and the 96-row tile (tile_perm.hpp tile_layout; GAZ_TILE_PERM=0: none)
@@ -600,7 +749,8 @@ struct ResNetEvaluator : Evaluator {
     }
     bool plan_uses_queue(const void* plan) const override { return plan && static_cast<const TrunkLaunchPlan*>(plan)->args.queue != nullptr; }
     bool shared_chip = false;
-    void set_shared_chip(bool on) override { static const bool off = !env_on("GAZ_GROUP_BIG_TILES", true); shared_chip = on && !off; }
+    bool grouped = false;                           // one of several game groups whose launches share the chip
+    void set_shared_chip(bool on) override { static const bool off = !env_on("GAZ_GROUP_BIG_TILES", true); shared_chip = on && !off; grouped = on; }
     int round_rows() const override { return 2 * n_cus * (128 / HW); }
     void forward(hipStream_t s, const int8_t* in, float* policy, float* value, int n, bool timing, int p0 = 0) override {
         forward_trunk(s, in, n, timing, p0);
@@ -709,6 +859,22 @@ struct ResNetEvaluator : Evaluator {
         float* const pfeat = this->pfeat + (size_t)p0 * HW * 8; float* const vfeat = this->vfeat + (size_t)p0 * HW * 8;
         float* const pd1 = this->pd1 + (size_t)p0 * 128; float* const vd1 = this->vd1 + (size_t)p0 * 128;
         const int F = HW * 8;
+        // one launch, no pd1 / vd1 (k_heads_c4) — but not for a game group's launch of more than heads_one_rows rows: measured slower than the two
+        // kernels there (Gumbel, 2 x 4096 games)
+        if (heads_one && filters == 128 && F % 16 == 0 && F <= 384 && A <= 8 && !(grouped && n > heads_one_rows)) {
+            HeadsC4Args h; h.B = n; h.F = F; h.A = A; h.logits = logits; h.policy = policy; h.value = value;
+            h.feat[0] = pfeat; h.feat[1] = vfeat;
+            for (int i = 0; i < 2; ++i) {
+                const std::string p = i == 0 ? "p" : "v";
+                h.w1[i] = st.g(p + ".d1.w"); h.s1[i] = st.g(p + ".d1.scale"); h.t1[i] = st.g(p + ".d1.shift");
+                h.w2[i] = st.g(p + ".d2.w"); h.b2[i] = st.g(p + ".d2.bias"); h.w3[i] = st.g(p + ".d3.w"); h.b3[i] = st.g(p + ".d3.bias");
+            }
+            // a launch with the chip to itself: a workgroup per item.  Among other game groups' trunk tiles (set_shared_chip): heads_wgs workgroups
+            // at the most, each of which walks through its items — the launch ends sooner with fewer slots to wait for
+            const int items = 2 * ((n + HC4_POS - 1) / HC4_POS);
+            hipLaunchKernelGGL(k_heads_c4, dim3(grouped ? std::min(items, heads_wgs) : items), dim3(HC4_THREADS), heads_c4_lds_bytes(F), s, h);
+            return;
+        }
         Dense1Args d; d.B = n; d.F = F;
         d.feat[0] = pfeat; d.w[0] = st.g("p.d1.w"); d.scale[0] = st.g("p.d1.scale"); d.shift[0] = st.g("p.d1.shift"); d.out[0] = pd1;
         d.feat[1] = vfeat; d.w[1] = st.g("v.d1.w"); d.scale[1] = st.g("v.d1.scale"); d.shift[1] = st.g("v.d1.shift"); d.out[1] = vd1;
@@ -1206,6 +1372,9 @@ Evaluator* make_resnet_evaluator(const gaz_engine_config& cfg, int H, int W, int
     e->trunk_whole = env_on("GAZ_TRUNK_WHOLE", true);
     e->trunk_mix = env_on("GAZ_TRUNK_MIX", true);
     e->trunk_m16 = env_on("GAZ_TRUNK_M16", true);
+    e->heads_one = env_on("GAZ_HEADS_ONE", true);
+    e->heads_wgs = std::max(1, env_int("GAZ_HEADS_WGS", e->heads_wgs));
+    e->heads_one_rows = env_int("GAZ_HEADS_ONE_ROWS", e->heads_one_rows);
     { hipDeviceProp_t pr; int dev = 0; hipGetDevice(&dev); if (hipGetDeviceProperties(&pr, dev) == hipSuccess) e->n_cus = pr.multiProcessorCount; }
     e->X = e->st.dalloc<bf16_t>(M * CW + 1024); e->Aa = e->st.dalloc<bf16_t>(M * CW + 1024); e->Hh = e->st.dalloc<bf16_t>(M * CW + 1024);
     e->pfeat = e->st.dalloc<float>((size_t)cfg.n_games * e->HW * 8); e->vfeat = e->st.dalloc<float>((size_t)cfg.n_games * e->HW * 8);
@@ -1215,6 +1384,7 @@ Evaluator* make_resnet_evaluator(const gaz_engine_config& cfg, int H, int W, int
     hipFuncSetAttribute((const void*)k_resblock, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)(k_resblock3<4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rb3_lds_bytes<4>());
     hipFuncSetAttribute((const void*)k_conv_heads, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hc_lds_bytes());
+    hipFuncSetAttribute((const void*)k_heads_c4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)heads_c4_lds_bytes(384));
     hipFuncSetAttribute((const void*)(k_trunk<2, 2, 8, 2, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes(128));
     hipFuncSetAttribute((const void*)(k_trunk_mix<8, 2, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes(128));
     hipFuncSetAttribute((const void*)(k_trunk<2, 2, 8, 2, true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes(128));
