@@ -14,19 +14,14 @@ for every legal action.  The `zeromass` cases also replay every record with grok
 want finite root_P / policies."""
 import numpy as np
 
+import selfplay_support
 from degenerate_eval import Constant, Evaluator
+from selfplay_support import A_OF, MAXT, SLOTS64, slots_for
 
-MAXT = {"TicTacToe": 9, "Connect4": 42, "Gomoku": 225}
-A_OF = {"TicTacToe": 9, "Connect4": 7, "Gomoku": 225}
-SLOTS64 = (0, 1, 15, 16, 31, 32, 62, 63)          # first / last game of a wavefront's four teams, both ends of a 64-game batch
 PUCT_KEYS = ("actions", "root_N", "root_W", "root_P", "policies", "q", "root_visits", "evals")
 PH_WAIT_HOST, PH_HALT = 5, 8                       # grok_alpha_zero_amd.engine
 TIE_KINDS = ("uniform", "dups", "zeros", "saturated")
 MIN_TIED_PLIES, MIN_ZEROMASS_ROWS = 10, 20
-
-
-def slots_for(G):
-    return SLOTS64 if G >= 64 else tuple(range(G))
 
 
 # ------------------------------------------------------------------------------------------------ the external evaluator loop
@@ -43,17 +38,11 @@ def serve_wave(eng, ev):
 
 
 def first_games(eng, ev, n_slots, launches=400000, every=8):
-    """a free-running external-evaluator engine until every slot's first game is there -> {slot: record}"""
-    first, seq0 = {}, int(eng.cfg.first_game_seq)
-    for k in range(launches):
-        serve_wave(eng, ev)
-        if k % every == every - 1:
-            for r in eng.drain_finished():
-                if r["game_seq"] == seq0:
-                    first[r["slot"]] = r
-            if len(first) == n_slots:
-                return first
-    raise AssertionError(f"only {len(first)} of {n_slots} games finished")
+    """a free-running external-evaluator engine until every slot's first game is there -> {slot: record}; drained after every `every` launches"""
+    def advance():
+        for _ in range(every):
+            serve_wave(eng, ev)
+    return selfplay_support.first_games(eng, n_slots, rounds=launches // every, advance=advance)
 
 
 def drive_move(eng, ev, launches=200000):

@@ -14,9 +14,9 @@ import ctypes as C
 import numpy as np
 
 import eval_symmetry_model as M
+from selfplay_support import (A_OF, MAXT, c4_one_block_weights, games_of_file, net_engine, play, refusal_message, scheduling_equalities,
+                              self_play_file)
 
-MAXT = {"TicTacToe": 9, "Connect4": 42, "Gomoku": 225}
-A_OF = {"TicTacToe": 9, "Connect4": 7, "Gomoku": 225}
 SEED, SALT = 11, 5
 RECORD_KEYS = ("actions", "policies", "q", "root_N", "root_W", "root_P", "root_visits", "evals")
 PH_WAIT_HOST, PH_HALT, PH_IDLE = 5, 8, 9
@@ -47,28 +47,6 @@ def make_engine(name, G, lib_path, games, on=True, **kw):
     a = dict(seed=SEED, hash_salt=SALT, ring_capacity=2 * games + 8, games_budget=games, lib_path=lib_path, eval_symmetry=on)
     a.update(_gumbel(m) if m else ekw); a.update(kw)
     return SelfPlayEngine(game, G, *args, **a)
-
-
-def play(eng, n, waves=32, rounds=40000, raw=False):
-    """a free-running engine until n games are there -> {(slot, game_seq): record}; raw: the records' bytes"""
-    out = {}
-    for _ in range(rounds):
-        eng.run_waves(waves)
-        if raw:
-            lay = eng.layout
-            buf = np.zeros((max(eng.cfg.ring_capacity, 1), lay.record_bytes), np.uint8)
-            got = C.c_int32()
-            eng._ck(eng.L.gaz_engine_drain_finished(eng.h, buf.ctypes.data, buf.shape[0], C.byref(got)))
-            for i in range(got.value):
-                hdr = buf[i, lay.off_hdr:lay.off_hdr + 16].view(np.int32)
-                out[(int(hdr[2]), int(hdr[3]))] = buf[i].tobytes()
-        else:
-            for r in eng.drain_finished():
-                out[(r["slot"], r["game_seq"])] = r
-        if len(out) >= n:
-            assert len(out) == n, (len(out), n)
-            return out
-    raise AssertionError(f"only {len(out)} of {n} games finished")
 
 
 def oracle_game(oracle, name, slot, seq, evaluator):
@@ -200,7 +178,7 @@ def gumbel_batch_case(name, G, lib_path):
     a.close(); b.close()
     assert sorted(ra) == sorted(rb)
     for k in ra:
-        assert ra[k] == rb[k], (name, k)
+        assert np.array_equal(ra[k], rb[k]), (name, k)
     assert (sa["evals"], sa["sims"], sa["plies"]) == (sb["evals"], sb["sims"], sb["plies"]) and sb["waves"] < sa["waves"], (sa, sb)
 
 
@@ -319,24 +297,16 @@ def samples_case(name, G, lib_path):
 def run_self_play_case(oracle, tmp, lib_path, games=24, G=12, game="TicTacToe"):
     """run_self_play with train_config["eval_symmetry"]: the file holds the games of a directly created engine with symmetry on — which
     are the oracle's (selfplay_case) — at both settings of device_samples; without the key, other games"""
-    import os
     from grok_alpha_zero_amd.engine import SelfPlayEngine
     from grok_alpha_zero_amd.games import GAMES
-    from grok_alpha_zero_amd.self_play import ReplayStore, record_to_samples, run_self_play
-    from samples_util import file_contents
+    from grok_alpha_zero_amd.self_play import record_to_samples
     n_aug = M.NSYM[game]
     train = dict(games_per_generation=games, MCTS_iteration_limit=16, max_actions=MAXT[game], num_explore_actions_first=2, num_explore_actions_second=1,
                  c_puct_init=1.25, dirichlet_alpha=1.0, use_gumbel=False)
-
-    def by_game(f):
-        return sorted(tuple((a.dtype.str, a.shape, a.tobytes()) for a in [f[f"{kind}_{n_aug * k + j}"] for j in range(n_aug) for kind in ("boards", "policies", "values")])
-                      for k in range(games))
     files = {}
     for key, extra, ds in (("on-host", dict(eval_symmetry=True), False), ("on-device", dict(eval_symmetry=True), True), ("off", {}, True)):
-        folder = os.path.join(str(tmp), key, "0")
-        store = ReplayStore(folder); store.create()
-        assert run_self_play(GAMES[game], ({}, dict(train, **extra)), folder, n_games=G, seed=SEED, hash_salt=SALT, lib_path=lib_path, device_samples=ds) == games
-        files[key] = by_game(file_contents(store))
+        f = self_play_file(tmp, key, game, dict(train, **extra), games, n_games=G, seed=SEED, hash_salt=SALT, lib_path=lib_path, device_samples=ds)
+        files[key] = games_of_file(f, games, n_aug)
     eng = SelfPlayEngine(game, G, 24, MAXT[game], 2, 1, 1.25, 1.0, seed=SEED, hash_salt=SALT, ring_capacity=4 * games, games_budget=games, eval_symmetry=True,
                          lib_path=lib_path)
     recs = play(eng, games, waves=16)
@@ -408,7 +378,7 @@ def mcts_gumbel_class_case(oracle, lib_path):
 # ------------------------------------------------------------------------------------------------ 7. refusals
 def refusal_case(lib_path):
     """-> the messages, each its own.  A refused call leaves the mode as it was"""
-    from grok_alpha_zero_amd.engine import EngineError, SelfPlayEngine
+    from grok_alpha_zero_amd.engine import SelfPlayEngine
     eng = SelfPlayEngine("Connect4", 4, 40, 42, 4, 4, 2.5, 0.5, seed=1, lib_path=lib_path)
     msgs = {}
     try:
@@ -432,13 +402,8 @@ def refusal_case(lib_path):
         grp.set_eval_symmetry(True)
         assert grp.eval_symmetry is True
         for fn in (grp.read_batch, grp.read_batch_symmetry):           # refused where read_batch is
-            try:
-                fn()
-            except EngineError as e:
-                msgs[fn.__name__] = str(e)
-                assert "game_groups = 1" in str(e)
-            else:
-                raise AssertionError(f"{fn.__name__} on a grouped engine was not refused")
+            msgs[fn.__name__] = refusal_message(fn, f"{fn.__name__} on a grouped engine was not refused")
+            assert "game_groups = 1" in msgs[fn.__name__]
     finally:
         grp.close()
     assert "read_batch_symmetry" in msgs["read_batch_symmetry"]
@@ -454,40 +419,11 @@ def abi_case(lib_path):
 
 
 # ------------------------------------------------------------------------------------------------ 8. scheduling with a 1-block ResNet (HIP build)
-def _net_engine(G, weights, fused=True, **kw):
-    from grok_alpha_zero_amd.engine import EVAL_RESNET, SelfPlayEngine
-    eng = SelfPlayEngine("Connect4", G, 40, 42, 4, 4, 2.5, 0.5, seed=SEED, evaluator=EVAL_RESNET, net_blocks=1, ring_capacity=4 * G, games_budget=G,
-                         eval_symmetry=True, **kw)
-    eng.load_weights(weights)
-    if not fused:
-        eng.set_fused_wave(False)
-    return eng
-
-
 def scheduling_case(which, G=64):
     """64 Connect4 games, 1-block network, symmetry on: the records do not depend on the fused launch, the game groups or the evaluation cache"""
-    from grok_alpha_zero_amd.net import Connect4Net
-    w = Connect4Net(1, seed=0).eval().export_engine_weights()
-
-    def run(fused=True, **kw):
-        eng = _net_engine(G, w, fused, **kw)
-        recs = play(eng, G, raw=True)
-        st = eng.stats()
-        eng.close()
-        return recs, st
-    if which == "fused":
-        (a, sa), (b, sb) = run(game_groups=1), run(fused=False, game_groups=1)
-        assert sa["fused_wave"] == 1 and sb["fused_wave"] == 0, (sa, sb)
-    elif which == "groups":
-        (a, sa), (b, sb) = run(game_groups=2), run(game_groups=1)
-        assert sa["game_groups"] == 2 and sb["game_groups"] == 1
-    else:
-        (a, sa), (b, sb) = run(game_groups=1, eval_cache_log2=14), run(game_groups=1)
-        assert sa["cache_hits"] > 0 and sb["cache_hits"] == 0
-    assert sorted(a) == sorted(b) == [(s, 0) for s in range(G)]
-    for k in a:
-        assert a[k] == b[k], (which, k)
-    print(f"scheduling {which}: {G} games identical", flush=True)
+    def symmetry_is_on(recs, on):
+        assert on is True
+    scheduling_equalities(which, G, dict(seed=SEED, eval_symmetry=True), lambda eng: (play(eng, G, raw=True), eng.eval_symmetry), symmetry_is_on)
 
 
 # ------------------------------------------------------------------------------------------------ 9. the real network (HIP build)
@@ -495,9 +431,8 @@ def network_case(oracle, G=64):
     """64 Connect4 games, symmetry on, 1-block network, against the oracle whose evaluator is sym_eval around a second engine's evaluate()
     on single rows (rows of a batch are independent bit for bit, tests/test_evaluator_gpu.py)"""
     from grok_alpha_zero_amd.engine import EVAL_RESNET, SelfPlayEngine
-    from grok_alpha_zero_amd.net import Connect4Net
-    w = Connect4Net(1, seed=0).eval().export_engine_weights()
-    eng = _net_engine(G, w)
+    w = c4_one_block_weights()
+    eng = net_engine(G, w, seed=SEED, eval_symmetry=True)
     recs = play(eng, G)
     assert eng.stats()["fused_wave"] == 1
     eng.close()

@@ -7,14 +7,12 @@ prune_target: the policy row from the RAW root rows), never read back from the e
 playout_cap_cases.kinds_of (oracle.uniform).  Every comparison is exact."""
 import numpy as np
 
-from playout_cap_cases import (A_OF, MAXT, N_AUG, RECORD_KEYS, SLOTS64, assert_records_equal, base_limits, first_games, kinds_of)
+from playout_cap_cases import base_limits, kinds_of
+from selfplay_support import (A_OF, MAXT, N_AUG, RECORD_KEYS, SLOTS64, assert_records_equal, first_games, games_of_file, refusal_message,
+                              scheduling_equalities, self_play_file, slots_for)
 
 SEED, SALT = 31, 8
 K = 2.0                                            # KataGo's k
-
-
-def slots_for(G, slots=SLOTS64):
-    return tuple(slots) if G >= 64 else tuple(range(G))
 
 
 def terminal_root(game, history):
@@ -234,20 +232,14 @@ def samples_case(name, lib_path, G=None):
 def run_self_play_case(tmp, lib_path, games=40, G=24):
     """run_self_play with train_config["forced_playouts_k"]: the same file at both settings of device_samples, and its games are those of
     an engine created with forced_playouts_k directly (pruned rows among them)"""
-    import os
     from grok_alpha_zero_amd.engine import SelfPlayEngine
     from grok_alpha_zero_amd.games import GAMES
-    from grok_alpha_zero_amd.self_play import ReplayStore, record_to_samples, run_self_play
+    from grok_alpha_zero_amd.self_play import record_to_samples
     from forced_playouts_model import raw_target
-    from samples_util import file_contents
     train = dict(games_per_generation=games, MCTS_iteration_limit=16, forced_playouts_k=K, max_actions=9, num_explore_actions_first=2,
                  num_explore_actions_second=1, c_puct_init=1.25, dirichlet_alpha=1.0, use_gumbel=False)
-    out = {}
-    for ds in (False, True):
-        folder = os.path.join(str(tmp), f"ds{ds}", "0")
-        store = ReplayStore(folder); store.create()
-        assert run_self_play(GAMES["TicTacToe"], ({}, train), folder, n_games=G, seed=11, hash_salt=4, lib_path=lib_path, device_samples=ds) == games
-        out[ds] = file_contents(store)
+    out = {ds: self_play_file(tmp, f"ds{ds}", "TicTacToe", train, games, n_games=G, seed=11, hash_salt=4, lib_path=lib_path, device_samples=ds)
+           for ds in (False, True)}
     eng = SelfPlayEngine("TicTacToe", G, 24, 9, 2, 1, 1.25, 1.0, seed=11, hash_salt=4, ring_capacity=4 * G, games_budget=games, forced_playouts_k=K,
                          lib_path=lib_path)
     recs = []
@@ -260,19 +252,13 @@ def run_self_play_case(tmp, lib_path, games=40, G=24):
     assert any(not np.array_equal(r["policies"][t], raw_target(r["root_N"][t])) for r in recs for t in range(r["T"])), "no pruned row"
     np.testing.assert_array_equal(out[False]["game_stats"], out[True]["game_stats"])
 
-    def as_bytes(arrs):
-        return tuple((a.dtype.str, a.shape, a.tobytes()) for a in arrs)
-
-    def by_game(f):                                  # a game = its eight augmentation triples, 24 consecutive datasets
-        return sorted(as_bytes([f[f"{kind}_{8 * g + j}"] for j in range(8) for kind in ("boards", "policies", "values")]) for g in range(games))
     want = []
     for r in recs:
         b, p, v, _ = record_to_samples(GAMES["TicTacToe"], r)
-        want.append(as_bytes([np.asarray(x[j]) for j in range(8) for x in (b, p, v)]))
+        want.append(tuple((a.dtype.str, a.shape, a.tobytes()) for a in [np.asarray(x[j]) for j in range(8) for x in (b, p, v)]))
     for ds in (False, True):
         assert len(out[ds]) == 1 + 3 * 8 * games
-    assert by_game(out[False]) == by_game(out[True])
-    assert by_game(out[True]) == sorted(want)
+    assert games_of_file(out[False], games, 8) == games_of_file(out[True], games, 8) == sorted(want)
 
 
 # ------------------------------------------------------------------------------------------------ (h) refusals
@@ -285,46 +271,22 @@ REFUSALS = {   # name -> engine arguments, what the message must say
 
 
 def refusal_case(name, lib_path):
-    from grok_alpha_zero_amd.engine import EngineError, SelfPlayEngine
+    from grok_alpha_zero_amd.engine import SelfPlayEngine
     kw, text = REFUSALS[name]
-    try:
-        SelfPlayEngine("Connect4", 8, 40, 42, 4, 4, 2.5, 0.5, seed=1, lib_path=lib_path, **kw).close()
-    except EngineError as e:
-        assert text in str(e) and "forced_playouts_k" in str(e), (name, str(e))
-        return str(e)
-    raise AssertionError(f"{name}: gaz_engine_create accepted {kw}")
+    msg = refusal_message(lambda: SelfPlayEngine("Connect4", 8, 40, 42, 4, 4, 2.5, 0.5, seed=1, lib_path=lib_path, **kw).close(),
+                          f"{name}: gaz_engine_create accepted {kw}")
+    assert text in msg and "forced_playouts_k" in msg, (name, msg)
+    return msg
 
 
 # ------------------------------------------------------------------------------------------------ (i) scheduling equalities (HIP build, network)
 def scheduling_case(which, G=64):
     """64 Connect4 games with a 1-block network and forced playouts on: the records do not depend on the fused launch, the game groups or
     the evaluation cache"""
-    from grok_alpha_zero_amd.engine import EVAL_RESNET, SelfPlayEngine
-    from grok_alpha_zero_amd.net import Connect4Net
     from forced_playouts_model import raw_target
-    w = Connect4Net(1, seed=0).eval().export_engine_weights()
 
-    def play(fused=True, **kw):
-        eng = SelfPlayEngine("Connect4", G, 40, 42, 4, 4, 2.5, 0.5, seed=SEED, evaluator=EVAL_RESNET, net_blocks=1, ring_capacity=4 * G, games_budget=G,
-                             forced_playouts_k=K, **kw)
-        eng.load_weights(w)
-        if not fused:
-            eng.set_fused_wave(False)
-        first = first_games(eng, G)
-        st = eng.stats()
-        eng.close()
-        return first, st
-    if which == "fused":
-        (a, sa), (b, sb) = play(game_groups=1), play(fused=False, game_groups=1)
-        assert sa["fused_wave"] == 1 and sb["fused_wave"] == 0, (sa, sb)
-    elif which == "groups":
-        (a, sa), (b, sb) = play(game_groups=2), play(game_groups=1)
-        assert sa["game_groups"] == 2 and sb["game_groups"] == 1
-    else:
-        (a, sa), (b, sb) = play(game_groups=1, eval_cache_log2=14), play(game_groups=1)
-        assert sa["cache_hits"] > 0 and sb["cache_hits"] == 0
-    pruned = 0
-    for s in range(G):
-        assert_records_equal(a[s], b[s], f"{which} slot {s}", keys=RECORD_KEYS + ("move_kind",))
-        pruned += sum(not np.array_equal(a[s]["policies"][t], raw_target(a[s]["root_N"][t])) for t in range(a[s]["T"]))
-    assert pruned > 0
+    def some_row_is_pruned(recs, _):
+        pruned = sum(not np.array_equal(r["policies"][t], raw_target(r["root_N"][t])) for r in recs.values() for t in range(r["T"]))
+        assert pruned > 0
+    scheduling_equalities(which, G, dict(seed=SEED, forced_playouts_k=K), lambda eng: (first_games(eng, G), None), some_row_is_pruned,
+                          keys=RECORD_KEYS + ("move_kind",))

@@ -8,12 +8,12 @@ import os
 
 import numpy as np
 
+from selfplay_support import MAXT, first_games
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 GUMBEL_FIXTURES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*_gumbel_*.npz")))
 CLASS_FIXTURES = ["c4_gsingle_nonoise", "ttt_gsingle_nonoise", "c4_gsingle_update"]
-MAXT = {"TicTacToe": 9, "Connect4": 42, "Gomoku": 225}
-A_OF = {"TicTacToe": 9, "Connect4": 7, "Gomoku": 225}
 RECORD_KEYS = ("actions", "root_N", "root_W", "root_P", "root_visits", "policies", "values", "q", "evals")
 PH_WAIT_HOST = 5
 
@@ -38,20 +38,6 @@ def assert_record_equals_oracle(r, o, what=""):
         np.testing.assert_array_equal(np.asarray(r[k]).reshape(np.asarray(o[k]).shape), o[k], err_msg=f"{what} {k}")
 
 
-def first_games(eng, n_slots, waves=64, rounds=20000):
-    """run a free-running engine until every slot's first game (game_seq = first_game_seq) is there: -> {slot: record}"""
-    first = {}
-    seq0 = int(eng.cfg.first_game_seq)
-    for _ in range(rounds):
-        eng.run_waves(waves)
-        for r in eng.drain_finished():
-            if r["game_seq"] == seq0:
-                first[r["slot"]] = r
-        if len(first) == n_slots:
-            return first
-    raise AssertionError(f"only {len(first)} of {n_slots} games finished")
-
-
 # ------------------------------------------------------------------------------------------------ 1. the reference's fixtures
 def play_gumbel_fixture(fx, K, lib_path):
     from grok_alpha_zero_amd.engine import SelfPlayEngine, SEARCH_GUMBEL
@@ -61,7 +47,7 @@ def play_gumbel_fixture(fx, K, lib_path):
                          gumbel_stablemax=bool(int(fx["stablemax"])) if "stablemax" in fx else False, first_game_seq=int(fx["game_seq"]),
                          gumbel_batch=K, lib_path=lib_path)
     assert eng.batch_rows == max(K, 1)
-    r = first_games(eng, 1)[int(fx["slot"])]
+    r = first_games(eng, 1, waves=64, rounds=20000)[int(fx["slot"])]
     eng.close()
     return r
 
@@ -127,7 +113,7 @@ def concurrent_case(oracle, name, G, lib_path, seed=23, salt=6, **kw):
     eng = SelfPlayEngine(game, G, iters, max_actions, 0, 0, 0.0, 0.0, seed=seed, hash_salt=salt, ring_capacity=4 * G, search=SEARCH_GUMBEL, gumbel_m=m,
                          c_visit=50.0, c_scale=1.0, gumbel_stablemax=stablemax, use_gumbel_noise=noise, gumbel_batch=K, lib_path=lib_path, **kw)
     assert eng.batch_rows == G * K and eng.stats()["fused_wave"] == 0 and eng.stats()["game_groups"] == 1
-    first = first_games(eng, G, waves=32)
+    first = first_games(eng, G, waves=32, rounds=20000)
     eng.close()
     for slot in range(G):
         o = oracle.selfplay_game_gumbel(game, iters, max_actions, m, 50.0, 1.0, seed, slot, 0, hash_salt=salt, stablemax=stablemax, gumbel_noise=noise)
@@ -242,7 +228,7 @@ def resnet_case(name, lib_path=None):
                              ring_capacity=4 * G, games_budget=G, search=SEARCH_GUMBEL, gumbel_m=m, c_visit=50.0, c_scale=1.0, gumbel_batch=k, lib_path=lib_path)
         eng.load_weights(w)
         assert eng.batch_rows == G * k
-        recs[k] = first_games(eng, G, waves=16)
+        recs[k] = first_games(eng, G, waves=16, rounds=20000)
         print(f"{name}: gumbel_batch {k}: {eng.stats()['waves']} waves, {eng.stats()['evals']} evaluator calls", flush=True)
         eng.close()
     for slot in range(G):

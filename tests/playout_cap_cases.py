@@ -7,13 +7,10 @@ the engine under test; the searches themselves are checked against tests/leaf_ba
 tests/test_leaf_batch_emu.py) and against engines created without the cap (Gumbel, anchors).  Every comparison is exact."""
 import numpy as np
 
-MAXT = {"TicTacToe": 9, "Connect4": 42, "Gomoku": 225}
-A_OF = {"TicTacToe": 9, "Connect4": 7, "Gomoku": 225}
-N_AUG = {"TicTacToe": 8, "Connect4": 2, "Gomoku": 8}
-SLOTS64 = (0, 1, 15, 16, 31, 32, 62, 63)          # first / last game of a wavefront's four teams, both ends of a 64-game batch
+from selfplay_support import (A_OF, MAXT, N_AUG, RECORD_KEYS, SEARCH_KEYS, assert_records_equal, check_batch, first_games, games_of_file,
+                              refusal_message, scheduling_equalities, self_play_file, slots_for)
+
 P_PLAYOUT_CAP = 5                                  # det::P_PLAYOUT_CAP
-RECORD_KEYS = ("actions", "root_N", "root_W", "root_P", "root_visits", "policies", "values", "q", "z", "evals")
-SEARCH_KEYS = ("actions", "policies", "q", "root_N", "root_W", "root_P", "root_visits", "evals")
 SEED = 31                                          # checked on the CPU (test_playout_cap_emu.py): both kinds occur after move 0 in every case below
 
 
@@ -30,50 +27,6 @@ def kinds_of(oracle, seed, slot, seq, T, p, start=0):
 
 def base_limits(kinds, R, F):
     return [R if k == 1 else min(F, R) for k in kinds]
-
-
-def slots_for(G):
-    return SLOTS64 if G >= 64 else tuple(range(G))
-
-
-def first_games(eng, n_slots, waves=32, rounds=40000, samples=False):
-    """a free-running engine until every slot's first game is there -> {slot: record}, or with `samples` {slot: (games row, boards,
-    policies, values)} through drain_samples"""
-    first, seq0 = {}, int(eng.cfg.first_game_seq)
-    for _ in range(rounds):
-        eng.run_waves(waves)
-        if samples:
-            b = eng.drain_samples()
-            check_batch(b)
-            for i in range(b.n):
-                if int(b.games[i, 3]) == seq0:
-                    bb, pp, vv, length, n_pos, w = b.game(i)
-                    assert length == n_pos == int(b.games[i, 0]) and w == int(b.games[i, 1])
-                    first[int(b.games[i, 2])] = (b.games[i].copy(), bb.copy(), pp.copy(), vv.copy())
-        else:
-            for r in eng.drain_finished():
-                if r["game_seq"] == seq0:
-                    first[r["slot"]] = r
-        if len(first) == n_slots:
-            return first
-    raise AssertionError(f"only {len(first)} of {n_slots} games finished")
-
-
-def check_batch(batch):
-    """row accounting of one SampleBatch: rows contiguous in the order of `games`, every game T - games[:, 5] of them"""
-    kept = batch.games[:, 0] - batch.games[:, 5]
-    assert (batch.games[:, 5] >= 0).all() and (kept >= 1).all() if batch.n else True
-    assert batch.boards.shape[1] == batch.policies.shape[1] == batch.values.shape[0] == int(kept.sum())
-    row = int(batch.games[0, 4]) if batch.n else 0
-    for i in range(batch.n):
-        assert int(batch.games[i, 4]) == row
-        row += int(kept[i])
-
-
-def assert_records_equal(a, b, what, keys=RECORD_KEYS):
-    assert (a["T"], a["winner"], a["slot"], a["game_seq"]) == (b["T"], b["winner"], b["slot"], b["game_seq"]), what
-    for k in keys:
-        np.testing.assert_array_equal(a[k], b[k], err_msg=f"{what} {k}")
 
 
 # ------------------------------------------------------------------------------------------------ 1. limits per move against the model
@@ -356,19 +309,11 @@ def row_accounting_case(lib_path, name="c4"):
 def run_self_play_case(tmp, lib_path, gumbel=False, games=40, G=24):
     """run_self_play with MCTS_fast_iteration_limit / full_search_prob: the same file at both settings of device_samples once the games
     are matched, total rows == the kept rows of an engine created with the scaled limits directly, game_stats count every ply"""
-    import os
     from grok_alpha_zero_amd.engine import SEARCH_GUMBEL, SelfPlayEngine
-    from grok_alpha_zero_amd.games import GAMES
-    from grok_alpha_zero_amd.self_play import ReplayStore, run_self_play
-    from samples_util import file_contents
     train = dict(games_per_generation=games, MCTS_iteration_limit=16, MCTS_fast_iteration_limit=4, full_search_prob=0.4, max_actions=9,
                  num_explore_actions_first=2, num_explore_actions_second=1, c_puct_init=1.25, dirichlet_alpha=1.0, use_gumbel=gumbel, m=4, c_visit=50.0, c_scale=1.0)
-    out = {}
-    for ds in (False, True):
-        folder = os.path.join(str(tmp), f"ds{ds}", "0")
-        store = ReplayStore(folder); store.create()
-        assert run_self_play(GAMES["TicTacToe"], ({}, train), folder, n_games=G, seed=11, hash_salt=4, lib_path=lib_path, device_samples=ds) == games
-        out[ds] = file_contents(store)
+    out = {ds: self_play_file(tmp, f"ds{ds}", "TicTacToe", train, games, n_games=G, seed=11, hash_salt=4, lib_path=lib_path, device_samples=ds)
+           for ds in (False, True)}
     R, F = (16, 4) if gumbel else (24, 6)                                             # PUCT: int(1.5 x) of both limits
     eng = SelfPlayEngine("TicTacToe", G, R, 9, 2, 1, 1.25, 1.0, seed=11, hash_salt=4, ring_capacity=4 * G, games_budget=games, fast_iterations=F,
                          full_search_prob=0.4, lib_path=lib_path, **(dict(search=SEARCH_GUMBEL, gumbel_m=4) if gumbel else {}))
@@ -391,14 +336,7 @@ def run_self_play_case(tmp, lib_path, gumbel=False, games=40, G=24):
         assert [gs[3], gs[4], gs[5]] == [winners.count(-1), winners.count(0), winners.count(1)]
         assert sum(f[f"values_{8 * k}"].shape[0] for k in range(games)) == kept
     np.testing.assert_array_equal(out[False]["game_stats"], out[True]["game_stats"])
-
-    def by_game(f):                                  # a game = its eight augmentation triples, 24 consecutive datasets
-        gs = []
-        for k in range(games):
-            arrs = [f[f"{kind}_{8 * k + j}"] for j in range(8) for kind in ("boards", "policies", "values")]
-            gs.append(tuple((a.dtype.str, a.shape, a.tobytes()) for a in arrs))
-        return sorted(gs)
-    assert by_game(out[False]) == by_game(out[True])
+    assert games_of_file(out[False], games, 8) == games_of_file(out[True], games, 8)
 
 
 # ------------------------------------------------------------------------------------------------ 7. refusals
@@ -415,14 +353,12 @@ REFUSALS = {   # name -> engine arguments, what the message must say
 
 
 def refusal_case(name, lib_path):
-    from grok_alpha_zero_amd.engine import EngineError, SelfPlayEngine
+    from grok_alpha_zero_amd.engine import SelfPlayEngine
     kw, text = REFUSALS[name]
-    try:
-        SelfPlayEngine("Connect4", 8, 40, 42, 4, 4, 2.5, 0.5, seed=1, lib_path=lib_path, **kw).close()
-    except EngineError as e:
-        assert text in str(e), (name, str(e))
-        return str(e)
-    raise AssertionError(f"{name}: gaz_engine_create accepted {kw}")
+    msg = refusal_message(lambda: SelfPlayEngine("Connect4", 8, 40, 42, 4, 4, 2.5, 0.5, seed=1, lib_path=lib_path, **kw).close(),
+                          f"{name}: gaz_engine_create accepted {kw}")
+    assert text in msg, (name, msg)
+    return msg
 
 
 def lower_run_iterations_case(oracle, lib_path):
@@ -453,31 +389,8 @@ def lower_run_iterations_case(oracle, lib_path):
 def scheduling_case(which, G=64):
     """64 Connect4 games with a 1-block network and the cap on: the records do not depend on the fused launch, the game groups or the
     evaluation cache"""
-    from grok_alpha_zero_amd.engine import EVAL_RESNET, SelfPlayEngine
-    from grok_alpha_zero_amd.net import Connect4Net
-    w = Connect4Net(1, seed=0).eval().export_engine_weights()
-
-    def play(fused=True, **kw):
-        eng = SelfPlayEngine("Connect4", G, 40, 42, 4, 4, 2.5, 0.5, seed=SEED, evaluator=EVAL_RESNET, net_blocks=1, ring_capacity=4 * G, games_budget=G,
-                             fast_iterations=8, full_search_prob=0.5, **kw)
-        eng.load_weights(w)
-        if not fused:
-            eng.set_fused_wave(False)
-        first = first_games(eng, G)
-        st = eng.stats()
-        eng.close()
-        return first, st
-    if which == "fused":
-        (a, sa), (b, sb) = play(game_groups=1), play(fused=False, game_groups=1)
-        assert sa["fused_wave"] == 1 and sb["fused_wave"] == 0, (sa, sb)
-    elif which == "groups":
-        (a, sa), (b, sb) = play(game_groups=2), play(game_groups=1)
-        assert sa["game_groups"] == 2 and sb["game_groups"] == 1
-    else:
-        (a, sa), (b, sb) = play(game_groups=1, eval_cache_log2=14), play(game_groups=1)
-        assert sa["cache_hits"] > 0 and sb["cache_hits"] == 0
-    n_fast = 0
-    for s in range(G):
-        assert_records_equal(a[s], b[s], f"{which} slot {s}", keys=RECORD_KEYS + ("move_kind",))
-        n_fast += int((a[s]["move_kind"] == 2).sum())
-    assert n_fast > 0
+    def some_move_is_fast(recs, _):
+        n_fast = sum(int((r["move_kind"] == 2).sum()) for r in recs.values())
+        assert n_fast > 0
+    scheduling_equalities(which, G, dict(seed=SEED, fast_iterations=8, full_search_prob=0.5), lambda eng: (first_games(eng, G), None), some_move_is_fast,
+                          keys=RECORD_KEYS + ("move_kind",))

@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from playout_cap_cases import MAXT, N_AUG, check_batch
+from selfplay_support import MAXT, N_AUG, check_batch, games_of_file, play, refusal_message, scheduling_equalities, self_play_file
 
 P_RESIGN = 6                                       # det::P_RESIGN
 SEED, SALT, NO_RESIGN_PROB = 31, 6, 0.5
@@ -107,28 +107,6 @@ def make_engine(name, G, lib_path, rule=None, games=None, **kw):
     if rule is not None:
         a.update(resign_threshold=rule[0], resign_consecutive=rule[1], resign_min_ply=rule[2], no_resign_prob=rule[3])
     return SelfPlayEngine(game, G, *args, **a)
-
-
-def play(eng, n, waves=32, rounds=40000, raw=False):
-    """a free-running engine until n games are there -> {(slot, game_seq): record}; raw: the records' bytes instead of dicts"""
-    out = {}
-    for _ in range(rounds):
-        eng.run_waves(waves)
-        if raw:
-            lay = eng.layout
-            buf = np.zeros((max(eng.cfg.ring_capacity, 1), lay.record_bytes), np.uint8)
-            got = C.c_int32()
-            eng._ck(eng.L.gaz_engine_drain_finished(eng.h, buf.ctypes.data, buf.shape[0], C.byref(got)))
-            for i in range(got.value):
-                hdr = buf[i, lay.off_hdr:lay.off_hdr + 16].view(np.int32)
-                out[(int(hdr[2]), int(hdr[3]))] = buf[i].copy()
-        else:
-            for r in eng.drain_finished():
-                out[(r["slot"], r["game_seq"])] = r
-        if len(out) >= n:
-            assert len(out) == n, (len(out), n)
-            return out
-    raise AssertionError(f"only {len(out)} of {n} games finished")
 
 
 def assert_prefix(on, off, e, what):
@@ -319,11 +297,7 @@ def run_self_play_case(tmp, lib_path, games=40, G=24, game="TicTacToe"):
     device_samples, engine_stats["resign"] filled, the tail's repack taken.  (Whether run_self_play meets a half-empty launch depends on how
     many games end between two of its drains: on the HIP build 64 waves finish a whole TicTacToe game, so the GPU suite plays Connect4,
     whose last games end over several hundred waves.)"""
-    import os
     from grok_alpha_zero_amd import engine as E
-    from grok_alpha_zero_amd.games import GAMES
-    from grok_alpha_zero_amd.self_play import ReplayStore, run_self_play
-    from samples_util import file_contents
     n_aug = N_AUG[game]
     train = dict(games_per_generation=games, MCTS_iteration_limit=16, max_actions=MAXT[game], num_explore_actions_first=2, num_explore_actions_second=1,
                  c_puct_init=1.25, dirichlet_alpha=1.0, use_gumbel=False, resign_threshold=RSP_RULE[0], resign_consecutive=RSP_RULE[1],
@@ -337,12 +311,9 @@ def run_self_play_case(tmp, lib_path, games=40, G=24, game="TicTacToe"):
     E.SelfPlayEngine.repack = counting
     try:
         for ds in (False, True):
-            folder = os.path.join(str(tmp), f"ds{ds}", "0")
-            store = ReplayStore(folder); store.create()
             est[ds] = {}
-            assert run_self_play(GAMES[game], ({}, train), folder, n_games=G, seed=11, hash_salt=4, lib_path=lib_path, device_samples=ds,
-                                 engine_stats=est[ds]) == games
-            out[ds] = file_contents(store)
+            out[ds] = self_play_file(tmp, f"ds{ds}", game, train, games, n_games=G, seed=11, hash_salt=4, lib_path=lib_path, device_samples=ds,
+                                     engine_stats=est[ds])
             assert repacks, "the tail of the generation was not repacked"
             del repacks[:]
     finally:
@@ -359,11 +330,7 @@ def run_self_play_case(tmp, lib_path, games=40, G=24, game="TicTacToe"):
         assert est[ds]["resign"] == direct, (est[ds]["resign"], direct)
         assert [int(x) for x in f["game_stats"]] == game_stats_of(recs), f["game_stats"]
         assert len(f) == 1 + 3 * n_aug * games and sum(f[f"values_{n_aug * k}"].shape[0] for k in range(games)) == plies
-
-    def by_game(f):                                  # a game = its augmentation triples, 3 n_aug consecutive datasets
-        return sorted(tuple((a.dtype.str, a.shape, a.tobytes()) for a in [f[f"{kind}_{n_aug * k + j}"] for j in range(n_aug) for kind in ("boards", "policies", "values")])
-                      for k in range(games))
-    assert by_game(out[False]) == by_game(out[True])
+    assert games_of_file(out[False], games, n_aug) == games_of_file(out[True], games, n_aug)
     return direct
 
 
@@ -408,7 +375,7 @@ REFUSALS = {   # name -> set_resignation arguments (threshold, consecutive, min_
 
 def refusal_case(name, lib_path):
     """-> the message.  A refused call leaves the engine as it was: off"""
-    from grok_alpha_zero_amd.engine import EngineError, ResignParams, SelfPlayEngine
+    from grok_alpha_zero_amd.engine import ResignParams, SelfPlayEngine
     eng = SelfPlayEngine("Connect4", 4, 40, 42, 4, 4, 2.5, 0.5, seed=1, lib_path=lib_path)
     try:
         if name == "struct-size":
@@ -418,20 +385,11 @@ def refusal_case(name, lib_path):
             assert "struct_size" in msg, msg
         else:
             args, text = REFUSALS[name]
-            try:
-                eng.set_resignation(*args)
-            except EngineError as e:
-                msg = str(e)
-                assert text in msg, (name, msg)
-            else:
-                raise AssertionError(f"{name}: gaz_engine_set_resignation accepted {args}")
-            try:                                     # the constructor keywords go through the same call
-                SelfPlayEngine("Connect4", 4, 40, 42, 4, 4, 2.5, 0.5, seed=1, lib_path=lib_path, resign_threshold=args[0], resign_consecutive=args[1],
-                               resign_min_ply=args[2], no_resign_prob=args[3]).close()
-            except EngineError as e:
-                assert text in str(e)
-            else:
-                raise AssertionError(f"{name}: the constructor accepted {args}")
+            msg = refusal_message(lambda: eng.set_resignation(*args), f"{name}: gaz_engine_set_resignation accepted {args}")
+            assert text in msg, (name, msg)
+            kw = dict(resign_threshold=args[0], resign_consecutive=args[1], resign_min_ply=args[2], no_resign_prob=args[3])
+            assert text in refusal_message(lambda: SelfPlayEngine("Connect4", 4, 40, 42, 4, 4, 2.5, 0.5, seed=1, lib_path=lib_path, **kw).close(),
+                                           f"{name}: the constructor accepted {args}")      # the constructor keywords go through the same call
         return msg
     finally:
         eng.close()
@@ -441,32 +399,9 @@ def refusal_case(name, lib_path):
 def scheduling_case(which, G=64):
     """64 Connect4 games with a 1-block network and resignation on: the records do not depend on the fused launch, the game groups or the
     evaluation cache"""
-    from grok_alpha_zero_amd.engine import EVAL_RESNET, SelfPlayEngine
-    from grok_alpha_zero_amd.net import Connect4Net
-    w = Connect4Net(1, seed=0).eval().export_engine_weights()
     rule = (0.3, 2, 0, 0.5)
 
-    def run(fused=True, **kw):
-        eng = SelfPlayEngine("Connect4", G, 40, 42, 4, 4, 2.5, 0.5, seed=SEED, evaluator=EVAL_RESNET, net_blocks=1, ring_capacity=4 * G, games_budget=G,
-                             resign_threshold=rule[0], resign_consecutive=rule[1], resign_min_ply=rule[2], no_resign_prob=rule[3], **kw)
-        eng.load_weights(w)
-        if not fused:
-            eng.set_fused_wave(False)
-        recs = play(eng, G, raw=True)
-        st, rs = eng.stats(), eng.resign_stats()
-        eng.close()
-        return recs, st, rs
-    if which == "fused":
-        (a, sa, ra), (b, sb, rb) = run(game_groups=1), run(fused=False, game_groups=1)
-        assert sa["fused_wave"] == 1 and sb["fused_wave"] == 0, (sa, sb)
-    elif which == "groups":
-        (a, sa, ra), (b, sb, rb) = run(game_groups=2), run(game_groups=1)
-        assert sa["game_groups"] == 2 and sb["game_groups"] == 1
-    else:
-        (a, sa, ra), (b, sb, rb) = run(game_groups=1, eval_cache_log2=14), run(game_groups=1)
-        assert sa["cache_hits"] > 0 and sb["cache_hits"] == 0
-    assert sorted(a) == sorted(b) == [(s, 0) for s in range(G)]
-    for k in a:
-        assert a[k].tobytes() == b[k].tobytes(), (which, k)
-    assert ra == rb and ra["resigned"] > 0 and ra["playout_games"] > 0, (ra, rb)
-    print(f"scheduling {which}: {ra}", flush=True)
+    def some_game_resigned(recs, rs):
+        assert rs["resigned"] > 0 and rs["playout_games"] > 0, rs
+    scheduling_equalities(which, G, dict(seed=SEED, resign_threshold=rule[0], resign_consecutive=rule[1], resign_min_ply=rule[2], no_resign_prob=rule[3]),
+                          lambda eng: (play(eng, G, raw=True), eng.resign_stats()), some_game_resigned)

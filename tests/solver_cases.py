@@ -7,7 +7,8 @@ status the engine exports is held against solver_model.minimax, which shares not
 returns a Witness: what it reached, so that a test can assert that it did not pass vacuously."""
 import numpy as np
 
-from playout_cap_cases import A_OF, MAXT, RECORD_KEYS, SLOTS64, assert_records_equal, first_games
+from selfplay_support import (A_OF, MAXT, RECORD_KEYS, assert_records_equal, c4_one_block_weights, first_games, games_of_file, net_engine, play,
+                              refusal_message, scheduling_equalities, self_play_file)
 
 SEED, SALT = 31, 8
 PH_WAIT_HOST, PH_HALT = 5, 8
@@ -310,18 +311,16 @@ REFUSALS = {   # name -> engine arguments, what the message must say
 
 
 def refusal_case(which, lib_path):
-    from grok_alpha_zero_amd.engine import EngineError, SelfPlayEngine
+    from grok_alpha_zero_amd.engine import SelfPlayEngine
     kw, text = REFUSALS[which]
     eng = SelfPlayEngine("Connect4", 4, 16, 42, 0, 0, 2.5, 0.5, seed=1, hash_salt=1, lib_path=lib_path, **kw)
     try:
-        eng.set_solver(True)
-    except EngineError as e:
-        assert text in str(e), (which, str(e))
+        msg = refusal_message(lambda: eng.set_solver(True), f"{which}: set_solver was not refused")
+        assert text in msg, (which, msg)
         assert not eng.solver and list(eng.solver_stats().values()) == [0] * 8
-        return str(e)
+        return msg
     finally:
         eng.close()
-    raise AssertionError(f"{which}: set_solver was not refused")
 
 
 # ------------------------------------------------------------------------------------------------ anchors
@@ -387,23 +386,12 @@ def samples_case(name, G, lib_path):
 
 def run_self_play_case(tmp, lib_path, games=12, G=8):
     """train_config["solver"]: absent and False give the same file, True another one"""
-    import os
-    from grok_alpha_zero_amd.games import GAMES
-    from grok_alpha_zero_amd.self_play import ReplayStore, run_self_play
-    from samples_util import file_contents
     train = dict(games_per_generation=games, MCTS_iteration_limit=200, max_actions=9, num_explore_actions_first=2, num_explore_actions_second=1,
                  c_puct_init=1.25, dirichlet_alpha=1.0, use_gumbel=False)
-    n_aug = 8
-
-    def by_game(f):                                  # (the order in which games reach the file is scheduling: compare them as a set)
-        return sorted(tuple((a.dtype.str, a.shape, a.tobytes()) for a in [f[f"{kind}_{n_aug * k + j}"] for j in range(n_aug) for kind in ("boards", "policies", "values")])
-                      for k in range(games))
     out = []
     for extra in ({}, dict(solver=False), dict(solver=True)):
-        folder = os.path.join(str(tmp), str(len(out)), "0")
-        store = ReplayStore(folder); store.create()
-        assert run_self_play(GAMES["TicTacToe"], ({}, dict(train, **extra)), folder, n_games=G, seed=11, hash_salt=4, lib_path=lib_path) == games
-        out.append(by_game(file_contents(store)))
+        f = self_play_file(tmp, str(len(out)), "TicTacToe", dict(train, **extra), games, n_games=G, seed=11, hash_salt=4, lib_path=lib_path)
+        out.append(games_of_file(f, games, 8))
     assert out[0] == out[1] and out[0] != out[2]
 
 
@@ -478,51 +466,19 @@ def gpu_slots(G=64):
     return (0, 1, 2, 3) + tuple(range(4, G, 4))
 
 
-def _net_engine(G, weights, fused=True, **kw):
-    from grok_alpha_zero_amd.engine import EVAL_RESNET, SelfPlayEngine
-    eng = SelfPlayEngine("Connect4", G, 40, 42, 4, 4, 2.5, 0.5, seed=SEED, evaluator=EVAL_RESNET, net_blocks=1, ring_capacity=4 * G, games_budget=G,
-                         solver=True, **kw)
-    eng.load_weights(weights)
-    if not fused:
-        eng.set_fused_wave(False)
-    return eng
-
-
 def scheduling_case(which, G=64):
     """64 Connect4 games, 1-block network, solver on: the records do not depend on the fused launch, the game groups or the evaluation cache"""
-    from grok_alpha_zero_amd.net import Connect4Net
-    from resign_cases import play
-    w = Connect4Net(1, seed=0).eval().export_engine_weights()
-
-    def run(fused=True, **kw):
-        eng = _net_engine(G, w, fused, **kw)
-        recs = play(eng, G, raw=True)
-        st, sv = eng.stats(), eng.solver_stats()
-        eng.close()
-        return recs, st, sv
-    if which == "fused":
-        (a, sa, va), (b, sb, vb) = run(game_groups=1), run(fused=False, game_groups=1)
-        assert sa["fused_wave"] == 1 and sb["fused_wave"] == 0, (sa, sb)
-    elif which == "groups":
-        (a, sa, va), (b, sb, vb) = run(game_groups=2), run(game_groups=1)
-        assert sa["game_groups"] == 2 and sb["game_groups"] == 1
-    else:
-        (a, sa, va), (b, sb, vb) = run(game_groups=1, eval_cache_log2=14), run(game_groups=1)
-        assert sa["cache_hits"] > 0 and sb["cache_hits"] == 0
-    assert sorted(a) == sorted(b) == [(s, 0) for s in range(G)]
-    for k in a:
-        assert np.array_equal(a[k], b[k]), (which, k)
-    assert va == vb and va["proven_moves"] > 0 and va["masked_levels"] > 0, (va, vb)
-    print(f"scheduling {which}: {G} games identical, {va}", flush=True)
+    def some_move_is_proven(recs, sv):
+        assert sv["proven_moves"] > 0 and sv["masked_levels"] > 0, sv
+    scheduling_equalities(which, G, dict(seed=SEED, solver=True), lambda eng: (play(eng, G, raw=True), eng.solver_stats()), some_move_is_proven)
 
 
 def network_case(oracle, G=64, slots=(0, 1, 2, 3, 32, 63)):
     """64 Connect4 games with the 1-block network in the fused launch, solver on; the compared slots replayed by the model whose evaluator is
     a second engine's evaluate() on single rows"""
     from grok_alpha_zero_amd.engine import EVAL_RESNET, SelfPlayEngine
-    from grok_alpha_zero_amd.net import Connect4Net
-    w = Connect4Net(1, seed=0).eval().export_engine_weights()
-    eng = _net_engine(G, w)
+    w = c4_one_block_weights()
+    eng = net_engine(G, w, seed=SEED, solver=True)
     first = first_games(eng, G)
     assert eng.stats()["fused_wave"] == 1
     eng.close()

@@ -11,20 +11,13 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from selfplay_support import emu_lib  # noqa: F401
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import abi_stub  # noqa: E402
 from grok_alpha_zero_amd import engine as E  # noqa: E402
 
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
 HDR = os.path.join(ROOT, "include", "gaz_engine.h")
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
 
 
 def _ctypes_fields(cls):

@@ -12,18 +12,11 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from selfplay_support import emu_lib  # noqa: F401
 
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
 BENCH = os.path.join(ROOT, "bench.py")
 SMALL = ["--evaluator", "hash", "--games", "6", "--sims", "20", "--steps", "2", "--warmup", "1", "--waves-per-step", "40",
          "--no-cpu-baseline", "--cache-leg", "0", "--ref-convention-leg", "0"]
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
 
 
 def _clean_env():

@@ -1,26 +1,15 @@
 """CPU suite: the searches on tied, zero and saturated evaluator outputs (tests/degenerate_eval.py) on the emulation build of the device
 code — the cases of tests/degenerate_cases.py at sizes the one-lane emulation plays in seconds.  Exact equality everywhere; the tie and
 zero-mass witnesses are asserted on the oracle's / the model's side."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import degenerate_cases as cases
 import degenerate_eval as E
-from conftest import ROOT
+from selfplay_support import emu_lib  # noqa: F401
 
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
 f32 = np.float32
 GAMES3 = ("TicTacToe", "Connect4", "Gomoku")
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
 
 
 # ------------------------------------------------------------------------------------------------ the evaluators

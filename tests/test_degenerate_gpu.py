@@ -3,84 +3,68 @@ tests/degenerate_cases.py with 64 games at once (four 16-lane teams per wavefron
 for Gomoku), where the tie rules are cross-lane butterflies (wave.hpp) and not the serial loops of the emulation build.  Bit-equal: no
 tolerance.  Every step prints its witness counts (tied plies, collisions, zero-mass rows) and asserts them.
 
-Every GPU step is a child process of its own under a time limit (this file run as a script with the case's name); after a child that
-was killed or ran out of time nothing more is started."""
+Every GPU case runs as a child step of the shared runner, tests/gpu_step.py."""
 import os
-import subprocess
 import sys
 
 import pytest
+
+from gpu_step import STEPS
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GAMES3 = ("TicTacToe", "Connect4", "Gomoku")
-_dead = []
-
-
-def _step(case, seconds, env=None):
-    if _dead:
-        pytest.fail(f"not started: the GPU step {_dead[0]} was killed or ran out of time")
-    try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), case], cwd=ROOT, timeout=seconds, capture_output=True, text=True,
-                           env=dict(os.environ, **(env or {})))
-    except subprocess.TimeoutExpired:
-        _dead.append(case)
-        pytest.fail(f"{case}: no result within {seconds} s")
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        _dead.append(case)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, f"{case}: exit status {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
 
 
 # ------------------------------------------------------------------------------------------------ a.
 @pytest.mark.parametrize("game", GAMES3)
 def test_puct_selfplay_on_tied_priors_equals_the_oracle(game):
-    _step(f"puct-ties:{game}", 240)
+    STEPS.run(__file__, f"puct-ties:{game}", 240)
 
 
 @pytest.mark.parametrize("game", GAMES3)
 def test_puct_selfplay_on_zero_mass_rows_equals_the_oracle(game):
-    _step(f"puct-zeromass:{game}", 240)
+    STEPS.run(__file__, f"puct-zeromass:{game}", 240)
 
 
 # ------------------------------------------------------------------------------------------------ b.
 @pytest.mark.parametrize("game", GAMES3)
 def test_gumbel_selfplay_equals_the_oracle_at_both_batch_sizes(game):
-    _step(f"gumbel:{game}", 240)
+    STEPS.run(__file__, f"gumbel:{game}", 240)
 
 
 def test_gumbel_connect4_four_games_per_wavefront():
     """GAZ_TREE_TEAMS=1: k_wave_gumbel_teams (16-lane teams) instead of one game per wavefront; the batched step is a team kernel either way"""
-    _step("gumbel:Connect4", 240, env={"GAZ_TREE_TEAMS": "1"})
+    STEPS.run(__file__, "gumbel:Connect4", 240, env={"GAZ_TREE_TEAMS": "1"})
 
 
 # ------------------------------------------------------------------------------------------------ c.
 @pytest.mark.parametrize("game,K", [("TicTacToe", 4), ("TicTacToe", 16), ("Connect4", 4), ("Connect4", 16), ("Gomoku", 16)])
 def test_leaf_batched_search_equals_the_model(game, K):
-    _step(f"leaf:{game}:{K}", 240)
+    STEPS.run(__file__, f"leaf:{game}:{K}", 240)
 
 
 @pytest.mark.parametrize("game", ("TicTacToe", "Connect4"))
 def test_forced_playouts_equal_the_model(game):
-    _step(f"forced:{game}", 240)
+    STEPS.run(__file__, f"forced:{game}", 240)
 
 
 @pytest.mark.parametrize("game", ("TicTacToe", "Connect4"))
 def test_leaf_batched_search_without_noise_sees_tied_priors(game):
-    _step(f"leaf-no-noise:{game}", 240)
+    STEPS.run(__file__, f"leaf-no-noise:{game}", 240)
 
 
 # ------------------------------------------------------------------------------------------------ d.
 @pytest.mark.parametrize("game", ("TicTacToe", "Connect4"))
 def test_tree_readout_after_a_uniform_search(game):
-    _step(f"readout:{game}", 240)
+    STEPS.run(__file__, f"readout:{game}", 240)
 
 
 # ------------------------------------------------------------------------------------------------ e.
 @pytest.mark.parametrize("case", ["groups1", "groups2", "groups1-cache", "groups2-cache", "gumbel", "gumbel-one-game-per-wave", "gomoku"])
 def test_constant_network_in_the_production_launch_shape(case):
-    _step(f"net:{case}", 240, env={"GAZ_FUSE_GUMBEL_TEAMS": "0"} if case == "gumbel-one-game-per-wave" else None)
+    STEPS.run(__file__, f"net:{case}", 240, env={"GAZ_FUSE_GUMBEL_TEAMS": "0"} if case == "gumbel-one-game-per-wave" else None)
 
 
 # ------------------------------------------------------------------------------------------------ the steps (run in the child)

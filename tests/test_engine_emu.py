@@ -3,22 +3,14 @@ logic (C ABI, state machine, record ring) against the golden vectors recorded fr
 This is test infrastructure: the product library is the hipcc build and is covered by the -m gpu tests."""
 import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
+from selfplay_support import EMU, emu_lib  # noqa: F401
 
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
 CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*_puct_*.npz")) if "_open" not in p)
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
 
 
 def play_fixture(fx, lib_path, **kw):

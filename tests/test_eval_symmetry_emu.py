@@ -1,24 +1,12 @@
 """CPU suite: the search's random evaluation symmetry (gaz_engine_set_eval_symmetry) on the emulation build of the device code — the
 cases of tests/eval_symmetry_cases.py at sizes the one-lane emulation plays in seconds.  Exact equality everywhere.  Every test switches
 the symmetry on, so none of them passes on a library without the entry points."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import eval_symmetry_cases as cases
 import eval_symmetry_model as M
-from conftest import ROOT
-
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
+from selfplay_support import emu_lib  # noqa: F401
 
 
 # ------------------------------------------------------------------------------------------------ the restated rule and the shipped helpers

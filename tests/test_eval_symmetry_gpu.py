@@ -5,32 +5,17 @@ slots, and the lock-step Connect4 games are capped at 16 plies: both keep the ho
 row-by-row answers) to seconds.  Then the scheduling equalities with a 1-block network, and whole games with that network against the
 oracle.  Exact equality everywhere: no tolerance.
 
-Every GPU step is a child process of its own under a time limit (this file run as a script with the case's name); after a child that
-was killed or ran out of time nothing more is started."""
+Every GPU case runs as a child step of the shared runner, tests/gpu_step.py."""
 import os
-import subprocess
 import sys
 
 import pytest
 
+from gpu_step import STEPS
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_dead = []
-
-
-def _step(case, seconds):
-    if _dead:
-        pytest.fail(f"not started: the GPU step {_dead[0]} was killed or ran out of time")
-    try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), case], cwd=ROOT, timeout=seconds, capture_output=True, text=True)
-    except subprocess.TimeoutExpired:
-        _dead.append(case)
-        pytest.fail(f"{case}: no result within {seconds} s")
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        _dead.append(case)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, f"{case}: exit status {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
 
 
 # ------------------------------------------------------------------------------------------------ the cases (run in the child)
@@ -81,60 +66,60 @@ def _run_case(name):
 # ------------------------------------------------------------------------------------------------ the tests
 @pytest.mark.parametrize("name", ["ttt", "c4", "gmk", "c4-gumbel", "gmk-gumbel"])
 def test_selfplay_equals_the_oracle_with_the_wrapped_evaluator(name):
-    _step("selfplay:" + name, 180)
+    STEPS.run(__file__, "selfplay:" + name, 180)
 
 
 @pytest.mark.parametrize("arg", ["Connect4,4,0", "Connect4,16,0", "Connect4,1,2", "Gomoku,4,0", "TicTacToe,16,0"])
 def test_engine_equals_the_models_with_the_wrapped_evaluator(arg):
-    _step("model:" + arg, 120)
+    STEPS.run(__file__, "model:" + arg, 120)
 
 
 def test_mode_0_after_mode_1_between_moves():
-    _step("switch:Connect4,4", 120)
+    STEPS.run(__file__, "switch:Connect4,4", 120)
 
 
 @pytest.mark.parametrize("name", ["c4-gumbel", "gmk-gumbel"])
 def test_gumbel_batch_4_equals_1(name):
-    _step("gumbel_batch:" + name, 120)
+    STEPS.run(__file__, "gumbel_batch:" + name, 120)
 
 
 @pytest.mark.parametrize("name", ["ttt", "c4", "gmk"])
 def test_lockstep_through_the_external_evaluator(name):
-    _step("lockstep:" + name, 180)
+    STEPS.run(__file__, "lockstep:" + name, 180)
 
 
 def test_lockstep_through_the_external_evaluator_gumbel():
-    _step("lockstep-gumbel", 180)
+    STEPS.run(__file__, "lockstep-gumbel", 180)
 
 
 def test_an_equivariant_evaluator_gives_the_off_records():
-    _step("equivariant", 120)
+    STEPS.run(__file__, "equivariant", 120)
 
 
 @pytest.mark.parametrize("name", ["c4", "c4-gumbel"])
 def test_drain_samples_equals_record_to_samples(name):
-    _step("samples:" + name, 120)
+    STEPS.run(__file__, "samples:" + name, 120)
 
 
 def test_run_self_play_reads_the_key():
-    _step("run_self_play", 120)
+    STEPS.run(__file__, "run_self_play", 120)
 
 
 def test_mcts_classes():
-    _step("mcts", 120)
+    STEPS.run(__file__, "mcts", 120)
 
 
 def test_refusals():
-    _step("refusals", 120)
+    STEPS.run(__file__, "refusals", 120)
 
 
 @pytest.mark.parametrize("which", ["fused", "groups", "cache"])
 def test_records_do_not_depend_on_scheduling(which):
-    _step("scheduling:" + which, 180)
+    STEPS.run(__file__, "scheduling:" + which, 180)
 
 
 def test_the_real_network_against_the_oracle():
-    _step("network", 180)
+    STEPS.run(__file__, "network", 180)
 
 
 if __name__ == "__main__":

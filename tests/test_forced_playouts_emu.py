@@ -1,25 +1,14 @@
 """CPU suite: forced playouts and policy target pruning (gaz_engine_config.forced_playouts_k) on the emulation build of the device
 code — the model's own anchors, then the cases of tests/forced_playouts_cases.py at sizes the one-lane emulation plays in seconds.
 Exact equality everywhere."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import forced_playouts_cases as cases
 import forced_playouts_model as model
-from conftest import ROOT
+from selfplay_support import emu_lib  # noqa: F401
 
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
 f32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
 
 
 # ------------------------------------------------------------------------------------------------ the model (no engine)

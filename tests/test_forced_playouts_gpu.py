@@ -3,32 +3,17 @@ tests/forced_playouts_cases.py with 64 games at once (four games per wavefront, 
 Gomoku's 225-child root spread four children to a lane), and the scheduling equalities with the network.  Exact equality
 everywhere: no tolerance.
 
-Every GPU step is a child process of its own under a time limit (this file run as a script with the case's name); after a child that
-was killed or ran out of time nothing more is started."""
+Every GPU case runs as a child step of the shared runner, tests/gpu_step.py."""
 import os
-import subprocess
 import sys
 
 import pytest
 
+from gpu_step import STEPS
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_dead = []
-
-
-def _step(case, seconds):
-    if _dead:
-        pytest.fail(f"not started: the GPU step {_dead[0]} was killed or ran out of time")
-    try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), case], cwd=ROOT, timeout=seconds, capture_output=True, text=True)
-    except subprocess.TimeoutExpired:
-        _dead.append(case)
-        pytest.fail(f"{case}: no result within {seconds} s")
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        _dead.append(case)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, f"{case}: exit status {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
 
 
 # ------------------------------------------------------------------------------------------------ the cases (run in the child)
@@ -62,34 +47,34 @@ def _run_case(name):
 # ------------------------------------------------------------------------------------------------ the tests
 @pytest.mark.parametrize("name", ["ttt", "c4-k1", "c4-k4", "gmk"])
 def test_sync_searches_equal_the_model_and_policy_is_the_pruned_target(name):
-    _step("hash:" + name, 120)
+    STEPS.run(__file__, "hash:" + name, 120)
 
 
 @pytest.mark.parametrize("cap", ["plain", "cap"])
 def test_continuous_selfplay_two_trees_equal_the_model(cap):
-    _step("selfplay:" + cap, 120)
+    STEPS.run(__file__, "selfplay:" + cap, 120)
 
 
 def test_k_0_anchor_and_terminal_parent_root():
-    _step("anchors", 120)
+    STEPS.run(__file__, "anchors", 120)
 
 
 @pytest.mark.parametrize("name", ["c4", "gmk"])
 def test_samples_carry_the_pruned_target(name):
-    _step("samples:" + name, 120)
+    STEPS.run(__file__, "samples:" + name, 120)
 
 
 def test_run_self_play_reads_the_train_config_key():
-    _step("run_self_play", 120)
+    STEPS.run(__file__, "run_self_play", 120)
 
 
 def test_refusals():
-    _step("refusals", 60)
+    STEPS.run(__file__, "refusals", 60)
 
 
 @pytest.mark.parametrize("which", ["fused", "groups", "cache"])
 def test_records_do_not_depend_on_scheduling(which):
-    _step("scheduling:" + which, 180)
+    STEPS.run(__file__, "scheduling:" + which, 180)
 
 
 if __name__ == "__main__":

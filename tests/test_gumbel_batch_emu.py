@@ -1,23 +1,11 @@
 """CPU suite: batched sequential halving (gaz_engine_config.gumbel_batch = K — the candidates of one halving phase of the Gumbel search
 in one evaluator batch) on the emulation build of the device code.  The search does not change, so the yardsticks are the reference's own
 fixtures and the oracle, unchanged, and every comparison is bit for bit (tests/gumbel_batch_cases.py)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
 import gumbel_batch_cases as GB
-
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
+from selfplay_support import emu_lib  # noqa: F401
 
 
 # ------------------------------------------------------------------------------------------------ 1. the reference's fixtures

@@ -1,24 +1,10 @@
 """CPU suite: the leaf-batched PUCT search (gaz_engine_config.leaf_batch = K) on the emulation build of the device code against the
 test model of tests/leaf_batch_model.py, which is itself anchored to the oracle at K = 1.  Bit-equal everywhere: no tolerance."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
 from leaf_batch_model import WIN as WIN_CHILD, Tree, selfplay_moves
-
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
-A_OF = {"TicTacToe": 9, "Connect4": 7, "Gomoku": 225}
-MAXT = {"TicTacToe": 9, "Connect4": 42, "Gomoku": 225}
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
+from selfplay_support import A_OF, MAXT, emu_lib  # noqa: F401 (emu_lib: a fixture)
 
 
 # ------------------------------------------------------------------------------------------------ 1. the model is sound

@@ -2,22 +2,13 @@
 run / prune_tree surface) on the emulation build, against fixtures recorded by driving the REFERENCE's classes the same way
 (single tree playing both sides, tools/gen_golden.py: ref_single_tree_puct) and against the Self_Play Gumbel fixtures."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 from grok_alpha_zero_amd.games import GAMES
-
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
+from selfplay_support import emu_lib  # noqa: F401
 
 
 class _HashSession:

@@ -1,22 +1,10 @@
 """CPU suite: playout cap randomisation (gaz_engine_config.fast_iterations / full_search_prob) on the emulation build of the device
 code — the cases of tests/playout_cap_cases.py at sizes the one-lane emulation plays in seconds.  Exact equality everywhere."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import playout_cap_cases as cases
-from conftest import ROOT
-
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
+from selfplay_support import emu_lib  # noqa: F401
 
 
 # ------------------------------------------------------------------------------------------------ the draws themselves (no engine)

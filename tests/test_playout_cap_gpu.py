@@ -3,32 +3,17 @@ tests/playout_cap_cases.py at the sizes where the launch shapes matter (64 games
 128 games in two game groups; Gomoku games longer than 128 plies through the sample kernel's compaction), and the scheduling
 equalities with the network.  Exact equality everywhere: no tolerance.
 
-Every GPU step is a child process of its own under a time limit (this file run as a script with the case's name); after a child that
-was killed or ran out of time nothing more is started."""
+Every GPU case runs as a child step of the shared runner, tests/gpu_step.py."""
 import os
-import subprocess
 import sys
 
 import pytest
 
+from gpu_step import STEPS
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_dead = []
-
-
-def _step(case, seconds):
-    if _dead:
-        pytest.fail(f"not started: the GPU step {_dead[0]} was killed or ran out of time")
-    try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), case], cwd=ROOT, timeout=seconds, capture_output=True, text=True)
-    except subprocess.TimeoutExpired:
-        _dead.append(case)
-        pytest.fail(f"{case}: no result within {seconds} s")
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        _dead.append(case)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, f"{case}: exit status {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
 
 
 # ------------------------------------------------------------------------------------------------ the cases (run in the child)
@@ -81,47 +66,47 @@ def _run_case(name):
 # ------------------------------------------------------------------------------------------------ the tests
 @pytest.mark.parametrize("name", ["ttt", "c4-k1", "c4-k4", "gmk"])
 def test_limits_per_move_equal_the_model(name):
-    _step("hash:" + name, 300 if name == "gmk" else 120)
+    STEPS.run(__file__, "hash:" + name, 300 if name == "gmk" else 120)
 
 
 @pytest.mark.parametrize("name", ["ttt", "c4"])
 def test_continuous_selfplay_two_trees_equal_the_model(name):
-    _step("selfplay:" + name, 120)
+    STEPS.run(__file__, "selfplay:" + name, 120)
 
 
 def test_anchors_p1_and_fast_equal_full():
-    _step("anchors", 120)
+    STEPS.run(__file__, "anchors", 120)
 
 
 def test_gumbel_comparator_holds_without_the_cap():
-    _step("gumbel:plain", 120)
+    STEPS.run(__file__, "gumbel:plain", 120)
 
 
 def test_gumbel_with_the_cap_equals_host_set_limits():
-    _step("gumbel:cap", 120)
+    STEPS.run(__file__, "gumbel:cap", 120)
 
 
 def test_gumbel_batch_4_with_the_cap_equals_gumbel_batch_1():
-    _step("gumbel:batch", 120)
+    STEPS.run(__file__, "gumbel:batch", 120)
 
 
 @pytest.mark.parametrize("name", ["ttt", "c4", "gmk", "c4-groups", "gmk-long", "rows"])
 def test_samples_device_path_equals_host_path_and_the_kept_rows(name):
-    _step("samples:" + name, 180)
+    STEPS.run(__file__, "samples:" + name, 180)
 
 
 @pytest.mark.parametrize("search", ["puct", "gumbel"])
 def test_run_self_play_reads_the_train_config_keys(search):
-    _step("run_self_play:" + search, 120)
+    STEPS.run(__file__, "run_self_play:" + search, 120)
 
 
 def test_refusals_and_lowered_run_iterations():
-    _step("refusals", 120)
+    STEPS.run(__file__, "refusals", 120)
 
 
 @pytest.mark.parametrize("which", ["fused", "groups", "cache"])
 def test_records_do_not_depend_on_scheduling(which):
-    _step("scheduling:" + which, 180)
+    STEPS.run(__file__, "scheduling:" + which, 180)
 
 
 if __name__ == "__main__":

@@ -2,26 +2,15 @@
 emulation build of the device code.  The one-lane emulation has no teams, tree blocks or tiles: what it checks here is the host side of
 a ragged count (launch sizes, the budget rule, the game groups' split, repack) and the case bodies themselves; the launch shapes are the
 -m gpu suite's (tests/test_ragged_gpu.py).  Exact equality everywhere."""
-import os
-import subprocess
-
 import pytest
 
 import degenerate_cases
 import gumbel_batch_cases
 import ragged_cases as cases
-from conftest import ROOT
+from selfplay_support import emu_lib  # noqa: F401
 
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
 SELFPLAY = [("Connect4", "puct", {}), ("TicTacToe", "puct", {}), ("Gomoku", "puct", {}), ("Connect4", "puct", dict(compact_trees=1)),
             ("Connect4", "gumbel", {}), ("TicTacToe", "gumbel", {})]
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
 
 
 # ------------------------------------------------------------------------------------------------ A.1

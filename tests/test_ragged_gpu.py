@@ -4,77 +4,61 @@ TicTacToe, one game per wavefront for Gomoku).  B: the one-launch wave (tree blo
 network against a regular engine of 128 slots that runs separate launches, and against the oracle.  Bit-equal: no tolerance.  Every case
 of B prints its witnesses (fused_wave, fused_faults, game_groups, records) and asserts them.
 
-Every GPU step is a child process of its own under a time limit (this file run as a script with the case's name; the limit is a kill
-guard, not a measurement); after a child that was killed or ran out of time nothing more is started."""
+Every GPU case runs as a child step of the shared runner, tests/gpu_step.py."""
 import os
-import subprocess
 import sys
 
 import pytest
 
+from gpu_step import STEPS
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_dead = []
-
-
-def _step(case, seconds=240, env=None):
-    if _dead:
-        pytest.fail(f"not started: the GPU step {_dead[0]} was killed or ran out of time")
-    try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), case], cwd=ROOT, timeout=seconds, capture_output=True, text=True,
-                           env=dict(os.environ, **(env or {})))
-    except subprocess.TimeoutExpired:
-        _dead.append(case)
-        pytest.fail(f"{case}: no result within {seconds} s")
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        _dead.append(case)
-    print(r.stdout[-6000:])
-    assert r.returncode == 0, f"{case}: exit status {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
 
 
 # ------------------------------------------------------------------------------------------------ A.1
 @pytest.mark.parametrize("game", ("Connect4", "TicTacToe", "Gomoku"))
 def test_puct_selfplay_of_ragged_counts_equals_the_oracle(game):
-    _step(f"selfplay:puct:{game}")
+    STEPS.run(__file__, f"selfplay:puct:{game}", 240, tail=6000)
 
 
 def test_puct_selfplay_of_ragged_counts_with_reroot_compaction():
-    _step("selfplay:compact:Connect4")
+    STEPS.run(__file__, "selfplay:compact:Connect4", 240, tail=6000)
 
 
 @pytest.mark.parametrize("game", ("Connect4", "TicTacToe"))
 def test_gumbel_selfplay_of_ragged_counts_equals_the_oracle(game):
-    _step(f"selfplay:gumbel:{game}")
+    STEPS.run(__file__, f"selfplay:gumbel:{game}", 240, tail=6000)
 
 
 @pytest.mark.parametrize("game", ("Connect4", "TicTacToe"))
 def test_gumbel_selfplay_of_ragged_counts_four_games_per_wavefront(game):
     """GAZ_TREE_TEAMS=1: k_wave_gumbel_teams (16-lane teams) instead of one game per wavefront"""
-    _step(f"selfplay:gumbel:{game}", env={"GAZ_TREE_TEAMS": "1"})
+    STEPS.run(__file__, f"selfplay:gumbel:{game}", 240, env={"GAZ_TREE_TEAMS": "1"}, tail=6000)
 
 
 # ------------------------------------------------------------------------------------------------ A.2
 @pytest.mark.parametrize("game,K", [("TicTacToe", 4), ("TicTacToe", 16), ("Connect4", 4), ("Connect4", 16)])
 def test_leaf_batched_search_of_ragged_counts_equals_the_model(game, K):
-    _step(f"leaf:{game}:{K}")
+    STEPS.run(__file__, f"leaf:{game}:{K}", 240, tail=6000)
 
 
 @pytest.mark.parametrize("name", ("c4-k7", "c4-k2", "ttt-k4", "gmk-k16"))
 def test_batched_gumbel_search_of_ragged_counts_equals_the_oracle(name):
-    _step(f"gumbel-batch:{name}")
+    STEPS.run(__file__, f"gumbel-batch:{name}", 240, tail=6000)
 
 
 # ------------------------------------------------------------------------------------------------ A.3
 @pytest.mark.parametrize("search", ("puct", "gumbel"))
 def test_game_groups_of_ragged_counts_play_exactly_the_budget(search):
-    _step(f"groups:{search}")
+    STEPS.run(__file__, f"groups:{search}", 240, tail=6000)
 
 
 # ------------------------------------------------------------------------------------------------ A.4
 @pytest.mark.parametrize("name", ("gumbel-c4", "puct-ttt", "puct-gmk"))
 def test_repack_to_one_slot_keeps_every_game(name):
-    _step(f"repack:{name}")
+    STEPS.run(__file__, f"repack:{name}", 240, tail=6000)
 
 
 # ------------------------------------------------------------------------------------------------ B
@@ -82,22 +66,22 @@ def test_repack_to_one_slot_keeps_every_game(name):
 def test_one_launch_wave_of_ragged_counts_equals_the_regular_engine_and_the_oracle(case):
     """gomoku: the 1-block network, for which the evaluator declines the one-launch form at every size (resnet.hip fusable(): blocks > 1) —
     asserted as fused_wave == 0; gomoku2: the 2-block network, fused_wave == 1"""
-    _step(f"net:{case}", env={"GAZ_FUSE_GUMBEL_TEAMS": "0"} if case == "gumbel-one-game-per-wave" else None)
+    STEPS.run(__file__, f"net:{case}", 240, env={"GAZ_FUSE_GUMBEL_TEAMS": "0"} if case == "gumbel-one-game-per-wave" else None, tail=6000)
 
 
 @pytest.mark.parametrize("kind", ("puct", "gumbel"))
 def test_one_launch_wave_of_ragged_game_groups(kind):
-    _step(f"net-groups:{kind}")
+    STEPS.run(__file__, f"net-groups:{kind}", 240, tail=6000)
 
 
 @pytest.mark.parametrize("kind", ("gumbel", "gomoku2"))
 def test_one_launch_wave_repacked_to_one_slot(kind):
-    _step(f"net-repack:{kind}")
+    STEPS.run(__file__, f"net-repack:{kind}", 240, tail=6000)
 
 
 @pytest.mark.parametrize("n", (5, 17))
 def test_bounded_wait_gives_up_on_a_partial_tile_without_changing_games(n):
-    _step(f"net-giveup:{n}")
+    STEPS.run(__file__, f"net-giveup:{n}", 240, tail=6000)
 
 
 # ------------------------------------------------------------------------------------------------ the steps (run in the child)

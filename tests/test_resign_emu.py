@@ -1,23 +1,12 @@
 """CPU suite: resignation in self-play and the games played out to calibrate it (gaz_engine_set_resignation) on the emulation build of
 the device code — the cases of tests/resign_cases.py at sizes the one-lane emulation plays in seconds.  Exact equality everywhere."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import resign_cases as cases
-from conftest import ROOT
+from selfplay_support import emu_lib  # noqa: F401
 
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
 BOTH = cases.MINIMUM + ("false_positive", "true_positive")
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
 
 
 # ------------------------------------------------------------------------------------------------ 1. draws and rule (no engine)

@@ -2,32 +2,17 @@
 the launch shapes matter (64 games: four games per wavefront, of which some resign while their neighbours play on; Gomoku's PUCT search
 with compacted trees; two game groups), and the scheduling equalities with the network.  Exact equality everywhere: no tolerance.
 
-Every GPU step is a child process of its own under a time limit (this file run as a script with the case's name); after a child that
-was killed or ran out of time nothing more is started."""
+Every GPU case runs as a child step of the shared runner, tests/gpu_step.py."""
 import os
-import subprocess
 import sys
 
 import pytest
 
+from gpu_step import STEPS
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_dead = []
-
-
-def _step(case, seconds):
-    if _dead:
-        pytest.fail(f"not started: the GPU step {_dead[0]} was killed or ran out of time")
-    try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), case], cwd=ROOT, timeout=seconds, capture_output=True, text=True)
-    except subprocess.TimeoutExpired:
-        _dead.append(case)
-        pytest.fail(f"{case}: no result within {seconds} s")
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        _dead.append(case)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, f"{case}: exit status {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
 
 
 # ------------------------------------------------------------------------------------------------ the cases (run in the child)
@@ -72,42 +57,42 @@ def _run_case(name):
 # ------------------------------------------------------------------------------------------------ the tests
 @pytest.mark.parametrize("name", ["c4", "ttt", "ttt-min4", "c4-gumbel", "gmk-gumbel", "gmk-puct", "c4-leaf4", "c4-single"])
 def test_records_are_prefixes_and_the_counters_follow(name):
-    _step("prefix:" + name, 180 if name == "gmk-puct" else 120)
+    STEPS.run(__file__, "prefix:" + name, 180 if name == "gmk-puct" else 120)
 
 
 def test_a_game_resigns_after_a_fast_ply():
-    _step("fast", 120)
+    STEPS.run(__file__, "fast", 120)
 
 
 def test_anchors_late_min_ply_all_playout_and_threshold_0():
-    _step("anchors", 120)
+    STEPS.run(__file__, "anchors", 120)
 
 
 @pytest.mark.parametrize("name", ["c4", "c4-cap-forced", "ttt", "c4-gumbel"])
 def test_drain_samples_equals_record_to_samples(name):
-    _step("samples:" + name, 120)
+    STEPS.run(__file__, "samples:" + name, 120)
 
 
 @pytest.mark.parametrize("which", ["plain", "prefix"])
 def test_sync_engine_halts_after_the_resigning_ply(which):
-    _step("sync:" + which, 120)
+    STEPS.run(__file__, "sync:" + which, 120)
 
 
 def test_run_self_play_reads_the_four_keys():
-    _step("run_self_play", 120)
+    STEPS.run(__file__, "run_self_play", 120)
 
 
 def test_resign_curve_equals_the_restated_rule():
-    _step("curve", 120)
+    STEPS.run(__file__, "curve", 120)
 
 
 def test_refusals():
-    _step("refusals", 120)
+    STEPS.run(__file__, "refusals", 120)
 
 
 @pytest.mark.parametrize("which", ["fused", "groups", "cache"])
 def test_records_do_not_depend_on_scheduling(which):
-    _step("scheduling:" + which, 180)
+    STEPS.run(__file__, "scheduling:" + which, 180)
 
 
 if __name__ == "__main__":

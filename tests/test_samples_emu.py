@@ -7,24 +7,15 @@ sides do in the same order.
   3  drain_finished and drain_samples mixed on one engine; refusals
   4  run_self_play: the replay file at both settings of device_samples; foreign plugins; a failing writer"""
 import os
-import subprocess
 import threading
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 from samples_util import (assert_matches_reference_fixture, assert_same_file, assert_same_game, device_games, file_contents,
                           host_games)
-
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
+from selfplay_support import emu_lib  # noqa: F401
 
 
 def _search_kw(search):

@@ -1,26 +1,15 @@
 """CPU suite: the solver (gaz_engine_set_solver) on the emulation build of the device code — the model's own anchors,
 then the cases of tests/solver_cases.py at sizes the one-lane emulation plays in seconds.  Exact equality everywhere; every case asserts
 the witnesses it is there for, so that it cannot pass vacuously."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import solver_cases as cases
 import solver_model as model
-from conftest import ROOT
+from selfplay_support import emu_lib  # noqa: F401
 
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
 f32 = np.float32
 U, WIN, DRAW, LOSS = model.U, model.WIN, model.DRAW, model.LOSS
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
 
 
 # ------------------------------------------------------------------------------------------------ the model (no engine)

@@ -5,32 +5,17 @@ games from the empty board: the first wavefront and two more slots, which keeps 
 those slots.  Then the scheduling equalities with a 1-block network, and games with that network against the model.  Exact equality
 everywhere: no tolerance.
 
-Every GPU step is a child process of its own under a time limit (this file run as a script with the case's name); after a child that
-was killed or ran out of time nothing more is started."""
+Every GPU case runs as a child step of the shared runner, tests/gpu_step.py."""
 import os
-import subprocess
 import sys
 
 import pytest
 
+from gpu_step import STEPS
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_dead = []
-
-
-def _step(case, seconds):
-    if _dead:
-        pytest.fail(f"not started: the GPU step {_dead[0]} was killed or ran out of time")
-    try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), case], cwd=ROOT, timeout=seconds, capture_output=True, text=True)
-    except subprocess.TimeoutExpired:
-        _dead.append(case)
-        pytest.fail(f"{case}: no result within {seconds} s")
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        _dead.append(case)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, f"{case}: exit status {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
 
 
 # ------------------------------------------------------------------------------------------------ the cases (run in the child)
@@ -94,57 +79,57 @@ def _run_case(name):
 # ------------------------------------------------------------------------------------------------ the tests
 @pytest.mark.parametrize("name", ["ttt", "ttt-two-trees-tau", "c4-20-two-trees", "c4-24-compact-no-noise", "gmk-open-four", "gmk-four-one-end"])
 def test_sync_games_equal_the_model_and_minimax(name):
-    _step("sync:" + name, 180)
+    STEPS.run(__file__, "sync:" + name, 180)
 
 
 def test_switching_between_moves():
-    _step("switch", 180)
+    STEPS.run(__file__, "switch", 180)
 
 
 @pytest.mark.parametrize("name", ["ttt", "c4"])
 def test_continuous_selfplay_equals_the_model(name):
-    _step("selfplay:" + name, 180)
+    STEPS.run(__file__, "selfplay:" + name, 180)
 
 
 def test_forced_playouts():
-    _step("forced", 180)
+    STEPS.run(__file__, "forced", 180)
 
 
 def test_playout_cap():
-    _step("cap", 180)
+    STEPS.run(__file__, "cap", 180)
 
 
 def test_quiet_anchor_and_records_that_differ():
-    _step("quiet", 120)
+    STEPS.run(__file__, "quiet", 120)
 
 
 def test_resignation():
-    _step("resign", 120)
+    STEPS.run(__file__, "resign", 120)
 
 
 def test_drain_samples_equals_record_to_samples():
-    _step("samples", 120)
+    STEPS.run(__file__, "samples", 120)
 
 
 def test_run_self_play_reads_the_key():
-    _step("run_self_play", 120)
+    STEPS.run(__file__, "run_self_play", 120)
 
 
 def test_mcts_class():
-    _step("mcts", 120)
+    STEPS.run(__file__, "mcts", 120)
 
 
 def test_refusals_and_abi():
-    _step("refusals", 120)
+    STEPS.run(__file__, "refusals", 120)
 
 
 @pytest.mark.parametrize("which", ["fused", "groups", "cache"])
 def test_records_do_not_depend_on_scheduling(which):
-    _step("scheduling:" + which, 180)
+    STEPS.run(__file__, "scheduling:" + which, 180)
 
 
 def test_the_real_network_against_the_model():
-    _step("network", 180)
+    STEPS.run(__file__, "network", 180)
 
 
 if __name__ == "__main__":

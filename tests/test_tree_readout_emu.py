@@ -3,23 +3,12 @@ MCTS.root / MCTS.pv) on the emulation build of the device code.  The PUCT trees 
 tests/leaf_batch_model.py, node for node and edge for edge; the case bodies are tests/tree_cases.py, shared with the -m gpu suite.
 Bit-equal everywhere: no tolerance."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import tree_cases as TC
-from conftest import ROOT
-
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-EMU = os.path.join(EMU_DIR, "libgaz_emu.so")
-
-
-@pytest.fixture(scope="module")
-def emu_lib():
-    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
-    return EMU
+from selfplay_support import emu_lib  # noqa: F401
 
 
 # ------------------------------------------------------------------------------------------------ whole-tree parity, PUCT

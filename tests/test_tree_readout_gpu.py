@@ -3,33 +3,18 @@ that tests/test_tree_readout_emu.py runs on the emulation build, with 64 games a
 of a wavefront and both ends of the batch.  The PUCT trees are held against the whole-tree model of tests/leaf_batch_model.py, node for
 node and edge for edge.  Bit-equal: no tolerance.
 
-Every GPU step is a child process of its own under a time limit (this file run as a script with the case's name); after a child that
-was killed or ran out of time nothing more is started."""
+Every GPU case runs as a child step of the shared runner, tests/gpu_step.py."""
 import os
-import subprocess
 import sys
 
 import pytest
 
+from gpu_step import STEPS
+from selfplay_support import SLOTS64 as SLOTS
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SLOTS = (0, 1, 15, 16, 31, 32, 62, 63)            # first / last game of a wavefront's four teams, both ends of the batch
-_dead = []
-
-
-def _step(case, seconds):
-    if _dead:
-        pytest.fail(f"not started: the GPU step {_dead[0]} was killed or ran out of time")
-    try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), case], cwd=ROOT, timeout=seconds, capture_output=True, text=True)
-    except subprocess.TimeoutExpired:
-        _dead.append(case)
-        pytest.fail(f"{case}: no result within {seconds} s")
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        _dead.append(case)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, f"{case}: exit status {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
 
 
 # ------------------------------------------------------------------------------------------------ the cases (run in the child)
@@ -107,11 +92,11 @@ CASES = ["c4-k1", "c4-k8", "gmk-k16", "ttt", "inflight", "gumbel-c4", "gumbel-gm
 
 @pytest.mark.parametrize("case", CASES)
 def test_export_cases(case):
-    _step(case, 240)
+    STEPS.run(__file__, case, 240)
 
 
 def test_gomoku_10_blocks_k16_export_equals_model():
-    _step("resnet-gmk-k16", 300)
+    STEPS.run(__file__, "resnet-gmk-k16", 300)
 
 
 if __name__ == "__main__":

@@ -10,10 +10,9 @@ import os
 import numpy as np
 
 from leaf_batch_model import DRAW, WIN, Tree, _Node
+from selfplay_support import A_OF, MAXT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MAXT = {"TicTacToe": 9, "Connect4": 42, "Gomoku": 225}
-A_OF = {"TicTacToe": 9, "Connect4": 7, "Gomoku": 225}
 PH_SIMS = 3
 FILTERED = -4
 TTT_DRAWN_GAME = [4, 0, 8, 2, 6, 3, 5, 7]        # + the forced 1: a draw; wins in one are left standing on the way (terminal roots and parents)
