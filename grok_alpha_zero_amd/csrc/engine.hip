@@ -1,6 +1,7 @@
 // engine.hip — host side of libgaz_engine.so: owns the HBM state, launches the wave kernel + evaluator
 // once per simulation wave on one HIP stream, and implements the C ABI of include/gaz_engine.h.
 #include <stdio.h>
+#include <chrono>
 #include <functional>
 #include <string>
 #include <vector>
@@ -11,6 +12,7 @@
 #include "samples.hpp"
 #include "tree_export.hpp"
 #include "evaluator.hpp"
+#include "match.hpp"
 
 using namespace gaz;
 
@@ -413,6 +415,12 @@ struct gaz_engine {
                     std::to_string(max_nodes) + " and max_edges is " + std::to_string(max_edges));
     }
     virtual int repack(int32_t*, int32_t*) = 0;
+    virtual int set_match(int32_t mode, uint32_t hash_salt_b) = 0;
+    virtual int get_match(int32_t* mode) = 0;
+    virtual int load_weights_b(const gaz_tensor* t, int n) = 0;
+    virtual int read_batch_network(uint8_t* net) = 0;
+    virtual int get_match_stats(uint64_t out[8]) = 0;
+    virtual int get_match_timing(double out[8]) = 0;
     virtual int probe_rules(const int32_t*, const int32_t*, int, int, int8_t*, uint8_t*, int32_t*, int8_t*, int32_t*, const float*, float*) = 0;
 };
 
@@ -525,7 +533,8 @@ template <class G> struct EngineT : gaz_engine {
             fprintf(stderr, "[tree prof] launches/game %.0f\n", (double)t[7] / E.n_games);
             for (int k = 0; k < 7; ++k) fprintf(stderr, "[tree prof] %-18s %8.0f cycles / game-launch (%.1f %%)\n", nm[k], (double)t[k] / (double)t[7], 100.0 * t[k] / t[6]);
         }
-        delete eval;
+        delete eval; delete eval_b;
+        if (h_match_cnt) hipHostFree(h_match_cnt);
         for (void* p : allocs) hipFree(p);
         if (dSamples) hipFree(dSamples);
         if (hSamples) hipHostFree(hSamples);
@@ -790,6 +799,7 @@ template <class G> struct EngineT : gaz_engine {
         return true;
     }
     int debug_fused_fault(int mod) override {
+        if (match_mode) return fail("debug_fused_fault: not while match play is on (gaz_engine_set_match runs separate launches only)");
         if (lbk > 1 && mod > 0) return fail(std::string("debug_fused_fault: ") + (gbk > 1 ? "gumbel_batch" : "leaf_batch") + " > 1 runs separate launches only");
         if (mod > 0 && !ensure_skip_buffers()) return 1;
         debug_fault_mod = mod > 0 ? (unsigned)mod : 0u;
@@ -804,6 +814,7 @@ template <class G> struct EngineT : gaz_engine {
     int32_t* dMoveList = nullptr;
     int repack(int32_t* n_active_out, int32_t* n_eff_out) override {
         if (E.sync_moves) return fail("repack needs continuous self-play (sync_moves = 0)");
+        if (match_mode) return fail("repack: not while match play is on (gaz_engine_set_match; the routing stage covers every slot)");
         if (gbk > 1) return fail("repack: not with gumbel_batch > 1 (a game owns gumbel_batch rows of the batch)");
         if (lbk > 1) return fail("repack: not with leaf_batch > 1 (a game owns leaf_batch rows of the batch)");
         if (quiesce()) return 1;
@@ -895,13 +906,13 @@ template <class G> struct EngineT : gaz_engine {
         const bool timing = this->timing && n_waves_total % TIMING_STRIDE == 0 && ev.size() + 4 <= MAX_TIMING_EVENTS;
         hipEvent_t e0 = 0, e1 = 0, e2 = 0;
         if (timing && (new_event(&e0) || new_event(&e1) || new_event(&e2))) return 1;
-        if (with_eval && eval && fuse_enabled && can_fuse()) { const int rc = fused_wave(timing, e0, e1, e2); if (rc >= 0) return rc; }
+        if (with_eval && eval && fuse_enabled && !match_mode && can_fuse()) { const int rc = fused_wave(timing, e0, e1, e2); if (rc >= 0) return rc; }
         if (timing) hipEventRecord(e0, stream);
         DevParams<G> P = wave_params();
         launch_wave(stream, 0, n_eff, P);
         prev_marked = false;                         // the separately launched evaluator pass covers every row
         if (timing) hipEventRecord(e1, stream);
-        if (with_eval && eval) eval->forward(stream, E.nn_in, E.nn_policy, E.nn_value, n_eff * lbk, timing);
+        if (with_eval && eval) { if (match_mode) { if (match_forward(timing)) return 1; } else eval->forward(stream, E.nn_in, E.nn_policy, E.nn_value, n_eff * lbk, timing); }
         if (timing) { hipEventRecord(e2, stream); ev_tree.push_back({e0, e1}); ev_eval.push_back({e1, e2}); n_waves_timed++; }
         P.eval_done = nullptr;
         if (with_eval && eval && debug_fault_mod && d_evaldone) {      // test hook: this wave behaves as a fused launch with workgroups that gave up
@@ -928,7 +939,7 @@ template <class G> struct EngineT : gaz_engine {
     int quiesce() { HIP_OK(hipStreamSynchronize(stream)); if (pipeline_ready) { HIP_OK(hipStreamSynchronize(tstream)); HIP_OK(hipStreamSynchronize(hstream)); } return 0; }
     bool can_pipeline() {
         static const char* spec = getenv("GAZ_PIPELINE");
-        if (!spec || !*spec || atoi(spec) == 0) return false;
+        if (!spec || !*spec || atoi(spec) == 0 || match_mode) return false;      // (match play: one batch, separate launches)
         // (the evaluation cache is read by tree kernels and written by k_cache_insert: they must not run concurrently)
         if (lbk > 1 || E.sync_moves || !eval || !eval->supports_split() || E.n_games < 1024 || E.cache || n_eff != E.n_games) return false;
         if (!pipeline_ready) {
@@ -998,6 +1009,7 @@ template <class G> struct EngineT : gaz_engine {
         if (!E.sync_moves) return fail("run_move needs sync_moves = 1");
         if (!eval) return fail("run_move needs a built-in evaluator (use wave_begin/wave_end with GAZ_EVAL_EXTERNAL)");
         if (!eval->ready()) return fail("run_move: evaluator weights not loaded (gaz_engine_load_weights)");
+        if (match_mode && !(eval_b && eval_b->ready())) return fail("run_move: weights of network B not loaded (gaz_engine_load_weights_b)");
         // a move needs at most iter_limit + 2 evaluations (both roots); poll the device every 16 waves (4 with leaf batching)
         // PUCT: a move needs at most iter_limit + 2 evaluations; Gumbel can overshoot its budget (vpc >= 1 per survivor)
         const int max_waves = cfg.search == GAZ_SEARCH_GUMBEL ? 4 * (E.run_iterations + 3 * G::A) + 64
@@ -1039,7 +1051,7 @@ template <class G> struct EngineT : gaz_engine {
         HIP_OK(hipGetLastError());
         // run the APPLY phase (do_action, win check, prune) up to the next evaluation request
         launch_wave();
-        if (eval) eval->forward(stream, E.nn_in, E.nn_policy, E.nn_value, (int)rows, false);
+        if (eval) { if (match_mode) { if (match_forward(false)) return 1; } else eval->forward(stream, E.nn_in, E.nn_policy, E.nn_value, (int)rows, false); }
         if (eval && E.cache) { GAZ_LAUNCH(k_cache_insert<G>, E.n_games, WAVE, stream, E, 0, E.n_games); E.cache_epoch++; }
         HIP_OK(hipGetLastError());
         return check_device_error();
@@ -1048,6 +1060,7 @@ template <class G> struct EngineT : gaz_engine {
     int run_waves(int n) override {
         if (!eval) return fail("run_waves needs a built-in evaluator");
         if (!eval->ready()) return fail("run_waves: evaluator weights not loaded (gaz_engine_load_weights)");
+        if (match_mode && !(eval_b && eval_b->ready())) return fail("run_waves: weights of network B not loaded (gaz_engine_load_weights_b)");
         if (can_pipeline()) return run_waves_pipelined(n);
         for (int i = 0; i < n; ++i) if (one_wave(true)) return 1;
         HIP_OK(hipGetLastError());
@@ -1235,7 +1248,7 @@ template <class G> struct EngineT : gaz_engine {
         out[9] = (uint64_t)n_waves_total; memcpy(&out[10], c + 8, 8);
         out[11] = pipeline_ready ? (uint64_t)n_grp : 0;
         if (poll_fuse_fault()) return 1;             // counts() synchronised the stream
-        out[12] = (fuse_state == 1 && fuse_enabled) ? 1 : 0;
+        out[12] = (fuse_state == 1 && fuse_enabled && !match_mode) ? 1 : 0;
         out[13] = fuse_faults;
         if (lbk > 1 && gbk <= 1) {
             unsigned long long* d = reinterpret_cast<unsigned long long*>(dCount);
@@ -1252,7 +1265,7 @@ template <class G> struct EngineT : gaz_engine {
     int timing_reset(int enable) override {
         HIP_OK(hipStreamSynchronize(stream));
         for (hipEvent_t e : ev) hipEventDestroy(e);
-        ev.clear(); ev_tree.clear(); ev_eval.clear(); ev_fused.clear(); n_waves_total = 0; n_waves_timed = 0; timing = enable != 0;
+        ev.clear(); ev_tree.clear(); ev_eval.clear(); ev_fused.clear(); ev_match_pre.clear(); ev_match_gap.clear(); ev_match_post.clear(); match_sync_ms = 0; match_waves_timed = 0; n_waves_total = 0; n_waves_timed = 0; timing = enable != 0;
         if (eval) eval->timing_reset();
         return 0;
     }
@@ -1469,6 +1482,120 @@ template <class G> struct EngineT : gaz_engine {
         }
         return check_device_error();
     }
+    // ---- match play (match.hpp): the games of this engine are played by two networks.  Network A = eval, network B =
+    // eval_b, a second instance of the same evaluator; the network of a row is a function of the game state (match_network), so the mode takes
+    // effect at the next evaluator pass and needs no migration.  With the mode on, the evaluator pass of one_wave / apply_moves is match_forward:
+    // launches are separate (no fused launch, no group pipeline) and the host waits once per wave for the two row counts.
+    int match_mode = 0; uint32_t match_salt_b = 0;
+    Evaluator* eval_b = nullptr;
+    uint8_t* m_net = nullptr; unsigned long long* m_blk = nullptr; uint32_t* m_cnt = nullptr; uint32_t* h_match_cnt = nullptr;
+    int32_t* m_idx_a = nullptr; int32_t* m_idx_b = nullptr;
+    int8_t* m_in_a = nullptr; int8_t* m_in_b = nullptr; float* m_pol_a = nullptr; float* m_pol_b = nullptr; float* m_val_a = nullptr; float* m_val_b = nullptr;
+    // timing (gaz_engine_timing_reset(1)), on the waves the other brackets are taken on: route + partition + copy; the stream's idle gap from the
+    // end of the copy to the first launch after the host's wait; the scatter; and the host's time inside that wait
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_match_pre, ev_match_gap, ev_match_post;
+    double match_sync_ms = 0; int64_t match_waves_timed = 0;
+    uint64_t match_stats[5] = {0, 0, 0, 0, 0};       // rows of A, rows of B, waves without a row for A, for B, evaluator passes with the mode on
+    // why this engine cannot play a match ("" = it can): the routing stage owns one row per game and one batch
+    std::string match_fault(const char* fn) const {
+        const std::string f = std::string(fn) + ": ";
+        if (cfg.single_tree) return f + "not with single_tree = 1 (one tree searches for both players: a request has no owner)";
+        if (cfg.leaf_batch > 1) return f + "not with leaf_batch > 1 (a game owns leaf_batch rows of the batch; match play routes one row per game)";
+        if (cfg.gumbel_batch > 1) return f + "not with gumbel_batch > 1 (a game owns gumbel_batch rows of the batch; match play routes one row per game)";
+        if (cfg.eval_cache_log2 > 0) return f + "not with eval_cache_log2 > 0 (the evaluation cache does not know which network answered an entry)";
+        return "";
+    }
+    int ensure_match_buffers() {
+        if (m_net) return 0;
+        const size_t n = (size_t)E.n_games, nblk = (n + WAVE - 1) / WAVE;
+        if (dalloc(&m_blk, nblk) || dalloc(&m_cnt, 2) || dalloc(&m_idx_a, n) || dalloc(&m_idx_b, n) ||
+            dalloc(&m_in_a, n * G::HW * G::C + 64) || dalloc(&m_in_b, n * G::HW * G::C + 64) || dalloc(&m_pol_a, n * G::A + 64) || dalloc(&m_pol_b, n * G::A + 64) ||
+            dalloc(&m_val_a, n + 64) || dalloc(&m_val_b, n + 64)) return 1;
+        void* h = nullptr;
+        HIP_OK(hipHostMalloc(&h, 2 * sizeof(uint32_t)));
+        h_match_cnt = (uint32_t*)h;
+        return dalloc(&m_net, n);                    // (last: its pointer says that all of them exist)
+    }
+    int ensure_eval_b() {
+        if (eval_b || cfg.evaluator == GAZ_EVAL_EXTERNAL) return 0;
+        std::string e2;
+        gaz_engine_config ecfg = cfg; ecfg.n_games = (int32_t)rows; ecfg.hash_salt = match_salt_b;
+        eval_b = make_evaluator(ecfg, G::H, G::W, G::C, G::A, &e2);
+        return eval_b ? 0 : fail("evaluator of network B: " + e2);
+    }
+    void match_route() {
+        const int nblk = (E.n_games + WAVE - 1) / WAVE;
+        GAZ_LAUNCH(k_match_route<G>, nblk, WAVE, stream, (const GameState<G>*)E.games, E.n_games, cfg.search == GAZ_SEARCH_GUMBEL ? 1 : 0, m_net, m_blk);
+    }
+    // the evaluator pass of a wave with the mode on, over all rows (n_eff == n_games: repack is refused)
+    int match_forward(bool timing) {
+        const int n = E.n_games, nblk = (n + WAVE - 1) / WAVE;
+        hipEvent_t m[5] = {0, 0, 0, 0, 0};
+        const bool timed = timing && ev.size() + 5 <= MAX_TIMING_EVENTS;
+        if (timed) { for (hipEvent_t& e : m) if (new_event(&e)) return 1; hipEventRecord(m[0], stream); }
+        match_route();
+        GAZ_LAUNCH(k_match_pack<G>, nblk, WAVE, stream, (const uint8_t*)m_net, (const unsigned long long*)m_blk, n, m_idx_a, m_idx_b, m_cnt);
+        HIP_OK(hipMemcpyAsync(h_match_cnt, m_cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        GAZ_LAUNCH_FLAT(k_match_copy<G>, n * MatchRow<G>::UNITS, 256, stream, (const int8_t*)E.nn_in, (const int32_t*)m_idx_a, (const int32_t*)m_idx_b,
+                        (const uint32_t*)m_cnt, n, m_in_a, m_in_b);
+        if (timed) hipEventRecord(m[1], stream);
+        const auto t0 = std::chrono::steady_clock::now();
+        HIP_OK(hipStreamSynchronize(stream));        // the host must know the two grid sizes
+        if (timed) { match_sync_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); hipEventRecord(m[2], stream); }
+        const int na = (int)h_match_cnt[0], nb = (int)h_match_cnt[1];
+        if (na < 0 || nb < 0 || na + nb > n) return fail("match play: internal error (row counts " + std::to_string(na) + " + " + std::to_string(nb) + " of " + std::to_string(n) + " rows)");
+        match_stats[0] += (uint64_t)na; match_stats[1] += (uint64_t)nb; match_stats[2] += na == 0; match_stats[3] += nb == 0; match_stats[4] += 1;
+        if (na) eval->forward(stream, m_in_a, m_pol_a, m_val_a, na, timing);
+        if (nb) eval_b->forward(stream, m_in_b, m_pol_b, m_val_b, nb, timing);
+        if (timed) hipEventRecord(m[3], stream);
+        if (na + nb) GAZ_LAUNCH_FLAT(k_match_scatter<G>, (na + nb) * (G::A + 1), 256, stream, (const int32_t*)m_idx_a, (const int32_t*)m_idx_b, na, nb,
+                                     (const float*)m_pol_a, (const float*)m_val_a, (const float*)m_pol_b, (const float*)m_val_b, E.nn_policy, E.nn_value);
+        if (timed) { hipEventRecord(m[4], stream); ev_match_pre.push_back({m[0], m[1]}); ev_match_gap.push_back({m[1], m[2]}); ev_match_post.push_back({m[3], m[4]}); match_waves_timed++; }
+        HIP_OK(hipGetLastError());
+        return 0;
+    }
+    int get_match_timing(double out[8]) override {
+        for (int i = 0; i < 8; ++i) out[i] = 0;
+        HIP_OK(hipStreamSynchronize(stream));
+        const std::vector<std::pair<hipEvent_t, hipEvent_t>>* v[3] = {&ev_match_pre, &ev_match_gap, &ev_match_post};
+        for (int k = 0; k < 3; ++k) for (auto& pr : *v[k]) { float a = 0; hipEventElapsedTime(&a, pr.first, pr.second); out[k] += a; }
+        out[3] = match_sync_ms; out[4] = (double)match_waves_timed;
+        return 0;
+    }
+    int set_match(int32_t mode, uint32_t hash_salt_b) override {
+        if (!mode) { match_mode = 0; return 0; }
+        if (const std::string f = match_fault("set_match"); !f.empty()) return fail(f);
+        if (n_eff != E.n_games) return fail("set_match: not after gaz_engine_repack (the routing stage covers every slot; reset all games first)");
+        if (debug_fault_mod) return fail("set_match: not while gaz_engine_debug_fused_fault is armed");
+        if (quiesce()) return 1;
+        if (cfg.evaluator == GAZ_EVAL_HASH && eval_b && hash_salt_b != match_salt_b) { delete eval_b; eval_b = nullptr; }
+        match_salt_b = hash_salt_b;
+        if (ensure_match_buffers() || ensure_eval_b()) return 1;
+        match_mode = 1;
+        return 0;
+    }
+    int get_match(int32_t* mode) override { *mode = match_mode; return 0; }
+    int load_weights_b(const gaz_tensor* t, int n) override {
+        if (const std::string f = match_fault("load_weights_b"); !f.empty()) return fail(f);
+        if (!eval) return fail("load_weights_b: no evaluator to load weights into");
+        if (quiesce() || ensure_eval_b()) return 1;
+        std::string m;
+        if (eval_b->load(t, n, stream, &m)) return fail("load_weights_b: " + m);
+        return 0;
+    }
+    int read_batch_network(uint8_t* net) override {
+        if (const std::string f = match_fault("read_batch_network"); !f.empty()) return fail(f);
+        if (ensure_match_buffers()) return 1;
+        match_route();
+        HIP_OK(hipMemcpyAsync(net, m_net, (size_t)E.n_games, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        return check_device_error();
+    }
+    int get_match_stats(uint64_t out[8]) override {
+        for (int i = 0; i < 8; ++i) out[i] = i < 5 ? match_stats[i] : 0;
+        return 0;
+    }
+
     int8_t* pr_board = nullptr; uint8_t* pr_legal = nullptr; int32_t* pr_winner = nullptr; int8_t* pr_input = nullptr; int32_t* pr_term = nullptr;
     int32_t* pr_actions = nullptr; int32_t* pr_n = nullptr; float* pr_pin = nullptr; float* pr_pout = nullptr; int pr_cap = 0, pr_stride = 0;
     int probe_rules(const int32_t* actions, const int32_t* n_actions, int n_pos, int stride, int8_t* o_board, uint8_t* o_legal,
@@ -1508,7 +1635,7 @@ template <class G> struct EngineT : gaz_engine {
         double f = 0; const char* k = eval ? eval->dominant_kernel(n_launch, &f) : "";
         if (eval && can_pipeline()) { double fa = 0; eval->dominant_kernel(E.n_games, &fa); f = fa / n_grp; }
         std::string label = k;
-        if (fuse_state == 1 && fuse_enabled) label = "k_wave_trunk = " + label + " FUSED with the " + std::string(cfg.search == GAZ_SEARCH_GUMBEL ? "Gumbel" : "PUCT") + " tree step of the same wave (one launch: tree blocks first, trunk workgroups start on the "
+        if (fuse_state == 1 && fuse_enabled && !match_mode) label = "k_wave_trunk = " + label + " FUSED with the " + std::string(cfg.search == GAZ_SEARCH_GUMBEL ? "Gumbel" : "PUCT") + " tree step of the same wave (one launch: tree blocks first, trunk workgroups start on the "
                                      "boards whose games are done; the launch duration therefore includes the part of the tree step it could not hide)";
         if (name && cap > 0) { strncpy(name, label.c_str(), cap - 1); name[cap - 1] = 0; }
         if (flops) *flops = f;
@@ -1777,6 +1904,14 @@ struct GroupEngine : gaz_engine {
         if (n_active) *n_active = a; if (n_launch) *n_launch = l;
         return 0;
     }
+    // match play routes the rows of ONE batch to two evaluators: an engine that resolved to game groups refuses it
+    int no_match(const char* fn) { return fail(std::string(fn) + ": this engine runs " + std::to_string(K()) + " game groups; match play needs one batch: create the engine with game_groups = 1"); }
+    int set_match(int32_t mode, uint32_t) override { return mode ? no_match("set_match") : 0; }
+    int get_match(int32_t* mode) override { *mode = 0; return 0; }
+    int load_weights_b(const gaz_tensor*, int) override { return no_match("load_weights_b"); }
+    int read_batch_network(uint8_t*) override { return no_match("read_batch_network"); }
+    int get_match_stats(uint64_t out[8]) override { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }
+    int get_match_timing(double out[8]) override { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }
     int probe_rules(const int32_t* actions, const int32_t* n_actions, int n_pos, int stride, int8_t* b, uint8_t* l, int32_t* w, int8_t* in, int32_t* t,
                     const float* pin, float* pout) override { return lead(&gaz_engine::probe_rules, actions, n_actions, n_pos, stride, b, l, w, in, t, pin, pout); }
 };
@@ -1894,6 +2029,19 @@ int gaz_engine_get_solver(gaz_engine* h, int32_t* mode) { return mode ? h->get_s
 int gaz_engine_get_solver_stats(gaz_engine* h, uint64_t out[8]) { return out ? h->get_solver_stats(out) : h->fail("get_solver_stats: null argument"); }
 int gaz_engine_get_eval_symmetry(gaz_engine* h, int32_t* mode) { return mode ? h->get_eval_symmetry(mode) : h->fail("get_eval_symmetry: null argument"); }
 int gaz_engine_read_batch_symmetry(gaz_engine* h, uint8_t* sym) { return sym ? h->read_batch_symmetry(sym) : h->fail("read_batch_symmetry: null argument"); }
+// match play: two networks in one engine
+int gaz_engine_set_match(gaz_engine* h, const gaz_match_params* p) {
+    if (!p) return h->fail("set_match: null argument");
+    if (p->struct_size != sizeof(gaz_match_params))
+        return h->fail("set_match: struct_size is " + std::to_string(p->struct_size) + ", this library's gaz_match_params has " + std::to_string(sizeof(gaz_match_params)) + " bytes");
+    if (p->mode != 0 && p->mode != 1) return h->fail("set_match: mode must be 0 (off) or 1 (network A against network B), not " + std::to_string(p->mode));
+    return h->set_match(p->mode, p->hash_salt_b);
+}
+int gaz_engine_get_match(gaz_engine* h, int32_t* mode) { return mode ? h->get_match(mode) : h->fail("get_match: null argument"); }
+int gaz_engine_load_weights_b(gaz_engine* h, const gaz_tensor* t, int32_t n) { return h->load_weights_b(t, n); }
+int gaz_engine_read_batch_network(gaz_engine* h, uint8_t* net) { return net ? h->read_batch_network(net) : h->fail("read_batch_network: null argument"); }
+int gaz_engine_get_match_stats(gaz_engine* h, uint64_t out[8]) { return out ? h->get_match_stats(out) : h->fail("get_match_stats: null argument"); }
+int gaz_engine_get_match_timing(gaz_engine* h, double out[8]) { return out ? h->get_match_timing(out) : h->fail("get_match_timing: null argument"); }
 int gaz_engine_set_fused_wave(gaz_engine* h, int32_t on) { return h->set_fused_wave(on); }
 int gaz_engine_debug_fused_fault(gaz_engine* h, int32_t mod) { return h->debug_fused_fault(mod); }
 int gaz_engine_read_positions(gaz_engine* h, int32_t* n_hist, uint8_t* hist, int32_t stride) { return h->read_positions(n_hist, hist, stride); }

@@ -58,6 +58,12 @@ class ResignParams(C.Structure):        # gaz_resign_params
                 ("threshold", C.c_double), ("no_resign_prob", C.c_double)]
 
 
+class MatchParams(C.Structure):         # gaz_match_params
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("hash_salt_b", C.c_uint32), ("reserved_", C.c_int32)]
+
+
+NET_A, NET_B, NET_NONE = 0, 1, 255      # gaz_engine_read_batch_network: the network that answers a row of the evaluator batch
+
 MK_KIND_MASK, MK_RESIGNED, MK_WOULD_RESIGN = 3, 0x10, 0x20      # the bits of a record's raw move_kind byte (gaz_record_layout.off_move_kind)
 MK_PROVEN = 0x40                                                 # solver (set_solver): the ply ended with a proven root
 PROVEN_UNKNOWN, PROVEN_WIN, PROVEN_DRAW, PROVEN_LOSS = 0, 1, 2, 3   # a node's status for the player to move there (SearchTree.proven)
@@ -127,6 +133,12 @@ def load_library(lib_path=None):
     L.gaz_engine_set_solver.argtypes = [H, C.c_int32]
     L.gaz_engine_get_solver.argtypes = [H, C.POINTER(C.c_int32)]
     L.gaz_engine_get_solver_stats.argtypes = [H, C.POINTER(C.c_uint64)]
+    L.gaz_engine_set_match.argtypes = [H, C.POINTER(MatchParams)]
+    L.gaz_engine_get_match.argtypes = [H, C.POINTER(C.c_int32)]
+    L.gaz_engine_load_weights_b.argtypes = [H, C.POINTER(Tensor), C.c_int32]
+    L.gaz_engine_read_batch_network.argtypes = [H, C.c_void_p]
+    L.gaz_engine_get_match_stats.argtypes = [H, C.POINTER(C.c_uint64)]
+    L.gaz_engine_get_match_timing.argtypes = [H, C.POINTER(C.c_double)]
     L.gaz_engine_probe_rules.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7
     L.gaz_engine_set_fused_wave.argtypes = [H, C.c_int32]
     L.gaz_engine_debug_fused_fault.argtypes = [H, C.c_int32]
@@ -141,7 +153,7 @@ def load_library(lib_path=None):
     for f in ("create", "load_weights", "reset_games", "run_move", "get_root_stats", "apply_moves", "run_waves", "wave_begin",
               "wave_end", "batch_ptrs", "read_batch", "write_outputs", "batch_rows", "evaluate", "record_layout", "drain_finished", "sample_layout", "drain_samples", "get_stats",
               "synchronize", "timing_reset", "timing_get", "dominant_kernel", "set_position", "set_search_params", "start_search", "stop_search",
-              "set_hyperparams", "set_resignation", "get_resign_stats", "set_eval_symmetry", "get_eval_symmetry", "read_batch_symmetry", "set_solver", "get_solver", "get_solver_stats", "probe_rules", "read_head_features", "set_fused_wave", "debug_fused_fault", "read_positions", "repack", "read_trees", "read_pv"):
+              "set_hyperparams", "set_resignation", "get_resign_stats", "set_eval_symmetry", "get_eval_symmetry", "read_batch_symmetry", "set_solver", "get_solver", "get_solver_stats", "set_match", "get_match", "load_weights_b", "read_batch_network", "get_match_stats", "get_match_timing", "probe_rules", "read_head_features", "set_fused_wave", "debug_fused_fault", "read_positions", "repack", "read_trees", "read_pv"):
         getattr(L, "gaz_engine_" + f).restype = C.c_int
     _LIBS[path] = L
     return L
@@ -310,14 +322,21 @@ class SelfPlayEngine:
             pass
 
     # ---- weights ------------------------------------------------------------------------------------
-    def load_weights(self, named_arrays):
+    def _load(self, fn, named_arrays):
         keep = []
         arr = (Tensor * len(named_arrays))()
         for i, (name, a) in enumerate(named_arrays.items()):
             a = np.ascontiguousarray(a, np.float32)
             keep.append(a)
             arr[i] = Tensor(name.encode(), a.ctypes.data_as(C.POINTER(C.c_float)), a.size)
-        self._ck(self.L.gaz_engine_load_weights(self.h, arr, len(named_arrays)))
+        self._ck(fn(self.h, arr, len(named_arrays)))
+
+    def load_weights(self, named_arrays):
+        self._load(self.L.gaz_engine_load_weights, named_arrays)
+
+    def load_weights_b(self, named_arrays):
+        """the weights of network B of a match (set_match): the names and shapes of load_weights"""
+        self._load(self.L.gaz_engine_load_weights_b, named_arrays)
 
     def evaluate(self, states_i8, repeats=0):
         """Evaluator probe (Compute_Speed.py:40-63): states int8 [n,H,W,C] -> (policy [n,A], value [n], ms per batch)."""
@@ -507,6 +526,45 @@ class SelfPlayEngine:
         s = [int(x) for x in out]
         return dict(proven_nodes=s[0], proven_hits=s[1], proven_moves=s[2], saved_sims=s[3], root_win=s[4], root_draw=s[5], root_loss=s[6],
                     masked_levels=s[7])
+
+    # ---- match play ---------------------------------------------------------------------------------
+    def set_match(self, on=True, hash_salt_b=0):
+        """Play the engine's games between two networks (gaz_engine_set_match), from the next evaluator pass on: network A = load_weights (the
+        hash evaluator: hash_salt), network B = load_weights_b (hash_salt_b).  In game (slot, game_seq) A plays the first player iff slot +
+        game_seq is even; a record's header therefore says who was A (self_play.match_result tallies records).  Refused with single_tree,
+        leaf_batch > 1, gumbel_batch > 1, the evaluation cache and game groups."""
+        p = MatchParams(struct_size=C.sizeof(MatchParams), mode=int(bool(on)), hash_salt_b=int(hash_salt_b), reserved_=0)
+        self._ck(self.L.gaz_engine_set_match(self.h, C.byref(p)))
+
+    @property
+    def match(self):
+        m = C.c_int32()
+        self._ck(self.L.gaz_engine_get_match(self.h, C.byref(m)))
+        return bool(m.value)
+
+    def read_batch_network(self):
+        """uint8 [n_games]: the network that answers every row of the evaluator batch — NET_A (0), NET_B (1), NET_NONE (255) where
+        read_batch's pending is 0.  An external evaluator answers each row with the network the byte names."""
+        net = np.zeros(self.n_games, np.uint8)
+        self._ck(self.L.gaz_engine_read_batch_network(self.h, net.ctypes.data))
+        return net
+
+    def match_stats(self):
+        """gaz_engine_get_match_stats as a dict, over the engine's life: `rows_a` / `rows_b` evaluated by each network, `waves_without_a` /
+        `waves_without_b` (evaluator passes in which that network got no row) and `passes` (evaluator passes with the mode on)"""
+        out = (C.c_uint64 * 8)()
+        self._ck(self.L.gaz_engine_get_match_stats(self.h, out))
+        s = [int(x) for x in out]
+        return dict(rows_a=s[0], rows_b=s[1], waves_without_a=s[2], waves_without_b=s[3], passes=s[4])
+
+    def match_timing(self):
+        """gaz_engine_get_match_timing as a dict, per bracketed wave (timing_reset(True) brackets every 8th): `ms_route_copy` (route +
+        partition + copy), `ms_sync_gap` (the stream idle from the end of the copy to the first launch after the host's wait), `ms_scatter`,
+        `ms_host_wait` (the host's time inside the wait) and `waves`, the waves bracketed"""
+        out = (C.c_double * 8)()
+        self._ck(self.L.gaz_engine_get_match_timing(self.h, out))
+        n = max(out[4], 1.0)
+        return dict(ms_route_copy=out[0] / n, ms_sync_gap=out[1] / n, ms_scatter=out[2] / n, ms_host_wait=out[3] / n, waves=int(out[4]))
 
     def read_batch_symmetry(self):
         """uint8 [batch_rows]: the symmetry k every row of the evaluator batch was encoded under (meaningful where read_batch's

@@ -14,6 +14,7 @@ out of scope): the caller supplies
 
 Generation 0 plays with the synthetic evaluator, like the reference's session=None dummy (Self_Play.py:40).
 """
+import json
 import os
 import time
 from glob import glob
@@ -21,7 +22,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .self_play import ReplayStore, run_self_play
+from .self_play import ReplayStore, play_match, run_self_play
 
 
 def make_generation_folder(root, generation):
@@ -74,9 +75,15 @@ def compute_speed(game_class, configs, weights, batch=None, iterations=200, devi
 
 
 def Run(game_class, configs, train_fn=None, weights_fn=None, root="Grok_Zero_Train", n_games=1024, seed=None, device=0,
-        lib_path=None, out=print, self_play_kwargs=None):
+        lib_path=None, out=print, self_play_kwargs=None, match=None):
     """The loop of <Game>/main.py:312-352: for every generation self-play (resumable), statistics, `train_fn`, next dataset file.
-    Returns the list of per-generation statistics."""
+    Returns the list of per-generation statistics.
+    `match` = None: nothing else.  match = dict(games=..., n_slots=None, threshold=None[, hash_salt_b=...]): after `train_fn` of a generation
+    g >= 1 the new network, weights_fn(folder g + 1), plays self_play.play_match as network A against the network that self-play currently
+    uses (the last accepted folder's; weights_fn returning None on both sides = the synthetic evaluator under two salts).  The result goes into
+    folder g + 1 as Match.json — `result`, `new_folder`, `old_folder`, `accepted`, `accepted_folder` — and into that generation's statistics
+    (`match`).  With a `threshold`, a new network whose score is below it is not accepted: the following generations' self-play keeps the
+    last accepted folder's weights.  A resumed Run reads the last accepted folder from the newest Match.json."""
     train_config = configs[1]
     total = int(train_config["total_generations"])
     gen = current_generation(root)
@@ -88,9 +95,18 @@ def Run(game_class, configs, train_fn=None, weights_fn=None, root="Grok_Zero_Tra
     if not ReplayStore(os.path.join(root, str(gen))).exists():                          # training of gen-1 finished, file missing
         make_dataset_file(os.path.join(root, str(gen)))
     stats = []
+    accepted = None                                                                     # folder whose weights self-play uses; None = the generation's own
+    if match is not None:
+        for g in range(gen, 0, -1):                                                     # resume: the newest Match.json says which folder was accepted last
+            mj = os.path.join(root, str(g), "Match.json")
+            if os.path.exists(mj):
+                with open(mj) as f:
+                    accepted = json.load(f)["accepted_folder"]
+                break
     for generation in range(gen, total):
         folder = os.path.join(root, str(generation))
-        weights = weights_fn(folder) if (weights_fn and generation > 0) else None
+        played_folder = folder if accepted is None else accepted
+        weights = weights_fn(played_folder) if (weights_fn and generation > 0) else None
         t0 = time.time()
         played = run_self_play(game_class, configs, folder, n_games=n_games, seed=None if seed is None else seed + generation,
                                weights=weights, device=device, lib_path=lib_path, **(self_play_kwargs or {}))
@@ -100,6 +116,19 @@ def Run(game_class, configs, train_fn=None, weights_fn=None, root="Grok_Zero_Tra
         if train_fn is not None:
             make_generation_folder(root, generation + 1)
             train_fn(generation, folder, os.path.join(root, str(generation + 1)))
+            if match is not None and generation >= 1:
+                new_folder = os.path.join(root, str(generation + 1))
+                kw = {k: v for k, v in match.items() if k not in ("games", "n_slots", "threshold")}
+                res = play_match(game_class, configs, weights_fn(new_folder) if weights_fn else None, weights, match["games"],
+                                 n_slots=match.get("n_slots"), seed=0 if seed is None else seed + generation, device=device, lib_path=lib_path, **kw)
+                res.pop("headers", None)
+                threshold = match.get("threshold")
+                ok = threshold is None or res["score"] >= threshold
+                accepted = new_folder if ok else played_folder
+                with open(os.path.join(new_folder, "Match.json"), "w") as f:
+                    json.dump(dict(result=res, new_folder=new_folder, old_folder=played_folder, accepted=bool(ok), accepted_folder=accepted), f, indent=1)
+                st["match"] = dict(res, accepted=bool(ok))
+                out(f"Match: generation {generation + 1} scored {res['score']:.3f} against {played_folder} over {res['n']} games: {'accepted' if ok else 'rejected'}")
         if generation < total - 1:
             make_generation_folder(root, generation + 1)
             make_dataset_file(os.path.join(root, str(generation + 1)))

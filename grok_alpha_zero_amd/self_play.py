@@ -13,6 +13,7 @@ importable and otherwise the system libhdf5 through h5io.py (ctypes) — a real 
 names / dtypes / shapes / libver either way.
 """
 import logging
+import math
 import os
 import queue
 import threading
@@ -428,6 +429,36 @@ class _ReplayWriter:
             raise self.error
 
 
+def engine_search_settings(game_class, configs):
+    """What train_config / build_config say about the search, as SelfPlayEngine takes it -> ((run_iterations, max_actions,
+    num_explore_actions_first, num_explore_actions_second, c_puct_init, dirichlet_alpha), keywords): the settings run_self_play and
+    play_match share."""
+    build_config, train_config = configs[0], configs[1]
+    gumbel = bool(train_config.get("use_gumbel"))
+    # PUCT runs int(1.5 * limit) iterations per move (Self_Play.py:99), Gumbel runs `limit` (Self_Play.py:110-112)
+    iters = int(train_config["MCTS_iteration_limit"]) if gumbel else int(train_config["MCTS_iteration_limit"] * 1.5)
+    fast = int(train_config.get("MCTS_fast_iteration_limit") or 0)
+    fast = fast if gumbel else int(fast * 1.5)
+    args = (iters, train_config["max_actions"], train_config.get("num_explore_actions_first", 0), train_config.get("num_explore_actions_second", 0),
+            train_config.get("c_puct_init", 0.0), train_config.get("dirichlet_alpha", 0.0))
+    kw = dict(search=SEARCH_GUMBEL if gumbel else SEARCH_PUCT, gumbel_m=train_config.get("m", 0),
+              c_visit=train_config.get("c_visit", 50.0), c_scale=train_config.get("c_scale", 1.0),
+              # policy head: raw logits for Gumbel, else Stablemax or softmax (Build_Model.py:54-60)
+              policy_is_logits=1 if gumbel else (2 if build_config.get("use_stablemax") else 0),
+              gumbel_stablemax=bool(gumbel and build_config.get("use_stablemax")),
+              opening_actions=[(game_class.action_to_index(a) if hasattr(game_class, "action_to_index") else int(a), w)
+                               for a, w in train_config.get("opening_actions", []) or []],
+              create_new_root=train_config.get("create_new_root", False),
+              # Self_Play.py:35,100-112: every MCTS.run gets time_limit = MCTS_time_limit next to its iteration limit; the engine keeps a
+              # wall clock per game and move (PUCT) / runs 3 x legal moves iterations per move (Gumbel, MCTS_Gumbel.py:576-578)
+              move_time_limit=float(train_config.get("MCTS_time_limit") or 0.0),
+              fast_iterations=fast, full_search_prob=float(train_config.get("full_search_prob") or 0.0) if fast else 0.0,
+              forced_playouts_k=float(train_config.get("forced_playouts_k") or 0.0),
+              resign_threshold=float(train_config.get("resign_threshold") or 0.0), resign_consecutive=int(train_config.get("resign_consecutive") or 1),
+              resign_min_ply=int(train_config.get("resign_min_ply") or 0), no_resign_prob=float(train_config.get("no_resign_prob") or 0.0))
+    return args, kw
+
+
 def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, *, n_games=1024, seed=None, weights=None,
                   device=0, slot_offset=0, hash_salt=0, lib_path=None, progress=None, eval_cache_log2=22, generation=None,
                   first_game_seq=None, allow_synthetic=False, engine_stats=None, game_groups=0, device_samples=None,
@@ -505,34 +536,14 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
     if first_game_seq is None:
         first_game_seq = games_done
     gumbel = bool(train_config.get("use_gumbel"))
-    # PUCT runs int(1.5 * limit) iterations per move (Self_Play.py:99), Gumbel runs `limit` (Self_Play.py:110-112)
-    iters = int(train_config["MCTS_iteration_limit"]) if gumbel else int(train_config["MCTS_iteration_limit"] * 1.5)
-    fast = int(train_config.get("MCTS_fast_iteration_limit") or 0)
-    fast = fast if gumbel else int(fast * 1.5)
-    eng = SelfPlayEngine(name, G, iters, train_config["max_actions"],
-                         train_config.get("num_explore_actions_first", 0), train_config.get("num_explore_actions_second", 0),
-                         train_config.get("c_puct_init", 0.0), train_config.get("dirichlet_alpha", 0.0), seed,
-                         search=SEARCH_GUMBEL if gumbel else SEARCH_PUCT, gumbel_m=train_config.get("m", 0),
-                         c_visit=train_config.get("c_visit", 50.0), c_scale=train_config.get("c_scale", 1.0),
-                         # policy head: raw logits for Gumbel, else Stablemax or softmax (Build_Model.py:54-60)
-                         policy_is_logits=1 if gumbel else (2 if build_config.get("use_stablemax") else 0),
-                         gumbel_stablemax=bool(gumbel and build_config.get("use_stablemax")),
-                         opening_actions=[(game_class.action_to_index(a) if hasattr(game_class, "action_to_index") else int(a), w)
-                                          for a, w in train_config.get("opening_actions", []) or []],
-                         create_new_root=train_config.get("create_new_root", False), slot_offset=slot_offset, device=device,
+    args, search_kw = engine_search_settings(game_class, configs)
+    eng = SelfPlayEngine(name, G, *args, seed, slot_offset=slot_offset, device=device,
                          evaluator=EVAL_RESNET if use_net else EVAL_HASH, hash_salt=hash_salt,
                          net_blocks=build_config.get("num_resnet_layers", 0) if use_net else 0,
                          net_filters=build_config.get("num_filters", 128), ring_capacity=max(4 * G, 64), lib_path=lib_path,
                          eval_cache_log2=0 if leaf_batch > 1 or gumbel_batch > 1 else eval_cache_log2,    # on-device Session_Cache (Self_Play.py:234-236): same games, fewer waves
-                         games_budget=games_left, first_game_seq=first_game_seq,
-                         # Self_Play.py:35,100-112: every MCTS.run gets time_limit = MCTS_time_limit next to its iteration limit; the engine keeps a
-                         # wall clock per game and move (PUCT) / runs 3 x legal moves iterations per move (Gumbel, MCTS_Gumbel.py:576-578)
-                         move_time_limit=float(train_config.get("MCTS_time_limit") or 0.0), game_groups=game_groups,
-                         leaf_batch=leaf_batch, gumbel_batch=gumbel_batch,
-                         fast_iterations=fast, full_search_prob=float(train_config.get("full_search_prob") or 0.0) if fast else 0.0,
-                         forced_playouts_k=float(train_config.get("forced_playouts_k") or 0.0),
-                         resign_threshold=float(train_config.get("resign_threshold") or 0.0), resign_consecutive=int(train_config.get("resign_consecutive") or 1),
-                         resign_min_ply=int(train_config.get("resign_min_ply") or 0), no_resign_prob=float(train_config.get("no_resign_prob") or 0.0))
+                         games_budget=games_left, first_game_seq=first_game_seq, game_groups=game_groups,
+                         leaf_batch=leaf_batch, gumbel_batch=gumbel_batch, **search_kw)
     if train_config.get("MCTS_time_limit") and gumbel:
         logging.getLogger("grok_alpha_zero_amd").warning("Time limit isn't allowed for gumbel MCTS defaulting to use 3 * len_legal_actions")   # MCTS_Gumbel.py:578
     logging.getLogger("grok_alpha_zero_amd").info("run_self_play: generation %d, %d games on %d slots, evaluator = %s, game_seq from %d",
@@ -597,3 +608,87 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
             writer.close(reraise=False)
         eng.close()
     return written
+
+
+# ------------------------------------------------------------------------------------------------ match play
+def _elo(score):
+    return None if score <= 0.0 or score >= 1.0 else -400.0 * math.log10(1.0 / score - 1.0)
+
+
+def match_result(records):
+    """The result of a match (SelfPlayEngine.set_match) from its finished games: records (drain_finished's dicts) or headers (T, winner,
+    slot, game_seq).  Network A plays the first player (-1) of game (slot, game_seq) iff slot + game_seq is even, so a header says who
+    was A.  -> dict: n, a_wins, draws, b_wins; `a_first` / `a_second`, the same counts over the games in which A was the first / the
+    second player; score = (a_wins + 0.5 draws) / n; elo = -400 log10(1 / score - 1), None at score 0 or 1; elo_ci95 = that formula on
+    score -+ 1.96 sqrt(var / n), var the (population) variance of the per-game scores 1 / 0.5 / 0 and both ends clipped into
+    [1e-9, 1 - 1e-9]."""
+    split = {True: dict(n=0, a_wins=0, draws=0, b_wins=0), False: dict(n=0, a_wins=0, draws=0, b_wins=0)}
+    scores = []
+    for r in records:
+        _, winner, slot, seq = (int(r[k]) for k in ("T", "winner", "slot", "game_seq")) if isinstance(r, dict) else (int(x) for x in r)
+        a_first = (slot + seq) % 2 == 0
+        key = "draws" if winner == 0 else ("a_wins" if (winner == -1) == a_first else "b_wins")
+        split[a_first]["n"] += 1; split[a_first][key] += 1
+        scores.append(0.5 if winner == 0 else (1.0 if key == "a_wins" else 0.0))
+    n = len(scores)
+    if n == 0:
+        raise ValueError("match_result: no games")
+    out = {k: split[True][k] + split[False][k] for k in ("n", "a_wins", "draws", "b_wins")}
+    score = (out["a_wins"] + 0.5 * out["draws"]) / n
+    var = sum((x - score) ** 2 for x in scores) / n
+    half = 1.96 * math.sqrt(var / n)
+    clip = lambda x: min(max(x, 1e-9), 1.0 - 1e-9)
+    out.update(a_first=split[True], a_second=split[False], score=score, elo=_elo(score), elo_ci95=(_elo(clip(score - half)), _elo(clip(score + half))))
+    return out
+
+
+def play_match(game_class, configs, weights_a, weights_b, games, n_slots=None, seed=0, **engine_kw):
+    """`games` games between network A (`weights_a`) and network B (`weights_b`) in one engine -> match_result of them, plus `positions`
+    (plies played), `seconds` and `match_stats`.  Weights are dicts from net.export_engine_weights(); None for both plays the synthetic
+    hash evaluator under engine_kw's hash_salt (A) and hash_salt_b (B).  `games` must be a positive multiple of 2 * n_slots (default
+    n_slots = games / 2): every slot then plays as many games with A first as with B first.  The search settings come from train_config
+    as in run_self_play; the engine has one game group and no evaluation cache (SelfPlayEngine.set_match)."""
+    build_config = configs[0]
+    if n_slots is None:
+        n_slots = max(int(games) // 2, 1)
+    if games <= 0 or n_slots <= 0 or games % (2 * n_slots):
+        raise ValueError(f"play_match: games ({games}) must be a positive multiple of 2 * n_slots ({2 * n_slots}), so that the colours balance")
+    if (weights_a is None) != (weights_b is None):
+        raise ValueError("play_match: give the weights of both networks, or of neither (the synthetic evaluator under two salts)")
+    use_net = weights_a is not None
+    name = getattr(game_class, "ENGINE_NAME", game_class.__name__)
+    if use_net:
+        from .net import check_engine_weights
+        for w in (weights_a, weights_b):
+            check_engine_weights(name, build_config.get("num_resnet_layers", 0), build_config.get("num_filters", 128), w)
+    args, kw = engine_search_settings(game_class, configs)
+    salt_b = engine_kw.pop("hash_salt_b", 0)
+    kw.update(evaluator=EVAL_RESNET if use_net else EVAL_HASH, net_blocks=build_config.get("num_resnet_layers", 0) if use_net else 0,
+              net_filters=build_config.get("num_filters", 128), ring_capacity=max(4 * n_slots, 64), games_budget=int(games), game_groups=1)
+    kw.update(engine_kw)
+    eng = SelfPlayEngine(name, n_slots, *args, seed, **kw)
+    try:
+        if use_net:
+            eng.load_weights(weights_a); eng.load_weights_b(weights_b)
+        eng.set_match(True, hash_salt_b=salt_b)
+        train_config = configs[1]
+        if train_config.get("eval_symmetry"):
+            eng.set_eval_symmetry(True)
+        if train_config.get("solver"):
+            eng.set_solver(True)
+        t0 = time.perf_counter()
+        records, idle = [], 0
+        while len(records) < games:
+            eng.run_waves(64)
+            got = eng.drain_finished()
+            records += got
+            idle = 0 if got else idle + 1
+            if idle > 100000:
+                raise RuntimeError("the match made no progress")
+        seconds = time.perf_counter() - t0
+        out = match_result(records)
+        out.update(positions=sum(int(r["T"]) for r in records), seconds=seconds, match_stats=eng.match_stats())
+        out["headers"] = [(int(r["T"]), int(r["winner"]), int(r["slot"]), int(r["game_seq"])) for r in records]
+    finally:
+        eng.close()
+    return out

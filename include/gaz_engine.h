@@ -48,6 +48,10 @@
  *   gaz_engine_set_eval_symmetry / gaz_engine_get_eval_symmetry / gaz_engine_read_batch_symmetry  (no reference counterpart: the reference
  *                              augments its training samples with the board symmetries, Guide.py:255-283, but always shows the search's
  *                              network one orientation; a random symmetry per evaluation is AlphaGo Zero's and KataGo's)
+ *   gaz_engine_set_match / gaz_engine_get_match / gaz_engine_load_weights_b / gaz_engine_read_batch_network / gaz_engine_get_match_stats /
+ *   gaz_engine_get_match_timing
+ *                              (no reference counterpart: the reference's Run has no evaluation step, every generation's network is played on
+ *                              unconditionally, <game>/main.py; a match between the new and the current network is AlphaGo Zero's evaluator)
  */
 #ifndef GAZ_ENGINE_H
 #define GAZ_ENGINE_H
@@ -262,6 +266,50 @@ int gaz_engine_get_eval_symmetry(gaz_engine* h, int32_t* mode);
  * without a request keeps the k of the last request written there (0 if none, and 0 everywhere while the mode has never been on).  Available and
  * refused where gaz_engine_read_batch is (game groups: refused). */
 int gaz_engine_read_batch_symmetry(gaz_engine* h, uint8_t* sym);
+
+/* Match play: the games of one engine played by TWO networks, to tell whether one is stronger (no reference counterpart).
+ * Network A is the weight set of gaz_engine_load_weights (GAZ_EVAL_HASH: the salt gaz_engine_config.hash_salt), network B that of
+ * gaz_engine_load_weights_b (hash_salt_b).  mode 0 = off (the state of a new engine), 1 = on.  No struct changes and GAZ_ENGINE_ABI_VERSION stays
+ * 10: the feature is detected by its symbols.
+ * RULE.  In game (slot, game_seq) — slot = the global slot, slot_offset + the slot the game started in, as in the record header — network A
+ * plays the first player (-1) iff (slot + game_seq) is even: colours alternate over the slots and over the successive games of a slot.  The
+ * OWNER of a pending request is, PUCT with two trees: the tree that asks (tree 0 searches for player -1, tree 1 for player 1; a root creation
+ * after a move belongs to the tree it builds); Gumbel: the player to move in the game, -1 -> 0, 1 -> 1.  The request is answered by network
+ *   owner XOR ((slot + game_seq) & 1)                                                     (0 = A, 1 = B).
+ * The rule is a function of the game state alone: switching the mode takes effect at the next evaluator pass and needs no migration, and a
+ * record's header (T, winner, slot, game_seq) says who was A, so results are tallied from records (records are unchanged).
+ * Allowed: PUCT with two trees and Gumbel; GAZ_EVAL_HASH, GAZ_EVAL_RESNET (every num_filters) and GAZ_EVAL_EXTERNAL; sync and continuous mode;
+ * games_budget, the playout cap, forced playouts, resignation, the solver and the evaluation symmetry (none of them is touched).
+ * Refused, each with its own last_error text: single_tree = 1, leaf_batch > 1, gumbel_batch > 1, eval_cache_log2 > 0, an engine that resolved to
+ * game groups (create it with game_groups = 1), a struct_size other than sizeof(gaz_match_params), a mode other than 0 or 1; and with the mode on
+ * and GAZ_EVAL_RESNET, gaz_engine_run_move / gaz_engine_run_waves before gaz_engine_load_weights_b ("weights of network B not loaded").
+ * While the mode is on the tree step and the evaluator pass are separate launches (gaz_engine_get_stats [12] is 0), the host waits once per
+ * wave for the two row counts, rows without a request are neither evaluated nor written, and gaz_engine_repack and
+ * gaz_engine_debug_fused_fault are refused; gaz_engine_evaluate stays network A.  Switching off restores everything.
+ * Out of scope: leaf_batch / gumbel_batch, the evaluation cache, game groups, the fused launch and repack with the mode on; more than two
+ * networks; matches over several GPUs. */
+typedef struct {
+    uint32_t struct_size;         /* = sizeof(gaz_match_params) */
+    int32_t mode;                 /* 0 off, 1 on */
+    uint32_t hash_salt_b;         /* GAZ_EVAL_HASH: the salt of network B (ignored by the other evaluators) */
+    int32_t reserved_;
+} gaz_match_params;
+int gaz_engine_set_match(gaz_engine* h, const gaz_match_params* p);
+int gaz_engine_get_match(gaz_engine* h, int32_t* mode);
+/* the weights of network B: the names and shapes of gaz_engine_load_weights.  Legal before the mode is switched on */
+int gaz_engine_load_weights_b(gaz_engine* h, const gaz_tensor* tensors, int32_t n);
+/* net[rows] (rows = n_games): the network that answers every row of the evaluator batch as the games stand — 0 = A, 1 = B, 255 = the row
+ * carries no request (exactly where gaz_engine_read_batch's pending is 0).  A GAZ_EVAL_EXTERNAL caller answers each row with the network the
+ * byte names.  Legal with the mode off too (the rule is stateless); refused where gaz_engine_set_match(1) is. */
+int gaz_engine_read_batch_network(gaz_engine* h, uint8_t* net);
+/* host counters over the engine's life: [0] rows evaluated by A, [1] by B, [2] waves in which A got no row, [3] in which B got none,
+ * [4] evaluator passes with the mode on, [5..7] 0.  (GAZ_EVAL_EXTERNAL: the engine runs no evaluator pass, all 0.) */
+int gaz_engine_get_match_stats(gaz_engine* h, uint64_t out[8]);
+/* what the routing stage costs (tools/match_bench.py), summed over the waves that gaz_engine_timing_reset(1) brackets (every 8th), in ms, HIP
+ * events on the engine's stream: [0] route + partition + copy, [1] the stream's idle gap from the end of the copy to the first launch after
+ * the host's wait for the row counts, [2] the scatter; [3] the host's time inside that wait (host clock), [4] the waves bracketed, [5..7] 0.
+ * A host synchronisation point. */
+int gaz_engine_get_match_timing(gaz_engine* h, double out[8]);
 
 /* Solver (MCTS-Solver): proven wins, draws and losses in the PUCT search.  mode 0 = off (the state of a new engine), 1 = on; any other value
  * is refused.  It takes effect at the next launch; statuses are written and used only while it is on.  Refused — each with its own last_error
