@@ -122,7 +122,9 @@ GAZ_DEV double normal(const Event& e, uint32_t lane, uint32_t& attempt) {
 }
 
 // Gamma(alpha, 1): Marsaglia & Tsang with the alpha < 1 boost
-GAZ_DEV double gamma(const Event& e, uint32_t lane, double alpha) {
+// info (the det probe only, det_probe.hpp; null in the search, where the stores fold away): [0] = Philox draws consumed, [1] = the test
+// that accepted, 1 = the squeeze, 2 = the log test
+GAZ_DEV double gamma(const Event& e, uint32_t lane, double alpha, uint32_t* info = nullptr) {
     uint32_t attempt = 0;
     double boost = 1.0, a = alpha;
     if (a < 1.0) {
@@ -140,8 +142,8 @@ GAZ_DEV double gamma(const Event& e, uint32_t lane, double alpha) {
         U4 r = draw(e, lane, attempt++);
         double u = u_open(r.x, r.y);
         const double x2 = x * x;                     // squeeze (same accepted pairs as the log test, see oracle/gaz_det.h)
-        if (u < 1.0 - 0.0331 * (x2 * x2)) return (d * v) * boost;
-        if (dlog(u) < ((0.5 * x) * x + d) - d * v + d * dlog(v)) return (d * v) * boost;
+        if (u < 1.0 - 0.0331 * (x2 * x2)) { if (info) { info[0] = attempt; info[1] = 1u; } return (d * v) * boost; }
+        if (dlog(u) < ((0.5 * x) * x + d) - d * v + d * dlog(v)) { if (info) { info[0] = attempt; info[1] = 2u; } return (d * v) * boost; }
     }
 }
 
@@ -180,11 +182,19 @@ GAZ_DEV T np_sum_block(const T* a, int n) {   // n <= 128
     for (; i < n; ++i) res = res + a[i];
     return res;
 }
-template <class T>
+// CAP: the size of the caller's array, n <= CAP <= 256.  Every array of the search (Scratch: APAD <= 232) is shorter than the 249 elements
+// at which numpy splits a second time, so the search's instantiations carry no code for that.
+template <class T, int CAP>
 GAZ_DEV T np_pairwise_sum(const T* a, int n) {
+    static_assert(CAP >= 8 && CAP <= 256, "np_sum_block reads eight elements; numpy's third level of splits (n > 256) is not restated");
     if (n <= 128) return np_sum_block(a, n);
-    int n2 = n / 2; n2 -= n2 % 8;                       // numpy splits once for 128 < n <= 256
-    return np_sum_block(a, n2) + np_sum_block(a + n2, n - n2);
+    int n2 = n / 2; n2 -= n2 % 8;                       // numpy splits 128 < n <= 256 into n2 <= 128 and the rest
+    if constexpr (CAP <= 248) return np_sum_block(a, n2) + np_sum_block(a + n2, n - n2);
+    const T lo = np_sum_block(a, n2);
+    a += n2; n -= n2;
+    if (n <= 128) return lo + np_sum_block(a, n);
+    n2 = n / 2; n2 -= n2 % 8;                           // 249 <= n <= 255 leave a rest of 129..135, which numpy splits once more
+    return lo + (np_sum_block(a, n2) + np_sum_block(a + n2, n - n2));
 }
 
 }  // namespace det

@@ -13,6 +13,7 @@
 #include "tree_export.hpp"
 #include "evaluator.hpp"
 #include "match.hpp"
+#include "det_probe.hpp"
 
 using namespace gaz;
 
@@ -422,6 +423,7 @@ struct gaz_engine {
     virtual int get_match_stats(uint64_t out[8]) = 0;
     virtual int get_match_timing(double out[8]) = 0;
     virtual int probe_rules(const int32_t*, const int32_t*, int, int, int8_t*, uint8_t*, int32_t*, int8_t*, int32_t*, const float*, float*) = 0;
+    virtual int probe_det(int, int, const uint64_t*, int, uint64_t*, int) = 0;
 };
 
 // device allocations that live for one call (gaz_engine_read_trees / gaz_engine_read_pv)
@@ -1628,6 +1630,41 @@ template <class G> struct EngineT : gaz_engine {
         HIP_OK(hipStreamSynchronize(stream));
         return 0;
     }
+    // gaz_engine_probe_det (det_probe.hpp): every count an item carries is checked here, so that no kernel indexes past its arrays
+    uint64_t* pd_in = nullptr; uint64_t* pd_out = nullptr; size_t pd_in_cap = 0, pd_out_cap = 0;
+    int probe_det(int op, int n, const uint64_t* in, int in_words, uint64_t* out, int out_words) override {
+        const bool whole = (op & DP_WHOLE_WAVE) != 0;
+        const int code = op & ~DP_WHOLE_WAVE;
+        DetProbeOp d;
+        if (!det_probe_op(code, &d)) return fail("probe_det: unknown op " + std::to_string(op));
+        if (n <= 0 || n > (1 << 22) || in_words <= 0 || out_words <= 0 || in_words > 4096 || out_words > 4096 || !in || !out) return fail("probe_det: bad arguments");
+        if (!d.team) {
+            if (whole) return fail("probe_det: DP_WHOLE_WAVE goes with the team ops only");
+            if (in_words != d.in || out_words != d.out) return fail("probe_det: op " + std::to_string(code) + " takes " + std::to_string(d.in) + " words per item and gives " + std::to_string(d.out));
+        } else {
+            const uint64_t limit = (code == DP_SUM_F32 || code == DP_SUM_F64) ? (uint64_t)DP_SUM_MAX : (uint64_t)G::A;
+            for (int i = 0; i < n; ++i) {
+                const uint64_t ni = in[(size_t)i * in_words];
+                if (ni < 1 || ni > limit) return fail("probe_det: item " + std::to_string(i) + " has n outside 1.." + std::to_string(limit));
+                const int nf = ni < 8 ? 8 : (int)ni;
+                if (in_words < d.in + d.in_per * nf || out_words < d.out + d.out_per * (int)ni) return fail("probe_det: item " + std::to_string(i) + " does not fit its words");
+            }
+        }
+        const size_t bi = (size_t)n * in_words, bo = (size_t)n * out_words;
+        if (bi > pd_in_cap) { if (dalloc(&pd_in, bi)) return 1; pd_in_cap = bi; }        // scratch grows, never shrinks (freed with the engine)
+        if (bo > pd_out_cap) { if (dalloc(&pd_out, bo)) return 1; pd_out_cap = bo; }
+        HIP_OK(hipMemcpyAsync(pd_in, in, bi * 8, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemsetAsync(pd_out, 0, bo * 8, stream));
+        typedef typename PuctVariant<G>::type GP;
+        constexpr int PER = WAVE / GP::TEAM;
+        if (!d.team) GAZ_LAUNCH(k_probe_det<G>, (n + WAVE - 1) / WAVE, WAVE, stream, E, code, n, (const uint64_t*)pd_in, in_words, pd_out, out_words);
+        else if (PER > 1 && !whole) GAZ_LAUNCH(k_probe_det_teams<GP>, (n + PER - 1) / PER, WAVE, stream, *reinterpret_cast<const DevParams<GP>*>(&E), code, n, (const uint64_t*)pd_in, in_words, pd_out, out_words);
+        else GAZ_LAUNCH(k_probe_det_wave<G>, n, WAVE, stream, E, code, n, (const uint64_t*)pd_in, in_words, pd_out, out_words);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(out, pd_out, bo * 8, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        return 0;
+    }
     int dominant(char* name, int cap, double* flops) override {
         // positions per evaluator launch; the pipelined run launches the trunk kernel once per group: price the MEAN launch (the
         // timing sums all launches, so FLOPs per launch x launches = FLOPs of the waves either way)
@@ -1914,6 +1951,7 @@ struct GroupEngine : gaz_engine {
     int get_match_timing(double out[8]) override { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }
     int probe_rules(const int32_t* actions, const int32_t* n_actions, int n_pos, int stride, int8_t* b, uint8_t* l, int32_t* w, int8_t* in, int32_t* t,
                     const float* pin, float* pout) override { return lead(&gaz_engine::probe_rules, actions, n_actions, n_pos, stride, b, l, w, in, t, pin, pout); }
+    int probe_det(int op, int n, const uint64_t* in, int iw, uint64_t* out, int ow) override { return lead(&gaz_engine::probe_det, op, n, in, iw, out, ow); }
 };
 
 // auto (game_groups = 0): two groups where that was measured to pay (see above; measured at num_filters = 128 only, so other widths run one group); GAZ_GAME_GROUPS overrides the automatic choice only
@@ -2080,6 +2118,9 @@ int gaz_engine_read_head_features(gaz_engine* h, int32_t n, float* p, float* v, 
 int gaz_engine_probe_rules(gaz_engine* h, const int32_t* actions, const int32_t* n_actions, int32_t n_positions, int32_t stride, int8_t* board,
                            uint8_t* legal, int32_t* winner, int8_t* input, int32_t* terminal, const float* policy_in, float* policy_out) {
     return h->probe_rules(actions, n_actions, n_positions, stride, board, legal, winner, input, terminal, policy_in, policy_out);
+}
+int gaz_engine_probe_det(gaz_engine* h, int32_t op, int32_t n_items, const uint64_t* in, int32_t in_words, uint64_t* out, int32_t out_words) {
+    return h->probe_det(op, n_items, in, in_words, out, out_words);
 }
 int gaz_engine_dominant_kernel(gaz_engine* h, char* name, int32_t cap, double* flops) { return h->dominant(name, cap, flops); }
 int gaz_engine_timing_get(gaz_engine* h, double* a, double* b, double* c, int64_t* d, int64_t* e) { return h->timing_get(a, b, c, d, e); }

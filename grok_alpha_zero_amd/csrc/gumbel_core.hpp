@@ -104,7 +104,7 @@ template <class G> GAZ_DEV void softmax_inplace(Scratch<G>& S, int n) {
     const double c = -mx;
     for (int i = tlane<G>(); i < n; i += G::TEAM) S.gam[i] = det::dexp(S.gam[i] + c);
     wave_sync();
-    const double s = det::np_pairwise_sum<double>(S.gam, n);
+    const double s = det::np_pairwise_sum<double, G::APAD>(S.gam, n);
     wave_sync();
     for (int i = tlane<G>(); i < n; i += G::TEAM) S.gam[i] = S.gam[i] / s;
     wave_sync();
@@ -225,7 +225,7 @@ template <class G> GAZ_DEV void compute_pi(const DevParams<G>& E, const NodeRef<
     if (stable) {                                           // stablemax(float32 logits), np.sum in float32
         for (int i = tlane<G>(); i < n; i += G::TEAM) { const float l = L[i]; S.spri[i] = l >= 0.0f ? l + 1.0f : 1.0f / ((1.0f - l) + F32_EPS); }
         wave_sync();
-        const float ssum = det::np_pairwise_sum<float>(S.spri, n);
+        const float ssum = det::np_pairwise_sum<float, G::APAD>(S.spri, n);
         wave_sync();
         for (int i = tlane<G>(); i < n; i += G::TEAM) S.gam[i] = (double)(S.spri[i] / ssum);
         wave_sync();
@@ -243,11 +243,11 @@ template <class G> GAZ_DEV void compute_pi(const DevParams<G>& E, const NodeRef<
     wave_sync();
     for (int i = tlane<G>(); i < n; i += G::TEAM) S.spri[i] = N[i] > 0 ? S.pri[i] : 0.0f;
     wave_sync();
-    const float sum_probs = det::np_pairwise_sum<float>(S.spri, n);
+    const float sum_probs = det::np_pairwise_sum<float, G::APAD>(S.spri, n);
     wave_sync();
     for (int i = tlane<G>(); i < n; i += G::TEAM) S.spri[i] = N[i] > 0 ? (S.pri[i] * S.aux[i]) / sum_probs : 0.0f;
     wave_sync();
-    const float weighted_q = det::np_pairwise_sum<float>(S.spri, n);
+    const float weighted_q = det::np_pairwise_sum<float, G::APAD>(S.spri, n);
     wave_sync();
     const double wq = (double)weighted_q * (double)sumv;
     for (int i = tlane<G>(); i < n; i += G::TEAM) {
@@ -273,7 +273,7 @@ template <class G> GAZ_DEV void compute_pi(const DevParams<G>& E, const NodeRef<
     if (stable) {                                           // stablemax in float64, result stays in S.gam
         for (int i = tlane<G>(); i < n; i += G::TEAM) { const double x = S.gam[i]; S.gam[i] = x >= 0.0 ? x + 1.0 : 1.0 / ((1.0 - x) + (double)F32_EPS); }
         wave_sync();
-        const double ssum = det::np_pairwise_sum<double>(S.gam, n);
+        const double ssum = det::np_pairwise_sum<double, G::APAD>(S.gam, n);
         wave_sync();
         for (int i = tlane<G>(); i < n; i += G::TEAM) S.gam[i] = S.gam[i] / ssum;
         wave_sync();

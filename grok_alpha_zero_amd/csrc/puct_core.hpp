@@ -467,7 +467,9 @@ GAZ_DEV void puct_factors(uint64_t parent_visits, double c_init, double c_base, 
 
 // Solver (`masked`, kernels with the solver's code only): slots whose edge value is -1 — the child is proven a win for its mover — are left out
 // of the argmax; `any_left_out` reports whether the team left one out.  Everything else of the score is unchanged.
-template <class G> GAZ_DEV int best_puct_slot(const NodeRef<G>& nd, int n_actions, double s, double c, bool masked = false, bool* any_left_out = nullptr) {
+// `scores` (the det probe only, det_probe.hpp; null in the search, where the store folds away): receives the float64 score of every slot scored.
+template <class G> GAZ_DEV int best_puct_slot(const NodeRef<G>& nd, int n_actions, double s, double c, bool masked = false, bool* any_left_out = nullptr,
+                                              double* scores = nullptr) {
     const uint32_t* N = nd.N(); const float* Wv = nd.W(); const float* P = nd.P();
     double best = 0.0; int bi = 0x7fffffff;
     bool left_out = false;
@@ -478,6 +480,7 @@ template <class G> GAZ_DEV int best_puct_slot(const NodeRef<G>& nd, int n_action
         float q = w;
         if (n > 0) q = (float)((double)w / (double)n);
         double sc = (double)q + u;
+        if (scores) scores[i] = sc;
         if (bi == 0x7fffffff || sc > best) { best = sc; bi = i; }
     }
     team_argmax<G>(best, bi);
@@ -495,7 +498,7 @@ template <class G> GAZ_DEV void make_priors(const DevParams<G>& E, int g, const 
     // `policy` is in the network's frame: under symmetry `sym` the entry of action a sits at eval_sym_policy_index(sym, a)
     for (int i = tlane<G>(); i < n_legal; i += G::TEAM) { const int a = S.legal[i]; S.pri[i] = policy[sym ? eval_sym_policy_index<G>(sym, a) : a]; }
     wave_sync();
-    const float sum = det::np_pairwise_sum<float>(S.pri, n_legal);   // uniform: every lane computes the same value
+    const float sum = det::np_pairwise_sum<float, G::APAD>(S.pri, n_legal);   // uniform: every lane computes the same value
     const bool flat = !(sum > 0.0f && sum <= 3.402823466e+38f);      // 0, negative, NaN, inf: the zero-mass rule
     const float flat_p = 1.0f / (float)n_legal;
     wave_sync();
@@ -1240,7 +1243,7 @@ template <class G> GAZ_DEV void move_end(const DevParams<G>& E, int g, GameState
             for (int i = tlane<G>(); i < n; i += G::TEAM) S.gam[i] = (solve && S.aux[i] == 0.0f) ? 0.0 : det::dpow((double)r.N()[i], ex) / den;
         }
         wave_sync();
-        const double s = det::np_pairwise_sum<double>(S.gam, n);
+        const double s = det::np_pairwise_sum<double, G::APAD>(S.gam, n);
         double acc = 0.0, last = 0.0;
         for (int i = 0; i < n; ++i) { acc = acc + S.gam[i] / s; last = acc; }
         acc = 0.0; chosen = n - 1;

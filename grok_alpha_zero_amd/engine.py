@@ -140,6 +140,9 @@ def load_library(lib_path=None):
     L.gaz_engine_get_match_stats.argtypes = [H, C.POINTER(C.c_uint64)]
     L.gaz_engine_get_match_timing.argtypes = [H, C.POINTER(C.c_double)]
     L.gaz_engine_probe_rules.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7
+    if hasattr(L, "gaz_engine_probe_det"):              # detected by its symbol: a library built before it has none
+        L.gaz_engine_probe_det.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.gaz_engine_probe_det.restype = C.c_int
     L.gaz_engine_set_fused_wave.argtypes = [H, C.c_int32]
     L.gaz_engine_debug_fused_fault.argtypes = [H, C.c_int32]
     L.gaz_engine_read_positions.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32]
@@ -161,6 +164,12 @@ def load_library(lib_path=None):
 
 class EngineError(RuntimeError):
     pass
+
+
+# the ops of SelfPlayEngine.probe_det (csrc/det_probe.hpp lists the words each reads and writes)
+(DP_PHILOX, DP_DRAW, DP_UNIT, DP_DLOG, DP_DEXP, DP_DPOW, DP_DSQRT, DP_DDIV, DP_PUCT_C, DP_PUCT_FACTORS, DP_SAMPLE) = range(11)
+(DP_SUM_F32, DP_SUM_F64, DP_PUCT_SCORES, DP_SOFTMAX, DP_PI) = range(16, 21)
+DP_WHOLE_WAVE = 0x100        # a team op of a small board on a whole wavefront instead of a 16-lane team
 
 
 class SampleBatch:
@@ -459,6 +468,19 @@ class SelfPlayEngine:
                                                out["terminal"].ctypes.data, None if pin is None else pin.ctypes.data,
                                                None if pout is None else pout.ctypes.data))
         out["legal"] = out["legal"].astype(bool)
+        return out
+
+    def probe_det(self, op, words, out_words):
+        """The device's bit-exact math on the caller's inputs (include/gaz_engine.h, gaz_engine_probe_det; the ops DP_* and their words are
+        listed in csrc/det_probe.hpp): `words` uint64 [n, in_words], one row per item -> uint64 [n, out_words], raw bits.  A float64 is
+        passed and returned as its bit pattern (`.view(np.uint64)`), a float32 / uint32 in the low half of its word."""
+        fn = getattr(self.L, "gaz_engine_probe_det", None)
+        if fn is None:
+            raise EngineError("this library has no gaz_engine_probe_det")
+        w = np.ascontiguousarray(words, np.uint64)
+        assert w.ndim == 2 and w.shape[0] > 0
+        out = np.zeros((w.shape[0], int(out_words)), np.uint64)
+        self._ck(fn(self.h, int(op), w.shape[0], w.ctypes.data, w.shape[1], out.ctypes.data, int(out_words)))
         return out
 
     def reset_games(self, slots=None):

@@ -26,7 +26,8 @@
  *   gaz_engine_set_hyperparams    MCTS.update_hyperparams(c_puct_*, dirichlet_*, tau) MCTS.py:134-168;
  *                                 MCTS_Gumbel.update_hyperparams(m, c_visit, c_scale)  MCTS_Gumbel.py:186-210
  *   gaz_engine_probe_rules     the Game plugin's static *_MCTS functions          Guide.py:135-283, Game_Tester.py:297-405
- *   gaz_engine_stop_search        run(time_limit)                              MCTS.py:560-563
+ *   gaz_engine_probe_det       (test probe; no reference counterpart: the device's float64 / Philox arithmetic as raw bits)
+ *   gaz_engine_stop_search        run(time_limit)                             MCTS.py:560-563
  *   gaz_engine_repack             finished workers no longer load the inference server  Self_Play.py:380-400
  *   gaz_engine_set_fused_wave     (scheduling switch; no reference counterpart: Client_Server.py's server loop is what it replaces)
  *   gaz_engine_debug_fused_fault  (test hook for that launch's bounded hand-over; what it replaces is the client's unbounded
@@ -408,6 +409,14 @@ int gaz_engine_start_search(gaz_engine* h);
 int gaz_engine_probe_rules(gaz_engine* h, const int32_t* actions, const int32_t* n_actions, int32_t n_positions, int32_t stride,
                            int8_t* board, uint8_t* legal, int32_t* winner, int8_t* input, int32_t* terminal,
                            const float* policy_in, float* policy_out);
+
+/* Math probe: the device's bit-exact arithmetic (csrc/det.hpp, the PUCT factors and scores, numpy's pairwise sum, the Gumbel softmax /
+ * compute_pi / deterministic selection), one function per op on n_items inputs of the caller, answered by the functions the search kernels
+ * call.  Everything is 64-bit words: item i reads in[i * in_words ...] and writes out[i * out_words ...]; a float64 is its bit pattern,
+ * a float32 / uint32 the low half of its word; nothing is formatted or rounded.  The ops, their words and the team shapes are listed at
+ * the top of csrc/det_probe.hpp (DP_*); counts an item carries are checked on the host.  The engine's games are not touched.  A library
+ * without this symbol predates it (GAZ_ENGINE_ABI_VERSION is unchanged: no struct changed). */
+int gaz_engine_probe_det(gaz_engine* h, int32_t op, int32_t n_items, const uint64_t* in, int32_t in_words, uint64_t* out, int32_t out_words);
 
 /* run the built-in evaluator on a host batch: inputs int8 [n][H*W*C] -> policy f32 [n][A], value f32 [n]; n <= n_games */
 int gaz_engine_evaluate(gaz_engine* h, const int8_t* inputs, int32_t n, float* policy, float* value, int32_t repeats, double* ms_per_batch);

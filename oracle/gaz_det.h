@@ -23,6 +23,7 @@
  */
 #ifndef GAZ_DET_H
 #define GAZ_DET_H
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -166,8 +167,9 @@ static inline double gaz_normal(const gaz_event* e, uint32_t lane, uint32_t* att
     }
 }
 
-/* Gamma(alpha, 1), Marsaglia & Tsang (2000) with the alpha<1 boost. */
-static inline double gaz_gamma(const gaz_event* e, uint32_t lane, double alpha) {
+/* Gamma(alpha, 1), Marsaglia & Tsang (2000) with the alpha<1 boost.  draws / test (each may be NULL; the det probe's cases read them):
+ * the Philox draws the variate consumed, and the test that accepted it, 1 = the squeeze, 2 = the log test. */
+static inline double gaz_gamma_info(const gaz_event* e, uint32_t lane, double alpha, uint32_t* draws, int* test) {
     uint32_t attempt = 0;
     double boost = 1.0, a = alpha;
     if (a < 1.0) {
@@ -187,10 +189,17 @@ static inline double gaz_gamma(const gaz_event* e, uint32_t lane, double alpha) 
         /* the paper's squeeze: inside the acceptance region of the log test below, so the accepted (x, u) pairs are the same
            (235 M random pairs, 0 disagreements in this arithmetic); it spares two logs for 3 of 4 draws */
         const double x2 = x * x;
-        if (u < 1.0 - 0.0331 * (x2 * x2)) return (d * v) * boost;
-        if (gaz_log(u) < ((0.5 * x) * x + d) - d * v + d * gaz_log(v)) return (d * v) * boost;
+        int ok = 0;
+        if (u < 1.0 - 0.0331 * (x2 * x2)) ok = 1;
+        else if (gaz_log(u) < ((0.5 * x) * x + d) - d * v + d * gaz_log(v)) ok = 2;
+        if (ok) {
+            if (draws) *draws = attempt;
+            if (test) *test = ok;
+            return (d * v) * boost;
+        }
     }
 }
+static inline double gaz_gamma(const gaz_event* e, uint32_t lane, double alpha) { return gaz_gamma_info(e, lane, alpha, NULL, NULL); }
 
 /* Dirichlet(alpha * 1_n): g_i / sum_i g_i, sum taken sequentially i = 0..n-1. */
 static inline void gaz_dirichlet(const gaz_event* e, double alpha, int n, double* out) {

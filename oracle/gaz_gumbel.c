@@ -389,3 +389,33 @@ int gaz_selfplay_game_gumbel_from(const gaz_sp_config* cfg, int m, double c_visi
     g_libm = 0;
     return T;
 }
+
+/* ---- flat entry points for the det probe's cases (tests/det_cases.py): the static functions above on caller-made statistics.  They sit
+ * here, not in gaz_api.c, because those functions are static to this file. */
+void gaz_api_softmax(const double* x, int n, double* out) { g_softmax(x, n, out); }
+static gnode api_node(int n, const uint32_t* visits, const float* values, const float* raw_values, const float* logits) {
+    gnode x; memset(&x, 0, sizeof(x));
+    x.n = n; x.visits = (uint32_t*)visits; x.values = (float*)values; x.raw_values = (float*)raw_values; x.logits = (float*)logits;
+    return x;
+}
+/* pi of compute_pi(use_softmax=True), float32 */
+void gaz_api_compute_pi(const uint32_t* visits, const float* values, const float* raw_values, const float* logits, int n, uint32_t N_b,
+                        double c_visit, double c_scale, float* pi) {
+    gnode x = api_node(n, visits, values, raw_values, logits); float q[MAXA];
+    g_mean_q(&x, q);
+    g_compute_pi(raw_values, q, logits, visits, n, N_b, c_visit, c_scale, pi);
+}
+/* pi of compute_pi(use_softmax=False), float64 */
+void gaz_api_compute_pi_stable(const uint32_t* visits, const float* values, const float* raw_values, const float* logits, int n, uint32_t N_b,
+                               double c_visit, double c_scale, double* pi) {
+    gnode x = api_node(n, visits, values, raw_values, logits); float q[MAXA];
+    g_mean_q(&x, q);
+    g_compute_pi_stable(raw_values, q, logits, visits, n, N_b, c_visit, c_scale, pi);
+}
+int gaz_api_det_select(const uint32_t* visits, const float* values, const float* raw_values, const float* logits, int n,
+                       double c_visit, double c_scale, int use_softmax) {
+    gnode x = api_node(n, visits, values, raw_values, logits);
+    ggumbel t; memset(&t, 0, sizeof(t));
+    t.c_visit = c_visit; t.c_scale = c_scale; t.use_softmax = use_softmax;
+    return g_det_select(&t, &x);
+}

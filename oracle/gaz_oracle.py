@@ -87,6 +87,27 @@ def lib():
         L.gaz_puct_best_index.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int,
                                           C.c_uint64, C.c_double, C.c_double, C.c_int]
         L.gaz_puct_best_index.restype = C.c_int
+        # the det math one function at a time (tests/det_cases.py)
+        ev = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]      # seed, slot, seq, tree, event, purpose
+        L.gaz_api_pow.argtypes = [C.c_double, C.c_double]; L.gaz_api_pow.restype = C.c_double
+        L.gaz_api_sqrt.argtypes = [C.c_double]; L.gaz_api_sqrt.restype = C.c_double
+        L.gaz_api_draw.argtypes = ev + [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.gaz_api_k52.argtypes = [C.c_uint32, C.c_uint32]; L.gaz_api_k52.restype = C.c_uint64
+        L.gaz_api_u_open.argtypes = [C.c_uint32, C.c_uint32]; L.gaz_api_u_open.restype = C.c_double
+        L.gaz_api_u_half.argtypes = [C.c_uint32, C.c_uint32]; L.gaz_api_u_half.restype = C.c_double
+        L.gaz_api_pick_p.argtypes = ev + [C.c_uint32]; L.gaz_api_pick_p.restype = C.c_uint32
+        L.gaz_api_gumbel_p.argtypes = ev + [C.c_uint32]; L.gaz_api_gumbel_p.restype = C.c_double
+        L.gaz_api_normal.argtypes = ev + [C.c_uint32, C.POINTER(C.c_uint32)]; L.gaz_api_normal.restype = C.c_double
+        L.gaz_api_gamma.argtypes = ev + [C.c_uint32, C.c_double, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]; L.gaz_api_gamma.restype = C.c_double
+        L.gaz_api_puct_factors.argtypes = [C.c_uint64, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.gaz_api_puct_scores.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int, C.c_double, C.c_double,
+                                          C.POINTER(C.c_double)]
+        L.gaz_api_puct_scores.restype = C.c_int
+        L.gaz_api_softmax.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]
+        node = [C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]   # visits, values, raw, logits, n
+        L.gaz_api_compute_pi.argtypes = node + [C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_float)]
+        L.gaz_api_compute_pi_stable.argtypes = node + [C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_double)]
+        L.gaz_api_det_select.argtypes = node + [C.c_double, C.c_double, C.c_int]; L.gaz_api_det_select.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -131,6 +152,115 @@ def best_puct_index(priors, values, visits, parent_visits, c_init, c_base, use_l
     visits = np.ascontiguousarray(visits, np.uint32)
     return int(lib().gaz_puct_best_index(_p(priors, C.c_float), _p(values, C.c_float), _p(visits, C.c_uint32),
                                          priors.size, int(parent_visits), float(c_init), float(c_base), int(use_libm)))
+
+
+# ---------------------------------------------------------------- the det math, one function at a time (tests/det_cases.py)
+# ev = (seed, slot, seq, tree, event, purpose).  Floats come back as Python floats (float64: exact), never formatted.
+def det_log(x):
+    return float(lib().gaz_api_log(float(x)))
+
+
+def det_exp(x):
+    return float(lib().gaz_api_exp(float(x)))
+
+
+def det_pow(x, y):
+    return float(lib().gaz_api_pow(float(x), float(y)))
+
+
+def det_sqrt(x):
+    return float(lib().gaz_api_sqrt(float(x)))
+
+
+def philox(ctr, key):
+    c = np.ascontiguousarray(ctr, np.uint32); k = np.ascontiguousarray(key, np.uint32); out = np.zeros(4, np.uint32)
+    lib().gaz_api_philox(_p(c, C.c_uint32), _p(k, C.c_uint32), _p(out, C.c_uint32))
+    return out
+
+
+def draw(ev, lane, attempt):
+    out = np.zeros(4, np.uint32)
+    lib().gaz_api_draw(*ev, int(lane), int(attempt), _p(out, C.c_uint32))
+    return out
+
+
+def k52(a, b):
+    return int(lib().gaz_api_k52(int(a), int(b)))
+
+
+def u_open(a, b):
+    return float(lib().gaz_api_u_open(int(a), int(b)))
+
+
+def u_half(a, b):
+    return float(lib().gaz_api_u_half(int(a), int(b)))
+
+
+def pick_p(ev, n):
+    return int(lib().gaz_api_pick_p(*ev, int(n)))
+
+
+def gumbel_p(ev, lane):
+    return float(lib().gaz_api_gumbel_p(*ev, int(lane)))
+
+
+def normal(ev, lane):
+    """-> (variate, Philox draws consumed)"""
+    d = C.c_uint32()
+    v = lib().gaz_api_normal(*ev, int(lane), C.byref(d))
+    return float(v), int(d.value)
+
+
+def gamma(ev, lane, alpha):
+    """-> (variate, Philox draws consumed, accepting test: 1 squeeze, 2 log)"""
+    d = C.c_uint32(); t = C.c_int()
+    v = lib().gaz_api_gamma(*ev, int(lane), float(alpha), C.byref(d), C.byref(t))
+    return float(v), int(d.value), int(t.value)
+
+
+def puct_factors(parent_visits, c_init, c_base):
+    s = C.c_double(); c = C.c_double()
+    lib().gaz_api_puct_factors(int(parent_visits), float(c_init), float(c_base), C.byref(s), C.byref(c))
+    return float(s.value), float(c.value)
+
+
+def puct_scores(priors, values, visits, s, c):
+    """-> (best slot, float64 score of every slot)"""
+    priors = np.ascontiguousarray(priors, np.float32); values = np.ascontiguousarray(values, np.float32)
+    visits = np.ascontiguousarray(visits, np.uint32); out = np.zeros(priors.size, np.float64)
+    best = lib().gaz_api_puct_scores(_p(priors, C.c_float), _p(values, C.c_float), _p(visits, C.c_uint32), priors.size, float(s), float(c),
+                                     _p(out, C.c_double))
+    return int(best), out
+
+
+def softmax(x):
+    x = np.ascontiguousarray(x, np.float64); out = np.zeros(x.size, np.float64)
+    lib().gaz_api_softmax(_p(x, C.c_double), x.size, _p(out, C.c_double))
+    return out
+
+
+def _node(visits, values, raw, logits):
+    v = np.ascontiguousarray(visits, np.uint32); w = np.ascontiguousarray(values, np.float32)
+    r = np.ascontiguousarray(raw, np.float32); lg = np.ascontiguousarray(logits, np.float32)
+    return (v, w, r, lg), (_p(v, C.c_uint32), _p(w, C.c_float), _p(r, C.c_float), _p(lg, C.c_float), v.size)
+
+
+def compute_pi(visits, values, raw, logits, c_visit, c_scale, stable=False):
+    """compute_pi of a node's statistics -> float32 [n] (softmax) or float64 [n] (stablemax); N_b = max(visits), as the callers pass it"""
+    keep, args = _node(visits, values, raw, logits)
+    n_b = int(keep[0].max())
+    if stable:
+        out = np.zeros(keep[0].size, np.float64)
+        lib().gaz_api_compute_pi_stable(*args, n_b, float(c_visit), float(c_scale), _p(out, C.c_double))
+    else:
+        out = np.zeros(keep[0].size, np.float32)
+        lib().gaz_api_compute_pi(*args, n_b, float(c_visit), float(c_scale), _p(out, C.c_float))
+    return out
+
+
+def det_select(visits, values, raw, logits, c_visit, c_scale, stable=False):
+    keep, args = _node(visits, values, raw, logits)
+    return int(lib().gaz_api_det_select(*args, float(c_visit), float(c_scale), int(not stable)))
 
 
 # ---------------------------------------------------------------- hash evaluator (numpy twin of gaz_hash_eval)

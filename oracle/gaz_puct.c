@@ -79,21 +79,31 @@ static void argsort_desc(const float* v, int n, int* idx) {
  *   Q = W (float32); Q[N>0] = float32(W / N) ; score = Q + U ; np.argmax -> first maximum.
  * use_libm = 1 uses libm sqrt/log exactly as CPython/numpy scalars do; 0 uses gaz_log (what the
  * HIP engine computes, bit for bit).  Both are checked against the fixtures. */
-int gaz_puct_best_index(const float* priors, const float* values, const uint32_t* visits, int n,
-                        uint64_t parent_visits, double c_init, double c_base, int use_libm) {
+void gaz_puct_factors(uint64_t parent_visits, double c_init, double c_base, int use_libm, double* s_out, double* c_out) {
     double pv = (double)parent_visits;
     double s = use_libm ? pow(pv, 0.5) : gaz_sqrt(pv);
     double larg = (pv + c_base + 1.0) / c_base;
     double c = c_init + (use_libm ? log(larg) : gaz_log(larg));
+    *s_out = s; *c_out = c;
+}
+/* the scores of all n slots from the two factors above; scores (may be NULL) receives every slot's float64 score */
+int gaz_puct_scores(const float* priors, const float* values, const uint32_t* visits, int n, double s, double c, double* scores) {
     int best = 0; double best_score = 0.0;
     for (int i = 0; i < n; ++i) {
         double u = ((double)priors[i] * (s / (double)(visits[i] + 1u))) * c;
         float q = values[i];
         if (visits[i] > 0) q = (float)((double)values[i] / (double)visits[i]);
         double score = (double)q + u;
+        if (scores) scores[i] = score;
         if (i == 0 || score > best_score) { best = i; best_score = score; }
     }
     return best;
+}
+int gaz_puct_best_index(const float* priors, const float* values, const uint32_t* visits, int n,
+                        uint64_t parent_visits, double c_init, double c_base, int use_libm) {
+    double s, c;
+    gaz_puct_factors(parent_visits, c_init, c_base, use_libm, &s, &c);
+    return gaz_puct_scores(priors, values, visits, n, s, c, NULL);
 }
 
 #ifndef GAZ_ORACLE_LIBM

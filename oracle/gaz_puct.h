@@ -75,6 +75,9 @@ void gaz_puct_prune(gaz_puct* t, int action, int create_new_root);
 /* K1 exposed for micro-fixtures: MCTS._get_best_PUCT_score_index (MCTS.py:172-191) */
 int gaz_puct_best_index(const float* priors, const float* values, const uint32_t* visits, int n,
                         uint64_t parent_visits, double c_init, double c_base, int use_libm);
+/* its two halves, for the det probe's cases: the factors that depend on the parent's visit count only, and the slots' scores from them */
+void gaz_puct_factors(uint64_t parent_visits, double c_init, double c_base, int use_libm, double* s_out, double* c_out);
+int gaz_puct_scores(const float* priors, const float* values, const uint32_t* visits, int n, double s, double c, double* scores);
 
 #ifdef __cplusplus
 }
