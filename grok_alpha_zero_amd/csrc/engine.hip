@@ -555,7 +555,9 @@ template <class G> struct EngineT : gaz_engine {
         const long long its = it < 3 * G::A ? 3 * G::A : it;
         if (cfg.search == GAZ_SEARCH_GUMBEL) return 2LL * (it + m) + 3 * G::A + 64;      // fresh tree every move
         if (E.compact) return 4 * its + 3 * G::A + 64;      // per half: kept subtree + one run; generous bound, ERR_ARENA_FULL if a game exceeds it
-        return (long long)((cfg.max_actions + 1) / 2 + 1) * (its + 2) + 64;      // a tree lives for the whole game and gains <= 1 record per simulation of its own moves
+        // a tree lives for the whole game and gains <= 1 record per simulation of its own moves: every other ply, or with single_tree every ply
+        const long long runs = cfg.single_tree ? (long long)cfg.max_actions + 1 : (cfg.max_actions + 1) / 2 + 1;
+        return runs * (its + 2) + 64;
     }
 
     int init() override {

@@ -334,7 +334,8 @@ template <class G> GAZ_DEV bool g_halving(const DevParams<G>& E, GumbelState<G>&
 }
 
 // create_expand_root, first half.  `row`: the game's row of the evaluator batch that takes the request (g, or g * K with gumbel_batch = K)
-template <class G> GAZ_DEV bool g_root_pre(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, Scratch<G>& S, int row) {
+// STEP_PENDING = the request was written, STEP_DONE = a terminal root, complete; STEP_FAULT = no node for it (puct_core.hpp)
+template <class G> GAZ_DEV int g_root_pre(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, Scratch<G>& S, int row) {
     if (tlane<G>() == 0) { ts.n_nodes = 0; ts.root = -1; ts.root_visits = 0; }
     wave_sync();
     copy_board<G>(S.board, gs.board);
@@ -345,7 +346,7 @@ template <class G> GAZ_DEV bool g_root_pre(const DevParams<G>& E, int g, GameSta
     uint8_t h3[3];
     for (int i = 0; i < 3; ++i) h3[i] = (gs.n_hist - 1 - i >= 0) ? gs.hist[gs.n_hist - 1 - i] : 0;
     const int idx = alloc_node(E, ts);
-    if (idx < 0) return false;
+    if (idx < 0) return STEP_FAULT;
     NodeRef<G> nd = node_at(E, g, 0, idx);
     if (tlane<G>() == 0) {
         NodeHdr h; memset(&h, 0, sizeof(h));
@@ -364,11 +365,11 @@ template <class G> GAZ_DEV bool g_root_pre(const DevParams<G>& E, int g, GameSta
         }
         if (tlane<G>() == 0) ts.root_visits = (uint64_t)nt;
         wave_sync();
-        return false;
+        return STEP_DONE;
     }
     encode_request<G>(E, gs, S.board, -gs.next_player, h3, gs.n_hist, (size_t)row, E.done_flag != nullptr);
     wave_sync();
-    return true;
+    return STEP_PENDING;
 }
 
 // children of a freshly evaluated node: raw logits of the legal actions in legal order (normalize=False), all unexpanded
@@ -389,10 +390,11 @@ template <class G> GAZ_DEV void g_write_children(const DevParams<G>& E, int g, c
     wave_sync();
 }
 
-// _expand of child `index` of `node`; path[0..depth) leads to node.  true = evaluation pending
+// _expand of child `index` of `node`; path[0..depth) leads to node.  STEP_PENDING = evaluation pending, STEP_DONE = a terminal parent, made and
+// backed up here, STEP_FAULT = the arena is full, nothing was written
 // `staged`: the descent left this node's header + child blocks in S.node (saves two dependent round trips)
 // `row`: the row of the evaluator batch (and of E.paths) that takes the request
-template <class G> GAZ_DEV bool g_expand_pre(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, Scratch<G>& S,
+template <class G> GAZ_DEV int g_expand_pre(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, Scratch<G>& S,
                                              int node, int index, int depth, int row, bool staged = false) {
     NodeRef<G> pn = node_at(E, g, 0, node);
     const NodeRef<G> ps = staged ? NodeRef<G>{reinterpret_cast<uint8_t*>(S.node)} : pn;
@@ -409,7 +411,7 @@ template <class G> GAZ_DEV bool g_expand_pre(const DevParams<G>& E, int g, GameS
     bool any_win;
     const int nt = terminal_probe_unsorted<G>(S.board, S.legal, n_legal, -mover, S.tact, S.twin, any_win, E.fast_find_win != 0);
     const int idx = alloc_node(E, ts);
-    if (idx < 0) return false;
+    if (idx < 0) return STEP_FAULT;
     NodeRef<G> nd = node_at(E, g, 0, idx);
     if (tlane<G>() == 0) {
         NodeHdr h; memset(&h, 0, sizeof(h));
@@ -431,7 +433,7 @@ template <class G> GAZ_DEV bool g_expand_pre(const DevParams<G>& E, int g, GameS
         if (tlane<G>() == 0) pn.child()[index] = idx;
         wave_sync();
         backup<G>(E, g, 0, ts, S.path, depth + 1, any_win ? -(float)nt : 0.0f, (uint32_t)nt);
-        return false;
+        return STEP_DONE;
     }
     uint8_t h3[3] = {(uint8_t)action, ph.hist3[0], ph.hist3[1]};
     encode_request<G>(E, gs, S.board, mover, h3, (int)ph.n_hist + 1, (size_t)row, E.done_flag != nullptr);
@@ -442,7 +444,7 @@ template <class G> GAZ_DEV bool g_expand_pre(const DevParams<G>& E, int g, GameS
         gs.pend_depth = depth + 1;
     }
     wave_sync();
-    return true;
+    return STEP_PENDING;
 }
 
 template <class G> GAZ_DEV void g_expand_post(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, Scratch<G>& S,
@@ -510,8 +512,10 @@ template <class G> GAZ_DEV bool g_visit(const DevParams<G>& E, int g, GameState<
             if (tlane<G>() == 0) gu.pend_counts = 1;
             wave_sync();
             const long long te0 = GAZ_PROF_NOW();
-            pending = g_expand_pre<G>(E, g, gs, ts, S, node, slot, depth, row, staged);
+            const int ep = g_expand_pre<G>(E, g, gs, ts, S, node, slot, depth, row, staged);
             GAZ_PROF(2, te0);
+            if (ep < 0) return false;
+            pending = ep > 0;
             break;
         }
         S.path[depth].node = node; S.path[depth].slot = slot; depth++;
@@ -554,13 +558,14 @@ template <class G> GAZ_DEV bool g_chunk_step(const DevParams<G>& E, const Gumbel
                 if (tlane<G>() == 0) R[j].stage = 1;
                 wave_sync();
                 if (tuni<G>(node_at(E, g, 0, ts.root).child()[id]) != CHILD_NONE) continue;
-                if (g_expand_pre<G>(E, g, gs, ts, S, ts.root, id, 0, row)) {
+                const int ep = g_expand_pre<G>(E, g, gs, ts, S, ts.root, id, 0, row);
+                if (ep < 0) return game_fault(gs);                                 // (the rows already in flight are dropped with the game)
+                if (ep) {
                     if (tlane<G>() == 0) { R[j].counts = 0; R[j].pend = 1; R[j].parent = gs.pend_parent; R[j].slot = gs.pend_slot; R[j].node = gs.pend_node; R[j].depth = gs.pend_depth; }
                     wave_sync();
                     open = true;
                     break;
                 }
-                if (tuni<G>(*E.error)) return true;
                 continue;
             }
             if (tuni<G>(R[j].sims_left) <= 0) break;                               // this candidate has used its visits
@@ -569,8 +574,7 @@ template <class G> GAZ_DEV bool g_chunk_step(const DevParams<G>& E, const Gumbel
             if (started >= E.max_tree_sims) { open = true; break; }
             started++;
             bool pending;
-            if (!g_visit<G>(E, g, gs, gu, ts, S, id, row, pending)) return true;
-            if (tuni<G>(*E.error)) return true;
+            if (!g_visit<G>(E, g, gs, gu, ts, S, id, row, pending)) return game_fault(gs);
             if (pending) {
                 if (tlane<G>() == 0) { R[j].counts = 1; R[j].pend = 1; R[j].parent = gs.pend_parent; R[j].slot = gs.pend_slot; R[j].node = gs.pend_node; R[j].depth = gs.pend_depth; }
                 wave_sync();
@@ -646,7 +650,9 @@ template <class G, bool GB = false, class Fin> GAZ_DEV void g_game_step_body(con
                 return false;
             }
             if (tlane<G>() == 0) gs.move_evals = 0;
-            if (g_root_pre<G>(E, g, gs, ts, S, row0)) {
+            const int rp = g_root_pre<G>(E, g, gs, ts, S, row0);
+            if (rp < 0) return game_fault(gs);
+            if (rp) {
                 const uint8_t* hit = E.cache ? cache_probe<G>(E, g) : nullptr;
                 if (hit) {                                                     // evaluation cache hit
                     g_write_children<G>(E, g, node_at(E, g, 0, ts.root), S, reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_POL), row0, true);
@@ -660,7 +666,6 @@ template <class G, bool GB = false, class Fin> GAZ_DEV void g_game_step_body(con
             }
             if (tlane<G>() == 0) gs.roots_todo = 0;
             wave_sync();
-            if (tuni<G>(*E.error)) return true;
         } else if (phase == PH_MOVE_BEGIN) {                                   // head of MCTS_Gumbel.run (:570-599)
             copy_board<G>(S.board, gs.board);
             wave_sync();
@@ -705,7 +710,9 @@ template <class G, bool GB = false, class Fin> GAZ_DEV void g_game_step_body(con
                 if (tlane<G>() == 0) { gu.stage = 1; gu.sims_left = gu.vpc; gu.pend_counts = 0; }
                 wave_sync();
                 if (tuni<G>(r.child()[id]) == CHILD_NONE) {
-                    if (g_expand_pre<G>(E, g, gs, ts, S, ts.root, id, 0, g)) {
+                    const int ep = g_expand_pre<G>(E, g, gs, ts, S, ts.root, id, 0, g);
+                    if (ep < 0) return game_fault(gs);
+                    if (ep) {
                         const uint8_t* hit = E.cache ? cache_probe<G>(E, g) : nullptr;
                         if (!hit) return true;
                         g_expand_post<G>(E, g, gs, ts, S, reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_POL),
@@ -713,7 +720,6 @@ template <class G, bool GB = false, class Fin> GAZ_DEV void g_game_step_body(con
                         if (tlane<G>() == 0) { gs.pend_kind = PEND_NONE; gs.n_evals += 1; gs.move_evals += 1; gs.n_hits += 1; }
                         wave_sync();
                     }
-                    if (tuni<G>(*E.error)) return true;
                 }
                 return false;
             }
@@ -727,13 +733,15 @@ template <class G, bool GB = false, class Fin> GAZ_DEV void g_game_step_body(con
             for (;;) {
                 // below the root the record of `node` is already in LDS (staged for its deterministic_selection)
                 const int c = staged ? tuni<G>(NodeRef<G>{reinterpret_cast<uint8_t*>(S.node)}.child()[slot]) : tuni<G>(node_at(E, g, 0, node).child()[slot]);
-                if (depth >= PathCap<G>::V - 1) { set_error(E.error, ERR_PATH_OVERFLOW); return true; }
+                if (depth >= PathCap<G>::V - 1) { set_error(E.error, ERR_PATH_OVERFLOW); return game_fault(gs); }
                 if (c == CHILD_NONE) {                                         // expand (node, slot)
                     if (tlane<G>() == 0) gu.pend_counts = 1;
                     wave_sync();
                     const long long te0 = GAZ_PROF_NOW();
-                    pending = g_expand_pre<G>(E, g, gs, ts, S, node, slot, depth, g, staged);
+                    const int ep = g_expand_pre<G>(E, g, gs, ts, S, node, slot, depth, g, staged);
                     GAZ_PROF(2, te0);
+                    if (ep < 0) return game_fault(gs);
+                    pending = ep > 0;
                     done = !pending;
                     break;
                 }
@@ -762,7 +770,6 @@ template <class G, bool GB = false, class Fin> GAZ_DEV void g_game_step_body(con
                 wave_sync();
                 done = true;
             }
-            if (tuni<G>(*E.error)) return true;
             if (done && tlane<G>() == 0) { gu.sims_left -= 1; gu.cur_iter += 1; gs.n_sims += 1; }
             wave_sync();
         } else if (phase == PH_MOVE_END) {
@@ -820,7 +827,7 @@ template <class G, bool GB = false, class Fin> GAZ_DEV void g_game_step_body(con
         if (!yielded && phase_step()) { fin(); yielded = true; }
         if (!ballot(!yielded)) return;              // wave-uniform exit: every team of this wavefront has yielded
     }
-    set_error(E.error, ERR_LOOP_GUARD);
+    set_error(E.error, ERR_LOOP_GUARD);             // the wavefront's, not a game's: nobody is parked (puct_core.hpp)
     if (!yielded) fin();
 }
 

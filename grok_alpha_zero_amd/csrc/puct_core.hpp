@@ -183,6 +183,21 @@ GAZ_DEV void set_error(int32_t* err, int32_t code) {      // any lane of any tea
     if (*err == 0) *err = code;
 }
 
+// What a step that may need a tree node reports (root_pre, expand_pre, prune and their Gumbel counterparts): the failure travels through the return
+// values to the phase that called, which parks the game with game_fault().  No phase polls *E.error: that word is for the host.
+enum : int { STEP_FAULT = -1, STEP_DONE = 0, STEP_PENDING = 1 };
+
+// A game whose own step raised a device error stops for good (DESIGN.md "Capacity limits and the device error word"): PH_FAULT yields in every
+// launch — in a fused launch the game still reports itself done — and the request the game may have in flight is dropped, so no later launch writes a
+// node, applies a move, pushes a record or asks the evaluator on its behalf.  The other games go on until the host reads the error.
+// Returns true, "the game yields".
+template <class G> GAZ_DEV bool game_fault(GameState<G>& gs) {
+    wave_sync();
+    if (tlane<G>() == 0) { gs.phase = PH_FAULT; gs.pend_kind = PEND_NONE; gs.pend_depth = 0; }
+    wave_sync();
+    return true;
+}
+
 template <class G> GAZ_DEV det::Event make_event(const DevParams<G>& E, int g, const GameState<G>& gs, TreeState& ts,
                                                  int tree, uint32_t purpose) {
     det::Event e;
@@ -593,10 +608,10 @@ template <class G> GAZ_DEV int alloc_node(const DevParams<G>& E, TreeState& ts) 
     return idx;
 }
 
-// K12 first half: create_expand_root for tree t at the game's current position.  Returns true when the
-// root needs an evaluation (input row written), false when it was completed here (terminal root).
+// K12 first half: create_expand_root for tree t at the game's current position.  Returns STEP_PENDING when the
+// root needs an evaluation (input row written), STEP_DONE when it was completed here (terminal root), STEP_FAULT when the arena has no node for it.
 // `row`: the game's row of the evaluator batch (g; g * K with leaf batching)
-template <class G> GAZ_DEV bool root_pre(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S, int row) {
+template <class G> GAZ_DEV int root_pre(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S, int row) {
     if (tlane<G>() == 0) { ts.n_nodes = 0; ts.root = -1; ts.root_visits = 0; }
     wave_sync();
     copy_board<G>(S.board, gs.board);
@@ -607,7 +622,7 @@ template <class G> GAZ_DEV bool root_pre(const DevParams<G>& E, int g, GameState
     uint8_t h3[3];
     for (int i = 0; i < 3; ++i) h3[i] = (gs.n_hist - 1 - i >= 0) ? gs.hist[gs.n_hist - 1 - i] : 0;
     const int idx = alloc_node(E, ts);
-    if (idx < 0) return false;
+    if (idx < 0) return STEP_FAULT;
     NodeRef<G> nd = node_at(E, g, t, idx);
     if (tlane<G>() == 0) {
         NodeHdr h; memset(&h, 0, sizeof(h));
@@ -622,11 +637,11 @@ template <class G> GAZ_DEV bool root_pre(const DevParams<G>& E, int g, GameState
         write_terminal_children<G>(nd, S, nt, any_win, true);
         if (tlane<G>() == 0) ts.root_visits = (uint64_t)nt;     // one backup per terminal child (MCTS.py:344)
         wave_sync();
-        return false;
+        return STEP_DONE;
     }
     encode_request<G>(E, gs, S.board, -gs.next_player, h3, gs.n_hist, (size_t)row, E.done_flag != nullptr);
     wave_sync();
-    return true;
+    return STEP_PENDING;
 }
 
 // K12 second half: the evaluator's policy row -> root priors (the value is discarded, MCTS.py:346-365)
@@ -833,10 +848,11 @@ template <class G> GAZ_DEV void cache_insert(const DevParams<G>& E, int g) {
     }
 }
 
-// K4 first half (+K3, K5): expand the next child of `node`.  Returns true if an evaluation is pending
-// (row g written), false if the simulation completed here (terminal parent created and backed up).
+// K4 first half (+K3, K5): expand the next child of `node`.  Returns STEP_PENDING if an evaluation is pending
+// (row g written), STEP_DONE if the simulation completed here (terminal parent created and backed up), STEP_FAULT if the arena is full
+// (nothing was written).
 // `staged`: puct_select left this node's header + child blocks in S.node (saves two dependent round trips)
-template <class G> GAZ_DEV bool expand_pre(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S,
+template <class G> GAZ_DEV int expand_pre(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S,
                                            int node, int depth, bool staged) {
     NodeRef<G> pn = node_at(E, g, t, node);
     const NodeRef<G> ps = staged ? NodeRef<G>{reinterpret_cast<uint8_t*>(S.node)} : pn;
@@ -854,7 +870,7 @@ template <class G> GAZ_DEV bool expand_pre(const DevParams<G>& E, int g, GameSta
     bool any_win;
     const int nt = terminal_probe<G>(S.board, S.legal, n_legal, -mover, S.tact, S.twin, any_win, E.fast_find_win != 0);
     const int idx = alloc_node(E, ts);
-    if (idx < 0) return false;
+    if (idx < 0) return STEP_FAULT;
     NodeRef<G> nd = node_at(E, g, t, idx);
     if (tlane<G>() == 0) {
         NodeHdr h; memset(&h, 0, sizeof(h));
@@ -872,7 +888,7 @@ template <class G> GAZ_DEV bool expand_pre(const DevParams<G>& E, int g, GameSta
         // value = -(len(terminal_mask)) if any win else 0; visits = len(terminal_mask)  (MCTS.py:373-380, 428)
         backup<G>(E, g, t, ts, S.path, depth + 1, any_win ? -(float)nt : 0.0f, (uint32_t)nt);
         if constexpr (G::SOLVE) { if (E.solver & 1) solver_propagate<G>(E, g, t, S.path, depth, any_win ? ST_WIN : ST_DRAW); }
-        return false;
+        return STEP_DONE;
     }
     copy_board<G>(nd.board(), S.board);
     uint8_t h3[3] = {(uint8_t)action, ph.hist3[0], ph.hist3[1]};
@@ -885,7 +901,7 @@ template <class G> GAZ_DEV bool expand_pre(const DevParams<G>& E, int g, GameSta
         gs.pend_depth = depth + 1;
     }
     wave_sync();
-    return true;
+    return STEP_PENDING;
 }
 
 // K4 second half: policy/value row of the leaf -> child record, link into the parent, backup(-value, 1)
@@ -1068,10 +1084,11 @@ template <class G> GAZ_DEV int compact_subtree(const DevParams<G>& E, int g, int
     return n_new;
 }
 
-// K11: prune_tree / _set_root for tree t after `action` was played.  Returns true if the tree must be
-// rebuilt with create_expand_root (MCTS.py:661-671).
-template <class G> GAZ_DEV bool prune(const DevParams<G>& E, int g, TreeState& ts, int t, int action) {
-    if (E.create_new_root || ts.root < 0) return true;
+// K11: prune_tree / _set_root for tree t after `action` was played.  Returns STEP_PENDING if the tree must be
+// rebuilt with create_expand_root (MCTS.py:661-671), STEP_DONE if it was re-rooted here, STEP_FAULT if the kept subtree does not fit the
+// other half of the arena (compact_subtree; the tree head is then left as it was, on the OLD root: the caller must not search it again).
+template <class G> GAZ_DEV int prune(const DevParams<G>& E, int g, TreeState& ts, int t, int action) {
+    if (E.create_new_root || ts.root < 0) return STEP_PENDING;
     NodeRef<G> r = node_at(E, g, t, ts.root);
     const int n_children = tuni<G>((int)r.hdr()->n_children);
     int found = -1;
@@ -1080,17 +1097,17 @@ template <class G> GAZ_DEV bool prune(const DevParams<G>& E, int g, TreeState& t
         uint64_t m = tballot<G>(i < n_children && r.act()[i] == (uint8_t)action);
         if (m) { found = base + ffsll0(m); break; }
     }
-    if (found < 0) return true;
+    if (found < 0) return STEP_PENDING;
     const int c = tuni<G>(G::SOLVE ? child_index(r.child()[found]) : r.child()[found]);
-    if (c < 0) return true;                                           // (terminal leaf: never pruned on a live game)
+    if (c < 0) return STEP_PENDING;                                   // (terminal leaf: never pruned on a live game)
     const uint32_t v = tuni<G>(r.N()[found]);
     wave_sync();
     if (E.compact) {
-        if (compact_subtree<G>(E, g, t, ts, c) < 0) return false;
+        if (compact_subtree<G>(E, g, t, ts, c) < 0) return STEP_FAULT;
         if (tlane<G>() == 0) ts.root_visits = (uint64_t)v;
     } else if (tlane<G>() == 0) { ts.root = c; ts.root_visits = (uint64_t)v; }   // MCTS.py:654-655
     wave_sync();
-    return false;
+    return STEP_DONE;
 }
 
 template <class G> GAZ_DEV uint8_t* rec_of(const DevParams<G>& E, int g) { return E.recs + (size_t)g * RecLayout<G>::SIZE; }
@@ -1171,11 +1188,12 @@ template <class G> GAZ_DEV void prune_policy_target(const DevParams<G>& E, const
 // end of MCTS.run (MCTS.py:591-613) + the bookkeeping of Self_Play.play (Self_Play.py:114-127)
 // Forced playouts (forced_playouts_k > 0, a full move, the root no terminal parent): the policy row is the pruned one
 // (prune_policy_target); everything else is what it is without them.
-template <class G> GAZ_DEV void move_end(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S) {
+// false = the root was not fully expanded: a device error, nothing was written
+template <class G> GAZ_DEV bool move_end(const DevParams<G>& E, int g, GameState<G>& gs, TreeState& ts, int t, Scratch<G>& S) {
     using RL = RecLayout<G>;
     NodeRef<G> r = node_at(E, g, t, ts.root);
     const int n = tuni<G>((int)r.hdr()->n_children);
-    if (n != tuni<G>((int)r.hdr()->n_actions)) { set_error(E.error, ERR_ROOT_NOT_EXPANDED); }
+    if (n != tuni<G>((int)r.hdr()->n_actions)) { set_error(E.error, ERR_ROOT_NOT_EXPANDED); return false; }
     uint8_t* rec = rec_of(E, g);
     const int ply = gs.n_hist;
     float* pol = reinterpret_cast<float*>(rec + RL::OFF_POL) + (size_t)ply * G::A;
@@ -1267,6 +1285,7 @@ template <class G> GAZ_DEV void move_end(const DevParams<G>& E, int g, GameState
         }
     }
     wave_sync();
+    return true;
 }
 
 // Self_Play.py:130-140: at move 0 the played action is drawn from opening_actions (+ the search's own move with the
@@ -1366,7 +1385,9 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
             const int todo = tuni<G>(gs.roots_todo);
             if (todo == 0) { if (tlane<G>() == 0) gs.phase = PH_MOVE_BEGIN; wave_sync(); return false; }
             const int t = (todo & 1) ? 0 : 1;
-            if (root_pre<G>(E, g, gs, trees[t], t, S, row0)) {
+            const int rp = root_pre<G>(E, g, gs, trees[t], t, S, row0);
+            if (rp < 0) return game_fault(gs);
+            if (rp) {
                 const uint8_t* hit = E.cache ? cache_probe<G>(E, g) : nullptr;
                 if (hit) {                                             // evaluation cache hit: the root is complete in this launch
                     root_post<G>(E, g, gs, trees[t], t, S, reinterpret_cast<const float*>(hit + CacheLayout<G>::OFF_POL), row0);
@@ -1380,7 +1401,6 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
             }
             if (tlane<G>() == 0) gs.roots_todo &= ~(1 << t);
             wave_sync();
-            if (tuni<G>(*E.error)) return true;
         } else if (phase == PH_MOVE_BEGIN) {                           // Self_Play.py:82-106 + MCTS.run head (MCTS.py:542-558)
             copy_board<G>(S.board, gs.board);
             wave_sync();
@@ -1480,12 +1500,13 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
             if (!tuni<G>(gs.fully_visited)) { node = ts.root; depth = 0; kind = 0; }
             else kind = puct_select<G, LB>(E, g, gs, ts, t, S, node, depth, leaf_win);
             GAZ_PROF(1, ts0);
-            if (kind < 0) return true;
+            if (kind < 0) return game_fault(gs);
             if (LB && kind == 2) return true;                               // collision with a leaf in flight: collecting ends for this launch
             if (LB && kind == 0) {
                 const int fl = tuni<G>(gs.pend_depth);
                 const int r = lb_reserve<G>(E, B, g, fl, gs, ts, t, S, node, depth, tuni<G>(gs.fully_visited) != 0);
-                if (r < 0 || r == 2) return true;
+                if (r < 0) return game_fault(gs);                          // (leaves already in flight are dropped with the game)
+                if (r == 2) return true;
                 if (tlane<G>() == 0) {
                     if (r == 1) { gs.sims_done += 1; gs.n_sims += 1; }
                     else { gs.pend_kind = PEND_EXPAND; gs.pend_tree = t; gs.pend_depth = fl + 1; }
@@ -1508,8 +1529,9 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
                 GAZ_PROF(5, tb0);
             } else {
                 const long long te0 = GAZ_PROF_NOW();
-                const bool pending = expand_pre<G>(E, g, gs, ts, t, S, node, depth, kind == 0 && tuni<G>(gs.fully_visited) != 0);
+                const int pending = expand_pre<G>(E, g, gs, ts, t, S, node, depth, kind == 0 && tuni<G>(gs.fully_visited) != 0);
                 GAZ_PROF(2, te0);
+                if (pending < 0) return game_fault(gs);
                 if (pending) {
                     const long long tc0 = GAZ_PROF_NOW();
                     const uint8_t* hit = E.cache ? cache_probe<G>(E, g) : nullptr;
@@ -1522,13 +1544,12 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
                     wave_sync();
                     GAZ_PROF(4, tx0);
                 }
-                if (tuni<G>(*E.error)) return true;
                 if (tlane<G>() == 0) { gs.sims_done += 1; gs.n_sims += 1; }
                 wave_sync();
             }
         } else if (phase == PH_MOVE_END) {
             const int t = tuni<G>(gs.runner);
-            move_end<G>(E, g, gs, trees[t], t, S);
+            if (!move_end<G>(E, g, gs, trees[t], t, S)) return game_fault(gs);
             if (tlane<G>() == 0) gs.phase = E.sync_moves ? PH_WAIT_HOST : PH_APPLY;
             wave_sync();
             if (E.sync_moves) return true;
@@ -1562,9 +1583,12 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
                 if (tshfl<G>(verdict, 0) == RESIGN_NOW) { winner = -mover; ended = true; }
             }
             int todo = 0;
-            if (!ended) {
-                if (prune<G>(E, g, trees[0], 0, action)) todo |= 1;   // both trees prune (Self_Play.py:149-150)
-                if (!E.single_tree && prune<G>(E, g, trees[1], 1, action)) todo |= 2;
+            if (!ended) {                                          // both trees prune (Self_Play.py:149-150)
+                const int p0 = prune<G>(E, g, trees[0], 0, action);
+                const int p1 = (p0 < 0 || E.single_tree) ? STEP_DONE : prune<G>(E, g, trees[1], 1, action);
+                if (p0 < 0 || p1 < 0) return game_fault(gs);       // the move stands; the game never searches the tree it could not re-root
+                if (p0) todo |= 1;
+                if (p1) todo |= 2;
             }
             // Self_Play.py:155-157: reaching max_actions forces winner = 0 — even when that last action won
             if (capped) { winner = 0; ended = true; }
@@ -1585,7 +1609,7 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
         } else if (phase == PH_RING_WAIT) {                            // hand the finished game to the host ring
             if (!ring_push<G>(E, g, gs)) return true;
             if (E.sync_moves) return true;
-        } else {                                                       // PH_WAIT_HOST, PH_HALT
+        } else {                                                       // PH_WAIT_HOST, PH_HALT, PH_IDLE, PH_FAULT
             return true;
         }
         return false;
@@ -1595,7 +1619,7 @@ template <class G, bool LB = false, class Fin> GAZ_DEV void game_step_body(const
         if (!done && phase_step()) { fin(); done = true; }
         if (!ballot(!done)) return;                 // wave-uniform exit: every team of this wavefront has yielded
     }
-    set_error(E.error, ERR_LOOP_GUARD);
+    set_error(E.error, ERR_LOOP_GUARD);             // the wavefront's, not a game's: nobody is parked, every phase left off between two steps
     if (!done) fin();
 }
 

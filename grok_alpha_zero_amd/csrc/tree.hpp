@@ -84,7 +84,8 @@ struct TreeState {        // 32 bytes, one per (game, tree)
 enum : int32_t {
     PH_NEW_GAME = 0, PH_ROOT = 1, PH_MOVE_BEGIN = 2, PH_SIMS = 3, PH_MOVE_END = 4, PH_WAIT_HOST = 5,
     PH_APPLY = 6, PH_RING_WAIT = 7, PH_HALT = 8,
-    PH_IDLE = 9            // sync + single-tree hosts (mcts.py): position set / move applied, waiting for run() or the next move
+    PH_IDLE = 9,           // sync + single-tree hosts (mcts.py): position set / move applied, waiting for run() or the next move
+    PH_FAULT = 10          // the game's own step raised a device error (puct_core.hpp game_fault): it yields in every launch from then on
 };
 enum : int32_t { PEND_NONE = 0, PEND_ROOT = 1, PEND_EXPAND = 2 };
 

@@ -17,6 +17,7 @@ GAME_DIMS = {0: (3, 3, 2, 9), 1: (6, 7, 4, 7), 2: (15, 15, 2, 225)}  # H, W, C, 
 SEARCH_PUCT, SEARCH_GUMBEL = 0, 1
 EVAL_HASH, EVAL_RESNET, EVAL_EXTERNAL = 0, 1, 2
 PH_WAIT_HOST, PH_HALT, PH_IDLE = 5, 8, 9
+PH_FAULT = 10                 # the game raised the engine's device error (gaz_engine.h "Capacity limits and the device error"): it stays where it is
 
 
 ABI_VERSION = 10              # GAZ_ENGINE_ABI_VERSION of include/gaz_engine.h this binding was written against

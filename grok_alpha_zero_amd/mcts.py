@@ -21,7 +21,7 @@ from warnings import warn
 
 import numpy as np
 
-from .engine import (CHILD_DRAW, CHILD_WIN, EVAL_EXTERNAL, EVAL_HASH, PH_HALT, PH_IDLE, PH_WAIT_HOST, SEARCH_GUMBEL, SEARCH_PUCT,
+from .engine import (CHILD_DRAW, CHILD_WIN, EVAL_EXTERNAL, EVAL_HASH, PH_FAULT, PH_HALT, PH_IDLE, PH_WAIT_HOST, SEARCH_GUMBEL, SEARCH_PUCT,
                      SelfPlayEngine)
 
 _W = {"TicTacToe": 3, "Gomoku": 15}
@@ -111,6 +111,8 @@ def _build_root(name, tree, root_visits, gumbel, base_board, history):
 
 
 class _EngineSearch:
+    _ARENA_NODES = 32768                         # iteration limits are per run() call: the one-game engine's arena is sized generously
+
     @property
     def root(self):
         """MCTS.root (MCTS.py:20-72,132): the whole tree below the current root as Root / Node objects, read from the engine with one
@@ -137,7 +139,7 @@ class _EngineSearch:
         self._eng = SelfPlayEngine(self._name, 1, 1, engine_kw.pop("max_actions"), 0, 0, engine_kw.pop("c_puct_init", 0.0),
                                    engine_kw.pop("dirichlet_alpha", 0.0), seed, sync_moves=True, single_tree=True,
                                    evaluator=EVAL_HASH if session is None else EVAL_EXTERNAL, ring_capacity=4,
-                                   nodes_per_tree=32768,     # iteration limits are per run() call: size the arena generously
+                                   nodes_per_tree=self._ARENA_NODES,
                                    lib_path=lib_path, **engine_kw)
         # the root (create_expand_root, MCTS.py:132) is built by the first run(): same evaluator call, same noise event
         self._eng.set_position(0, [_to_index(self._name, a) for a in game.action_history])
@@ -149,6 +151,13 @@ class _EngineSearch:
         eng = self._eng
         eng.start_search()
         stopped = False
+
+        def waits():
+            """the game has yielded for good; a game parked by a device error (PH_FAULT) never moves again: synchronize() raises that error"""
+            phase = eng.root_stats()["phase"][0]
+            if phase == PH_FAULT:
+                eng.synchronize()
+            return phase in (PH_WAIT_HOST, PH_HALT, PH_IDLE, PH_FAULT)
         try:
             if self.session is None and deadline is None:
                 eng.run_move()
@@ -158,7 +167,7 @@ class _EngineSearch:
                     eng.stop_search(True); stopped = True
                 if self.session is None:
                     eng.run_waves(4)
-                    if eng.root_stats()["phase"][0] in (PH_WAIT_HOST, PH_HALT, PH_IDLE):
+                    if waits():
                         return
                     continue
                 x, pend = eng.read_batch()
@@ -168,7 +177,7 @@ class _EngineSearch:
                     pol = np.zeros((eng.batch_rows, eng.A), np.float32); val = np.zeros(eng.batch_rows, np.float32)
                     pol[rows] = np.asarray(policy, np.float32).reshape(rows.size, -1); val[rows] = np.asarray(value, np.float32).reshape(-1)
                     eng.write_outputs(pol, val)
-                elif eng.root_stats()["phase"][0] in (PH_WAIT_HOST, PH_HALT, PH_IDLE):
+                elif waits():
                     return
                 eng.wave_begin()
             raise RuntimeError("search did not finish")
@@ -197,7 +206,7 @@ class _EngineSearch:
 
 
 class MCTS(_EngineSearch):
-    _MAX_TIMED_ITERATIONS = 30_000               # one-game engines are created with a 32768-node arena per run() call
+    _MAX_TIMED_ITERATIONS = 30_000               # one-game engines are created with a 32768-node arena (_ARENA_NODES) per run() call
 
     def __init__(self, game, session=None, use_njit=None, c_puct_init=2.5, c_puct_base=19_652, use_dirichlet=True,
                  dirichlet_alpha=1.11, dirichlet_epsilon=0.25, tau=1.0, fast_find_win=False, *, seed=None, hash_salt=0,

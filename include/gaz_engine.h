@@ -219,6 +219,29 @@ int gaz_engine_create(const gaz_engine_config* cfg, gaz_engine** out);
 void gaz_engine_destroy(gaz_engine* h);
 const char* gaz_engine_last_error(gaz_engine* h);   /* h may be NULL: last create() error */
 
+/* Capacity limits and the device error.  The kernels report what they cannot carry on with through one error word on the
+ * device, first code wins: 1 "tree arena full (raise nodes_per_tree)", 2 "root not fully expanded at move end", 3 "selection path longer than the
+ * game can last", 4 "state-machine loop guard", 5 "PUCT picked an un-poppable child".  A call that synchronises with the device — gaz_engine_run_move,
+ * gaz_engine_apply_moves, gaz_engine_drain_finished, gaz_engine_drain_samples, gaz_engine_get_stats, gaz_engine_get_resign_stats,
+ * gaz_engine_read_batch, gaz_engine_read_batch_symmetry, gaz_engine_synchronize — reads the word and fails with last_error "device error: <text>".
+ * gaz_engine_run_waves only queues launches and does not look.  It is a return value, not a GPU fault: the process and the device go on.
+ *   - The game that raised error 1, 2, 3 or 5 does not advance again, in that launch or in any later one: no further node is written, no move applied,
+ *     no record pushed, no evaluator request made on its behalf (its phase is 10, "fault", in gaz_engine_get_root_stats' out_phase).  In a launch that
+ *     runs the tree step and the network together it still reports itself done, so nothing waits for it.  Error 4 belongs to no game: it says that a
+ *     wavefront used up its steps for one launch; its games keep their phases, consistent, and go on in the next launch.
+ *   - The other games are unaffected until the host reads the error: what they push into the ring is what they would have played in a larger arena.
+ *   - The error is sticky on the handle: the word is never cleared, every later synchronising call fails with the same text, and the only way on is
+ *     gaz_engine_destroy and a new engine (with a larger nodes_per_tree).  A caller that wants no doubtful data drops what a failing call handed out.
+ *   - Reading state after the error: gaz_engine_read_positions and gaz_engine_get_root_stats do not look at the word and succeed;
+ *     gaz_engine_get_stats and gaz_engine_drain_finished fill their outputs and then return the error.
+ * The tree arena.  nodes_per_tree = 0 sizes every tree for the longest game the configuration can play: (plies the tree searches + 1) x
+ * (max(run_iterations, 3 x actions) + 2) + 64 nodes, where a tree searches every other ply of its game, or every ply with single_tree = 1; with
+ * re-root compaction 4 x max(run_iterations, 3 x actions) + 3 x actions + 64 per half; Gumbel 2 x (run_iterations + gumbel_m) + 3 x actions + 64; plus
+ * leaf_batch nodes for the leaves in flight.  gaz_engine_set_hyperparams holds later run_iterations / gumbel_m against the same formula and refuses what
+ * the arena was not sized for; with an explicit nodes_per_tree it accepts every value, and a game that outgrows the arena raises error 1.
+ * The record ring.  A game that finishes while ring_capacity records wait to be drained keeps its record and retries the push in every launch; it
+ * is counted in game_stats once, when it finishes.  Nothing is lost or duplicated however small the ring (>= 1) and however little a drain takes. */
+
 int gaz_engine_load_weights(gaz_engine* h, const gaz_tensor* tensors, int32_t n);
 int gaz_engine_reset_games(gaz_engine* h, const int32_t* slots, int32_t n);   /* slots NULL = all */
 

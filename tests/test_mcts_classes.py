@@ -96,6 +96,24 @@ def test_mcts_run_with_time_limit(emu_lib, oracle):
     mcts.close()
 
 
+def test_timed_run_in_a_full_arena_raises_the_device_error(emu_lib):
+    """A timed MCTS.run watches the game's phase between launches.  A game that a device error has parked (PH_FAULT, DESIGN.md "Capacity
+    limits and the device error word") never reaches a waiting phase: run() raises the engine's error at once, long before its clock."""
+    import time
+    from grok_alpha_zero_amd.engine import EngineError
+    from grok_alpha_zero_amd.mcts import MCTS
+
+    class TinyArena(MCTS):
+        _ARENA_NODES = 64
+
+    mcts = TinyArena(GAMES["Connect4"](), None, c_puct_init=2.5, dirichlet_alpha=0.5, tau=0.0, seed=3, hash_salt=1, lib_path=emu_lib)
+    t0 = time.time()
+    with pytest.raises(EngineError, match="tree arena full"):
+        mcts.run(iteration_limit=None, time_limit=120.0, use_bar=False)
+    assert time.time() - t0 < 60.0
+    mcts.close()
+
+
 def _drive_puct_fixture(MCTS, fx, lib_path, oracle, with_session):
     import json
     game = GAMES[str(fx["game"])]()
