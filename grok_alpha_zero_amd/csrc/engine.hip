@@ -380,8 +380,12 @@ struct gaz_engine {
     virtual int sample_layout(gaz_sample_layout*) = 0;
     // gaz_engine_drain_samples for one ring: the caller's arrays start at this call's first game / row, their augmentation planes are `plane_rows`
     // rows apart, games[i][4] = row_base + the row in this call.  *blocked_T = rows of the oldest game when it alone is more than max_rows (else 0).
+    // row_ply (may be null): the ply of every row, from this call's first row on
     virtual int drain_samples(int max_games, int64_t max_rows, int64_t plane_rows, int64_t row_base, int32_t* games, int8_t* boards, float* policies,
-                              float* values, int32_t* n_games, int64_t* n_rows, int32_t* blocked_T) = 0;
+                              float* values, uint8_t* row_ply, int32_t* n_games, int64_t* n_rows, int32_t* blocked_T) = 0;
+    // policy surprise weighting of the rows (samples.hpp): lambda = 0 is off, the state of a new engine; read by the next drain
+    double sw_lambda = 0.0, sw_fast_factor = 1.5;
+    virtual int set_sample_weighting(double lambda, double fast_factor) { sw_lambda = lambda; sw_fast_factor = fast_factor; return 0; }
     virtual int get_stats(uint64_t out[16]) = 0;
     virtual int synchronize() = 0;
     virtual int timing_reset(int enable) = 0;
@@ -1176,10 +1180,13 @@ template <class G> struct EngineT : gaz_engine {
         o->n_aug = SampleAug<G>::N; o->state_bytes = G::HW * G::C; o->A = G::A; o->max_T = G::MAXT;
         return 0;
     }
-    // the R rows of the n games of `plan` (ring slots, then row0) -> the caller's arrays
-    int build_samples(const std::vector<int32_t>& plan, int n, int64_t R, int64_t plane_rows, int8_t* boards, float* policies, float* values) {
+    // the R rows of the n games of `plan` (ring slots, then row0) -> the caller's arrays.  weighted: k_build_samples_w with the counts of
+    // k_sample_weights (dCounts), and the ply of every row behind the values
+    int build_samples(const std::vector<int32_t>& plan, int n, int64_t R, int64_t plane_rows, int8_t* boards, float* policies, float* values,
+                      bool weighted = false, uint8_t* row_ply = nullptr) {
         constexpr int SB = G::HW * G::C, NA = SampleAug<G>::N;
-        const size_t off_p = al256((size_t)NA * R * SB), off_v = off_p + al256((size_t)NA * R * G::A * 4), total = off_v + al256((size_t)R * 4);
+        const size_t off_p = al256((size_t)NA * R * SB), off_v = off_p + al256((size_t)NA * R * G::A * 4), off_rp = off_v + al256((size_t)R * 4),
+                     total = off_rp + (weighted ? al256((size_t)R) : 0);
         if (total > samples_cap) {
             if (dSamples) HIP_OK(hipFree(dSamples));
             if (hSamples) HIP_OK(hipHostFree(hSamples));
@@ -1192,22 +1199,28 @@ template <class G> struct EngineT : gaz_engine {
             HIP_OK(hipHostMalloc(&hp, want, 0));
             hSamples = (uint8_t*)hp; samples_cap = want;
         }
-        int32_t* d_plan = dPlan + (size_t)SAMPLE_HDR_INTS * E.ring_cap;
+        int32_t* d_plan = dPlan + (size_t)SAMPLE_HDR_W_INTS * E.ring_cap;
         HIP_OK(hipMemcpyAsync(d_plan, plan.data(), plan.size() * 4, hipMemcpyHostToDevice, stream));
-        GAZ_LAUNCH(k_build_samples<G>, n, SAMPLES_THREADS, stream, (const uint8_t*)E.ring, E.ring_cap, (const int32_t*)d_plan, n, (long long)R,
-                   reinterpret_cast<int8_t*>(dSamples), reinterpret_cast<float*>(dSamples + off_p), reinterpret_cast<float*>(dSamples + off_v));
+        if (weighted)
+            GAZ_LAUNCH(k_build_samples_w<G>, n, SAMPLES_THREADS, stream, (const uint8_t*)E.ring, E.ring_cap, (const int32_t*)d_plan, n, (long long)R, (const uint8_t*)dCounts,
+                       reinterpret_cast<int8_t*>(dSamples), reinterpret_cast<float*>(dSamples + off_p), reinterpret_cast<float*>(dSamples + off_v), dSamples + off_rp);
+        else
+            GAZ_LAUNCH(k_build_samples<G>, n, SAMPLES_THREADS, stream, (const uint8_t*)E.ring, E.ring_cap, (const int32_t*)d_plan, n, (long long)R,
+                       reinterpret_cast<int8_t*>(dSamples), reinterpret_cast<float*>(dSamples + off_p), reinterpret_cast<float*>(dSamples + off_v));
         HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpyAsync(hSamples, dSamples, off_v + (size_t)R * 4, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipMemcpyAsync(hSamples, dSamples, weighted ? off_rp + (size_t)R : off_v + (size_t)R * 4, hipMemcpyDeviceToHost, stream));
         HIP_OK(hipStreamSynchronize(stream));
         for (int k = 0; k < NA; ++k) {
             memcpy(boards + (size_t)k * plane_rows * SB, hSamples + (size_t)k * R * SB, (size_t)R * SB);
             memcpy(policies + (size_t)k * plane_rows * G::A, hSamples + off_p + (size_t)k * R * G::A * 4, (size_t)R * G::A * 4);
         }
         memcpy(values, hSamples + off_v, (size_t)R * 4);
+        if (weighted && row_ply) memcpy(row_ply, hSamples + off_rp, (size_t)R);
         return 0;
     }
+    uint8_t* dCounts = nullptr; int32_t* dRows = nullptr;      // k_sample_weights: u8 [ring_cap][TPAD] rows per ply | [ring_cap][2] rows, plies without a row
     int drain_samples(int max_games, int64_t max_rows, int64_t plane_rows, int64_t row_base, int32_t* games, int8_t* boards, float* policies,
-                      float* values, int32_t* n_games, int64_t* n_rows, int32_t* blocked_T) override {
+                      float* values, uint8_t* row_ply, int32_t* n_games, int64_t* n_rows, int32_t* blocked_T) override {
         *n_games = 0; *n_rows = 0; *blocked_T = 0;
         if (E.ring_cap <= 0) return 0;
         uint32_t avail = 0;
@@ -1215,27 +1228,39 @@ template <class G> struct EngineT : gaz_engine {
         if (avail > (uint32_t)E.ring_cap) avail = (uint32_t)E.ring_cap;
         if ((int64_t)avail > (int64_t)max_games) avail = (uint32_t)(max_games > 0 ? max_games : 0);
         if (!avail) return check_device_error();
-        if (!dPlan && dalloc(&dPlan, (size_t)(SAMPLE_HDR_INTS + 2) * E.ring_cap)) return 1;
-        GAZ_LAUNCH_FLAT(k_sample_headers<G>, (int)avail, SAMPLES_THREADS, stream, (const uint8_t*)E.ring, E.ring_cap, ring_consumed, (int)avail, dPlan);
+        if (!dPlan && dalloc(&dPlan, (size_t)(SAMPLE_HDR_W_INTS + 2) * E.ring_cap)) return 1;
+        // weighted: the rows of a ply are a count (k_sample_weights).  Off (lambda = 0), a caller that wants the ply of every row is served by the
+        // same kernels: at lambda = 0 the counts are 1 for the plies kept today and 0 for the fast ones
+        const bool weighted = sw_lambda > 0.0 || row_ply != nullptr;
+        const int HI = weighted ? SAMPLE_HDR_W_INTS : SAMPLE_HDR_INTS;
+        if (weighted) {
+            if (!dCounts && dalloc(&dCounts, (size_t)E.ring_cap * G::TPAD)) return 1;
+            if (!dRows && dalloc(&dRows, (size_t)2 * E.ring_cap)) return 1;
+            GAZ_LAUNCH(k_sample_weights<G>, (int)avail, SAMPLES_THREADS, stream, (const uint8_t*)E.ring, E.ring_cap, ring_consumed, (int)avail, E.key0, E.key1,
+                       sw_lambda, sw_fast_factor, dCounts, dRows);
+            GAZ_LAUNCH_FLAT(k_sample_headers_w<G>, (int)avail, SAMPLES_THREADS, stream, (const uint8_t*)E.ring, E.ring_cap, ring_consumed, (int)avail, (const int32_t*)dRows, dPlan);
+        } else {
+            GAZ_LAUNCH_FLAT(k_sample_headers<G>, (int)avail, SAMPLES_THREADS, stream, (const uint8_t*)E.ring, E.ring_cap, ring_consumed, (int)avail, dPlan);
+        }
         HIP_OK(hipGetLastError());
-        std::vector<int32_t> hdr((size_t)SAMPLE_HDR_INTS * avail);
+        std::vector<int32_t> hdr((size_t)HI * avail);
         HIP_OK(hipMemcpyAsync(hdr.data(), dPlan, hdr.size() * 4, hipMemcpyDeviceToHost, stream));
         HIP_OK(hipStreamSynchronize(stream));
-        int n = 0; int64_t R = 0;                    // whole games, oldest first, while their rows (the plies that were not fast searches) fit
+        int n = 0; int64_t R = 0;                    // whole games, oldest first, while their rows (the plies that were not fast searches; weighted: the counts' total) fit
         std::vector<int32_t> plan;
         for (; n < (int)avail; ++n) {
-            const int32_t* h = &hdr[(size_t)SAMPLE_HDR_INTS * n];
-            const int T = sample_plies<G>(h[0]), rows = h[4] < 0 ? 0 : (h[4] > T ? T : h[4]);
+            const int32_t* h = &hdr[(size_t)HI * n];
+            const int T = sample_plies<G>(h[0]), most = weighted ? sample_rows_cap<G>() : T, rows = h[4] < 0 ? 0 : (h[4] > most ? most : h[4]);
             if (R + rows > max_rows) { if (n == 0) *blocked_T = rows; break; }
             plan.push_back((int32_t)((ring_consumed + (uint32_t)n) % (uint32_t)E.ring_cap));
             games[6 * n] = T; games[6 * n + 1] = h[1]; games[6 * n + 2] = h[2]; games[6 * n + 3] = h[3];
-            games[6 * n + 4] = (int32_t)(row_base + R); games[6 * n + 5] = T - rows;
+            games[6 * n + 4] = (int32_t)(row_base + R); games[6 * n + 5] = weighted ? h[5] : T - rows;
             R += rows;
         }
         if (!n) return check_device_error();
         if (row_base + R > 0x7fffffffLL) return fail("drain_samples: more than 2^31 rows in one call");
         for (int i = 0; i < n; ++i) plan.push_back(games[6 * i + 4] - (int32_t)row_base);
-        if (R > 0 && build_samples(plan, n, R, plane_rows, boards, policies, values)) return 1;
+        if (R > 0 && build_samples(plan, n, R, plane_rows, boards, policies, values, weighted, row_ply)) return 1;
         if (ring_commit((uint32_t)n)) return 1;
         *n_games = n; *n_rows = R;
         return check_device_error();
@@ -1825,20 +1850,24 @@ struct GroupEngine : gaz_engine {
     }
     int sample_layout(gaz_sample_layout* o) override { *o = slay; return 0; }
     int drain_samples(int max_games, int64_t max_rows, int64_t plane_rows, int64_t row_base, int32_t* games, int8_t* boards, float* policies,
-                      float* values, int32_t* n_games, int64_t* n_rows, int32_t* blocked_T) override {
+                      float* values, uint8_t* row_ply, int32_t* n_games, int64_t* n_rows, int32_t* blocked_T) override {
         const gaz_sample_layout& sl = slay;
         int total = 0, blocked = 0; int64_t rows = 0;
         for (int i = 0; i < K() && total < max_games; ++i) {         // children append at the running game / row offset
             gaz_engine* k = kid[(drain_from + i) % K()];
             int32_t got = 0, b = 0; int64_t r = 0;
             if (up(k, k->drain_samples(max_games - total, max_rows - rows, plane_rows, row_base + rows, games + (size_t)6 * total, boards + (size_t)rows * sl.state_bytes,
-                                       policies + (size_t)rows * sl.A, values + rows, &got, &r, &b))) return 1;
+                                       policies + (size_t)rows * sl.A, values + rows, row_ply ? row_ply + rows : row_ply, &got, &r, &b))) return 1;
             if (b && !blocked) blocked = b;
             total += got; rows += r;
         }
         drain_from = (drain_from + 1) % K();
         *n_games = total; *n_rows = rows; *blocked_T = total ? 0 : blocked;
         return 0;
+    }
+    int set_sample_weighting(double lambda, double fast_factor) override {
+        sw_lambda = lambda; sw_fast_factor = fast_factor;
+        return all(&gaz_engine::set_sample_weighting, lambda, fast_factor);
     }
     int get_stats(uint64_t out[16]) override {
         for (int i = 0; i < 16; ++i) out[i] = 0;
@@ -2020,15 +2049,34 @@ int gaz_engine_evaluate(gaz_engine* h, const int8_t* in, int32_t n, float* p, fl
 int gaz_engine_record_layout(gaz_engine* h, gaz_record_layout* o) { return h->record_layout(o); }
 int gaz_engine_drain_finished(gaz_engine* h, void* out, int32_t max_records, int32_t* n_out) { return h->drain(out, max_records, n_out); }
 int gaz_engine_sample_layout(gaz_engine* h, gaz_sample_layout* o) { return o ? h->sample_layout(o) : h->fail("sample_layout: null argument"); }
-int gaz_engine_drain_samples(gaz_engine* h, int32_t max_games, int64_t max_rows, int32_t* games, int8_t* boards, float* policies, float* values,
-                             int32_t* n_games, int64_t* n_rows) {
+int gaz_engine_drain_samples2(gaz_engine* h, int32_t max_games, int64_t max_rows, int32_t* games, int8_t* boards, float* policies, float* values,
+                              uint8_t* row_ply, int32_t* n_games, int64_t* n_rows) {
     if (!games || !boards || !policies || !values || !n_games || !n_rows) return h->fail("drain_samples: null argument");
     if (max_games < 0 || max_rows < 0) return h->fail("drain_samples: max_games and max_rows must be >= 0");
     int32_t blocked = 0;
-    if (h->drain_samples(max_games, max_rows, max_rows, 0, games, boards, policies, values, n_games, n_rows, &blocked)) return 1;
+    if (h->drain_samples(max_games, max_rows, max_rows, 0, games, boards, policies, values, row_ply, n_games, n_rows, &blocked)) return 1;
     if (*n_games == 0 && blocked)
         return h->fail("drain_samples: the oldest finished game has " + std::to_string(blocked) + " rows, max_rows is " + std::to_string(max_rows) +
-                       " (no game was taken: call again with room for at least max_T rows)");
+                       (h->sw_lambda > 0.0 ? " (no game was taken: call again with room for at least 2 * max_T rows)"
+                                           : " (no game was taken: call again with room for at least max_T rows)"));
+    return 0;
+}
+int gaz_engine_drain_samples(gaz_engine* h, int32_t max_games, int64_t max_rows, int32_t* games, int8_t* boards, float* policies, float* values,
+                             int32_t* n_games, int64_t* n_rows) {
+    return gaz_engine_drain_samples2(h, max_games, max_rows, games, boards, policies, values, nullptr, n_games, n_rows);
+}
+// policy surprise weighting of the training rows (samples.hpp): lambda = 0 is off (a new engine), legal at any time, read by the next drain
+int gaz_engine_set_sample_weighting(gaz_engine* h, double lambda, double fast_factor) {
+    if (h->cfg.search == GAZ_SEARCH_GUMBEL)
+        return h->fail("set_sample_weighting: not with the Gumbel search (the surprise is taken against the priors of a PUCT root; a Gumbel record's policy is not a visit distribution over them)");
+    if (!(lambda >= 0.0 && lambda <= 1.0)) return h->fail("set_sample_weighting: lambda must be in [0, 1] (0 = off), not " + std::to_string(lambda));
+    if (!(fast_factor > 0.0) || fast_factor > 1.7976931348623157e308)
+        return h->fail("set_sample_weighting: fast_factor must be a finite number above 0, not " + std::to_string(fast_factor));
+    return h->set_sample_weighting(lambda, fast_factor);
+}
+int gaz_engine_get_sample_weighting(gaz_engine* h, double* lambda, double* fast_factor) {
+    if (!lambda || !fast_factor) return h->fail("get_sample_weighting: null argument");
+    *lambda = h->sw_lambda; *fast_factor = h->sw_fast_factor;
     return 0;
 }
 int gaz_engine_get_stats(gaz_engine* h, uint64_t out[16]) { return h->get_stats(out); }

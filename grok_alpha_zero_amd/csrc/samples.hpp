@@ -179,4 +179,199 @@ template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_build_samples(const uint
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Policy surprise weighting (gaz_engine_set_sample_weighting; DESIGN.md "Policy surprise weighting"; KataGo, Wu 2019, section 3.3): the
+// rows a ply gives become a COUNT c_p, a function of the finished record, (lambda, fast_factor) and the engine's seed alone.
+//   s_p  = max(0, sum_a pi_p[a] (dlog pi_p[a] - dlog P_p[a])) over pi_p[a] > 0 and P_p[a] > 0, a ascending, sequential float64; NaN / inf = 0
+//   w0_p = 1 for a full ply, 0 for a fast one; a ply without a search (set_position prefix) keeps its one row and takes no part
+//   mean = (sum of s_p over the full plies, in ply order) / n_full;  a fast ply is eligible iff s_p > fast_factor * mean
+//   S    = sum of s_p over E = full + eligible fast plies, in ply order
+//   w_p  = (1 - lambda) w0_p + lambda n_full s_p / S on E, 0 elsewhere; w0_p if n_full == 0 or S is 0 or not finite
+//   c_p  = floor(w_p) + (u_p < w_p - floor(w_p)), u_p = uniform(seed, slot, game_seq, tree 2, event 0x40000000 + p, P_PLAYOUT_CAP)
+// (det::draw puts all 32 bits of the event into Philox counter word 2, so the variate shares nothing with the cap's own draw, event p.)
+// P_p is the record's P row: the priors the root searched with, Dirichlet noise included — the only prior a record keeps.
+constexpr uint32_t SURPRISE_EVENT = 0x40000000u;
+// The two clamps of k_sample_weights keep the tables of k_build_samples_w in bounds whatever a record holds; with a record the engine wrote
+// they cannot act (the counts would then differ from self_play.sample_row_counts), and the emulation build, which the tests run, aborts if one does.
+#ifdef GAZ_HOST_EMU
+inline void emu_unreachable() { abort(); }
+#else
+GAZ_DEV void emu_unreachable() {}
+#endif
+template <class G> constexpr int sample_rows_cap() { return 2 * G::MAXT; }        // rows of one game: < n_full + |E| + 1 <= 2 T
+
+template <class G> GAZ_DEV double ply_surprise(const float* pi, const float* P) {
+    double s = 0.0;
+    for (int a = 0; a < G::A; ++a) {
+        const float x = pi[a], y = P[a];
+        if (x > 0.0f && y > 0.0f) s = s + (double)x * (det::dlog((double)x) - det::dlog((double)y));
+    }
+    if (!(s == s) || s > 1.7976931348623157e308 || s < -1.7976931348623157e308) return 0.0;
+    return s > 0.0 ? s : 0.0;
+}
+
+// one workgroup per ring record of the drain window [first, first + n): counts[b][p] = c_p (0 from the record's T on), rows[2 b] = the game's
+// rows, rows[2 b + 1] = its plies that give no row.  One lane per ply walks its A actions; the sums over plies are one lane's, in ply order.
+template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_sample_weights(const uint8_t* ring, int ring_cap, uint32_t first, int n, uint32_t key0, uint32_t key1,
+                                                                        double lambda, double fast_factor, uint8_t* counts, int32_t* rows) {
+    using RL = RecLayout<G>;
+#ifdef GAZ_HOST_EMU
+    const int b = block_id(), nT = 1, t = 0;
+#else
+    const int b = blockIdx.x, nT = blockDim.x, t = threadIdx.x;
+#endif
+    GAZ_SHARED double s[G::TPAD];
+    GAZ_SHARED double sums[2];                                            // n_full * lambda (0: w = w0), S
+    GAZ_SHARED double mean_cut;                                           // fast_factor * mean
+    GAZ_SHARED uint8_t cnt[G::TPAD];
+    if (b >= n) return;
+    const uint8_t* rec = ring + (size_t)((first + (uint32_t)b) % (uint32_t)ring_cap) * RL::SIZE;
+    const int32_t* hdr = reinterpret_cast<const int32_t*>(rec + RL::OFF_HDR);
+    const int T = sample_plies<G>(hdr[0]);
+    const uint8_t* mk = rec + RL::OFF_MK;
+    const float* pol = reinterpret_cast<const float*>(rec + RL::OFF_POL);
+    const float* pri = reinterpret_cast<const float*>(rec + RL::OFF_P);
+    for (int p = t; p < T; p += nT) s[p] = (mk[p] & MK_KIND_MASK) == MK_NONE ? 0.0 : ply_surprise<G>(pol + (size_t)p * G::A, pri + (size_t)p * G::A);
+    group_sync();
+    if (t == 0) {
+        int n_full = 0;
+        double sum_full = 0.0, S = 0.0;
+        for (int p = 0; p < T; ++p) if ((mk[p] & MK_KIND_MASK) == MK_FULL) { ++n_full; sum_full = sum_full + s[p]; }
+        const double cut = n_full ? fast_factor * (sum_full / (double)n_full) : 0.0;
+        for (int p = 0; p < T; ++p) {
+            const int kind = mk[p] & MK_KIND_MASK;
+            if (kind == MK_FULL || (kind == MK_FAST && s[p] > cut)) S = S + s[p];
+        }
+        const bool plain = n_full == 0 || !(S > 0.0) || S > 1.7976931348623157e308 || lambda == 0.0;
+        sums[0] = plain ? 0.0 : lambda * (double)n_full; sums[1] = S; mean_cut = cut;
+    }
+    group_sync();
+    for (int p = t; p < G::TPAD; p += nT) {
+        int c = 0;
+        if (p < T) {
+            const int kind = mk[p] & MK_KIND_MASK;
+            const double w0 = kind == MK_FULL ? 1.0 : 0.0;
+            double w = w0;
+            if (sums[0] != 0.0) w = (kind == MK_FULL || (kind == MK_FAST && s[p] > mean_cut)) ? (1.0 - lambda) * w0 + (sums[0] * s[p]) / sums[1] : 0.0;
+            if (kind == MK_NONE) c = 1;
+            else if (w > 0.0) {
+                const double fl = (double)(long long)w;                   // floor: w > 0, far below 2^63
+                det::Event e; e.key0 = key0; e.key1 = key1; e.slot = (uint32_t)hdr[2]; e.game_seq = (uint32_t)hdr[3];
+                e.event = SURPRISE_EVENT + (uint32_t)p; e.tree = 2; e.purpose = det::P_PLAYOUT_CAP;
+                c = (int)fl + (det::uniform(e) < w - fl ? 1 : 0);
+                if (c > 255) { emu_unreachable(); c = 255; }        // (w <= n_full + 1 <= 226)
+            }
+        }
+        cnt[p] = (uint8_t)c;
+    }
+    group_sync();
+    if (t == 0) {                                                         // the total, held to the table of k_build_samples_w (never reached: rows < 2 T + 1)
+        int total = 0, none = 0;
+        for (int p = 0; p < T; ++p) {
+            int c = cnt[p];
+            if (total + c > sample_rows_cap<G>()) { emu_unreachable(); c = sample_rows_cap<G>() - total; cnt[p] = (uint8_t)c; }
+            total += c; none += c == 0;
+        }
+        rows[2 * b] = total; rows[2 * b + 1] = none;
+    }
+    group_sync();
+    for (int p = t; p < G::TPAD; p += nT) counts[(size_t)b * G::TPAD + p] = cnt[p];
+}
+
+// k_sample_headers with the rows from k_sample_weights: SAMPLE_HDR_W_INTS per game, [T, winner, slot, game_seq, rows, plies without a row]
+constexpr int SAMPLE_HDR_W_INTS = 6;
+template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_sample_headers_w(const uint8_t* ring, int ring_cap, uint32_t first, int n, const int32_t* rows, int32_t* out) {
+#ifdef GAZ_HOST_EMU
+    const int i = block_id();
+#else
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+#endif
+    if (i >= n) return;
+    const uint8_t* rec = ring + (size_t)((first + (uint32_t)i) % (uint32_t)ring_cap) * RecLayout<G>::SIZE;
+    const int32_t* hdr = reinterpret_cast<const int32_t*>(rec + RecLayout<G>::OFF_HDR);
+    for (int j = 0; j < 4; ++j) out[SAMPLE_HDR_W_INTS * i + j] = hdr[j];
+    out[SAMPLE_HDR_W_INTS * i + 4] = rows[2 * i]; out[SAMPLE_HDR_W_INTS * i + 5] = rows[2 * i + 1];
+}
+
+// inclusive prefix sum of v over the workgroup's lanes of one pass, on top of `carry` (the sum of the passes before): every wavefront scans its
+// lanes by shuffles, the wavefronts' totals meet in LDS.  -> this lane's inclusive sum; carry grows by the pass's total.  (One-lane emulation: WAVE = 1.)
+GAZ_DEV int group_scan(int v, int t, int nT, int* wave_sum, int& carry) {
+    const int lane = t % WAVE, wv = t / WAVE, n_wv = (nT + WAVE - 1) / WAVE;
+    int x = v;
+    for (int d = 1; d < WAVE; d <<= 1) { const int y = shfl(x, lane - d < 0 ? lane : lane - d); if (lane >= d) x += y; }
+    if (lane == WAVE - 1) wave_sum[wv] = x;
+    group_sync();
+    int below = 0, all = 0;
+    for (int w = 0; w < n_wv; ++w) { const int c = wave_sum[w]; below += w < wv ? c : 0; all += c; }
+    const int incl = carry + below + x;
+    carry += all;
+    group_sync();
+    return incl;
+}
+
+// k_build_samples with c_p rows per ply: counts = k_sample_weights' table of the drain window, game b of the plan = record b of the window.
+// The compaction is a scan over the counts (end[p] = rows of plies 0 .. p), and "output row -> ply" a table of up to 2 MAXT entries that the
+// lanes fill by output row, in passes of nT rows: row j belongs to the first ply whose end exceeds j.  row_ply (may be null) receives it.
+template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_build_samples_w(const uint8_t* ring, int ring_cap, const int32_t* plan, int n, long long R, const uint8_t* counts,
+                                                                         int8_t* boards, float* policies, float* values, uint8_t* row_ply) {
+    using RL = RecLayout<G>;
+    constexpr int SB = G::HW * G::C, NA = SampleAug<G>::N, NEVER = 0x7ffffffe, CAP = sample_rows_cap<G>();
+#ifdef GAZ_HOST_EMU
+    const int b = block_id(), nT = 1, t = 0;
+#else
+    const int b = blockIdx.x, nT = blockDim.x, t = threadIdx.x;
+#endif
+    GAZ_SHARED int fill[G::HW];
+    GAZ_SHARED uint8_t act[G::TPAD];
+    GAZ_SHARED uint16_t end[G::TPAD];                                     // rows of plies 0 .. p
+    GAZ_SHARED uint8_t kept[CAP];                                         // output row -> ply (MAXT <= 255)
+    GAZ_SHARED int wave_sum[SAMPLES_THREADS / 64 + 1];
+    if (b >= n) return;
+    const int slot = plan[b];
+    if (slot < 0 || slot >= ring_cap) return;
+    const uint8_t* rec = ring + (size_t)slot * RL::SIZE;
+    const int32_t* hdr = reinterpret_cast<const int32_t*>(rec + RL::OFF_HDR);
+    const int T = sample_plies<G>(hdr[0]), winner = hdr[1];
+    const long long row0 = plan[n + b];
+    for (int i = t; i < G::HW; i += nT) fill[i] = NEVER;
+    for (int i = t; i < T; i += nT) act[i] = rec[RL::OFF_ACT + i];
+    int K = 0;
+    for (int base = 0; base < T; base += nT) {
+        const int p = base + t;
+        const int incl = group_scan(p < T ? (int)counts[(size_t)b * G::TPAD + p] : 0, t, nT, wave_sum, K);
+        if (p < T) end[p] = (uint16_t)(incl < 0xffff ? incl : 0xffff);
+    }
+    group_sync();                                                         // (T = 0: no pass ran)
+    if (K > CAP || row0 < 0 || row0 + K > R) return;                     // (the host built row0 from k_sample_weights' totals of these very counts)
+    for (int j = t; j < K; j += nT) {                                     // the first ply with end[p] > j: j < K = end[T - 1], so there is one
+        int lo = 0, hi = T - 1;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if ((int)end[mid] > j) hi = mid; else lo = mid + 1; }
+        kept[j] = (uint8_t)lo;
+    }
+    if (G::ID == GAME_C4) {
+        for (int p = t; p < T; p += nT) {                                 // row = 5 - the earlier moves in the same column
+            const int a = act[p];
+            int below = 0;
+            for (int e = 0; e < p; ++e) below += act[e] == a;
+            if (a < G::W && below < G::H) fill[(G::H - 1 - below) * G::W + a] = p;
+        }
+    } else {
+        for (int p = t; p < T; p += nT) if (act[p] < G::HW) fill[act[p]] = p;
+    }
+    group_sync();
+    const float* q = reinterpret_cast<const float*>(rec + RL::OFF_Q);
+    const float* pol = reinterpret_cast<const float*>(rec + RL::OFF_POL);
+    for (int j = t; j < K; j += nT) {                                     // z as in k_build_samples
+        const int p = kept[j];
+        const float z = (float)(((p & 1) ? 1 : -1) * winner);
+        values[row0 + j] = 0.5f * (z + q[p]);
+        if (row_ply) row_ply[row0 + j] = (uint8_t)p;
+    }
+    for (int k = 0; k < NA; ++k) {
+        const size_t row = (size_t)k * (size_t)R + (size_t)row0;
+        emit_range<int8_t>(boards, row * SB, K * SB, t, nT, [&](int i) { return state_element<G>(fill, kept[i / SB], k, i % SB); });
+        emit_range<float>(policies, row * G::A, K * G::A, t, nT, [&](int i) { return pol[kept[i / G::A] * G::A + policy_src_index<G>(k, i % G::A)]; });
+    }
+}
+
 }  // namespace gaz

@@ -118,6 +118,13 @@ def load_library(lib_path=None):
     L.gaz_engine_sample_layout.argtypes = [H, C.POINTER(SampleLayout)]
     L.gaz_engine_drain_samples.argtypes = [H, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    if hasattr(L, "gaz_engine_set_sample_weighting"):   # policy surprise weighting, detected by its symbols: a library built before it has none
+        L.gaz_engine_set_sample_weighting.argtypes = [H, C.c_double, C.c_double]
+        L.gaz_engine_get_sample_weighting.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.gaz_engine_drain_samples2.argtypes = [H, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        for f in ("set_sample_weighting", "get_sample_weighting", "drain_samples2"):
+            getattr(L, "gaz_engine_" + f).restype = C.c_int
     L.gaz_engine_get_stats.argtypes = [H, C.POINTER(C.c_uint64)]
     L.gaz_engine_synchronize.argtypes = [H]
     L.gaz_engine_timing_reset.argtypes = [H, C.c_int32]
@@ -177,10 +184,17 @@ class SampleBatch:
     """The finished games of one SelfPlayEngine.drain_samples() call as training samples (include/gaz_engine.h, gaz_engine_drain_samples):
     `games` int32 [n, 6] (T, winner, slot, game_seq, first row, plies left out), `boards` int8 [n_aug, R, H, W, C], `policies` f32 [n_aug, R, A],
     `values` f32 [R, 1]; rows = the games in the order handed out, plies in order.  With playout cap randomisation (fast_iterations) the
-    plies of fast searches give no row: game i has T - games[i, 5] rows."""
+    plies of fast searches give no row: game i has T - games[i, 5] rows.  With policy surprise weighting (set_sample_weighting) a ply gives
+    0, 1 or more adjacent rows: games[i, 5] counts the plies that gave none, game i has rows_of(i) rows, and `plies` (uint8 [R], with
+    drain_samples(with_plies=True), else None) is the ply of every row."""
 
-    def __init__(self, games, boards, policies, values):
-        self.games, self.boards, self.policies, self.values = games, boards, policies, values
+    def __init__(self, games, boards, policies, values, plies=None):
+        self.games, self.boards, self.policies, self.values, self.plies = games, boards, policies, values, plies
+
+    def rows_of(self, i):
+        """the rows of game i: the difference of successive first rows, the batch's rows closing the last one"""
+        end = int(self.games[i + 1, 4]) if i + 1 < self.n else int(self.games[0, 4]) + self.rows
+        return end - int(self.games[i, 4])
 
     @property
     def n(self):
@@ -199,14 +213,14 @@ class SampleBatch:
 
     def copy(self):
         """an owning, compact copy (what another thread may keep)"""
-        return SampleBatch(self.games.copy(), self.boards.copy(), self.policies.copy(), self.values.copy())
+        return SampleBatch(self.games.copy(), self.boards.copy(), self.policies.copy(), self.values.copy(), None if self.plies is None else self.plies.copy())
 
     def game(self, i):
         """game i as ReplayStore.append_game takes it: (boards [n_aug, n, H, W, C], policies [n_aug, n, A], values [n_aug, n, 1],
-        game_length, n_positions, winner) — views, no copy.  n = the game's rows (T minus the plies of fast searches); game_length and
-        n_positions stay T, the plies played"""
+        game_length, n_positions, winner) — views, no copy.  n = the game's rows (T minus the plies of fast searches; rows_of(i) with
+        policy surprise weighting); game_length and n_positions stay T, the plies played"""
         T, winner, r0 = int(self.games[i, 0]), int(self.games[i, 1]), int(self.games[i, 4]) - int(self.games[0, 4])
-        n = T - int(self.games[i, 5])
+        n = self.rows_of(i)
         v = np.broadcast_to(self.values[None, r0:r0 + n], (self.policies.shape[0], n, 1))
         return self.boards[:, r0:r0 + n], self.policies[:, r0:r0 + n], v, T, T, winner
 
@@ -263,7 +277,8 @@ class SelfPlayEngine:
                  compact_trees=0, single_tree=False, opening_actions=None, eval_cache_log2=0, gumbel_stablemax=False, fast_find_win=False,
                  use_gumbel_noise=True, first_game_seq=0, games_budget=0, tau=-1.0, move_time_limit=0.0, game_groups=0, leaf_batch=1, gumbel_batch=1,
                  fast_iterations=0, full_search_prob=0.0, forced_playouts_k=0.0,
-                 resign_threshold=0.0, resign_consecutive=1, resign_min_ply=0, no_resign_prob=0.0, eval_symmetry=False, solver=False, lib_path=None):
+                 resign_threshold=0.0, resign_consecutive=1, resign_min_ply=0, no_resign_prob=0.0, eval_symmetry=False, solver=False,
+                 sample_weighting=None, lib_path=None):
         self.L = load_library(lib_path)
         self.game_id = GAME_IDS[game] if isinstance(game, str) else int(game)
         self.H, self.W, self.Cc, self.A = GAME_DIMS[self.game_id]
@@ -313,6 +328,12 @@ class SelfPlayEngine:
             try:
                 self.set_solver(True)
             except EngineError:
+                self.close()
+                raise
+        if sample_weighting and sample_weighting[0]:     # (lambda, fast_factor); lambda 0 = off, the state of a new engine
+            try:
+                self.set_sample_weighting(*sample_weighting)
+            except (EngineError, ValueError):
                 self.close()
                 raise
 
@@ -643,30 +664,63 @@ class SelfPlayEngine:
 
     sample_buffer_bytes = 256 << 20     # host buffers of drain_samples (at least one game of max_T plies)
 
-    def drain_samples(self, max_games=None, max_rows=None):
+    def set_sample_weighting(self, lam, fast_factor=1.5):
+        """Policy surprise weighting of the training rows (gaz_engine_set_sample_weighting; KataGo), from the next drain_samples on: a
+        game's row weight — one per fully searched ply — moves towards the plies whose search policy differs most from the priors their root
+        searched with, a fast ply whose surprise exceeds `fast_factor` times the mean of the full plies earns rows too, and every weight
+        becomes a whole number of rows by stochastic rounding keyed by (seed, slot, game_seq, ply).  lam in [0, 1]: 0 = off (KataGo: 0.5).
+        PUCT engines only.  self_play.sample_row_counts is the host definition."""
+        lam, fast_factor = float(lam), float(fast_factor)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"set_sample_weighting: lambda must be in [0, 1] (0 = off), not {lam}")
+        if not (fast_factor > 0.0 and fast_factor != float("inf")):
+            raise ValueError(f"set_sample_weighting: fast_factor must be a finite number above 0, not {fast_factor}")
+        if not hasattr(self.L, "gaz_engine_set_sample_weighting"):
+            raise EngineError("this library has no gaz_engine_set_sample_weighting")
+        self._ck(self.L.gaz_engine_set_sample_weighting(self.h, lam, fast_factor))
+
+    @property
+    def sample_weighting(self):
+        """(lambda, fast_factor) of set_sample_weighting; (0.0, 1.5) on a new engine"""
+        if not hasattr(self.L, "gaz_engine_get_sample_weighting"):
+            return 0.0, 1.5
+        a, b = C.c_double(), C.c_double()
+        self._ck(self.L.gaz_engine_get_sample_weighting(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def drain_samples(self, max_games=None, max_rows=None, with_plies=False):
         """Finished games as training samples, built on the device (gaz_engine_drain_samples): a SampleBatch of the games that have
         finished, oldest first; what the buffers (or `max_games` / `max_rows`) do not hold stays in the engine for the next call; a
         `max_rows` below the oldest game's rows is an EngineError.  With forced_playouts_k > 0 the policies are the pruned targets (the
         kernel reads the record's policy rows).  May be mixed with drain_finished():
         a game is handed out once.  The host buffers are allocated once per engine and REUSED: the batch's arrays are views into them,
         valid until the next drain_samples() of this engine — a batch that goes to another thread, or is kept, is copied first
-        (SampleBatch.copy(); run_self_play does that before it hands a batch to its writer thread)."""
-        if getattr(self, "_sbuf", None) is None:
+        (SampleBatch.copy(); run_self_play does that before it hands a batch to its writer thread).
+        With set_sample_weighting a game has up to 2 T rows (SampleBatch.rows_of); with_plies: the batch's `plies` is the ply of every row."""
+        most = 2 if self.sample_weighting[0] else 1                  # rows a ply may average: the buffers hold a game of most * max_T rows
+        if getattr(self, "_sbuf", None) is None or self._sbuf[0] != most:
             sl = SampleLayout()
             self._ck(self.L.gaz_engine_sample_layout(self.h, C.byref(sl)))
             cap_games = max(int(self.cfg.ring_capacity), 1)
             row_bytes = sl.n_aug * (sl.state_bytes + 4 * sl.A) + 4
-            cap_rows = max(min(cap_games * sl.max_T, self.sample_buffer_bytes // row_bytes), sl.max_T)
-            self._sbuf = (sl, cap_games, cap_rows, np.empty((cap_games, 6), np.int32), np.empty((sl.n_aug, cap_rows, self.H, self.W, self.Cc), np.int8),
-                          np.empty((sl.n_aug, cap_rows, sl.A), np.float32), np.empty((cap_rows, 1), np.float32))
-        sl, cap_games, cap_rows, games, boards, policies, values = self._sbuf
+            cap_rows = max(min(cap_games * most * sl.max_T, self.sample_buffer_bytes // row_bytes), most * sl.max_T)
+            self._sbuf = (most, sl, cap_games, cap_rows, np.empty((cap_games, 6), np.int32), np.empty((sl.n_aug, cap_rows, self.H, self.W, self.Cc), np.int8),
+                          np.empty((sl.n_aug, cap_rows, sl.A), np.float32), np.empty((cap_rows, 1), np.float32), np.empty(cap_rows, np.uint8))
+        _, sl, cap_games, cap_rows, games, boards, policies, values, plies = self._sbuf
         n, r = C.c_int32(), C.c_int64()
         take_rows, b, p = cap_rows, boards, policies
         if max_rows is not None and int(max_rows) < cap_rows:        # the augmentation planes are max_rows apart: arrays of that shape
             take_rows = int(max_rows)
             b = np.empty((sl.n_aug, max(take_rows, 1), self.H, self.W, self.Cc), np.int8)
             p = np.empty((sl.n_aug, max(take_rows, 1), sl.A), np.float32)
-        self._ck(self.L.gaz_engine_drain_samples(self.h, min(int(max_games), cap_games) if max_games else cap_games, take_rows, games.ctypes.data,
+        take_games = min(int(max_games), cap_games) if max_games else cap_games
+        if with_plies:
+            if not hasattr(self.L, "gaz_engine_drain_samples2"):
+                raise EngineError("this library has no gaz_engine_drain_samples2")
+            self._ck(self.L.gaz_engine_drain_samples2(self.h, take_games, take_rows, games.ctypes.data, b.ctypes.data, p.ctypes.data, values.ctypes.data,
+                                                      plies.ctypes.data, C.byref(n), C.byref(r)))
+            return SampleBatch(games[:n.value], b[:, :r.value], p[:, :r.value], values[:r.value], plies[:r.value])
+        self._ck(self.L.gaz_engine_drain_samples(self.h, take_games, take_rows, games.ctypes.data,
                                                  b.ctypes.data, p.ctypes.data, values.ctypes.data, C.byref(n), C.byref(r)))
         return SampleBatch(games[:n.value], b[:, :r.value], p[:, :r.value], values[:r.value])
 

@@ -301,11 +301,58 @@ def _fast_states(name, actions):
     return st
 
 
-def record_to_samples(game_class, rec):
+SURPRISE_EVENT = 0x40000000                        # the event of ply p's rounding variate is SURPRISE_EVENT + p (csrc/samples.hpp)
+
+
+def sample_row_counts(rec, lam, fast_factor, seed):
+    """Policy surprise weighting (SelfPlayEngine.set_sample_weighting; include/gaz_engine.h states the rule, steps 1-5): the rows every ply
+    of one finished PUCT record gives -> int array [T].  The prior of a ply is rec["root_P"], the priors its root searched with (Dirichlet
+    noise included).  Every sum is a sequential float64 sum, in action / ply order, as the kernel's."""
+    from . import det
+    lam, fast_factor = float(lam), float(fast_factor)
+    kind = [int(k) & 3 for k in rec["move_kind"]]
+    T = len(kind)
+    s = [0.0] * T
+    for p in range(T):
+        if kind[p] == 0:
+            continue
+        acc = 0.0
+        for x, y in zip(rec["policies"][p], rec["root_P"][p]):
+            if x > 0 and y > 0:
+                acc = acc + float(x) * (det.dlog(float(x)) - det.dlog(float(y)))
+        s[p] = acc if math.isfinite(acc) and acc > 0.0 else 0.0
+    full = [p for p in range(T) if kind[p] == 1]
+    n_full = len(full)
+    total = 0.0
+    for p in full:
+        total = total + s[p]
+    cut = fast_factor * (total / n_full) if n_full else 0.0
+    in_E = [kind[p] == 1 or (kind[p] == 2 and s[p] > cut) for p in range(T)]
+    S = 0.0
+    for p in range(T):
+        if in_E[p]:
+            S = S + s[p]
+    plain = n_full == 0 or not S > 0.0 or not math.isfinite(S) or lam == 0.0
+    counts = np.zeros(T, np.int64)
+    for p in range(T):
+        if kind[p] == 0:
+            counts[p] = 1
+            continue
+        w0 = 1.0 if kind[p] == 1 else 0.0
+        w = w0 if plain else ((1.0 - lam) * w0 + lam * n_full * s[p] / S if in_E[p] else 0.0)
+        fl = math.floor(w)
+        u = det.uniform(int(seed), int(rec["slot"]), int(rec["game_seq"]), 2, SURPRISE_EVENT + p, det.P_PLAYOUT_CAP)
+        counts[p] = int(fl) + (1 if u < w - fl else 0)
+    return counts
+
+
+def record_to_samples(game_class, rec, weighting=None):
     """Rebuild what Self_Play.play() collected for one finished game (Self_Play.py:80,114-127,159-175): input states by
     replaying the moves through the Game plugin, improved policies, values = 0.5 (z + q), then augment_sample.  Plies whose search was
     a fast one (rec["move_kind"] == 2, playout cap randomisation) give no row; the length returned stays the plies played.  With forced
-    playouts (forced_playouts_k > 0) rec["policies"] already holds the pruned targets: nothing is recomputed here."""
+    playouts (forced_playouts_k > 0) rec["policies"] already holds the pruned targets: nothing is recomputed here.
+    weighting = (lambda, fast_factor, seed) — seed the engine's — applies policy surprise weighting: ply p gives sample_row_counts()[p]
+    adjacent copies of the row it has with the cap off; lambda = 0 or None is the plain rule above."""
     game = game_class()
     from . import games as _builtin
     if game_class in (_builtin.Connect4, _builtin.Gomoku, _builtin.TicTacToe):
@@ -321,7 +368,13 @@ def record_to_samples(game_class, rec):
     policies = np.asarray(rec["policies"], np.float32)
     values = np.asarray(rec["values"], np.float32).reshape(-1, 1)
     kind = rec.get("move_kind")
-    if kind is not None and np.any(np.asarray(kind) == 2):
+    if weighting is not None and float(weighting[0]) != 0.0:
+        rows = np.repeat(np.arange(len(values)), sample_row_counts(rec, *weighting))
+        if rows.size == 0 and len(values):           # every count rounded to 0: arrays of no rows, shaped by the augmentations of one row
+            aug_b, aug_p = (np.asarray(a) for a in game.augment_sample(board_states[:1], policies[:1]))
+            return aug_b[:, :0], aug_p[:, :0], np.zeros((aug_p.shape[0], 0, 1), np.float32), n_plies
+        board_states, policies, values = board_states[rows], policies[rows], values[rows]
+    elif kind is not None and np.any(np.asarray(kind) == 2):
         keep = np.asarray(kind) != 2
         board_states, policies, values = board_states[keep], policies[keep], values[keep]
     aug_b, aug_p = game.augment_sample(board_states, policies)
@@ -455,7 +508,9 @@ def engine_search_settings(game_class, configs):
               fast_iterations=fast, full_search_prob=float(train_config.get("full_search_prob") or 0.0) if fast else 0.0,
               forced_playouts_k=float(train_config.get("forced_playouts_k") or 0.0),
               resign_threshold=float(train_config.get("resign_threshold") or 0.0), resign_consecutive=int(train_config.get("resign_consecutive") or 1),
-              resign_min_ply=int(train_config.get("resign_min_ply") or 0), no_resign_prob=float(train_config.get("no_resign_prob") or 0.0))
+              resign_min_ply=int(train_config.get("resign_min_ply") or 0), no_resign_prob=float(train_config.get("no_resign_prob") or 0.0),
+              # policy surprise weighting of the training rows (SelfPlayEngine.set_sample_weighting; absent or 0 = off, and then no call is made)
+              sample_weighting=(float(train_config.get("policy_surprise_weight") or 0.0), float(train_config.get("policy_surprise_fast_factor") or 1.5)))
     return args, kw
 
 
@@ -490,6 +545,10 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
     is the player who did not resign, and game_stats count it like any other game.  `engine_stats["resign"]` receives
     SelfPlayEngine.resign_stats() (the false positives among the games played out); resign_curve() picks a threshold from the records
     of a generation played with no_resign_prob = 1.
+    Policy surprise weighting: train_config["policy_surprise_weight"] (lambda in [0, 1]; absent or 0 = off; KataGo uses 0.5; PUCT only) and
+    ["policy_surprise_fast_factor"] (default 1.5) — SelfPlayEngine.set_sample_weighting: a game's rows are redistributed towards the plies whose
+    search policy differs most from the prior, and fast plies that surprise enough earn rows too.  The replay file just gets the rows;
+    game_stats are unchanged.
     Solver: train_config["solver"] (absent or False = off, and then no call is made) — SelfPlayEngine.set_solver: the PUCT search proves
     wins, draws and losses; proven plies end early, and their value targets use the exact q.  PUCT with leaf_batch 1 only (else an EngineError).
     Random evaluation symmetry: train_config["eval_symmetry"] (absent or False = off, and then no call is made) —
@@ -554,6 +613,7 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
         eng.set_eval_symmetry(True)
     if train_config.get("solver"):
         eng.set_solver(True)
+    weighting = (*eng.sample_weighting, seed) if eng.sample_weighting[0] else None      # (the host path's: record_to_samples)
     written = 0
     launch = G                                          # slots the launches cover (shrinks in the generation's tail, see repack)
     clock = time.perf_counter
@@ -587,7 +647,7 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
             else:
                 for rec in recs:
                     t0 = clock()
-                    aug_b, aug_p, aug_v, length = record_to_samples(game_class, rec)
+                    aug_b, aug_p, aug_v, length = record_to_samples(game_class, rec, weighting)
                     t_samples += clock() - t0
                     writer.put((aug_b, aug_p, aug_v, length, rec["T"], rec["winner"]), aug_b.nbytes + aug_p.nbytes + aug_v.nbytes)
             if progress:

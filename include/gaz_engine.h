@@ -479,6 +479,41 @@ int gaz_engine_drain_samples(gaz_engine* h, int32_t max_games, int64_t max_rows,
                              int32_t* games, int8_t* boards, float* policies, float* values,
                              int32_t* n_games, int64_t* n_rows);
 
+/* POLICY SURPRISE WEIGHTING of the training rows (KataGo, Wu 2019, section 3.3; DESIGN.md "Policy surprise weighting"; no reference
+ * counterpart).  A game's row weight — one row per fully searched ply — is redistributed towards the plies whose search policy differs most
+ * from the prior; fast plies (playout cap randomisation) that surprise enough earn rows too; a weight becomes an integer number of rows by
+ * stochastic rounding.  PUCT records only.  No struct changes and GAZ_ENGINE_ABI_VERSION stays 10: the feature is detected by its symbols
+ * (gaz_engine_set_sample_weighting, gaz_engine_get_sample_weighting, gaz_engine_drain_samples2).
+ * The rule is stateless — a function of one finished record, (lambda, fast_factor) and gaz_engine_config.seed.  For ply p of a record with T
+ * plies, kind = move_kind[p] & 3, pi_p = the record's policy row (the pruned target with forced playouts), P_p = the record's P row: the
+ * priors the root searched with, Dirichlet noise included when it is on — the only prior a record keeps:
+ *   1  surprise  s_p = max(0, sum over a ascending of (double)pi_p[a] * (dlog((double)pi_p[a]) - dlog((double)P_p[a]))), only terms with
+ *      pi_p[a] > 0 and P_p[a] > 0, a sequential float64 sum in that order with the engine's dlog (csrc/det.hpp); NaN or infinite counts as 0
+ *   2  base weight  w0_p = 1 for kind 1 (full), 0 for kind 2 (fast).  A ply of kind 0 (a gaz_engine_set_position prefix) keeps exactly one
+ *      row, as without the mode, and takes no part in anything below
+ *   3  n_full = the number of full plies, mean = (sum of s_p over the full plies, in ply order) / n_full; a fast ply is eligible iff
+ *      s_p > fast_factor * mean; E = the full plies and the eligible fast plies; S = the sum of s_p over E, in ply order
+ *   4  w_p = (1 - lambda) * w0_p + lambda * n_full * s_p / S on E (evaluated left to right), 0 elsewhere; w_p = w0_p if n_full == 0 or S is
+ *      0 or not finite.  The game's weight is conserved: sum w_p == n_full up to rounding
+ *   5  rows  c_p = floor(w_p) + (u_p < w_p - floor(w_p)), u_p = the uniform variate of (seed, the record's slot, its game_seq, tree 2,
+ *      event 0x40000000 + p, purpose 5 = the playout cap's): all 32 bits of the event enter the Philox counter, so it collides with no other
+ *      draw (the cap's own uses event p), and no tree's event counter moves
+ *   6  a game's rows stay one contiguous range, in ply order, the c_p copies of a ply adjacent.  A row is byte for byte what that ply's row is
+ *      without the mode — for a fast ply what it would be with the cap off: the board shows every earlier move, the value is 0.5 * (z + q[p]).
+ *      A game has at most n_full + |E| <= 2 * T rows
+ * lambda in [0, 1]: 0 = off, the state of a new engine (KataGo uses 0.5); with lambda == 0 every output is what it is without the mode, byte
+ * for byte.  fast_factor > 0, finite (default 1.5).  Legal at any time; it takes effect at the next drain.  Refused, with its own text, on an
+ * engine with the Gumbel search, for lambda outside [0, 1] or NaN, and for fast_factor <= 0, NaN or infinite.
+ * With the mode on, for gaz_engine_drain_samples and gaz_engine_drain_samples2: games[i][5] is the number of plies that gave no row; a game's
+ * rows are the difference of successive games[i][4], *n_rows closing the last one; max_rows >= 2 * max_T always makes progress, and an oldest
+ * game with more rows than max_rows is the same error as before.
+ * gaz_engine_drain_samples2 = gaz_engine_drain_samples plus row_ply (u8 [max_rows], may be NULL): the ply of every row, mode on or off. */
+int gaz_engine_set_sample_weighting(gaz_engine* h, double lambda, double fast_factor);
+int gaz_engine_get_sample_weighting(gaz_engine* h, double* lambda, double* fast_factor);
+int gaz_engine_drain_samples2(gaz_engine* h, int32_t max_games, int64_t max_rows,
+                              int32_t* games, int8_t* boards, float* policies, float* values, uint8_t* row_ply,
+                              int32_t* n_games, int64_t* n_rows);
+
 int gaz_engine_get_stats(gaz_engine* h, uint64_t out[16]);  /* [0..5] game_stats, [6] evaluator calls, [7] simulations,
                                                                [8] plies played (= positions, incl. games in progress), [9] waves launched,
                                                                [10] evaluations answered by the evaluation cache, [11] groups of the group pipeline (0 = off),
