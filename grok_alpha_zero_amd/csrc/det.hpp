@@ -15,13 +15,15 @@ namespace det {
 
 enum : uint32_t { P_DIRICHLET = 0, P_TERMINAL_PICK = 1, P_MOVE = 2, P_GUMBEL = 3, P_OPENING = 4, P_PLAYOUT_CAP = 5, P_RESIGN = 6,
                   P_EVAL_SYMMETRY = 7 };   // three bits in draw(): 7 is the last free value
+// Trees (two bits in draw()): 0 / 1 the PUCT trees, 2 the game-level stream and the Gumbel tree, 3 the opening book's draw (book.hpp: event 0,
+// purpose P_OPENING, game_seq with its low bit cleared for a match pair) — all four values are taken.
 
 struct Event {
     uint32_t key0, key1;  // 64-bit seed
     uint32_t slot;        // global game slot
     uint32_t game_seq;    // k-th game in that slot
     uint32_t event;       // per-tree event counter
-    uint32_t tree;        // 0/1 PUCT trees, 2 game-level / Gumbel
+    uint32_t tree;        // 0/1 PUCT trees, 2 game-level / Gumbel, 3 opening book
     uint32_t purpose;
 };
 

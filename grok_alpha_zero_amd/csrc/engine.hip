@@ -10,6 +10,7 @@
 #include "puct_core.hpp"
 #include "gumbel_core.hpp"
 #include "samples.hpp"
+#include "book_start.hpp"
 #include "tree_export.hpp"
 #include "evaluator.hpp"
 #include "match.hpp"
@@ -398,6 +399,10 @@ struct gaz_engine {
     virtual int set_hyperparams(const gaz_search_hyperparams*) = 0;
     virtual int set_resignation(const gaz_resign_params*) = 0;
     virtual int get_resign_stats(uint64_t out[8]) = 0;
+    // opening book (book.hpp) behind the argument checks of the C entry point: n_entries = 0 removes the book
+    virtual int set_opening_book(int n_entries, int stride, int mode, const uint8_t* actions, const int32_t* lengths) = 0;
+    virtual int read_book_counts(uint64_t* counts, uint64_t out[8]) = 0;
+    int book_entries = 0, book_mode = 0;             // what gaz_engine_get_opening_book reports: the book in force
     virtual int set_eval_symmetry(int32_t mode) = 0;
     virtual int get_eval_symmetry(int32_t* mode) = 0;
     virtual int read_batch_symmetry(uint8_t* sym) = 0;
@@ -542,6 +547,7 @@ template <class G> struct EngineT : gaz_engine {
         delete eval; delete eval_b;
         if (h_match_cnt) hipHostFree(h_match_cnt);
         for (void* p : allocs) hipFree(p);
+        free_book(book_act, book_len, book_cnt);
         if (dSamples) hipFree(dSamples);
         if (hSamples) hipHostFree(hSamples);
         for (hipEvent_t e : ev) hipEventDestroy(e);
@@ -640,7 +646,7 @@ template <class G> struct EngineT : gaz_engine {
             E.puct_table = tb;
             if (init_puct_table()) return 1;
         }
-        if (dalloc(&E.stats, RESIGN_STATS_OFFSET + (sizeof(ResignBlock) + 7) / 8)) return 1;      // zeroed: resignation off
+        if (dalloc(&E.stats, BOOK_STATS_OFFSET + BOOK_STATS_WORDS)) return 1;      // zeroed: resignation off, no opening book
         if (dalloc(&E.error, 4)) return 1;
         if (dalloc(&dN, (size_t)n * G::A) || dalloc(&dW, (size_t)n * G::A) || dalloc(&dP, (size_t)n * G::A) ||
             dalloc(&dPol, (size_t)n * G::A) || dalloc(&dRV, n) || dalloc(&dQ, n) || dalloc(&dChosen, n) ||
@@ -699,9 +705,14 @@ template <class G> struct EngineT : gaz_engine {
     // every tree launch carries the wave's epoch, and the marks of the previous wave's evaluator pass if that pass made any (a fused launch, or
     // the test hook): DevParams::eval_done
     bool prev_marked = false;                        // the wave before this one wrote eval_done
-    DevParams<G> wave_params() { DevParams<G> P = E; P.wave_epoch = ++fuse_epoch; P.eval_done = prev_marked ? d_evaldone : nullptr; return P; }
+    DevParams<G> wave_params() {
+        DevParams<G> P = E; P.wave_epoch = ++fuse_epoch; P.eval_done = prev_marked ? d_evaldone : nullptr;
+        if (book_entries > 0 && !E.sync_moves) P.games_budget = 1;      // opening book (book.hpp): a finished game parks in PH_HALT until k_book_start starts the next one
+        return P;
+    }
     void launch_wave(hipStream_t st, int g0, int g1) { const DevParams<G> P = wave_params(); prev_marked = false; launch_wave(st, g0, g1, P); }   // (callers follow with a full evaluator pass)
     void launch_wave(hipStream_t st, int g0, int g1, const DevParams<G>& E) {
+        book_start(st, g0, g1, E);
         if (E.solver) { if (E.eval_symmetry) launch_wave_v<true, true>(st, g0, g1, E); else launch_wave_v<false, true>(st, g0, g1, E); return; }
         if (E.eval_symmetry) launch_wave_v<true>(st, g0, g1, E); else launch_wave_v<false>(st, g0, g1, E);
     }
@@ -743,6 +754,75 @@ template <class G> struct EngineT : gaz_engine {
         else GAZ_LAUNCH(k_wave<GS>, g1 - g0, WAVE, st, *reinterpret_cast<const DevParams<GS>*>(&E), g0, g1);
     }
     void launch_wave() { launch_wave(stream, 0, n_eff); }
+
+    // ---- opening book (book.hpp).  While a book is set, k_book_start runs in front of every tree step — separate or fused — and starts the
+    // games that wait (PH_NEW_GAME, or parked in PH_HALT under the budget of 1 that wave_params hands the tree steps); an engine without a
+    // book launches nothing here, and the tree kernels are the same with and without one.  The table, the lengths and the per-entry counters are
+    // one set of device arrays per book; the block behind the game_stats counters points at them.
+    uint8_t* book_act = nullptr; int32_t* book_len = nullptr; unsigned long long* book_cnt = nullptr;
+    static void free_book(uint8_t* a, int32_t* l, unsigned long long* c) { if (a) hipFree(a); if (l) hipFree(l); if (c) hipFree(c); }
+    void book_start(hipStream_t st, int g0, int g1, const DevParams<G>& P, bool release = false) {
+        if ((book_entries <= 0 && !release) || g1 <= g0) return;
+        typedef typename PuctVariant<G>::type GP;
+        constexpr int PER = WAVE / GP::TEAM;
+        DevParams<G> B = P; B.games_budget = E.games_budget;               // the true budget: which parked slots have a next game (book_start.hpp)
+        GAZ_LAUNCH(k_book_start<GP>, (g1 - g0 + PER - 1) / PER, WAVE, st, *reinterpret_cast<const DevParams<GP>*>(&B), g0, g1);
+    }
+    int set_opening_book(int n, int stride, int mode, const uint8_t* actions, const int32_t* lengths) override {
+        typedef typename PuctVariant<G>::type GP;
+        constexpr int PER = WAVE / GP::TEAM;
+        uint8_t* a = nullptr; int32_t* l = nullptr; unsigned long long* c = nullptr;
+        if (n > 0) {
+            int32_t* d_status = nullptr;
+            const size_t bytes = (size_t)n * (size_t)stride;
+            if (hipMalloc((void**)&a, bytes) != hipSuccess || hipMalloc((void**)&l, sizeof(int32_t) * (size_t)n) != hipSuccess ||
+                hipMalloc((void**)&c, sizeof(unsigned long long) * (size_t)n) != hipSuccess || hipMalloc((void**)&d_status, sizeof(int32_t) * (size_t)n) != hipSuccess) {
+                free_book(a, l, c); if (d_status) hipFree(d_status);
+                return fail("set_opening_book: out of device memory");
+            }
+            std::vector<int32_t> status((size_t)n, 0);
+            bool ok = hipMemcpyAsync(a, actions, bytes, hipMemcpyHostToDevice, stream) == hipSuccess &&
+                      hipMemcpyAsync(l, lengths, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, stream) == hipSuccess &&
+                      hipMemsetAsync(c, 0, sizeof(unsigned long long) * (size_t)n, stream) == hipSuccess;
+            if (ok) {
+                GAZ_LAUNCH(k_book_validate<GP>, (n + PER - 1) / PER, WAVE, stream, (const uint8_t*)a, (const int32_t*)l, n, stride, (int)E.max_actions, d_status);
+                ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(status.data(), d_status, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream) == hipSuccess &&
+                     hipStreamSynchronize(stream) == hipSuccess;
+            }
+            hipFree(d_status);
+            if (!ok) { free_book(a, l, c); return fail("set_opening_book: the validation of the table failed on the device"); }
+            for (int i = 0; i < n; ++i) {
+                if (status[i] == BOOK_OK) continue;
+                const int ply = status[i] >> 8, why = status[i] & 0xff;
+                free_book(a, l, c);
+                const std::string e = "set_opening_book: entry " + std::to_string(i) + ": ";
+                if (why == BOOK_BAD_ILLEGAL) return fail(e + "illegal move " + std::to_string((int)actions[(size_t)i * stride + ply]) + " at ply " + std::to_string(ply));
+                if (why == BOOK_BAD_OVER) return fail(e + "the game is over after ply " + std::to_string(ply) + " (a win, or a draw on a full board): a book position must have a move to search");
+                return fail(e + "a length of " + std::to_string(ply) + " plies leaves no move below max_actions = " + std::to_string(E.max_actions));
+            }
+        }
+        if (quiesce()) { free_book(a, l, c); return 1; }          // (no launch in flight reads the block or the old table while they change)
+        BookBlock b{};
+        b.n_entries = n; b.stride = n ? stride : 0; b.mode = n ? mode : 0; b.actions = a; b.lengths = l; b.counts = c;
+        if (hipMemcpy(book_block(E.stats), &b, offsetof(BookBlock, started), hipMemcpyHostToDevice) != hipSuccess) { free_book(a, l, c); return fail("set_opening_book: hipMemcpy failed"); }
+        if (n == 0 && book_entries > 0) {                           // removed: the slots parked for k_book_start go on to PH_NEW_GAME
+            book_start(stream, 0, E.n_games, E, true);
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return fail("set_opening_book: releasing the waiting games failed");
+        }
+        free_book(book_act, book_len, book_cnt);
+        book_act = a; book_len = l; book_cnt = c; book_entries = n; book_mode = n ? mode : 0;
+        return 0;
+    }
+    int read_book_counts(uint64_t* counts, uint64_t out[8]) override {
+        for (int i = 0; i < 8; ++i) out[i] = 0;
+        if (quiesce()) return 1;
+        BookBlock b;
+        HIP_OK(hipMemcpy(&b, book_block(E.stats), sizeof(b), hipMemcpyDeviceToHost));
+        out[0] = b.started; out[1] = b.plies;
+        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are copied as they are");
+        if (book_entries > 0 && counts) HIP_OK(hipMemcpy(counts, book_cnt, sizeof(uint64_t) * (size_t)book_entries, hipMemcpyDeviceToHost));
+        return check_device_error();
+    }
 
     // ---- fused tree + trunk launch (resnet.hip k_wave_trunk): Connect4 PUCT with the whole-trunk ResNet evaluator, no evaluation
     // cache (its probe reads rows other teams are writing).  GAZ_FUSE_WAVE=0 -> separate launches.
@@ -826,6 +906,7 @@ template <class G> struct EngineT : gaz_engine {
         if (gbk > 1) return fail("repack: not with gumbel_batch > 1 (a game owns gumbel_batch rows of the batch)");
         if (lbk > 1) return fail("repack: not with leaf_batch > 1 (a game owns leaf_batch rows of the batch)");
         if (quiesce()) return 1;
+        book_start(stream, 0, n_eff, E);             // opening book: a slot parked for its next game is no hole — start that game first
         GAZ_LAUNCH(k_gather_root<G>, E.n_games, WAVE, stream, E, dN, dW, dP, dPol, dRV, dQ, dChosen, dPhase, dPending);
         std::vector<int32_t> ph(E.n_games);
         HIP_OK(hipMemcpyAsync(ph.data(), dPhase, (size_t)E.n_games * 4, hipMemcpyDeviceToHost, stream));
@@ -871,6 +952,7 @@ template <class G> struct EngineT : gaz_engine {
         if (!plan) return -1;
         if (timing) hipEventRecord(e0, stream);
         DevParams<G> Ef = wave_params(); Ef.done_flag = d_done;
+        book_start(stream, 0, n_eff, Ef);
         if (eval->plan_uses_queue(plan)) {   // the trunk workgroups take queue entries: the tree blocks rank their games as they finish
             typedef typename PuctVariant<G>::type GPq;
             static const bool gumbel_teams = env_on("GAZ_FUSE_GUMBEL_TEAMS", true);
@@ -1914,6 +1996,24 @@ struct GroupEngine : gaz_engine {
     int get_solver(int32_t* mode) override { return lead(&gaz_engine::get_solver, mode); }
     int get_solver_stats(uint64_t out[8]) override { return sum8(&gaz_engine::get_solver_stats, out); }
     int get_resign_stats(uint64_t out[8]) override { return sum8(&gaz_engine::get_resign_stats, out); }
+    // every group keeps a copy of the book (and validates it: the same table, the same verdict); the per-entry counters are summed
+    int set_opening_book(int n, int stride, int mode, const uint8_t* actions, const int32_t* lengths) override {
+        if (all(&gaz_engine::set_opening_book, n, stride, mode, actions, lengths)) return 1;
+        book_entries = n; book_mode = n ? mode : 0;
+        return 0;
+    }
+    int read_book_counts(uint64_t* counts, uint64_t out[8]) override {
+        for (int i = 0; i < 8; ++i) out[i] = 0;
+        for (int i = 0; i < book_entries && counts; ++i) counts[i] = 0;
+        std::vector<uint64_t> part((size_t)(book_entries > 0 ? book_entries : 1));
+        return each([&](gaz_engine* k, int) {
+            uint64_t s[8];
+            if (k->read_book_counts(counts ? part.data() : nullptr, s)) return 1;
+            for (int i = 0; i < 8; ++i) out[i] += s[i];
+            for (int i = 0; i < book_entries && counts; ++i) counts[i] += part[i];
+            return 0;
+        });
+    }
     int read_head_features(int n, float* p, float* v, int32_t* p_row, int32_t* v_row) override {
         if (n < 0 || n > cfg.n_games) return fail("read_head_features: n must be in [0, n_games]");
         int32_t pr = 0, vr = 0;
@@ -2102,6 +2202,32 @@ int gaz_engine_set_resignation(gaz_engine* h, const gaz_resign_params* p) {
     if (p->min_ply < 0) return h->fail("set_resignation: min_ply must be >= 0, not " + std::to_string(p->min_ply));
     if (!(p->no_resign_prob >= 0.0 && p->no_resign_prob <= 1.0)) return h->fail("set_resignation: no_resign_prob must be in [0, 1], not " + std::to_string(p->no_resign_prob));
     return h->set_resignation(p);
+}
+// opening book: every refusal that needs no device state, then the engine validates the entries on the device (book_start.hpp)
+int gaz_engine_set_opening_book(gaz_engine* h, const gaz_book_params* p, const uint8_t* actions, const int32_t* lengths) {
+    if (!p) return h->fail("set_opening_book: null argument");
+    if (p->struct_size != sizeof(gaz_book_params))
+        return h->fail("set_opening_book: struct_size is " + std::to_string(p->struct_size) + ", this library's gaz_book_params has " + std::to_string(sizeof(gaz_book_params)) + " bytes");
+    if (p->mode < 0 || p->mode > 2) return h->fail("set_opening_book: mode must be 0 (no book), 1 (an entry per game) or 2 (an entry per pair of games), not " + std::to_string(p->mode));
+    if (p->n_entries < 0 || p->n_entries > BOOK_MAX_ENTRIES)
+        return h->fail("set_opening_book: n_entries must be in [0, " + std::to_string(BOOK_MAX_ENTRIES) + "], not " + std::to_string(p->n_entries));
+    if (p->mode == 0 || p->n_entries == 0) return h->set_opening_book(0, 0, 0, nullptr, nullptr);
+    const int max_t = h->cfg.game == GAZ_GAME_TICTACTOE ? Game<GAME_TTT>::MAXT : (h->cfg.game == GAZ_GAME_CONNECT4 ? Game<GAME_C4>::MAXT : Game<GAME_GMK>::MAXT);
+    if (p->stride < 1 || p->stride > max_t) return h->fail("set_opening_book: stride must be in [1, " + std::to_string(max_t) + "] (the longest game), not " + std::to_string(p->stride));
+    if (!actions || !lengths) return h->fail("set_opening_book: actions and lengths must not be null with n_entries > 0");
+    for (int32_t i = 0; i < p->n_entries; ++i)
+        if (lengths[i] < 0 || lengths[i] > p->stride)
+            return h->fail("set_opening_book: entry " + std::to_string(i) + ": a length of " + std::to_string(lengths[i]) + " is outside [0, stride = " + std::to_string(p->stride) + "]");
+    return h->set_opening_book(p->n_entries, p->stride, p->mode, actions, lengths);
+}
+int gaz_engine_get_opening_book(gaz_engine* h, int32_t* n_entries, int32_t* mode) {
+    if (!n_entries || !mode) return h->fail("get_opening_book: null argument");
+    *n_entries = h->book_entries; *mode = h->book_mode;
+    return 0;
+}
+int gaz_engine_read_book_counts(gaz_engine* h, uint64_t* counts, uint64_t out[8]) {
+    if (!out || (h->book_entries > 0 && !counts)) return h->fail("read_book_counts: null argument");
+    return h->read_book_counts(counts, out);
 }
 int gaz_engine_get_resign_stats(gaz_engine* h, uint64_t out[8]) { return out ? h->get_resign_stats(out) : h->fail("get_resign_stats: null argument"); }
 // random board symmetry per evaluator request: 0 = off (a new engine), 1 = on

@@ -6,6 +6,8 @@
 //     p >= min_ply  and  p >= 2 (consecutive - 1)  and  for i in 0 .. consecutive-1: kind(p - 2i) != 0  and  q[p - 2i] < -threshold
 // i.e. the mover's last `consecutive` searched plies all saw the game as lost (the float32 q widened to double, strict <).  A ply no search
 // ran at (a set_position prefix, a move the host played: kind 0) breaks the run; fast plies of the playout cap count like full ones.
+// A ply of an opening-book prefix (kind 3, book.hpp MK_BOOK) breaks the run exactly as kind 0 does: its recorded q is the 0 the start wrote
+// there, and 0 < -threshold never holds, so the test below needs no case of its own.
 // Whether a game is a PLAY-OUT game (resignation disabled, to measure false positives, as AlphaGo Zero does for a tenth of its games) is
 // one uniform variate of the game-level stream, keyed by (seed, slot, game_seq) like the opening draw: tree 2, event 0, purpose P_RESIGN,
 // u < no_resign_prob.  Nothing is kept in GameState or TreeState, no tree's event counter moves and no search changes, so the record of a

@@ -15,6 +15,8 @@
 // The workgroup compacts the plies it keeps into a table in LDS (kept row -> ply, a ballot / popcount scan) and every output element is
 // indexed through it: the rows of a game stay one contiguous range, and a kept row is what it is without the cap — its state shows every
 // move played before it, fast ones included.  With the cap off the table is the identity.
+// A ply of an opening-book prefix (move_kind 3, book.hpp MK_BOOK) gives no row either, with or without the surprise weighting, and takes no
+// part in the weighting's means and counts: kinds 2 and 3 are left out alike.  (A gaz_engine_set_position prefix, kind 0, keeps its rows.)
 #pragma once
 #include "tree.hpp"
 
@@ -83,7 +85,7 @@ template <class T, class F> GAZ_DEV void emit_range(T* dst, size_t start, int co
     for (int i = head + n_vec * VEC + t; i < count; i += nT) dst[start + i] = f(i);
 }
 
-// the [T, winner, slot, game_seq] headers of `n` ring slots from `first` on and the rows each game gives (its plies that are not MK_FAST),
+// the [T, winner, slot, game_seq] headers of `n` ring slots from `first` on and the rows each game gives (its plies that are neither MK_FAST nor MK_BOOK),
 // dense, SAMPLE_HDR_INTS per game: what the host needs to choose the games of a drain
 constexpr int SAMPLE_HDR_INTS = 5;
 template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_sample_headers(const uint8_t* ring, int ring_cap, uint32_t first, int n, int32_t* out) {
@@ -102,7 +104,7 @@ template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_sample_headers(const uin
     int fast = 0;
     for (int w = 0; w * 4 < T; ++w) {
         const uint32_t v = mk[w];
-        for (int j = 0; j < 4; ++j) fast += (w * 4 + j < T) && ((v >> (8 * j)) & MK_KIND_MASK) == MK_FAST;   // (the kind: the bits above it mark resignation)
+        for (int j = 0; j < 4; ++j) fast += (w * 4 + j < T) && ((v >> (8 * j)) & MK_KIND_MASK) >= MK_FAST;   // fast and book plies (the kind: the bits above it mark resignation)
     }
     out[SAMPLE_HDR_INTS * i + 4] = T - fast;
 }
@@ -139,7 +141,7 @@ template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_build_samples(const uint
     int K = 0;
     for (int base = 0; base < T; base += nT) {
         const int p = base + t;
-        const bool keep = p < T && (rec[RL::OFF_MK + p] & MK_KIND_MASK) != MK_FAST;
+        const bool keep = p < T && (rec[RL::OFF_MK + p] & MK_KIND_MASK) < MK_FAST;          // neither a fast ply nor a book ply (kind 3)
         const uint64_t m = ballot(keep);
         if (lane == 0) wave_kept[wv] = popcll(m);
         group_sync();
@@ -183,7 +185,8 @@ template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_build_samples(const uint
 // Policy surprise weighting (gaz_engine_set_sample_weighting; DESIGN.md "Policy surprise weighting"; KataGo, Wu 2019, section 3.3): the
 // rows a ply gives become a COUNT c_p, a function of the finished record, (lambda, fast_factor) and the engine's seed alone.
 //   s_p  = max(0, sum_a pi_p[a] (dlog pi_p[a] - dlog P_p[a])) over pi_p[a] > 0 and P_p[a] > 0, a ascending, sequential float64; NaN / inf = 0
-//   w0_p = 1 for a full ply, 0 for a fast one; a ply without a search (set_position prefix) keeps its one row and takes no part
+//   w0_p = 1 for a full ply, 0 for a fast one; a ply without a search (set_position prefix) keeps its one row and takes no part; a book
+//          ply (kind 3) gives no row and takes no part
 //   mean = (sum of s_p over the full plies, in ply order) / n_full;  a fast ply is eligible iff s_p > fast_factor * mean
 //   S    = sum of s_p over E = full + eligible fast plies, in ply order
 //   w_p  = (1 - lambda) w0_p + lambda n_full s_p / S on E, 0 elsewhere; w0_p if n_full == 0 or S is 0 or not finite
@@ -231,7 +234,7 @@ template <class G> GAZ_SAMPLES_BOUNDS GAZ_KERNEL_WIDE k_sample_weights(const uin
     const uint8_t* mk = rec + RL::OFF_MK;
     const float* pol = reinterpret_cast<const float*>(rec + RL::OFF_POL);
     const float* pri = reinterpret_cast<const float*>(rec + RL::OFF_P);
-    for (int p = t; p < T; p += nT) s[p] = (mk[p] & MK_KIND_MASK) == MK_NONE ? 0.0 : ply_surprise<G>(pol + (size_t)p * G::A, pri + (size_t)p * G::A);
+    for (int p = t; p < T; p += nT) s[p] = ((mk[p] & MK_KIND_MASK) == MK_NONE || (mk[p] & MK_KIND_MASK) == MK_KIND_MASK) ? 0.0 : ply_surprise<G>(pol + (size_t)p * G::A, pri + (size_t)p * G::A);
     group_sync();
     if (t == 0) {
         int n_full = 0;

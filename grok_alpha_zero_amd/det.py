@@ -5,6 +5,7 @@ the hot path calls this."""
 import struct
 
 M32 = 0xFFFFFFFF
+P_OPENING = 4                                      # det::P_OPENING (tree 2: the opening_actions draw; tree 3: the opening book's)
 P_PLAYOUT_CAP = 5                                  # det::P_PLAYOUT_CAP
 
 

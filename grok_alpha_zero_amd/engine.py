@@ -63,6 +63,13 @@ class MatchParams(C.Structure):         # gaz_match_params
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("hash_salt_b", C.c_uint32), ("reserved_", C.c_int32)]
 
 
+class BookParams(C.Structure):          # gaz_book_params
+    _fields_ = [("struct_size", C.c_uint32), ("n_entries", C.c_int32), ("stride", C.c_int32), ("mode", C.c_int32)]
+
+
+BOOK_MODES = {None: 0, "game": 1, "pair": 2}    # gaz_book_params.mode: an entry per game, or per pair (slot, 2k), (slot, 2k + 1)
+MK_BOOK = 3                                     # move_kind of a ply of an opening-book prefix
+
 NET_A, NET_B, NET_NONE = 0, 1, 255      # gaz_engine_read_batch_network: the network that answers a row of the evaluator batch
 
 MK_KIND_MASK, MK_RESIGNED, MK_WOULD_RESIGN = 3, 0x10, 0x20      # the bits of a record's raw move_kind byte (gaz_record_layout.off_move_kind)
@@ -124,6 +131,12 @@ def load_library(lib_path=None):
         L.gaz_engine_drain_samples2.argtypes = [H, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         for f in ("set_sample_weighting", "get_sample_weighting", "drain_samples2"):
+            getattr(L, "gaz_engine_" + f).restype = C.c_int
+    if hasattr(L, "gaz_engine_set_opening_book"):       # opening book, detected by its symbols: a library built before it has none
+        L.gaz_engine_set_opening_book.argtypes = [H, C.POINTER(BookParams), C.c_void_p, C.c_void_p]
+        L.gaz_engine_get_opening_book.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.gaz_engine_read_book_counts.argtypes = [H, C.c_void_p, C.POINTER(C.c_uint64)]
+        for f in ("set_opening_book", "get_opening_book", "read_book_counts"):
             getattr(L, "gaz_engine_" + f).restype = C.c_int
     L.gaz_engine_get_stats.argtypes = [H, C.POINTER(C.c_uint64)]
     L.gaz_engine_synchronize.argtypes = [H]
@@ -648,9 +661,48 @@ class SelfPlayEngine:
         return dict(resigned=s[0], resigned_by_minus1=s[1], resigned_by_plus1=s[2], playout_games=s[3], would_resign=s[4], false_positives=s[5],
                     resigned_plies=s[6])
 
+    # ---- opening book --------------------------------------------------------------------------------
+    def set_opening_book(self, entries, mode="game"):
+        """Start games from book positions (gaz_engine_set_opening_book): `entries` is a list of action-index sequences — an empty one means
+        "the empty board" — and every game that starts after the call draws one of them, a function of (seed, slot, game_seq) alone
+        (self_play.book_entry restates it).  mode "game": an entry per game; "pair": the games (slot, 2k) and (slot, 2k + 1) share their
+        entry — with set_match the two colour assignments of one pairing.  mode None, or no entries, removes the book.  The prefix plies of a
+        record have move_kind 3 and give no training rows.  A refused call (EngineError) leaves the book in force as it was."""
+        if mode not in BOOK_MODES:
+            raise ValueError(f"set_opening_book: mode must be 'game', 'pair' or None, not {mode!r}")
+        if not hasattr(self.L, "gaz_engine_set_opening_book"):
+            raise EngineError("this library has no gaz_engine_set_opening_book")
+        entries = [np.asarray(e, np.int64).reshape(-1) for e in (entries if entries is not None else [])]
+        for i, e in enumerate(entries):
+            if e.size and (e.min() < 0 or e.max() > 255):
+                raise ValueError(f"set_opening_book: entry {i} holds an action index outside [0, 255]")
+        n = len(entries) if BOOK_MODES[mode] else 0
+        stride = max([1] + [int(e.size) for e in entries[:n]])
+        acts = np.zeros((max(n, 1), stride), np.uint8); lens = np.zeros(max(n, 1), np.int32)
+        for i, e in enumerate(entries[:n]):
+            acts[i, :e.size] = e; lens[i] = e.size
+        prm = BookParams(struct_size=C.sizeof(BookParams), n_entries=n, stride=stride, mode=BOOK_MODES[mode] if n else 0)
+        self._ck(self.L.gaz_engine_set_opening_book(self.h, C.byref(prm), acts.ctypes.data, lens.ctypes.data))
+
+    def opening_book(self):
+        """(n_entries, mode) of the book in force — mode "game" or "pair" —, (0, None) without one"""
+        if not hasattr(self.L, "gaz_engine_get_opening_book"):
+            return 0, None
+        n, m = C.c_int32(), C.c_int32()
+        self._ck(self.L.gaz_engine_get_opening_book(self.h, C.byref(n), C.byref(m)))
+        return int(n.value), {0: None, 1: "game", 2: "pair"}[int(m.value)]
+
+    def book_counts(self):
+        """gaz_engine_read_book_counts as a dict: `counts` uint64 [n_entries] — the games started from every entry of the book in force since
+        it was set —, and over the engine's life `started` (games started with a book set) and `prefix_plies`.  A synchronisation point."""
+        n = self.opening_book()[0]
+        counts = np.zeros(max(n, 1), np.uint64); out = (C.c_uint64 * 8)()
+        self._ck(self.L.gaz_engine_read_book_counts(self.h, counts.ctypes.data, out))
+        return dict(counts=counts[:n], started=int(out[0]), prefix_plies=int(out[1]))
+
     def drain_finished(self, max_records=None):
         """Finished games as dicts: actions, policies [T,A], q, z, values (=0.5(z+q), Self_Play.py:165-172),
-        root_N/W/P [T,A], root_visits, evals, move_kind (uint8 [T]: 0 no search, 1 full, 2 fast), proven (bool [T]: the ply ended with a root
+        root_N/W/P [T,A], root_visits, evals, move_kind (uint8 [T]: 0 no search, 1 full, 2 fast, 3 opening-book prefix), proven (bool [T]: the ply ended with a root
         the solver had proven, set_solver; its q is exact), winner, slot, game_seq, and of
         resignation (set_resignation) resigned (bool), resign_ply (the last ply of a resigned game, else -1) and would_resign_plies (the
         plies at which a game that was played out would have been resigned).

@@ -83,7 +83,10 @@ def Run(game_class, configs, train_fn=None, weights_fn=None, root="Grok_Zero_Tra
     uses (the last accepted folder's; weights_fn returning None on both sides = the synthetic evaluator under two salts).  The result goes into
     folder g + 1 as Match.json — `result`, `new_folder`, `old_folder`, `accepted`, `accepted_folder` — and into that generation's statistics
     (`match`).  With a `threshold`, a new network whose score is below it is not accepted: the following generations' self-play keeps the
-    last accepted folder's weights.  A resumed Run reads the last accepted folder from the newest Match.json."""
+    last accepted folder's weights.  A resumed Run reads the last accepted folder from the newest Match.json.
+    match["book"] (an opening book: a list of action-index sequences or a file, as train_config["opening_book"]) and match["paired"] go
+    to play_match: with a book the games are played in colour-swapped pairs from shared openings, and `result` in Match.json carries the
+    paired block — `pairs`, `incomplete`, `elo_ci95_paired` — and `book` (the entries' counts)."""
     train_config = configs[1]
     total = int(train_config["total_generations"])
     gen = current_generation(root)

@@ -314,7 +314,7 @@ def sample_row_counts(rec, lam, fast_factor, seed):
     T = len(kind)
     s = [0.0] * T
     for p in range(T):
-        if kind[p] == 0:
+        if kind[p] in (0, 3):                        # no search ran there: a set_position prefix, an opening-book prefix
             continue
         acc = 0.0
         for x, y in zip(rec["policies"][p], rec["root_P"][p]):
@@ -338,6 +338,8 @@ def sample_row_counts(rec, lam, fast_factor, seed):
         if kind[p] == 0:
             counts[p] = 1
             continue
+        if kind[p] == 3:                             # a book ply gives no row and takes no part
+            continue
         w0 = 1.0 if kind[p] == 1 else 0.0
         w = w0 if plain else ((1.0 - lam) * w0 + lam * n_full * s[p] / S if in_E[p] else 0.0)
         fl = math.floor(w)
@@ -349,7 +351,8 @@ def sample_row_counts(rec, lam, fast_factor, seed):
 def record_to_samples(game_class, rec, weighting=None):
     """Rebuild what Self_Play.play() collected for one finished game (Self_Play.py:80,114-127,159-175): input states by
     replaying the moves through the Game plugin, improved policies, values = 0.5 (z + q), then augment_sample.  Plies whose search was
-    a fast one (rec["move_kind"] == 2, playout cap randomisation) give no row; the length returned stays the plies played.  With forced
+    a fast one (rec["move_kind"] == 2, playout cap randomisation) give no row, nor do the plies of an opening-book prefix (move_kind 3,
+    SelfPlayEngine.set_opening_book); the length returned stays the plies played.  With forced
     playouts (forced_playouts_k > 0) rec["policies"] already holds the pruned targets: nothing is recomputed here.
     weighting = (lambda, fast_factor, seed) — seed the engine's — applies policy surprise weighting: ply p gives sample_row_counts()[p]
     adjacent copies of the row it has with the cap off; lambda = 0 or None is the plain rule above."""
@@ -374,8 +377,8 @@ def record_to_samples(game_class, rec, weighting=None):
             aug_b, aug_p = (np.asarray(a) for a in game.augment_sample(board_states[:1], policies[:1]))
             return aug_b[:, :0], aug_p[:, :0], np.zeros((aug_p.shape[0], 0, 1), np.float32), n_plies
         board_states, policies, values = board_states[rows], policies[rows], values[rows]
-    elif kind is not None and np.any(np.asarray(kind) == 2):
-        keep = np.asarray(kind) != 2
+    elif kind is not None and np.any(np.asarray(kind) >= 2):     # fast plies (2) and the plies of an opening-book prefix (3)
+        keep = np.asarray(kind) < 2
         board_states, policies, values = board_states[keep], policies[keep], values[keep]
     aug_b, aug_p = game.augment_sample(board_states, policies)
     aug_b, aug_p = np.asarray(aug_b), np.asarray(aug_p)
@@ -386,11 +389,12 @@ def record_to_samples(game_class, rec, weighting=None):
 def resign_trigger_plies(q, move_kind, threshold, consecutive=1, min_ply=0):
     """The plies of one game at which the resign rule of SelfPlayEngine.set_resignation triggers, from the record's q and move_kind:
     ply p < T - 1 (the game went on after it) with p >= min_ply, p >= 2 (consecutive - 1) and, for i in 0 .. consecutive-1, ply p - 2i
-    searched (move_kind != 0) and q[p - 2i] < -threshold (the float32 widened to double, strict)."""
+    searched (move_kind 1 or 2) and q[p - 2i] < -threshold (the float32 widened to double, strict).  A ply of an opening-book prefix
+    (move_kind 3) breaks a run as move_kind 0 does: no search ran there, and its recorded q is 0."""
     T = len(q)
     out = []
     for p in range(max(int(min_ply), 2 * (int(consecutive) - 1)), T - 1):
-        if all((int(move_kind[p - 2 * i]) & 3) != 0 and float(q[p - 2 * i]) < -float(threshold) for i in range(int(consecutive))):
+        if all((int(move_kind[p - 2 * i]) & 3) in (1, 2) and float(q[p - 2 * i]) < -float(threshold) for i in range(int(consecutive))):
             out.append(p)
     return out
 
@@ -416,6 +420,97 @@ def resign_curve(records, thresholds, consecutive=1, min_ply=0):
             false_pos += int(r["winner"]) != -resigner
         rows.append(dict(threshold=float(thr), games=len(records), would_resign=would, false_positives=false_pos, plies_saved=saved, plies=plies))
     return rows
+
+
+# ------------------------------------------------------------------------------------------------ opening book
+BOOK_TREE = 3                                      # the stream of the book's draw (csrc/det.hpp: trees 0 / 1 / 2 are the searches')
+
+
+def book_entry(seed, slot, game_seq, n_entries, mode="game"):
+    """The entry of an n_entries book that game (slot, game_seq) starts from (SelfPlayEngine.set_opening_book; include/gaz_engine.h states
+    the rule): idx = min(int(u * n_entries), n_entries - 1), u the uniform variate of (seed, slot, key_seq, tree 3, event 0, P_OPENING),
+    key_seq = game_seq in mode "game" and game_seq & ~1 in mode "pair".  slot is the GLOBAL slot, as in the record header."""
+    from . import det
+    if mode not in ("game", "pair"):
+        raise ValueError(f"book_entry: mode must be 'game' or 'pair', not {mode!r}")
+    if n_entries <= 0:
+        raise ValueError("book_entry: the book has no entries")
+    seq = int(game_seq) & 0xFFFFFFFF
+    u = det.uniform(int(seed), int(slot), seq & ~1 if mode == "pair" else seq, BOOK_TREE, 0, det.P_OPENING)
+    return min(int(u * n_entries), n_entries - 1)
+
+
+def book_from_records(records, plies, min_count=1):
+    """The distinct `plies`-long prefixes of finished games (drain_finished's dicts, or action sequences) that occur at least `min_count`
+    times, most frequent first (ties: in action order) -> list of lists of action indices.  Games of `plies` plies or fewer are left out:
+    their prefix is a finished game, which no book may hold."""
+    seen = {}
+    for r in records:
+        a = [int(x) for x in (r["actions"] if isinstance(r, dict) else r)]
+        if len(a) > plies:
+            key = tuple(a[:plies])
+            seen[key] = seen.get(key, 0) + 1
+    return [list(k) for k, c in sorted(seen.items(), key=lambda kc: (-kc[1], kc[0])) if c >= min_count]
+
+
+def enumerate_openings(game_class, plies):
+    """Every legal unfinished position `plies` moves from the empty board, through the Game API (get_legal_actions, do_action, check_win),
+    as action-index sequences in depth-first order of the legal actions.  Different sequences that reach the same position are all listed
+    (a position's history is part of the network's input)."""
+    to_index = game_class.action_to_index if hasattr(game_class, "action_to_index") else int
+    to_action = game_class.index_to_action if hasattr(game_class, "index_to_action") else (lambda i: i)
+    out = []
+
+    def walk(seq):
+        game = game_class()
+        for i in seq:
+            game.do_action(to_action(i))
+        if seq and game.check_win() != -2:
+            return
+        if len(seq) == plies:
+            out.append(list(seq))
+            return
+        for a in game.get_legal_actions():
+            walk(seq + [int(to_index(a))])
+    walk([])
+    return out
+
+
+def save_book(path, entries):
+    """a book as the file run_self_play's train_config["opening_book"] names: .json (a list of lists) or .npy (int16 [n, stride], rows
+    padded with -1)"""
+    entries = [[int(a) for a in e] for e in entries]
+    if str(path).endswith(".json"):
+        import json
+        with open(path, "w") as f:
+            json.dump(entries, f)
+        return
+    if not str(path).endswith(".npy"):
+        raise ValueError("save_book: the path must end in .json or .npy")
+    arr = np.full((len(entries), max([1] + [len(e) for e in entries])), -1, np.int16)
+    for i, e in enumerate(entries):
+        arr[i, :len(e)] = e
+    np.save(path, arr)
+
+
+def load_book(book):
+    """train_config["opening_book"] -> list of lists of action indices: a list as it is, or the .json / .npy file save_book writes"""
+    if isinstance(book, (str, os.PathLike)):
+        if str(book).endswith(".json"):
+            import json
+            with open(book) as f:
+                book = json.load(f)
+        elif str(book).endswith(".npy"):
+            book = [[int(a) for a in row if a >= 0] for row in np.load(book)]
+        else:
+            raise ValueError(f"opening_book: {book} is neither a .json nor a .npy file")
+    return [[int(a) for a in e] for e in book]
+
+
+def _book_mode(mode):
+    if mode in (None, "game", "pair"):
+        return mode
+    raise ValueError(f"opening_book_mode must be 'game' or 'pair', not {mode!r}")
 
 
 class _ReplayWriter:
@@ -554,6 +649,10 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
     Random evaluation symmetry: train_config["eval_symmetry"] (absent or False = off, and then no call is made) —
     SelfPlayEngine.set_eval_symmetry: the network sees every search position under a board symmetry drawn per game and position, and the
     search uses the policy mapped back.  Records and samples stay in the board's own frame; the file format does not change.
+    Opening book: train_config["opening_book"] (absent = none) — a list of action-index sequences, or the path of a .json / .npy file that
+    save_book writes from book_from_records / enumerate_openings — and ["opening_book_mode"] ("game", the default, or "pair") —
+    SelfPlayEngine.set_opening_book: every game starts from the entry that book_entry(seed, slot, game_seq, ...) names; an empty entry is the
+    empty board.  The prefix plies give no rows; game_stats count every ply of a game, the prefix included.
     `configs` = (build_config, train_config[, optimizer_config]).  `weights` = dict from net.export_engine_weights()
     (generation > 0); generation 0 (folder name "0") plays with the synthetic evaluator like the reference's
     session=None dummy (Self_Play.py:40, MCTS.py:237-241).
@@ -613,6 +712,12 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
         eng.set_eval_symmetry(True)
     if train_config.get("solver"):
         eng.set_solver(True)
+    if train_config.get("opening_book") is not None:
+        try:
+            eng.set_opening_book(load_book(train_config["opening_book"]), _book_mode(train_config.get("opening_book_mode") or "game"))
+        except BaseException:
+            eng.close()
+            raise
     weighting = (*eng.sample_weighting, seed) if eng.sample_weighting[0] else None      # (the host path's: record_to_samples)
     written = 0
     launch = G                                          # slots the launches cover (shrinks in the generation's tail, see repack)
@@ -675,21 +780,27 @@ def _elo(score):
     return None if score <= 0.0 or score >= 1.0 else -400.0 * math.log10(1.0 / score - 1.0)
 
 
-def match_result(records):
+def match_result(records, paired=False):
     """The result of a match (SelfPlayEngine.set_match) from its finished games: records (drain_finished's dicts) or headers (T, winner,
     slot, game_seq).  Network A plays the first player (-1) of game (slot, game_seq) iff slot + game_seq is even, so a header says who
     was A.  -> dict: n, a_wins, draws, b_wins; `a_first` / `a_second`, the same counts over the games in which A was the first / the
     second player; score = (a_wins + 0.5 draws) / n; elo = -400 log10(1 / score - 1), None at score 0 or 1; elo_ci95 = that formula on
     score -+ 1.96 sqrt(var / n), var the (population) variance of the per-game scores 1 / 0.5 / 0 and both ends clipped into
-    [1e-9, 1 - 1e-9]."""
+    [1e-9, 1 - 1e-9].
+    paired=True (a match from an opening book in mode "pair": the games (slot, 2k) and (slot, 2k + 1) share their opening and swap colours,
+    so the PAIR is the statistical unit) adds three keys: `pairs`, the counts of the pair scores {0, 0.5, 1, 1.5, 2} (A's points over the
+    two games) over the complete pairs (slot, game_seq >> 1); `incomplete`, the pairs of which only one game is there; and
+    `elo_ci95_paired`, the elo formula on m -+ 1.96 sqrt(var / n_pairs) with m and var the mean and (population) variance of the pair
+    means (pair score / 2) over the complete pairs, clipped as above; None without a complete pair.  The other keys do not change."""
     split = {True: dict(n=0, a_wins=0, draws=0, b_wins=0), False: dict(n=0, a_wins=0, draws=0, b_wins=0)}
-    scores = []
+    scores, by_pair = [], {}
     for r in records:
         _, winner, slot, seq = (int(r[k]) for k in ("T", "winner", "slot", "game_seq")) if isinstance(r, dict) else (int(x) for x in r)
         a_first = (slot + seq) % 2 == 0
         key = "draws" if winner == 0 else ("a_wins" if (winner == -1) == a_first else "b_wins")
         split[a_first]["n"] += 1; split[a_first][key] += 1
         scores.append(0.5 if winner == 0 else (1.0 if key == "a_wins" else 0.0))
+        by_pair.setdefault((slot, (seq & 0xFFFFFFFF) >> 1), {})[seq & 1] = scores[-1]
     n = len(scores)
     if n == 0:
         raise ValueError("match_result: no games")
@@ -699,16 +810,34 @@ def match_result(records):
     half = 1.96 * math.sqrt(var / n)
     clip = lambda x: min(max(x, 1e-9), 1.0 - 1e-9)
     out.update(a_first=split[True], a_second=split[False], score=score, elo=_elo(score), elo_ci95=(_elo(clip(score - half)), _elo(clip(score + half))))
+    if paired:
+        whole = [g[0] + g[1] for g in by_pair.values() if len(g) == 2]
+        out["pairs"] = {s: sum(1 for x in whole if x == s) for s in (0.0, 0.5, 1.0, 1.5, 2.0)}
+        out["incomplete"] = len(by_pair) - len(whole)
+        out["elo_ci95_paired"] = None
+        if whole:
+            means = [x / 2.0 for x in whole]
+            m = sum(means) / len(means)
+            half_p = 1.96 * math.sqrt(sum((x - m) ** 2 for x in means) / len(means) / len(means))
+            out["elo_ci95_paired"] = (_elo(clip(m - half_p)), _elo(clip(m + half_p)))
     return out
 
 
-def play_match(game_class, configs, weights_a, weights_b, games, n_slots=None, seed=0, **engine_kw):
+def play_match(game_class, configs, weights_a, weights_b, games, n_slots=None, seed=0, book=None, paired=None, **engine_kw):
     """`games` games between network A (`weights_a`) and network B (`weights_b`) in one engine -> match_result of them, plus `positions`
     (plies played), `seconds` and `match_stats`.  Weights are dicts from net.export_engine_weights(); None for both plays the synthetic
     hash evaluator under engine_kw's hash_salt (A) and hash_salt_b (B).  `games` must be a positive multiple of 2 * n_slots (default
     n_slots = games / 2): every slot then plays as many games with A first as with B first.  The search settings come from train_config
-    as in run_self_play; the engine has one game group and no evaluation cache (SelfPlayEngine.set_match)."""
+    as in run_self_play; the engine has one game group and no evaluation cache (SelfPlayEngine.set_match).
+    book: an opening book (a list of action-index sequences, or a file as train_config["opening_book"]); paired (default: True with a book)
+    sets its mode to "pair" — the two games (slot, 2k), (slot, 2k + 1), which swap colours, start from the same entry — and the result
+    carries match_result(paired=True)'s keys; paired=False draws an entry per game.  A match at playing strength (tau 0, no root noise)
+    needs a book: without one every slot plays the same two games."""
     build_config = configs[0]
+    if paired is None:
+        paired = book is not None
+    if paired and engine_kw.get("first_game_seq", 0) % 2:
+        raise ValueError("play_match: paired games need an even first_game_seq (a pair is (slot, 2k), (slot, 2k + 1))")
     if n_slots is None:
         n_slots = max(int(games) // 2, 1)
     if games <= 0 or n_slots <= 0 or games % (2 * n_slots):
@@ -731,6 +860,8 @@ def play_match(game_class, configs, weights_a, weights_b, games, n_slots=None, s
         if use_net:
             eng.load_weights(weights_a); eng.load_weights_b(weights_b)
         eng.set_match(True, hash_salt_b=salt_b)
+        if book is not None:
+            eng.set_opening_book(load_book(book), "pair" if paired else "game")
         train_config = configs[1]
         if train_config.get("eval_symmetry"):
             eng.set_eval_symmetry(True)
@@ -746,7 +877,10 @@ def play_match(game_class, configs, weights_a, weights_b, games, n_slots=None, s
             if idle > 100000:
                 raise RuntimeError("the match made no progress")
         seconds = time.perf_counter() - t0
-        out = match_result(records)
+        out = match_result(records, paired=bool(paired))
+        if book is not None:
+            bc = eng.book_counts()
+            out["book"] = dict(entries=len(bc["counts"]), mode="pair" if paired else "game", counts=[int(c) for c in bc["counts"]], prefix_plies=bc["prefix_plies"])
         out.update(positions=sum(int(r["T"]) for r in records), seconds=seconds, match_stats=eng.match_stats())
         out["headers"] = [(int(r["T"]), int(r["winner"]), int(r["slot"]), int(r["game_seq"])) for r in records]
     finally:

@@ -53,6 +53,10 @@
  *   gaz_engine_get_match_timing
  *                              (no reference counterpart: the reference's Run has no evaluation step, every generation's network is played on
  *                              unconditionally, <game>/main.py; a match between the new and the current network is AlphaGo Zero's evaluator)
+ *   gaz_engine_set_opening_book / gaz_engine_get_opening_book / gaz_engine_read_book_counts and the kind 3 of a record's move_kind
+ *                              (no reference counterpart: Self_Play.play() starts every game on the empty board and opening_actions,
+ *                              Self_Play.py:130-140, overrides move 0 only; an opening book played in colour-swapped pairs is the usual
+ *                              remedy of engine testing, starting a share of the self-play games from book positions is KataGo's)
  */
 #ifndef GAZ_ENGINE_H
 #define GAZ_ENGINE_H
@@ -206,8 +210,9 @@ typedef struct {
     int32_t record_bytes, max_T, A, t_pad;
     int32_t off_hdr, off_actions, off_q, off_root_visits, off_evals, off_policy, off_N, off_W, off_P;
     int32_t off_move_kind;        /* u8 [t_pad] per ply: 0 = no search ran there (a gaz_engine_set_position prefix), 1 = full search, 2 = fast search
-                                     (gaz_engine_config.fast_iterations); always 1 for a searched ply with the cap off.  That kind is the byte's
-                                     low two bits (& 3).  With resignation on (gaz_engine_set_resignation) two more bits may be set: 0x10 on the last
+                                     (gaz_engine_config.fast_iterations), 3 = a ply of an opening-book prefix (gaz_engine_set_opening_book: no search
+                                     ran there either, and unlike kind 0 it gives no training row); always 1 for a searched ply with the cap off.
+                                     That kind is the byte's low two bits (& 3).  With resignation on (gaz_engine_set_resignation) two more bits may be set: 0x10 on the last
                                      ply of a game that was resigned after it, 0x20 on every ply of a game played out with resignation
                                      disabled at which it would have been resigned.  With the solver on (gaz_engine_set_solver) 0x40 marks a ply
                                      that ended with a proven root (its q is the exact +1 / 0 / -1); all other bits are 0 */
@@ -380,7 +385,8 @@ int gaz_engine_get_solver_stats(gaz_engine* h, uint64_t out[8]);
  * last-moves input planes and the max_actions cap count the prefix: the game ends by the cap at ply max_actions, so n must be
  * below max_actions (refused otherwise).  No opening override for n > 0.  The drained record of that game spans all plies from
  * the empty board: T counts the prefix, actions[0, n) are the prefix and every per-move field of rows [0, n) (policy, q, root
- * N / W / P, root visits, evaluator calls) is 0 — no search ran there. */
+ * N / W / P, root visits, evaluator calls) is 0 — no search ran there.  Their move_kind is 0, and they keep their training rows — which tells them
+ * from the prefix of an opening book (gaz_engine_set_opening_book, kind 3). */
 int gaz_engine_set_position(gaz_engine* h, int32_t slot, const int32_t* actions, int32_t n);
 /* iteration_limit of the following MCTS.run calls (<= 0: unchanged); tau_mode -1 = Self_Play schedule, 0 / 1 = fixed tau */
 int gaz_engine_set_search_params(gaz_engine* h, int32_t run_iterations, int32_t tau_mode);
@@ -415,6 +421,40 @@ int gaz_engine_set_resignation(gaz_engine* h, const gaz_resign_params* p);
  * would-have-resigned ply, [5] of those false positives (the would-be resigner of the FIRST such ply drew or won), [6] plies of the
  * resigned games (sum of T), [7] 0 */
 int gaz_engine_get_resign_stats(gaz_engine* h, uint64_t out[8]);
+
+/* OPENING BOOK: games that start from book positions, paired for matches (no reference counterpart).  No struct changes and
+ * GAZ_ENGINE_ABI_VERSION stays 10: the feature is detected by its symbols.
+ * The book is a table of n_entries action sequences, actions[i * stride + k] = ply k of entry i as an action index (the encoding of
+ * gaz_engine_set_position / gaz_engine_read_positions), entry i having lengths[i] plies, 0 <= lengths[i] <= stride.  A length of 0 is "start
+ * on the empty board": a book that is half empty entries starts half the games from the book, so there is no probability parameter.  The engine
+ * keeps a copy in device memory (every game group one of its own); mode = 0 or n_entries = 0 removes the book.
+ * RULE, stateless, a function of the game's identity.  Game (slot, game_seq) — slot = the global slot, as in the record header — draws
+ *   u   = the uniform variate of (seed, slot, key_seq, tree 3, event 0, purpose 4)     key_seq = game_seq in mode 1, game_seq & ~1 in mode 2
+ *   idx = min((int)(u * n_entries), n_entries - 1)                                       (float64)
+ * Tree 3 is the book's stream alone: no other variate changes and no tree's event counter moves.  In mode 2 the games (slot, 2k) and
+ * (slot, 2k + 1) — with match play the two colour assignments of one pairing — start from the same entry; everything else about them differs as
+ * before (their streams are keyed by game_seq).  The rule survives gaz_engine_repack, game groups, slot_offset and first_game_seq.
+ * It applies to every game that STARTS after the call — the first game of a slot when set before the first run, the next game of a slot in
+ * continuous mode, a game after gaz_engine_reset_games — in sync and continuous mode, PUCT and Gumbel, on every engine configuration.
+ * gaz_engine_set_position does not start a game and stays as it is.  A game that starts while a book is set is started by a kernel of its own
+ * in front of the next tree step (one wave later than without a book; results do not depend on it).
+ * A game started from entry e of length n is what gaz_engine_set_position(e, n) makes of a slot: the prefix on the board, the next player from
+ * the parity of n, both trees fresh (event counter 0), and the tau schedule, the last-moves planes and the max_actions cap count the prefix.  No
+ * opening override for n > 0; for n = 0 the game is byte for byte the game without a book, opening_actions included.  Its record carries the
+ * prefix in actions[0, n), zeros in every per-move field of rows [0, n), and move_kind[0, n) = 3.  A ply of kind 3 gives NO training row
+ * (gaz_engine_drain_samples / drain_samples2: kinds 2 and 3 are left out alike; a kept row's state still shows every prefix move), takes no part
+ * in the surprise weighting (neither the means nor the rows), and breaks a resignation run as kind 0 does.
+ * Refused, each with its own last_error text, the book in force staying as it was: a struct_size other than sizeof(gaz_book_params); a mode
+ * outside 0 .. 2; n_entries < 0 or above 2^20; stride < 1 or above the game's max_T; null pointers with n_entries > 0; a length outside
+ * [0, stride]; and — found by a kernel that replays every entry with the search's own rules, the first bad entry named with its ply — an illegal
+ * move, an entry after one of whose plies (the last included) the game is won or drawn, a length that is not below max_actions. */
+typedef struct { uint32_t struct_size; int32_t n_entries, stride, mode; } gaz_book_params;   /* mode 0 off, 1 per game, 2 per pair */
+int gaz_engine_set_opening_book(gaz_engine* h, const gaz_book_params* p, const uint8_t* actions /* [n_entries][stride] */, const int32_t* lengths /* [n_entries] */);
+int gaz_engine_get_opening_book(gaz_engine* h, int32_t* n_entries, int32_t* mode);      /* the book in force: 0, 0 = none */
+/* a host synchronisation point.  counts[i] (n_entries of the book in force; may be NULL without one) = the games started from entry i since
+ * that book was set — a device atomic per entry, summed over game groups; a new book starts its counters at 0.  Over the engine's life:
+ * out[0] = games started with a book set, out[1] = prefix plies placed; out[2..7] = 0. */
+int gaz_engine_read_book_counts(gaz_engine* h, uint64_t* counts, uint64_t out[8]);
 /* MCTS.run(time_limit=...) (MCTS.py:528-563): stop != 0 makes every running search finish its move at the next launch, as the
  * reference's `time.time() - start_time < time_limit` test does between iterations; stop = 0 re-arms.  The host owns the clock. */
 int gaz_engine_stop_search(gaz_engine* h, int32_t stop);
@@ -457,7 +497,8 @@ int gaz_engine_drain_finished(gaz_engine* h, void* out, int32_t max_records, int
 /* Finished games as TRAINING SAMPLES, built on the device from the same ring gaz_engine_drain_finished empties: the arrays
  * Self_Play.play() collects and augments for the replay file (Self_Play.py:159-175; augment_sample, Guide.py:255-283 —
  * Connect4.py:442-443 [identity, np.fliplr], Gomoku.py:265-303 / Tictactoe.py:321-358 the 8 symmetries in the reference's order).
- * A ply whose search was a fast one (move_kind 2, gaz_engine_config.fast_iterations) gives no row; with the cap off every ply does.  For the
+ * A ply whose search was a fast one (move_kind 2, gaz_engine_config.fast_iterations) gives no row, nor does a ply of an opening-book prefix
+ * (move_kind 3, gaz_engine_set_opening_book); with the cap off and no book every ply does.  For the
  * R = sum of the KEPT rows of the games taken, row = games in the order handed out, kept plies in order (a kept row is what it would be
  * without the cap: its state shows every move played before it, fast ones included):
  *   boards   int8 [n_aug][R][state_bytes]   get_input_state() before the move ([H][W][C]), augmented
