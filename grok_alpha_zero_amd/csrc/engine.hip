@@ -15,6 +15,7 @@
 #include "evaluator.hpp"
 #include "match.hpp"
 #include "det_probe.hpp"
+#include "replay.hpp"
 
 using namespace gaz;
 

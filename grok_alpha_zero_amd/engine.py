@@ -98,7 +98,10 @@ def load_library(lib_path=None):
     if not os.path.exists(path):
         raise RuntimeError(f"{path} not found: build the HIP engine first (python -c 'import __graft_entry__ as g; g.build()'); "
                            "there is no CPU fallback")
+    import sys
+    torch_first = "torch" in sys.modules             # (replay.ReplayWindow.batch_torch: which HIP runtime this process ends up with)
     L = C.CDLL(path)
+    L._gaz_torch_first = torch_first
     H = C.c_void_p
     L.gaz_engine_abi_version.restype = C.c_int; L.gaz_engine_config_size.restype = C.c_int
     if L.gaz_engine_abi_version() != ABI_VERSION or L.gaz_engine_config_size() != C.sizeof(EngineConfig):

@@ -75,7 +75,7 @@ def compute_speed(game_class, configs, weights, batch=None, iterations=200, devi
 
 
 def Run(game_class, configs, train_fn=None, weights_fn=None, root="Grok_Zero_Train", n_games=1024, seed=None, device=0,
-        lib_path=None, out=print, self_play_kwargs=None, match=None):
+        lib_path=None, out=print, self_play_kwargs=None, match=None, replay=None):
     """The loop of <Game>/main.py:312-352: for every generation self-play (resumable), statistics, `train_fn`, next dataset file.
     Returns the list of per-generation statistics.
     `match` = None: nothing else.  match = dict(games=..., n_slots=None, threshold=None[, hash_salt_b=...]): after `train_fn` of a generation
@@ -86,7 +86,11 @@ def Run(game_class, configs, train_fn=None, weights_fn=None, root="Grok_Zero_Tra
     last accepted folder's weights.  A resumed Run reads the last accepted folder from the newest Match.json.
     match["book"] (an opening book: a list of action-index sequences or a file, as train_config["opening_book"]) and match["paired"] go
     to play_match: with a book the games are played in colour-swapped pairs from shared openings, and `result` in Match.json carries the
-    paired block — `pairs`, `incomplete`, `elo_ci95_paired` — and `book` (the entries' counts)."""
+    paired block — `pairs`, `incomplete`, `elo_ci95_paired` — and `book` (the entries' counts).
+    `replay` = None: nothing else.  replay = dict(capacity_rows=..., generations=N[, test_fraction=..., target_ratio=..., seed=...]): one
+    replay.ReplayWindow lives through the run and holds the rows of the last N generations on the device.  A resumed Run refills it from the
+    replay files of the last N generation folders (ReplayWindow.append_file), every generation's run_self_play feeds it (replay=window), and
+    `train_fn` is called as train_fn(generation, folder, save_folder, replay=window)."""
     train_config = configs[1]
     total = int(train_config["total_generations"])
     gen = current_generation(root)
@@ -106,19 +110,36 @@ def Run(game_class, configs, train_fn=None, weights_fn=None, root="Grok_Zero_Tra
                 with open(mj) as f:
                     accepted = json.load(f)["accepted_folder"]
                 break
+    window, keep = None, 0
+    if replay is not None:
+        from .replay import ReplayWindow
+        name = getattr(game_class, "ENGINE_NAME", game_class.__name__)
+        keep = max(int(replay.get("generations", 1)), 1)
+        window = ReplayWindow(name, replay["capacity_rows"], replay.get("seed", 0 if seed is None else seed), test_fraction=replay.get("test_fraction", 0.1),
+                              target_ratio=replay.get("target_ratio", 0.5), device=device, lib_path=lib_path)
+        for g in range(max(gen - keep + 1, 0), gen + 1):                                # resume: what the files of the last N generations hold
+            if ReplayStore(os.path.join(root, str(g))).exists():
+                window.append_file(os.path.join(root, str(g)), g)
     for generation in range(gen, total):
         folder = os.path.join(root, str(generation))
+        sp_kw = dict(self_play_kwargs or {})
+        if window is not None:
+            window.evict(generation - keep + 1)
+            sp_kw["replay"] = window
         played_folder = folder if accepted is None else accepted
         weights = weights_fn(played_folder) if (weights_fn and generation > 0) else None
         t0 = time.time()
         played = run_self_play(game_class, configs, folder, n_games=n_games, seed=None if seed is None else seed + generation,
-                               weights=weights, device=device, lib_path=lib_path, **(self_play_kwargs or {}))
+                               weights=weights, device=device, lib_path=lib_path, **sp_kw)
         st = print_stats(folder, out)
         st.update(generation=generation, played_now=played, seconds=time.time() - t0)
         stats.append(st)
         if train_fn is not None:
             make_generation_folder(root, generation + 1)
-            train_fn(generation, folder, os.path.join(root, str(generation + 1)))
+            if window is not None:
+                train_fn(generation, folder, os.path.join(root, str(generation + 1)), replay=window)
+            else:
+                train_fn(generation, folder, os.path.join(root, str(generation + 1)))
             if match is not None and generation >= 1:
                 new_folder = os.path.join(root, str(generation + 1))
                 kw = {k: v for k, v in match.items() if k not in ("games", "n_slots", "threshold")}
@@ -137,4 +158,6 @@ def Run(game_class, configs, train_fn=None, weights_fn=None, root="Grok_Zero_Tra
             make_dataset_file(os.path.join(root, str(generation + 1)))
             out(f"Generation: {generation + 1} / {total - 1}")
     out("-----------Training Done!-----------")
+    if window is not None:
+        window.close()
     return stats

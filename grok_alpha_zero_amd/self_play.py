@@ -612,7 +612,7 @@ def engine_search_settings(game_class, configs):
 def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, *, n_games=1024, seed=None, weights=None,
                   device=0, slot_offset=0, hash_salt=0, lib_path=None, progress=None, eval_cache_log2=22, generation=None,
                   first_game_seq=None, allow_synthetic=False, engine_stats=None, game_groups=0, device_samples=None,
-                  max_pending_bytes=1 << 30, leaf_batch=1, gumbel_batch=1):
+                  max_pending_bytes=1 << 30, leaf_batch=1, gumbel_batch=1, replay=None):
     """Generate `games_per_generation - game_stats[2]` self-play games into `folder_path` (Self_Play.py:259-272).
     (`engine_stats`: a dict that receives the engine's counters — evaluator calls, simulations, waves — when the generation is done,
     and the host's timers: `gpu_wait_seconds` / `sample_seconds` / `queue_wait_seconds` of the thread that queues the waves (waiting for
@@ -653,6 +653,9 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
     save_book writes from book_from_records / enumerate_openings — and ["opening_book_mode"] ("game", the default, or "pair") —
     SelfPlayEngine.set_opening_book: every game starts from the entry that book_entry(seed, slot, game_seq, ...) names; an empty entry is the
     empty board.  The prefix plies give no rows; game_stats count every ply of a game, the prefix included.
+    `replay`: a replay.ReplayWindow that receives every drained batch as well (ReplayWindow.append(generation, batch)), in the order the
+    writer gets them — the window then holds what the file holds, un-augmented, on the device.  `device_samples` path only (a ValueError
+    otherwise); the file is byte for byte what it is without the argument.
     `configs` = (build_config, train_config[, optimizer_config]).  `weights` = dict from net.export_engine_weights()
     (generation > 0); generation 0 (folder name "0") plays with the synthetic evaluator like the reference's
     session=None dummy (Self_Play.py:40, MCTS.py:237-241).
@@ -669,6 +672,8 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
     if device_samples and not builtin:
         raise ValueError(f"device_samples=True: {game_class.__name__} is not one of the built-in plugins; its own augment_sample has to run on the host")
     device_samples = builtin if device_samples is None else bool(device_samples)
+    if replay is not None and not device_samples:
+        raise ValueError("replay=: the window is fed from the device-built samples; it needs device_samples=True (a built-in plugin)")
     store = ReplayStore(folder_path)
     if not store.exists():
         raise ValueError("Dataset file hasn't been created. Self play depends on that file!")     # Self_Play.py:264-265
@@ -748,6 +753,8 @@ def run_self_play(game_class, configs, folder_path, per_process_wait_time=1e-3, 
             eng.run_waves(64)                       # queue the next ones right away: the GPU works while the host converts and writes
             if device_samples:                      # every game is one of the admitted games (games_budget)
                 if got:
+                    if replay is not None:
+                        replay.append(generation, batch)
                     writer.put(batch, batch.nbytes)
             else:
                 for rec in recs:

@@ -665,6 +665,81 @@ int gaz_engine_dominant_kernel(gaz_engine* h, char* name, int32_t cap, double* f
  * launch; a per-kernel roofline is measured on an engine with game_groups = 1 (bench.py does) */
 int gaz_engine_timing_get(gaz_engine* h, double* ms_tree, double* ms_eval, double* ms_dominant, int64_t* n_dominant, int64_t* n_waves);
 
+/* ---- REPLAY WINDOW: the training rows of the last generations on the device, served as shuffled, augmented minibatches.
+ * Replaces the reference's Dataloader.py (split(): :68-145, the per-row batch copy: :178-189).  A handle of its own, because a window outlives
+ * the engines of several generations.  No existing entry point or struct changes and GAZ_ENGINE_ABI_VERSION stays 10: the feature is detected by
+ * its symbols (gaz_replay_create).  One host thread per window; every call returns 0 or non-zero with gaz_replay_last_error's text.
+ * STORE.  A circular store of capacity_rows rows: state int8 [state_bytes], policy f32 [A], value f32 — un-augmented, the sizes of
+ * gaz_sample_layout — plus the row's game and its row within the game.  The STORE ORDER numbers the live rows from 0 = the oldest.  The host
+ * keeps the game table: generation, index of the game within its generation in append order, first row, rows.
+ * RULES, stateless functions of the window's contents and its seed.  ph(c0, c1, c2, c3) = Philox4x32-10 (csrc/det.hpp) with the key (low, high 32
+ * bits of seed ^ 0x5245504C41590000); u52(x, y) = the mapping of gaz::det::uniform, ((x >> 6) << 26 | (y >> 6)) / 2^52, of the first two output
+ * words.  A row is (g, i, j) = (generation, game within g in append order, row within the game): no rule depends on where a row sits in the
+ * ring, so a window refilled from the replay files draws what the live one drew.
+ *   1  held-out   the row is held out iff u52(ph(g, i, j, 0x80000000)) < test_fraction; membership never changes
+ *   2  admission  the reference's parity rule (Dataloader.py:90-105), on the host at begin_epoch: generations newest to oldest starting at
+ *      newest_generation, games in append order, counters f = s = 0; a game is "first" iff its row count is odd; ratio = f + s == 0 ? 0.0 :
+ *      f / (f + s); a first game is skipped iff ratio - 0.02 > target_ratio, else f += 1; any other game is skipped iff ratio + 0.02 <
+ *      target_ratio, else s += 1.  target_ratio NaN: every game is admitted.  Known blind spots of the parity: a draw on a board with an odd
+ *      number of cells counts as a first-player win, a resigned game has the parity of the resigner's last ply, and a game thinned by the
+ *      playout cap, the surprise weighting or a book prefix has whatever parity its rows are left with
+ *   3  inclusion  a = newest_generation - g (rows with g > newest_generation are out), p = max(percent - (double)a * decay, 0.0) — linear, as
+ *      Dataloader.py:134-138 is despite the name.  A row is in the PLAN iff its game is admitted, its held-out bit equals split and
+ *      u52(ph(g, i, j, 0x40000000 | epoch)) < p.  The plan lists the included rows in store order; M is their count
+ *   4  order      position q of the epoch is plan entry perm(q): h = the smallest value >= 1 with 4^h >= M, mask = 2^h - 1; x = q, then repeat
+ *      until x < M: (L, R) = (x >> h, x & mask); for r = 0 .. 3: (L, R) = (R, L ^ (ph(R, r, epoch, 0xC0000010 | split)[0] & mask));
+ *      x = (L << h) | R.  An exact permutation of [0, M)
+ *   5  symmetry   position q uses k = augment ? (ph(epoch, q, split, 0xC0000000)[0] * n_aug) >> 32 : 0; the sampled board and policy are plane
+ *      k of gaz_engine_drain_samples for that row, byte for byte; the value is unchanged
+ * Per-row independent draws replace the reference's exact-count np.random.choice; the expectations are the same, and a held-out row never
+ * reaches a training plan. */
+typedef struct gaz_replay gaz_replay;
+typedef struct {
+    uint32_t struct_size;         /* = sizeof(gaz_replay_config); gaz_replay_create rejects any other value */
+    int32_t game;                 /* GAZ_GAME_* */
+    int32_t device;               /* HIP device ordinal */
+    int32_t reserved_;
+    int64_t capacity_rows;        /* 1 .. 2^31 - 1 */
+    uint64_t seed;
+    double test_fraction;         /* in [0, 1) */
+    double target_ratio;          /* NaN = no balancing, else in [0, 1] */
+} gaz_replay_config;
+int gaz_replay_config_size(void);
+/* refused, each with its own text: a stale struct_size, an unknown game, capacity_rows outside its range, test_fraction outside [0, 1) or NaN,
+ * target_ratio outside [0, 1] (NaN allowed), allocation failure */
+int gaz_replay_create(const gaz_replay_config* cfg, gaz_replay** out);
+void gaz_replay_destroy(gaz_replay* h);
+const char* gaz_replay_last_error(gaz_replay* h);   /* h may be NULL: last create() error */
+/* games int32 [n_games][6], boards, policies, values, n_rows: host arrays exactly as gaz_engine_drain_samples2 returns them; only augmentation
+ * plane 0 is read (n_rows rows from the pointers on).  Game i has the rows games[i][4] - games[0][4] .. games[i + 1][4] - games[0][4], n_rows
+ * closing the last one (0 rows is legal).  Generations must arrive in non-decreasing order.  If the rows do not fit, whole oldest generations
+ * are evicted, never the one being appended to; a generation that alone exceeds capacity_rows is an error and leaves the window unchanged.
+ * A host synchronisation point; drops the epoch's plan */
+int gaz_replay_append(gaz_replay* h, int32_t generation, int32_t n_games, const int32_t* games, const int8_t* boards, const float* policies,
+                      const float* values, int64_t n_rows);
+int gaz_replay_evict(gaz_replay* h, int32_t before_generation);      /* every generation below it leaves; drops the plan */
+/* out: [0] live rows, [1] live games, [2] oldest, [3] newest generation (-1: empty), [4] held-out rows among the live ones (counted on the
+ * device), [5] capacity_rows, [6] generations, [7] rows of the current plan (-1: none).  generations (may be NULL) int64 [max_generations][3]:
+ * generation, games, rows, oldest first; *n_generations (may be NULL) = their number */
+int gaz_replay_info(gaz_replay* h, int64_t out[8], int32_t max_generations, int64_t* generations, int32_t* n_generations);
+/* rows first .. first + n - 1 of the store order as stored; meta int32 [n][3] = generation, game within it, row within the game; any output may be NULL */
+int gaz_replay_read_rows(gaz_replay* h, int64_t first, int64_t n, int8_t* boards, float* policies, float* values, int32_t* meta);
+/* builds the plan of (split 0 train / 1 test, epoch < 2^30) on the device: a flag per row with per-block counts, a scan of the counts, a
+ * compaction.  The host's part is the admission pass over the game table.  *n_rows = M.  A host synchronisation point */
+int gaz_replay_begin_epoch(gaz_replay* h, int32_t split, uint32_t epoch, int32_t newest_generation, double percent, double decay, int64_t* n_rows);
+int gaz_replay_read_plan(gaz_replay* h, int64_t first, int64_t n, uint32_t* rows);      /* plan entries (store-order rows), ascending */
+/* positions first .. first + n - 1 of the current plan's order into the window's own output buffers (grown on demand), queued on the window's
+ * stream.  first + n beyond the plan is an error; n = 0 is legal */
+int gaz_replay_sample(gaz_replay* h, int64_t first, int32_t n, int32_t augment);
+/* measurement hook (tools/replay_bench.py): the same batch `repeats` times between two HIP events on the window's stream, after one warm-up */
+int gaz_replay_sample_timed(gaz_replay* h, int64_t first, int32_t n, int32_t augment, int32_t repeats, double* ms_per_batch);
+/* device pointers of those buffers, valid until a later gaz_replay_sample has to grow them: boards int8 [n][H][W][C], policies f32 [n][A],
+ * values f32 [n], source row (store order) u32 [n], symmetry u8 [n]; any pointer may be NULL */
+int gaz_replay_batch_ptrs(gaz_replay* h, void** boards, void** policies, void** values, void** rows, void** sym);
+/* the synchronising host copy of the last sampled batch; any pointer may be NULL */
+int gaz_replay_read_batch(gaz_replay* h, int8_t* boards, float* policies, float* values, uint32_t* rows, uint8_t* sym);
+int gaz_replay_synchronize(gaz_replay* h);
+
 #ifdef __cplusplus
 }
 #endif
