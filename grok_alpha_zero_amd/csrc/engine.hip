@@ -16,6 +16,7 @@
 #include "match.hpp"
 #include "det_probe.hpp"
 #include "replay.hpp"
+#include "score.hpp"
 
 using namespace gaz;
 
@@ -361,7 +362,19 @@ struct gaz_engine {
     std::string err;
     int grouped = 0;                                 // > 1: this engine is one of that many game groups of a GroupEngine (launch-shape defaults differ)
     virtual void note_grouped() {}
-    virtual ~gaz_engine() {}
+    virtual ~gaz_engine() { delete score; }
+    // held-out loss (score.hpp): the scorer's buffers, made on first use; wave_open: between gaz_engine_wave_begin and gaz_engine_wave_end
+    ScoreState* score = nullptr;
+    bool wave_open = false;
+    ScoreState* score_state() {
+        if (!score) { score = new ScoreState(); score->game = cfg.game; score->device = cfg.device; score->A = cfg.game == GAZ_GAME_TICTACTOE ? 9 : (cfg.game == GAZ_GAME_CONNECT4 ? 7 : 225); }
+        return score;
+    }
+    int score_mode() const { return cfg.policy_is_logits == 1 ? (cfg.gumbel_stablemax ? 3 : 1) : (cfg.policy_is_logits == 2 ? 2 : 0); }
+    // gaz_engine_score_replay behind the checks of the totals struct; an engine of several game groups keeps this refusal
+    virtual int score_replay(gaz_replay*, int, int, gaz_score_totals*, double*, double*, double*, uint8_t*, double*) {
+        return fail("score_replay: game groups hold one evaluator batch each: like read_batch it needs game_groups = 1");
+    }
     int fail(const std::string& m) { err = m; return 1; }
     virtual int init() = 0;
     virtual int load_weights(const gaz_tensor* t, int n) = 0;
@@ -1207,6 +1220,38 @@ template <class G> struct EngineT : gaz_engine {
         if (ms) *ms = repeats > 0 ? (double)t / repeats : 0.0;
         HIP_OK(hipGetLastError());
         return 0;
+    }
+
+    // the built-in evaluator (network A) on the window's current plan: per batch a gather on the window's stream, the forward pass and
+    // k_score_rows on the engine's, handed over by events; one host synchronisation at the end (ScoreState::finish)
+    int score_replay(gaz_replay* w, int batch, int augment, gaz_score_totals* t, double* row_ce, double* row_ent, double* row_se, uint8_t* row_flags, double* ms) override {
+        if (wave_open) return fail("score_replay: called between wave_begin and wave_end: the evaluator batch is in the caller's hands, call wave_end first");
+        if (!eval) return fail("score_replay: no built-in evaluator (GAZ_EVAL_EXTERNAL): score its outputs with gaz_engine_score_outputs");
+        if (!eval->ready()) return fail("score_replay: evaluator weights not loaded (gaz_engine_load_weights)");
+        if (!w) return fail("score_replay: null window");
+        if (w->cfg.game != cfg.game) return fail("score_replay: the window holds rows of game " + std::to_string(w->cfg.game) + ", this engine plays game " + std::to_string(cfg.game));
+        if (w->cfg.device != cfg.device) return fail("score_replay: the window is on device " + std::to_string(w->cfg.device) + ", this engine on device " + std::to_string(cfg.device));
+        if (!w->plan_valid) return fail("score_replay: no plan: call gaz_replay_begin_epoch (append and evict drop the plan)");
+        if (batch < 1 || (size_t)batch > rows) return fail("score_replay: batch_rows must be in [1, " + std::to_string(rows) + "] (the rows of the evaluator batch), not " + std::to_string(batch));
+        ScoreState* S = score_state();
+        const long long M = w->plan_M;
+        if (S->init() || S->ensure(batch, 0, M)) return fail(S->err);
+        if (M > 0 && w->grow_outputs(batch + 8)) return fail(w->err);      // (spare rows behind a full batch, as the engine's own input buffer has spare bytes)
+        const int act = ScoreState::act_of(score_mode());
+        HIP_OK(hipEventRecord(S->ev_t0, stream));
+        for (long long first = 0; first < M; first += batch) {
+            const int n = M - first < batch ? (int)(M - first) : batch;
+            if (first > 0) HIP_OK(hipStreamWaitEvent(w->stream, S->ev_scored, 0));      // the gather reuses the buffers the last batch was scored from
+            if (w->sample(first, n, augment)) return fail(w->err);
+            HIP_OK(hipEventRecord(S->ev_gather, w->stream));
+            HIP_OK(hipStreamWaitEvent(stream, S->ev_gather, 0));
+            eval->forward(stream, w->o_boards, S->d_pp, S->d_pv, n, false);
+            S->launch_rows(stream, S->d_pp, S->d_pv, w->o_pol, w->o_val, n, first, act);
+            HIP_OK(hipEventRecord(S->ev_scored, stream));
+        }
+        HIP_OK(hipGetLastError());
+        if (S->finish(stream, M, score_mode(), t, row_ce, row_ent, row_se, row_flags, true, ms)) return fail(S->err);
+        return check_device_error();
     }
 
     int read_head_features(int n, float* p, float* v, int32_t* p_row, int32_t* v_row) override {
@@ -2140,8 +2185,8 @@ int gaz_engine_get_root_stats(gaz_engine* h, uint32_t* N, float* W, float* P, fl
                               int32_t* phase) { return h->get_root_stats(N, W, P, pol, rv, q, chosen, phase); }
 int gaz_engine_apply_moves(gaz_engine* h, const int32_t* moves) { return h->apply_moves(moves); }
 int gaz_engine_run_waves(gaz_engine* h, int32_t n) { return h->run_waves(n); }
-int gaz_engine_wave_begin(gaz_engine* h) { return h->wave_begin(); }
-int gaz_engine_wave_end(gaz_engine* h) { return h->wave_end(); }
+int gaz_engine_wave_begin(gaz_engine* h) { const int rc = h->wave_begin(); if (!rc) h->wave_open = true; return rc; }
+int gaz_engine_wave_end(gaz_engine* h) { h->wave_open = false; return h->wave_end(); }
 int gaz_engine_batch_ptrs(gaz_engine* h, void** a, void** b, void** c) { return h->batch_ptrs(a, b, c); }
 int gaz_engine_read_batch(gaz_engine* h, int8_t* in, int32_t* pending) { return h->read_batch(in, pending); }
 int gaz_engine_batch_rows(gaz_engine* h, int32_t* rows) { return h->batch_rows(rows); }
@@ -2301,5 +2346,34 @@ int gaz_engine_probe_det(gaz_engine* h, int32_t op, int32_t n_items, const uint6
 }
 int gaz_engine_dominant_kernel(gaz_engine* h, char* name, int32_t cap, double* flops) { return h->dominant(name, cap, flops); }
 int gaz_engine_timing_get(gaz_engine* h, double* a, double* b, double* c, int64_t* d, int64_t* e) { return h->timing_get(a, b, c, d, e); }
+
+// ---- held-out loss (score.hpp)
+int gaz_score_totals_size(void) { return (int)sizeof(gaz_score_totals); }
+static int score_totals_fault(gaz_engine* h, const char* fn, const gaz_score_totals* t) {
+    if (!t) return h->fail(std::string(fn) + ": null totals");
+    if (t->struct_size != sizeof(gaz_score_totals))
+        return h->fail("gaz_score_totals.struct_size is " + std::to_string(t->struct_size) + ", this library's gaz_score_totals has " + std::to_string(sizeof(gaz_score_totals)) +
+                       " bytes: rebuild the binding from include/gaz_engine.h");
+    return 0;
+}
+int gaz_engine_score_outputs(gaz_engine* h, const float* pp, const float* pv, const float* tp, const float* tv, int64_t n, int32_t mode, gaz_score_totals* t, double* row_ce,
+                             double* row_ent, double* row_se, uint8_t* row_flags) {
+    if (score_totals_fault(h, "score_outputs", t)) return 1;
+    if (n < 0 || n > 0x7fffffffll) return h->fail("score_outputs: n must be in [0, 2^31 - 1], not " + std::to_string(n));
+    if (n > 0 && (!pp || !pv || !tp || !tv)) return h->fail("score_outputs: null arrays");
+    if (mode < -1 || mode > 3) return h->fail("score_outputs: policy_mode must be -1 (the engine's own) or 0 .. 3, not " + std::to_string(mode));
+    ScoreState* S = h->score_state();
+    if (S->outputs(pp, pv, tp, tv, n, mode < 0 ? h->score_mode() : mode, t, row_ce, row_ent, row_se, row_flags)) return h->fail(S->err);
+    return 0;
+}
+int gaz_engine_score_replay(gaz_engine* h, gaz_replay* w, int32_t batch_rows, int32_t augment, gaz_score_totals* t, double* row_ce, double* row_ent, double* row_se,
+                            uint8_t* row_flags, double* ms_total) {
+    if (score_totals_fault(h, "score_replay", t)) return 1;
+    return h->score_replay(w, batch_rows, augment != 0, t, row_ce, row_ent, row_se, row_flags, ms_total);
+}
+int gaz_engine_score_rows_timed(gaz_engine* h, int32_t repeats, double* ms_per_launch) {
+    ScoreState* S = h->score_state();
+    return S->rows_timed(repeats, ms_per_launch) ? h->fail(S->err) : 0;
+}
 
 }  // extern "C"

@@ -88,6 +88,29 @@ TREE_EDGE_DTYPE = np.dtype([("action", np.int32), ("N", np.uint32), ("W", np.flo
 CHILD_NONE, CHILD_DRAW, CHILD_WIN, CHILD_FILTERED = -1, -2, -3, -4
 NF_TERMINAL_PARENT = 1
 
+class ScoreTotals(C.Structure):         # gaz_score_totals — tests/test_score_emu.py checks names, order and sizeof against the header
+    _fields_ = [("struct_size", C.c_uint32), ("policy_mode", C.c_int32), ("rows", C.c_int64), ("bad_rows", C.c_int64), ("top1", C.c_int64),
+                ("value_rows", C.c_int64), ("value_sign", C.c_int64), ("ce_sum", C.c_double), ("entropy_sum", C.c_double), ("se_sum", C.c_double)]
+
+
+def score_dict(t):
+    """gaz_score_totals -> the raw sums and counts and the means derived from them with plain `/` (include/gaz_engine.h "HELD-OUT LOSS"); a
+    mean over no rows is NaN.  val_loss is what Train.py monitors: policy cross entropy + value loss for a probability head (modes 0, 2),
+    policy KL divergence + value loss for a logits head (modes 1, 3; Train.py:33-48)."""
+    nan = float("nan")
+    good = int(t.rows) - int(t.bad_rows)
+    d = dict(policy_mode=int(t.policy_mode), rows=int(t.rows), bad_rows=int(t.bad_rows), good=good, top1_rows=int(t.top1), value_rows=int(t.value_rows),
+             value_sign_rows=int(t.value_sign), ce_sum=float(t.ce_sum), entropy_sum=float(t.entropy_sum), se_sum=float(t.se_sum))
+    d["policy_loss"] = d["ce_sum"] / good if good else nan
+    d["policy_entropy"] = d["entropy_sum"] / good if good else nan
+    d["policy_kl"] = (d["ce_sum"] - d["entropy_sum"]) / good if good else nan
+    d["value_loss"] = d["se_sum"] / good if good else nan
+    d["top1"] = d["top1_rows"] / good if good else nan
+    d["value_sign"] = d["value_sign_rows"] / d["value_rows"] if d["value_rows"] else nan
+    d["val_loss"] = (d["policy_kl"] if d["policy_mode"] in (1, 3) else d["policy_loss"]) + d["value_loss"]
+    return d
+
+
 _LIBS = {}
 
 
@@ -167,6 +190,15 @@ def load_library(lib_path=None):
     if hasattr(L, "gaz_engine_probe_det"):              # detected by its symbol: a library built before it has none
         L.gaz_engine_probe_det.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
         L.gaz_engine_probe_det.restype = C.c_int
+    if hasattr(L, "gaz_engine_score_outputs"):          # held-out loss, detected by its symbols: a library built before it has none
+        L.gaz_score_totals_size.argtypes = []; L.gaz_score_totals_size.restype = C.c_int
+        L.gaz_engine_score_outputs.argtypes = [H] + [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.POINTER(ScoreTotals)] + [C.c_void_p] * 4
+        L.gaz_engine_score_replay.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ScoreTotals)] + [C.c_void_p] * 4 + [C.POINTER(C.c_double)]
+        L.gaz_engine_score_rows_timed.argtypes = [H, C.c_int32, C.POINTER(C.c_double)]
+        for f in ("score_outputs", "score_replay", "score_rows_timed"):
+            getattr(L, "gaz_engine_" + f).restype = C.c_int
+        if L.gaz_score_totals_size() != C.sizeof(ScoreTotals):
+            raise RuntimeError(f"{path}: gaz_score_totals has {L.gaz_score_totals_size()} bytes in the library, {C.sizeof(ScoreTotals)} in this binding: rebuild the library")
     L.gaz_engine_set_fused_wave.argtypes = [H, C.c_int32]
     L.gaz_engine_debug_fused_fault.argtypes = [H, C.c_int32]
     L.gaz_engine_read_positions.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32]
@@ -392,6 +424,44 @@ class SelfPlayEngine:
         pol = np.zeros((n, self.A), np.float32); val = np.zeros(n, np.float32); ms = C.c_double()
         self._ck(self.L.gaz_engine_evaluate(self.h, x.ctypes.data, n, pol.ctypes.data, val.ctypes.data, repeats, C.byref(ms)))
         return pol, val, ms.value
+
+    # ---- held-out loss (include/gaz_engine.h "HELD-OUT LOSS") ---------------------------------
+    def _score_call(self, fn, n, per_row):
+        if not hasattr(self.L, "gaz_engine_score_outputs"):
+            raise EngineError("this library has no gaz_engine_score_outputs: rebuild it")
+        t = ScoreTotals(struct_size=C.sizeof(ScoreTotals))
+        rows = (np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.uint8)) if per_row else None
+        self._ck(fn(t, *([a.ctypes.data for a in rows] if per_row else [None] * 4)))
+        d = score_dict(t)
+        if per_row:
+            d.update(row_ce=rows[0], row_entropy=rows[1], row_se=rows[2], row_flags=rows[3])
+        return d
+
+    def score_outputs(self, policy_pred, value_pred, policy_target, value_target, policy_mode=None, per_row=False):
+        """Scores given predictions (f32 [n, A], [n]) against targets on the device -> dict of the raw sums (ce_sum, entropy_sum, se_sum), the
+        counts (rows, bad_rows, good, top1_rows, value_rows, value_sign_rows) and the means (policy_loss, policy_entropy, policy_kl, value_loss,
+        top1, value_sign, val_loss); per_row: also row_ce, row_entropy, row_se (f64 [n]) and row_flags (u8 [n]: 1 top1, 2 value sign, 4 z != 0,
+        8 bad).  policy_mode None = the engine's own head; 0 probabilities, 1 logits + softmax, 2 Stablemax probabilities, 3 logits + Stablemax.
+        Needs no evaluator and touches no game."""
+        pp, tp = np.ascontiguousarray(policy_pred, np.float32), np.ascontiguousarray(policy_target, np.float32)
+        pv, tv = np.ascontiguousarray(value_pred, np.float32).reshape(-1), np.ascontiguousarray(value_target, np.float32).reshape(-1)
+        n = pv.shape[0]
+        if pp.size != n * self.A or tp.size != n * self.A or tv.shape[0] != n:
+            raise ValueError(f"score_outputs: {n} values with policies {pp.shape}, targets {tp.shape} and {tv.shape}")
+        mode = -1 if policy_mode is None else int(policy_mode)
+        return self._score_call(lambda t, *r: self.L.gaz_engine_score_outputs(self.h, pp.ctypes.data, pv.ctypes.data, tp.ctypes.data, tv.ctypes.data, n, mode, C.byref(t), *r), n, per_row)
+
+    def score_replay(self, window, batch_rows=None, augment=False, per_row=False):
+        """Scores this engine's built-in evaluator on the current plan of a replay.ReplayWindow (begin_epoch), positions 0 .. M - 1 of its order,
+        batch_rows at a time (default: the whole evaluator batch) -> the dict of score_outputs plus ms (device time of the pass).  The games
+        of the engine are not touched; the window's batch buffers are overwritten."""
+        if window._plan is None:
+            raise EngineError("score_replay: no plan: call begin_epoch")
+        ms = C.c_double()
+        b = self.batch_rows if batch_rows is None else int(batch_rows)
+        d = self._score_call(lambda t, *r: self.L.gaz_engine_score_replay(self.h, window.h, b, 1 if augment else 0, C.byref(t), *r, C.byref(ms)), window._plan[2], per_row)
+        d["ms"] = ms.value
+        return d
 
     def head_features(self, n):
         """Flat head features of the last evaluate() call (numerics tests): (p_feat [n, F], v_feat [n, F]) float32."""

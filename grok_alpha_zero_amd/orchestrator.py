@@ -90,7 +90,11 @@ def Run(game_class, configs, train_fn=None, weights_fn=None, root="Grok_Zero_Tra
     `replay` = None: nothing else.  replay = dict(capacity_rows=..., generations=N[, test_fraction=..., target_ratio=..., seed=...]): one
     replay.ReplayWindow lives through the run and holds the rows of the last N generations on the device.  A resumed Run refills it from the
     replay files of the last N generation folders (ReplayWindow.append_file), every generation's run_self_play feeds it (replay=window), and
-    `train_fn` is called as train_fn(generation, folder, save_folder, replay=window)."""
+    `train_fn` is called as train_fn(generation, folder, save_folder, replay=window).
+    replay["score"] = dict(batch_rows=...) (absent: nothing else): after `train_fn` of generation g the new network, weights_fn(folder g + 1), and the
+    network self-play is using are both scored on the window's test split (replay.score_network: the held-out loss of the engine's own
+    evaluator).  Both dicts go into folder g + 1 as Score.json — `new`, `current`, `new_folder`, `current_folder` — and into that generation's
+    statistics (`score`).  Nothing is decided from them: acceptance stays with `match`."""
     train_config = configs[1]
     total = int(train_config["total_generations"])
     gen = current_generation(root)
@@ -140,6 +144,16 @@ def Run(game_class, configs, train_fn=None, weights_fn=None, root="Grok_Zero_Tra
                 train_fn(generation, folder, os.path.join(root, str(generation + 1)), replay=window)
             else:
                 train_fn(generation, folder, os.path.join(root, str(generation + 1)))
+            if window is not None and replay.get("score") is not None:
+                from .replay import score_network
+                new_folder = os.path.join(root, str(generation + 1))
+                skw = dict(batch_rows=int(replay["score"].get("batch_rows", 1024)), device=device, lib_path=lib_path, hash_salt=(self_play_kwargs or {}).get("hash_salt", 0))
+                new = score_network(window, game_class, configs, weights_fn(new_folder) if weights_fn else None, **skw)
+                cur = score_network(window, game_class, configs, weights, **skw)
+                with open(os.path.join(new_folder, "Score.json"), "w") as f:
+                    json.dump(dict(new=new, current=cur, new_folder=new_folder, current_folder=played_folder, split="test"), f, indent=1)
+                st["score"] = dict(new=new, current=cur)
+                out(f"Score: generation {generation + 1} val_loss {new['val_loss']:.4f} (current {cur['val_loss']:.4f}) on {new['rows']} held-out rows")
             if match is not None and generation >= 1:
                 new_folder = os.path.join(root, str(generation + 1))
                 kw = {k: v for k, v in match.items() if k not in ("games", "n_slots", "threshold")}

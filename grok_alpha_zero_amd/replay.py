@@ -250,3 +250,28 @@ class ReplayWindow:
         """yields the current epoch, batch by batch"""
         for first, n in self.batch_sizes(batch_size):
             yield (self.batch_torch if torch else self.batch)(first, n, augment)
+
+
+def score_network(window, game_class, configs, weights, split="test", epoch=0, batch_rows=1024, device=0, lib_path=None, hash_salt=0):
+    """The held-out loss of a network on the window's rows (SelfPlayEngine.score_replay; include/gaz_engine.h "HELD-OUT LOSS"): what the
+    reference reads off its test dataloader as val_loss (Train.py:46-64), for the network as self-play runs it — the engine's evaluator with
+    these weights, under the head mode of engine_search_settings.  A small scoring engine is made as orchestrator.compute_speed makes its
+    own (n_games = batch_rows, no record ring, one game group) and closed again; weights = None scores the synthetic hash evaluator under
+    `hash_salt`.  The window gets the plan begin_epoch(split, epoch, percent=1.0, decay=0.0): every row of the split.  -> the dict of score_replay."""
+    from .engine import EVAL_HASH, EVAL_RESNET, SelfPlayEngine
+    from .self_play import engine_search_settings
+    build_config = configs[0]
+    args, kw = engine_search_settings(game_class, configs)
+    head = {k: kw[k] for k in ("search", "gumbel_m", "c_visit", "c_scale", "policy_is_logits", "gumbel_stablemax")}
+    name = getattr(game_class, "ENGINE_NAME", game_class.__name__)
+    use_net = weights is not None
+    eng = SelfPlayEngine(name, int(batch_rows), *args, 0, evaluator=EVAL_RESNET if use_net else EVAL_HASH, hash_salt=hash_salt,
+                         net_blocks=build_config.get("num_resnet_layers", 0) if use_net else 0, net_filters=build_config.get("num_filters", 128),
+                         ring_capacity=0, game_groups=1, device=device, lib_path=lib_path, **head)
+    try:
+        if use_net:
+            eng.load_weights(weights)
+        window.begin_epoch(split, epoch, percent=1.0, decay=0.0)
+        return eng.score_replay(window, batch_rows=int(batch_rows))
+    finally:
+        eng.close()

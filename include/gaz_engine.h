@@ -740,6 +740,61 @@ int gaz_replay_batch_ptrs(gaz_replay* h, void** boards, void** policies, void** 
 int gaz_replay_read_batch(gaz_replay* h, int8_t* boards, float* policies, float* values, uint32_t* rows, uint8_t* sym);
 int gaz_replay_synchronize(gaz_replay* h);
 
+/* ---- HELD-OUT LOSS: what a network's predictions score on training rows, computed on the device (csrc/score.hpp).
+ * Replaces the reference's validation pass — Train.py:46-57, model.fit(validation_data=...) with the losses of Net/Alpha_Loss.py or
+ * Net/Gumbel_Loss.py and KL divergence as the metric — for the network self-play really runs: the engine's own evaluator with its imported
+ * weights.  No existing entry point or struct changes and GAZ_ENGINE_ABI_VERSION stays 10: the feature is detected by its symbols
+ * (gaz_engine_score_outputs).
+ * THE RULE.  Everything is float64, out of operations the project pins bit for bit: no tolerance anywhere.  A row has a prediction P[A] (f32)
+ * and v (f32), a target y[A] (f32) and z (f32), and is scored under a policy_mode: 0 = P are probabilities, 1 = P are logits of a softmax head,
+ * 2 = P are Stablemax probabilities, 3 = P are logits of a Stablemax head; -1 = the engine's own (policy_is_logits 0 -> 0, 2 -> 2, 1 -> 1 or,
+ * with gumbel_stablemax, 3).
+ *   q          modes 0 and 2: q_a = (double)P_a as given, NOT renormalised.  Mode 1: x = (double)P, q = softmax(x) exactly as gumbel_core.hpp
+ *              softmax_inplace: e_a = dexp(x_a + (-max x)), q_a = e_a / np.sum(e).  Mode 3: s_a = x_a >= 0 ? x_a + 1 : 1 / (1 - x_a),
+ *              q_a = s_a / np.sum(s)
+ *   ce         -np.sum_a(t_a), t_a = y_a > 0 ? (double)y_a * dlog(max(q_a, 1e-7)) : +0.0 — all A entries in action order, numpy's pairwise
+ *              order (det::np_pairwise_sum<double>), dlog = det::dlog; 1e-7 is Keras' epsilon.  Each product is stored before it is summed
+ *   entropy    -np.sum_a(y_a > 0 ? (double)y_a * dlog((double)y_a) : +0.0)
+ *   se         d * d, d = (double)v - (double)z
+ *   flags      bit 0 top1: argmax of the raw P == argmax of y, the lowest index among equals (the activations are monotone: the raw outputs
+ *              decide); bit 1: z != 0 and v z > 0 (the exact product); bit 2: z != 0; bit 3 bad: some P_a or v is not finite
+ *   bad rows   ce = entropy = se = 0 and only bit 3: they count in bad_rows and in nothing else.  Targets are taken to be finite
+ * TOTALS over the M rows 0 .. M - 1 (epoch positions of a window, caller order of arrays): for block b, S_b = np.sum(x[128 b : 128 b + 128])
+ * (det::np_sum_block) of ce, entropy and se; the total is the left-to-right float64 sum of S_0, S_1, .. on the host; the counts are integers.
+ * The blocks follow the row index, never the evaluator batch, and the evaluator's rows are independent: the totals are the same bits for every
+ * batch_rows.  The caller derives policy_loss = ce_sum / good, policy_kl = (ce_sum - entropy_sum) / good, value_loss = se_sum / good with
+ * good = rows - bad_rows, top1 / good, value_sign / value_rows, and val_loss = policy_loss + value_loss (modes 0, 2) or policy_kl + value_loss
+ * (modes 1, 3), as Train.py:33-48 pairs the losses.
+ * DIFFERENCES FROM KERAS: float64 where Keras computes in float32; the prediction is not renormalised (Keras' categorical cross entropy divides
+ * by its sum); y is not clipped (KLDivergence clips y to [1e-7, 1]). */
+typedef struct {
+    uint32_t struct_size;         /* = sizeof(gaz_score_totals), set by the caller; any other value is refused */
+    int32_t policy_mode;          /* out: the mode the rows were scored under (0 .. 3) */
+    int64_t rows, bad_rows, top1, value_rows, value_sign;
+    double ce_sum, entropy_sum, se_sum;
+} gaz_score_totals;
+int gaz_score_totals_size(void);
+/* replaces Net/Alpha_Loss.py / Net/Gumbel_Loss.py applied to given outputs: scores caller-supplied predictions (host arrays policy_pred f32
+ * [n][A], value_pred f32 [n]) against targets (policy_target f32 [n][A], value_target f32 [n]).  Needs no evaluator, works on every engine
+ * (game groups included) and touches no game.  policy_mode -1 .. 3 as above.  The per-row outputs (f64 [n] each, flags u8 [n]) may be NULL.
+ * n = 0 gives zero totals.  A host synchronisation point on a stream of its own */
+int gaz_engine_score_outputs(gaz_engine* h, const float* policy_pred, const float* value_pred, const float* policy_target, const float* value_target,
+                             int64_t n, int32_t policy_mode, gaz_score_totals* totals, double* row_ce, double* row_entropy, double* row_se,
+                             uint8_t* row_flags);
+/* replaces the validation pass of Train.py:46-57: scores the engine's built-in evaluator (network A, also in match mode; the evaluation cache
+ * is not consulted) on the window's CURRENT plan, positions 0 .. M - 1 of its order, batch_rows at a time, under the engine's own policy_mode.
+ * Per batch: gaz_replay_sample on the window's stream, an event the engine's stream waits on, the forward pass straight from the window's
+ * board buffer into buffers of the scorer's own (the games' pending outputs are not touched), k_score_rows against the window's policy and
+ * value buffers, an event the window's stream waits on before its next gather.  Then k_score_blocks, ONE read-back and the host's sum: one
+ * host synchronisation at the end, none per batch.  *ms_total (may be NULL): HIP-event time on the engine's stream from the first batch to the
+ * block sums.  Refused, each by its text, leaving the engine and the window as they were: a wrong struct_size, game_groups > 1, a call
+ * between gaz_engine_wave_begin and gaz_engine_wave_end, no built-in evaluator, weights not loaded, a window of another game or device, no
+ * plan, batch_rows outside [1, gaz_engine_batch_rows].  M = 0 gives zero totals */
+int gaz_engine_score_replay(gaz_engine* h, gaz_replay* window, int32_t batch_rows, int32_t augment, gaz_score_totals* totals, double* row_ce,
+                            double* row_entropy, double* row_se, uint8_t* row_flags, double* ms_total);
+/* measurement hook (tools/score_bench.py): the k_score_rows launch of the last gaz_engine_score_outputs call, `repeats` times between two HIP events */
+int gaz_engine_score_rows_timed(gaz_engine* h, int32_t repeats, double* ms_per_launch);
+
 #ifdef __cplusplus
 }
 #endif
