@@ -53,11 +53,11 @@ GAZ_DEV uint64_t k52(uint32_t a, uint32_t b) { return ((uint64_t)(a >> 6) << 26)
 GAZ_DEV double u_open(uint32_t a, uint32_t b) { return (double)(2 * k52(a, b) + 1) * (1.0 / 9007199254740992.0); }
 GAZ_DEV double u_half(uint32_t a, uint32_t b) { return (double)k52(a, b) * (1.0 / 4503599627370496.0); }
 
-GAZ_DEV double bits2d(uint64_t u) { double d; memcpy(&d, &u, 8); return d; }
-GAZ_DEV uint64_t d2bits(double d) { uint64_t u; memcpy(&u, &d, 8); return u; }
+GAZ_HD double bits2d(uint64_t u) { double d; memcpy(&d, &u, 8); return d; }
+GAZ_HD uint64_t d2bits(double d) { uint64_t u; memcpy(&u, &d, 8); return u; }
 
-// natural log, x > 0 finite
-GAZ_DEV double dlog(double x) {
+// natural log, x > 0 finite.  (dlog, dexp and dpow are host functions too: optim.hpp computes its bias corrections on the host)
+GAZ_HD double dlog(double x) {
     const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
     const double Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01, Lg3 = 2.857142874366239149e-01,
                  Lg4 = 2.222219843214978396e-01, Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
@@ -82,7 +82,7 @@ GAZ_DEV double dlog(double x) {
     return dk * ln2_hi - ((hfsq - (s * (hfsq + R) + dk * ln2_lo)) - f);
 }
 
-GAZ_DEV double dexp(double x) {
+GAZ_HD double dexp(double x) {
     const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10,
                  invln2 = 1.44269504088896338700e+00;
     const double P1 = 1.66666666666666019037e-01, P2 = -2.77777777770155933842e-03, P3 = 6.61375632143793436117e-05,
@@ -105,7 +105,7 @@ GAZ_DEV double dexp(double x) {
 
 // x ** y for x >= 0 (np.float64 power, MCTS.py:607-608): exp(y * log x); x == 0 -> 0 for y > 0.  Not libm's pow bit for bit
 // (relative error ~ |y ln x| * 2^-52); used only for move-sampling weights, where that moves a cdf step by < 1e-13.
-GAZ_DEV double dpow(double x, double y) {
+GAZ_HD double dpow(double x, double y) {
     if (x == 0.0) return y > 0.0 ? 0.0 : 1.0;
     if (x == 1.0 || y == 0.0) return 1.0;
     return dexp(y * dlog(x));

@@ -17,6 +17,7 @@
 #include "det_probe.hpp"
 #include "replay.hpp"
 #include "score.hpp"
+#include "optim.hpp"
 
 using namespace gaz;
 

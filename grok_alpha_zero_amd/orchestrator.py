@@ -4,8 +4,9 @@
 
 keeps the reference's on-disk contract (`Grok_Zero_Train/<generation>/Self_Play_Data.h5`, resume from the highest generation
 folder and from `game_stats[2]` inside it, `Print_Stats`, `compute_speed`) and replaces `run_self_play`'s worker processes +
-inference server by one engine per GPU.  Training, ONNX export and TensorRT caching are NOT part of this path (SURVEY §2.1:
-out of scope): the caller supplies
+inference server by one engine per GPU.  ONNX export and TensorRT caching are NOT part of this path (out of scope).  Training: either
+Run(..., replay=dict(...), train=dict()) — the loop trains by itself with train.train_generation and plays with what it trained — or the caller
+supplies
 
     train_fn(generation, folder_path, save_folder_path)   # Train_NN of <Game>/main.py:99-136; must leave the next
                                                           # generation's weights where weights_fn finds them
@@ -75,7 +76,7 @@ def compute_speed(game_class, configs, weights, batch=None, iterations=200, devi
 
 
 def Run(game_class, configs, train_fn=None, weights_fn=None, root="Grok_Zero_Train", n_games=1024, seed=None, device=0,
-        lib_path=None, out=print, self_play_kwargs=None, match=None, replay=None):
+        lib_path=None, out=print, self_play_kwargs=None, match=None, replay=None, train=None):
     """The loop of <Game>/main.py:312-352: for every generation self-play (resumable), statistics, `train_fn`, next dataset file.
     Returns the list of per-generation statistics.
     `match` = None: nothing else.  match = dict(games=..., n_slots=None, threshold=None[, hash_salt_b=...]): after `train_fn` of a generation
@@ -94,7 +95,26 @@ def Run(game_class, configs, train_fn=None, weights_fn=None, root="Grok_Zero_Tra
     replay["score"] = dict(batch_rows=...) (absent: nothing else): after `train_fn` of generation g the new network, weights_fn(folder g + 1), and the
     network self-play is using are both scored on the window's test split (replay.score_network: the held-out loss of the engine's own
     evaluator).  Both dicts go into folder g + 1 as Score.json — `new`, `current`, `new_folder`, `current_folder` — and into that generation's
-    statistics (`score`).  Nothing is decided from them: acceptance stays with `match`."""
+    statistics (`score`).  Nothing is decided from them: acceptance stays with `match`.
+    `train` = None: nothing else.  train = dict() (its keys are keywords of train.train_generation, e.g. seed=...): the loop trains by itself —
+    where it would call `train_fn` it calls train.train_generation(window, game_class, configs, generation, folder, save_folder), which continues
+    from folder/train_state.pt and leaves train_state.pt, weights.npz and Train.json in the next generation's folder (its dict goes into the
+    generation's statistics as `train`), and `weights_fn` defaults to train.weights_from_folder.  It needs `replay` and excludes `train_fn`.  A
+    resumed Run continues from the last train_state.pt."""
+    if train is not None:
+        if train_fn is not None:
+            raise ValueError("Run: train= and train_fn= exclude each other: train= makes the loop call train.train_generation itself")
+        if replay is None:
+            raise ValueError("Run: train= needs replay=dict(capacity_rows=..., generations=...): train_generation reads its rows from the replay window")
+        if not isinstance(train, dict):
+            raise ValueError(f"Run: train must be a dict of train_generation's keywords (an empty one will do), not {type(train).__name__}")
+        from . import train as T                                                        # (imports torch before the first library handle of the run)
+        T.optimizer_settings(configs)                                                   # refusals (muon, mixed_precision) before anything is played
+        if weights_fn is None:
+            weights_fn = T.weights_from_folder
+
+        def train_fn(generation, folder, save_folder, replay=None):
+            stats[-1]["train"] = T.train_generation(replay, game_class, configs, generation, folder, save_folder, device=device, lib_path=lib_path, out=out, **train)
     train_config = configs[1]
     total = int(train_config["total_generations"])
     gen = current_generation(root)

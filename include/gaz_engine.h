@@ -795,6 +795,69 @@ int gaz_engine_score_replay(gaz_engine* h, gaz_replay* window, int32_t batch_row
 /* measurement hook (tools/score_bench.py): the k_score_rows launch of the last gaz_engine_score_outputs call, `repeats` times between two HIP events */
 int gaz_engine_score_rows_timed(gaz_engine* h, int32_t repeats, double* ms_per_launch);
 
+/* ---- OPTIMIZER: the reference's chain Orthograd(Grokfast_EMA(Adam | Nadam)) (Train.py:25-31, Net/Optimizers/{ortho_grad,grok_fast,adam,nadam}.py)
+ * as ONE multi-tensor step over flat arenas (csrc/optim.hpp).  A handle of its own, independent of any engine.  No existing
+ * entry point or struct changes and GAZ_ENGINE_ABI_VERSION stays 10: the feature is detected by its symbols (gaz_optim_create).  One host thread
+ * per object; every call returns 0 or non-zero with gaz_optim_last_error's text.  The kernels run on the device's default stream, in order with
+ * whatever else the process queues there (PyTorch's default stream is that stream).
+ * ARENAS.  Five flat f32 arenas of one layout: 0 params, 1 grads, 2 momentum, 3 velocity, 4 ema (only with grokfast).  Tensor k starts at
+ * offsets[k] elements, offsets[0] = 0, offsets[k + 1] = offsets[k] + sizes[k] rounded up to a multiple of 4 (16 bytes); total = the end of
+ * the last tensor, rounded likewise.  The pad elements are zero and stay zero.  Everything starts at zero.
+ * ONE STEP, per tensor with params w, grads g and state m, v, e.  Every elementwise operation is f32 and rounded on its own (no fused
+ * multiply-add), division and square root are the correctly rounded ones, denormals are kept.  The scalars are rounded to f32 once: lr, wd,
+ * b1, b2, eps, alpha, lamb, 1 - b1, 1 - b2, 1 - alpha (each difference an f32 subtraction from 1.0f), c1 = (float)(1.0 - dpow(beta_1, t)), c2 =
+ * (float)(1.0 - dpow(beta_2, t)) with dpow = det::dpow on doubles.
+ *   1  decay      wd != 0:  w = w - (w * wd) * lr                                  (Keras' decoupled decay, before the update)
+ *   2  orthograd  proj = f32(w.g) / (f32(w.w) + 1e-30f);  go = g - proj * w;  s = sqrt(f32(g.g)) / (sqrt(f32(go.go)) + 1e-30f);  g1 = go * s
+ *   3  grokfast   e = e * alpha + g1 * (1 - alpha);  g2 = g1 + e * lamb
+ *   4  adam       m = b1 * m + (1 - b1) * g2;  v = b2 * v + (1 - b2) * (g2 * g2);  u = (m / c1) / (sqrt(v / c2) + eps);  w = w - u * lr
+ *      nadam      the same with the numerator (m / c1) * b1 + ((1 - b1) * g2) / c1
+ *   5  zero_grads g = 0
+ * (a stage that is off passes its input on: g1 = g, g2 = g1.)  THE DOT PRODUCTS w.g, w.w, g.g, go.go are float64 sums of the exact products of
+ * f32 values, in a fixed order that depends on nothing but the tensor's size: the tensor is cut into CHUNKS of 2048 elements; in a chunk of
+ * len elements with G = len / 4 whole groups of four, slot s (0 .. 255) adds, starting from +0.0, the elements of group s and then of group
+ * s + 256 (those below G) in ascending order, and slot 0 then adds the len % 4 elements behind the last whole group; the 256 slot sums are
+ * combined by six butterfly rounds x[s] = x[s] + x[s ^ d], d = 32, 16, 8, 4, 2, 1, and the chunk's sum is ((x[0] + x[64]) + x[128]) + x[192];
+ * the tensor's sum is the chunks' sums added in ascending order starting from +0.0, rounded to f32 once by f32().
+ * REFERENCE QUIRK, not reproduced: a wrapped Keras optimizer's update_step is called directly, so its iterations never advance (the bias
+ * correction stays at t = 1) and its weight decay is never applied.  Here t is the caller's step number and the decay is applied. */
+typedef struct gaz_optim gaz_optim;
+typedef struct {
+    uint32_t struct_size;         /* = sizeof(gaz_optim_config); gaz_optim_create rejects any other value */
+    int32_t device;               /* HIP device ordinal */
+    int32_t n_tensors;            /* >= 1 */
+    int32_t kind;                 /* 0 Adam, 1 Nadam */
+    const int64_t* sizes;         /* [n_tensors], each >= 1; read by create only */
+    double beta_1, beta_2;        /* in [0, 1) */
+    double epsilon, weight_decay; /* finite, >= 0 */
+    int32_t orthograd, grokfast;  /* 0 / 1 */
+    double alpha, lamb;           /* Grokfast's EMA factor and gain; finite */
+} gaz_optim_config;
+int gaz_optim_config_size(void);
+/* refused, each with its own text: a stale struct_size, n_tensors < 1, a size < 1 (or a total of 2^40 elements and more), an unknown kind, a
+ * beta outside [0, 1), epsilon / weight_decay / alpha / lamb not finite or a negative epsilon / weight_decay, allocation failure */
+int gaz_optim_create(const gaz_optim_config* cfg, gaz_optim** out);
+void gaz_optim_destroy(gaz_optim* h);
+const char* gaz_optim_last_error(gaz_optim* h);     /* h may be NULL: last create() error */
+/* offsets (may be NULL) int64 [n_tensors]; info: [0] total elements of an arena, [1] chunks, [2] elements per chunk, [3] kernel launches per step,
+ * [4] 1 when the arenas are host memory (the one-lane test build), else 0 */
+int gaz_optim_layout(gaz_optim* h, int64_t* offsets, int64_t info[5]);
+/* the five device pointers (ema NULL without grokfast), valid for the object's life; any argument may be NULL */
+int gaz_optim_ptrs(gaz_optim* h, void** params, void** grads, void** momentum, void** velocity, void** ema);
+/* elements first .. first + n - 1 of arena 0 .. 4 (pads included) to / from n host floats.  A range past the arena, or arena 4 without grokfast,
+ * is refused.  write leaves the pad elements inside the range zero whatever the caller passes.  Host synchronisation points */
+int gaz_optim_read(gaz_optim* h, int32_t arena, int64_t first, int64_t n, float* out);
+int gaz_optim_write(gaz_optim* h, int32_t arena, int64_t first, int64_t n, const float* in);
+/* one step at learning rate lr (finite) and step number t >= 1: queued, not waited for.  Without orthograd one launch (k_optim_apply); with
+ * it three: k_optim_dots, k_optim_gogo (which first finishes the three sums of its tensor), k_optim_apply (which finishes go.go) */
+int gaz_optim_step(gaz_optim* h, double lr, int64_t t, int32_t zero_grads);
+/* measurement hook (tools/optim_bench.py): `repeats` steps at t, t + 1, .. between two HIP events, after one warm-up step; the state moves */
+int gaz_optim_step_timed(gaz_optim* h, double lr, int64_t t, int32_t zero_grads, int32_t repeats, double* ms_per_step);
+/* f64 [n_tensors][4]: the sums w.g, w.w, g.g, go.go of the last step before their rounding to f32 (zeros before the first step and without
+ * orthograd).  A host synchronisation point */
+int gaz_optim_read_norms(gaz_optim* h, double* out);
+int gaz_optim_synchronize(gaz_optim* h);
+
 #ifdef __cplusplus
 }
 #endif
