@@ -188,9 +188,8 @@ GAZ_OPT_BOUNDS GAZ_KERNEL_WIDE k_optim_gogo(OptArgs a) {
     }
 }
 
-// one element through the stages 1 .. 5
-GAZ_DEV void opt_update(const OptArgs& a, float proj, float s, float& w, float& g, float& m, float& v, float& e) {
-    const float w1 = opt_decayed(w, a.wd, a.lr);
+// stages 2 and 3 of one element: Orthograd's rescale and Grokfast -> g2
+GAZ_DEV float opt_g2(const OptArgs& a, float proj, float s, float w1, float g, float& e) {
     float g1 = g;
     if (a.ortho) {
         const float p = proj * w1;
@@ -205,6 +204,11 @@ GAZ_DEV void opt_update(const OptArgs& a, float proj, float s, float& w, float& 
         const float el = e * a.lamb;
         g2 = g1 + el;
     }
+    return g2;
+}
+
+// stage 4 of one element up to the update u, which the caller scales by its learning rate
+GAZ_DEV float opt_adam(const OptArgs& a, float g2, float& m, float& v) {
     const float m1 = a.b1 * m;
     const float m2 = a.omb1 * g2;
     m = m1 + m2;
@@ -221,7 +225,14 @@ GAZ_DEV void opt_update(const OptArgs& a, float proj, float s, float& w, float& 
         num = n1 + n2;
     }
     const float den = __builtin_sqrtf(vh) + a.eps;
-    const float u = num / den;
+    return num / den;
+}
+
+// one element through the stages 1 .. 5
+GAZ_DEV void opt_update(const OptArgs& a, float proj, float s, float& w, float& g, float& m, float& v, float& e) {
+    const float w1 = opt_decayed(w, a.wd, a.lr);
+    const float g2 = opt_g2(a, proj, s, w1, g, e);
+    const float u = opt_adam(a, g2, m, v);
     const float ul = u * a.lr;
     w = w1 - ul;
     if (a.zero) g = 0.f;
@@ -271,6 +282,8 @@ GAZ_OPT_BOUNDS GAZ_KERNEL_WIDE k_optim_apply(OptArgs a) {
 
 }  // namespace gaz
 
+#include "muon.hpp"
+
 // ------------------------------------------------------------------------------------------------------------------------ the host side
 struct gaz_optim {
     gaz_optim_config cfg;
@@ -283,6 +296,15 @@ struct gaz_optim {
     hipStream_t stream{};                                                     // the default stream: in order with the caller's own work there
     hipEvent_t ev0{}, ev1{}; bool have_events = false;
     gaz::OptArgs base;
+    // Muon mode (gaz_muon_set): the per-tensor table, the work tables, two X buffers of the arenas' layout, A and B of every Muon tensor
+    bool muon = false, stepped = false;
+    int ns_steps = 0, n_pp = 0, n_pq = 0, n_thin = 0, n_muon = 0;
+    double adam_lr_ratio = 1.0;
+    std::vector<gaz::MuonTensor> mtens;
+    long long ab_total = 0;
+    gaz::MuonTensor* d_mt = nullptr; gaz::MuonTile* d_pp = nullptr; gaz::MuonTile* d_pq = nullptr; gaz::MuonTile* d_thin = nullptr;
+    float* d_x[2] = {nullptr, nullptr}; float* d_A = nullptr; float* d_B = nullptr; float* d_nrm = nullptr; double* d_gpart = nullptr; double* d_npart = nullptr;
+    gaz::MuonArgs mbase;
 
     int fail(const std::string& m) { err = m; return 1; }
 #define GAZ_OP_CK(expr) \
@@ -291,11 +313,15 @@ struct gaz_optim {
     ~gaz_optim() {
         hipStreamSynchronize(stream);
         for (float* p : d_arena) if (p) hipFree(p);
-        void* all[] = {d_tens, d_chunks, d_part, d_norms};
+        void* all[] = {d_tens, d_chunks, d_part, d_norms, d_mt, d_pp, d_pq, d_thin, d_x[0], d_x[1], d_A, d_B, d_nrm, d_gpart, d_npart};
         for (void* p : all) if (p) hipFree(p);
         if (have_events) { hipEventDestroy(ev0); hipEventDestroy(ev1); }
     }
-    int launches() const { return cfg.orthograd ? 3 : 1; }
+    int launches() const {
+        const int base_launches = cfg.orthograd ? 3 : 1;
+        if (!muon || n_muon == 0) return base_launches;
+        return base_launches + 2 + ns_steps * ((n_pp + n_thin > 0) + (n_pp > 0) + 1);     // norm and finish; gram, poly (general tensors only), update
+    }
 
     int init(std::string* why) {
         const int T = cfg.n_tensors;
@@ -360,9 +386,119 @@ struct gaz_optim {
         return 0;
     }
 
+    int set_muon(const gaz_muon_config* c) {
+        if (!c) return fail("muon_set: null argument");
+        if (c->struct_size != sizeof(gaz_muon_config))
+            return fail("gaz_muon_config.struct_size is " + std::to_string(c->struct_size) + ", this library's gaz_muon_config has " + std::to_string(sizeof(gaz_muon_config)) +
+                        " bytes: rebuild the binding from include/gaz_engine.h");
+        if (muon) return fail("muon_set: this optimizer is in Muon mode already");
+        if (stepped) return fail("muon_set: call it before the first step");
+        const int T = cfg.n_tensors;
+        if (c->n_tensors != T) return fail("muon_set: n_tensors is " + std::to_string(c->n_tensors) + ", the optimizer has " + std::to_string(T) + " tensors");
+        if (!c->rows || !c->cols || !c->scale) return fail("muon_set: null rows, cols or scale");
+        if (c->ns_steps < 0 || c->ns_steps > 16) return fail("muon_set: ns_steps must be in 0 .. 16, not " + std::to_string(c->ns_steps));
+        if (!(c->muon_a - c->muon_a == 0.0 && c->muon_b - c->muon_b == 0.0 && c->muon_c - c->muon_c == 0.0)) return fail("muon_set: muon_a, muon_b and muon_c must be finite");
+        if (!(c->muon_beta >= 0.0 && c->muon_beta < 1.0)) return fail("muon_set: muon_beta must be in [0, 1), not " + std::to_string(c->muon_beta));
+        if (!(c->adam_lr_ratio >= 0.0 && c->adam_lr_ratio - c->adam_lr_ratio == 0.0)) return fail("muon_set: adam_lr_ratio must be finite and not negative");
+        if (c->nesterov != 0 && c->nesterov != 1) return fail("muon_set: nesterov must be 0 or 1");
+        std::vector<gaz::MuonTensor> mt((size_t)T);
+        std::vector<gaz::MuonTile> pp, pq, thin;
+        long long ab = 0;
+        int nm = 0;
+        for (int k = 0; k < T; ++k) {
+            gaz::MuonTensor& m = mt[(size_t)k];
+            memset(&m, 0, sizeof(m));
+            const long long r = c->rows[k], q = c->cols[k];
+            if (r == 0 && q == 0) continue;                                       // an Adam tensor
+            if (r < 1 || q < 1 || r * q != sizes[(size_t)k])
+                return fail("muon_set: tensor " + std::to_string(k) + ": rows * cols = " + std::to_string(r) + " * " + std::to_string(q) + " is not its size " + std::to_string(sizes[(size_t)k]));
+            if (!(c->scale[k] - c->scale[k] == 0.f)) return fail("muon_set: tensor " + std::to_string(k) + ": scale must be finite");
+            const bool tr = r > q;                                                // iterate on the transpose: element (p, q) of X at p * sp + q * sq
+            m.off = offs[(size_t)k]; m.aoff = ab; m.P = (int)(tr ? q : r); m.Q = (int)(tr ? r : q); m.sp = tr ? 1 : (int)q; m.sq = tr ? (int)q : 1; m.scale = c->scale[k];
+            m.thin = m.P <= gaz::MU_THIN;
+            ab += ((long long)m.P * m.P + 3) / 4 * 4;
+            ++nm;
+            if (m.thin) {
+                m.first_thin = (int)thin.size(); m.n_thin = (m.Q + gaz::OPT_CHUNK - 1) / gaz::OPT_CHUNK;
+                for (int ch = 0; ch < m.n_thin; ++ch) thin.push_back(gaz::MuonTile{k, ch, 0});
+            } else {
+                const int tp = (m.P + gaz::MU_TILE - 1) / gaz::MU_TILE, tq = (m.Q + gaz::MU_TILE - 1) / gaz::MU_TILE;
+                for (int i = 0; i < tp; ++i) for (int j = 0; j < tp; ++j) pp.push_back(gaz::MuonTile{k, i, j});
+                for (int i = 0; i < tp; ++i) for (int j = 0; j < tq; ++j) pq.push_back(gaz::MuonTile{k, i, j});
+            }
+        }
+        auto table = [](auto** dst, const auto& v) {
+            const size_t bytes = (v.size() ? v.size() : 1) * sizeof(v[0]);
+            return hipMalloc((void**)dst, bytes) == hipSuccess && (v.empty() || hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice) == hipSuccess);
+        };
+        auto zeros = [](auto** dst, size_t bytes) { return hipMalloc((void**)dst, bytes ? bytes : 1) == hipSuccess && hipMemset(*dst, 0, bytes ? bytes : 1) == hipSuccess; };
+        bool ok = hipStreamSynchronize(stream) == hipSuccess && table(&d_mt, mt) && table(&d_pp, pp) && table(&d_pq, pq) && table(&d_thin, thin)
+               && zeros(&d_x[0], (size_t)total * 4) && zeros(&d_x[1], (size_t)total * 4) && zeros(&d_A, (size_t)ab * 4) && zeros(&d_B, (size_t)ab * 4)
+               && zeros(&d_nrm, (size_t)T * 4) && zeros(&d_gpart, thin.size() * gaz::MU_PAIRS * 8) && zeros(&d_npart, (size_t)n_chunks * 32)
+               && hipDeviceSynchronize() == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            void** all[] = {(void**)&d_mt, (void**)&d_pp, (void**)&d_pq, (void**)&d_thin, (void**)&d_x[0], (void**)&d_x[1], (void**)&d_A, (void**)&d_B, (void**)&d_nrm, (void**)&d_gpart, (void**)&d_npart};
+            for (void** p : all) { if (*p) hipFree(*p); *p = nullptr; }
+            return fail("muon_set: allocation failure: two X buffers of " + std::to_string(total) + " floats and A, B of " + std::to_string(ab) + " do not fit");
+        }
+        mtens = mt; ab_total = ab; n_pp = (int)pp.size(); n_pq = (int)pq.size(); n_thin = (int)thin.size(); n_muon = nm;
+        ns_steps = c->ns_steps; adam_lr_ratio = c->adam_lr_ratio;
+        gaz::MuonArgs& m = mbase;
+        memset(&m, 0, sizeof(m));
+        m.mt = d_mt; m.pp = d_pp; m.pq = d_pq; m.thin = d_thin; m.n_pp = n_pp; m.n_pq = n_pq; m.n_thin = n_thin; m.nesterov = c->nesterov;
+        m.A = d_A; m.B = d_B; m.nrm = d_nrm; m.gpart = d_gpart; m.npart = d_npart;
+        m.beta = (float)c->muon_beta; m.omb = 1.0f - m.beta;
+        m.ca = gaz::bf16r((float)c->muon_a); m.cb = gaz::bf16r((float)c->muon_b); m.cc = gaz::bf16r((float)c->muon_c);
+        m.wd = base.wd;
+        base.wd = 0.f;                                                            // Orthograd sees the undecayed w; the decay follows the update
+        muon = true;
+        return 0;
+    }
+
+    int step_muon(gaz::OptArgs a) {
+        gaz::MuonArgs m = mbase;
+        m.lr_adam = (float)adam_lr_ratio * a.lr;
+        m.xs = d_x[1]; m.xd = d_x[0];
+        GAZ_LAUNCH(gaz::k_optim_apply_muon, n_chunks, gaz::OPT_THREADS, stream, a, m);
+        if (n_muon == 0) return 0;
+        GAZ_LAUNCH(gaz::k_muon_norm, n_chunks, gaz::OPT_THREADS, stream, a, m);
+        int cur = 0;
+        for (int it = 0; it < ns_steps; ++it) {
+            m.xs = d_x[cur]; m.xd = d_x[cur ^ 1];
+            GAZ_LAUNCH(gaz::k_muon_gram, n_pp + n_thin, gaz::OPT_THREADS, stream, m);
+            if (n_pp) GAZ_LAUNCH(gaz::k_muon_poly, n_pp, gaz::OPT_THREADS, stream, m);
+            GAZ_LAUNCH(gaz::k_muon_update, n_pq + n_thin, gaz::OPT_THREADS, stream, m);
+            cur ^= 1;
+        }
+        m.xs = d_x[cur]; m.xd = d_x[cur ^ 1];
+        GAZ_LAUNCH(gaz::k_muon_finish, n_chunks, gaz::OPT_THREADS, stream, a, m);
+        return 0;
+    }
+
+    // what: 0 X0 [size], 1 n [1], 2 the final X [size], 3 / 4 A / B of the last iteration [P * P], P = min(rows, cols)
+    int read_muon(int32_t tensor, int32_t what, float* out) {
+        if (!muon) return fail("muon_read: this optimizer is not in Muon mode");
+        if (tensor < 0 || tensor >= cfg.n_tensors) return fail("muon_read: tensor " + std::to_string(tensor) + " of " + std::to_string(cfg.n_tensors));
+        const gaz::MuonTensor& t = mtens[(size_t)tensor];
+        if (t.P == 0) return fail("muon_read: tensor " + std::to_string(tensor) + " is an Adam tensor");
+        if (what < 0 || what > 4) return fail("muon_read: what must be 0 (X0), 1 (n), 2 (X), 3 (A) or 4 (B), not " + std::to_string(what));
+        if (!out) return fail("muon_read: null argument");
+        GAZ_OP_CK(hipStreamSynchronize(stream));
+        const size_t n = (size_t)sizes[(size_t)tensor], pp = (size_t)t.P * t.P;
+        if (what == 0) {
+            GAZ_OP_CK(hipMemcpy(out, d_arena[3] + t.off, n * 4, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n; ++i) out[i] = gaz::bf16r(out[i]);
+        } else if (what == 1) GAZ_OP_CK(hipMemcpy(out, d_nrm + tensor, 4, hipMemcpyDeviceToHost));
+        else if (what == 2) GAZ_OP_CK(hipMemcpy(out, d_x[ns_steps & 1] + t.off, n * 4, hipMemcpyDeviceToHost));
+        else GAZ_OP_CK(hipMemcpy(out, (what == 3 ? d_A : d_B) + t.aoff, pp * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+
     int step(double lr, int64_t t, int32_t zero_grads) {
         if (t < 1) return fail("optim_step: t must be at least 1, not " + std::to_string(t));
         if (!(lr - lr == 0.0)) return fail("optim_step: lr must be finite");
+        stepped = true;
         gaz::OptArgs a = base;
         a.lr = (float)lr; a.zero = zero_grads != 0;
         a.c1 = (float)(1.0 - gaz::det::dpow(cfg.beta_1, (double)t)); a.c2 = (float)(1.0 - gaz::det::dpow(cfg.beta_2, (double)t));
@@ -370,7 +506,8 @@ struct gaz_optim {
             GAZ_LAUNCH(gaz::k_optim_dots, n_chunks, gaz::OPT_THREADS, stream, a);
             GAZ_LAUNCH(gaz::k_optim_gogo, n_chunks, gaz::OPT_THREADS, stream, a);
         }
-        GAZ_LAUNCH(gaz::k_optim_apply, n_chunks, gaz::OPT_THREADS, stream, a);
+        if (muon) step_muon(a);
+        else GAZ_LAUNCH(gaz::k_optim_apply, n_chunks, gaz::OPT_THREADS, stream, a);
         GAZ_OP_CK(hipGetLastError());
         return 0;
     }
@@ -450,6 +587,9 @@ int gaz_optim_write(gaz_optim* h, int32_t arena, int64_t first, int64_t n, const
 int gaz_optim_step(gaz_optim* h, double lr, int64_t t, int32_t zero_grads) { return h->step(lr, t, zero_grads); }
 int gaz_optim_step_timed(gaz_optim* h, double lr, int64_t t, int32_t zero_grads, int32_t repeats, double* ms_per_step) { return h->step_timed(lr, t, zero_grads, repeats, ms_per_step); }
 int gaz_optim_read_norms(gaz_optim* h, double* out) { return h->read_norms(out); }
+int gaz_muon_config_size(void) { return (int)sizeof(gaz_muon_config); }
+int gaz_muon_set(gaz_optim* h, const gaz_muon_config* cfg) { return h->set_muon(cfg); }
+int gaz_muon_read(gaz_optim* h, int32_t tensor, int32_t what, float* out) { return h->read_muon(tensor, what, out); }
 int gaz_optim_synchronize(gaz_optim* h) {
     const hipError_t e = hipStreamSynchronize(h->stream);
     return e == hipSuccess ? 0 : h->fail(std::string("optim_synchronize: ") + hipGetErrorString(e));

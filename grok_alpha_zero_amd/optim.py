@@ -7,6 +7,13 @@ kernel launch (three with Orthograd) whatever the number of tensors.
     opt.attach(net)                                # .data and .grad of every parameter become views of the arenas
     loss(net(x), y).backward()
     opt.step(lr)                                   # t counts from 1; the grads arena is zero afterwards
+
+Muon (the reference's Net/Optimizers/muon.py; csrc/muon.hpp): with muon=dict(...) and the tensors' shapes, every tensor of two
+and more dimensions that is not listed in muon["adam_tensors"] takes momentum and five Newton-Schulz iterations on f32 MFMA, every other one
+muon.py's Adam / Nadam; the launch count of a step still does not depend on the number of tensors.
+
+    opt = FusedOptimizer(sizes, kind="nadam", beta_2=0.995, epsilon=1e-8, weight_decay=0.004, orthograd=True, grokfast=True,
+                         muon=dict(adam_tensors=[k for k, name in enumerate(names) if "bias" in name]), shapes=[tuple(p.shape) for p in params])
 """
 import ctypes as C
 
@@ -23,6 +30,36 @@ class OptimConfig(C.Structure):         # gaz_optim_config — tests/test_optim_
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_tensors", C.c_int32), ("kind", C.c_int32), ("sizes", C.c_void_p),
                 ("beta_1", C.c_double), ("beta_2", C.c_double), ("epsilon", C.c_double), ("weight_decay", C.c_double), ("orthograd", C.c_int32),
                 ("grokfast", C.c_int32), ("alpha", C.c_double), ("lamb", C.c_double)]
+
+
+class MuonConfig(C.Structure):          # gaz_muon_config — tests/test_muon_emu.py checks names, order and sizeof against the header
+    _fields_ = [("struct_size", C.c_uint32), ("n_tensors", C.c_int32), ("rows", C.c_void_p), ("cols", C.c_void_p), ("scale", C.c_void_p),
+                ("muon_beta", C.c_double), ("nesterov", C.c_int32), ("ns_steps", C.c_int32), ("muon_a", C.c_double), ("muon_b", C.c_double),
+                ("muon_c", C.c_double), ("adam_lr_ratio", C.c_double)]
+
+
+MUON_DEFAULTS = dict(muon_beta=0.95, nesterov=True, muon_a=3.4445, muon_b=-4.7750, muon_c=2.0315, ns_steps=5, adam_lr_ratio=1.0, adam_tensors=())
+MUON_WHAT = {"X0": 0, "n": 1, "X": 2, "A": 3, "B": 4}
+
+
+def muon_scale(shape):
+    """muon.py's scaling_factor of a tensor of this shape, in f32 as TensorFlow computes it: 0.2 * sqrt(max(1, shape[-2] / shape[-1]))"""
+    f = np.float32
+    return f(0.2) * np.sqrt(np.maximum(f(1.0), f(shape[-2]) / f(shape[-1])))
+
+
+def muon_table(shapes, adam_tensors=()):
+    """(rows i32, cols i32, scale f32) of gaz_muon_config: a tensor of two and more dimensions outside adam_tensors is a Muon tensor, read as
+    shape[0] x the rest; rows = cols = 0 names an Adam tensor"""
+    n, adam = len(shapes), {int(k) for k in adam_tensors}
+    if adam - set(range(n)):
+        raise ValueError(f"muon: adam_tensors names the tensors {sorted(adam - set(range(n)))} of {n}")
+    rows, cols, scale = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+    for k, sh in enumerate(shapes):
+        sh = tuple(int(d) for d in sh)
+        if len(sh) >= 2 and k not in adam:
+            rows[k], cols[k], scale[k] = sh[0], int(np.prod(sh[1:], dtype=np.int64)), muon_scale(sh)
+    return rows, cols, scale
 
 
 def bind(L):
@@ -52,12 +89,31 @@ def bind(L):
     return L
 
 
+def bind_muon(L):
+    """the gaz_muon_* entry points; a library built before Muon has none of them"""
+    if getattr(L, "_gaz_muon_bound", False):
+        return L
+    if not hasattr(L, "gaz_muon_set"):
+        raise EngineError("this library has no gaz_muon_set: rebuild it")
+    L.gaz_muon_config_size.argtypes = []
+    L.gaz_muon_set.argtypes = [C.c_void_p, C.POINTER(MuonConfig)]
+    L.gaz_muon_read.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    for f in ("config_size", "set", "read"):
+        getattr(L, "gaz_muon_" + f).restype = C.c_int
+    if L.gaz_muon_config_size() != C.sizeof(MuonConfig):
+        raise RuntimeError(f"gaz_muon_config has {L.gaz_muon_config_size()} bytes in the library, {C.sizeof(MuonConfig)} in this binding: rebuild the library")
+    L._gaz_muon_bound = True
+    return L
+
+
 class FusedOptimizer:
     """One optimizer over the tensors of `sizes` (elements each) on one device.  kind "adam" / "nadam" (or 0 / 1); weight_decay is Keras'
-    decoupled decay; orthograd / grokfast switch the two gradient stages on, alpha and lamb are Grokfast's."""
+    decoupled decay; orthograd / grokfast switch the two gradient stages on, alpha and lamb are Grokfast's.  muon = a dict over MUON_DEFAULTS
+    (muon.py's keywords, and adam_tensors: the indices of the tensors of two and more dimensions that take Adam all the same) with shapes = the
+    shape of every tensor: Muon mode, in which kind, beta_1, beta_2 and epsilon are those of muon.py's own Adam."""
 
     def __init__(self, sizes, kind="nadam", beta_1=0.9, beta_2=0.999, epsilon=1e-7, weight_decay=0.0, orthograd=False, grokfast=False, alpha=0.99,
-                 lamb=5.0, device=0, lib_path=None):
+                 lamb=5.0, device=0, lib_path=None, muon=None, shapes=None):
         self.L = bind(load_library(lib_path))
         if isinstance(kind, str):
             if kind.lower() not in KINDS:
@@ -81,6 +137,45 @@ class FusedOptimizer:
         self.ptrs = tuple(x.value or 0 for x in p)
         self.steps = 0
         self._views = {}
+        self.muon = None
+        if muon is not None:
+            try:
+                self._set_muon(dict(muon), shapes)
+            except Exception:
+                self.close()
+                raise
+
+    def _set_muon(self, muon, shapes):
+        unknown = set(muon) - set(MUON_DEFAULTS)
+        if unknown:
+            raise ValueError(f"muon: unknown keys {sorted(unknown)}")
+        if shapes is None or len(shapes) != len(self.sizes) or any(int(np.prod(sh, dtype=np.int64)) != n for sh, n in zip(shapes, self.sizes)):
+            raise ValueError("muon: shapes must give the shape of every tensor of sizes")
+        bind_muon(self.L)
+        m = dict(MUON_DEFAULTS, **muon)
+        self.shapes = [tuple(int(d) for d in sh) for sh in shapes]
+        self._muon_rows, self._muon_cols, self._muon_scale = muon_table(self.shapes, m["adam_tensors"])
+        mc = MuonConfig(struct_size=C.sizeof(MuonConfig), n_tensors=len(self.sizes), rows=self._muon_rows.ctypes.data, cols=self._muon_cols.ctypes.data,
+                        scale=self._muon_scale.ctypes.data, muon_beta=float(m["muon_beta"]), nesterov=int(bool(m["nesterov"])), ns_steps=int(m["ns_steps"]),
+                        muon_a=float(m["muon_a"]), muon_b=float(m["muon_b"]), muon_c=float(m["muon_c"]), adam_lr_ratio=float(m["adam_lr_ratio"]))
+        self._ck(self.L.gaz_muon_set(self.h, C.byref(mc)))
+        info = (C.c_int64 * 5)()
+        self._ck(self.L.gaz_optim_layout(self.h, None, info))
+        self.launches_per_step = int(info[3])
+        self.muon = dict(m, adam_tensors=sorted(int(k) for k in m["adam_tensors"]))
+        self.muon_tensors = [k for k in range(len(self.sizes)) if self._muon_rows[k] > 0]
+
+    def muon_debug(self, k):
+        """of Muon tensor k after the last step: X0 and the final X [rows, cols], n, and A, B [P, P] of the last iteration, P = min(rows, cols)"""
+        if self.muon is None:
+            raise EngineError("this optimizer is not in Muon mode")
+        r, c = int(self._muon_rows[k]), int(self._muon_cols[k])
+        p, out = max(min(r, c), 1), {}
+        for name, shape in (("X0", (r, c)), ("n", ()), ("X", (r, c)), ("A", (p, p)), ("B", (p, p))):
+            buf = np.zeros(max(int(np.prod(shape, dtype=np.int64)), 1), np.float32)
+            self._ck(self.L.gaz_muon_read(self.h, int(k), MUON_WHAT[name], buf.ctypes.data))
+            out[name] = buf[:int(np.prod(shape, dtype=np.int64))].reshape(shape) if shape else buf[0]
+        return out
 
     def _ck(self, rc):
         if rc != 0:

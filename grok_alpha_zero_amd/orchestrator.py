@@ -109,7 +109,7 @@ def Run(game_class, configs, train_fn=None, weights_fn=None, root="Grok_Zero_Tra
         if not isinstance(train, dict):
             raise ValueError(f"Run: train must be a dict of train_generation's keywords (an empty one will do), not {type(train).__name__}")
         from . import train as T                                                        # (imports torch before the first library handle of the run)
-        T.optimizer_settings(configs)                                                   # refusals (muon, mixed_precision) before anything is played
+        T.optimizer_settings(configs)                                                   # refusals (an unknown optimizer, mixed_precision) before anything is played
         if weights_fn is None:
             weights_fn = T.weights_from_folder
 

@@ -858,6 +858,52 @@ int gaz_optim_step_timed(gaz_optim* h, double lr, int64_t t, int32_t zero_grads,
 int gaz_optim_read_norms(gaz_optim* h, double* out);
 int gaz_optim_synchronize(gaz_optim* h);
 
+/* -- MUON (Net/Optimizers/muon.py; csrc/muon.hpp): gaz_muon_set turns an optimizer into the reference's Muon, wrapped like
+ * the chain above: Orthograd(Grokfast_EMA(Muon)).  The feature is detected by its symbols (gaz_muon_set); gaz_optim_config does not change.
+ * A tensor with rows = cols = 0 is an ADAM TENSOR, every other one a MUON TENSOR whose flat memory is read as a rows x cols matrix (muon.py's
+ * reshape(update, (shape[0], -1)); rows * cols = its size).  The binding decides which is which (_should_use_adamw) and computes
+ * scale = 0.2 * sqrt(max(1, shape[-2] / shape[-1])) from the tensor's real shape.
+ * ONE STEP IN MUON MODE, with the rounding rules of the OPTIMIZER section (f32 operations rounded one by one, scalars rounded to f32 once):
+ *   1  orthograd  as stage 2 above, on the UNDECAYED w
+ *   2  grokfast   as stage 3 above -> g2
+ *   3a Adam tensor   stage 4 above (kind, beta_1, beta_2, epsilon of the optimizer's config) with lr_a = f32(adam_lr_ratio) * lr in place of lr
+ *   3b Muon tensor   m = beta * m + g2 * (1 - beta);  u = g2 + m * beta with nesterov, else u = m;  X = NS(u);  w = w - (X * scale) * lr
+ *   4  decay      wd != 0:  w = w - ((l * wd) * w), l = lr_a for an Adam tensor, lr for a Muon tensor       (muon.py: after the update)
+ *   5  zero_grads g = 0
+ * m lives in the momentum arena; the velocity arena's range of a Muon tensor holds u.
+ * NS(u), the Newton-Schulz iteration on bf16 VALUES HELD IN F32; bf16() rounds an f32 to nearest even on its bit pattern.  P = min(rows, cols),
+ * Q = max(rows, cols); X is P x Q: the matrix itself, or its transpose when rows > cols (read transposed, never copied).
+ *   X0 = bf16(u);  n = sqrtf(f32(sum X0^2)), the sum a float64 sum over the tensor's flat memory in the OPTIMIZER section's chunk order;
+ *   X = bf16(X0 / (n + 1e-7f));  a, b, c = bf16(f32(muon_a)), bf16(f32(muon_b)), bf16(f32(muon_c));  then ns_steps times
+ *   A = bf16(X X^T);  B = bf16(bf16(b * A) + bf16(c * bf16(A A)));  X = bf16(bf16(a * X) + bf16(B X))
+ * EVERY MATRIX PRODUCT element is one f32 chain acc = fmaf(x, y, acc) over k ascending from 0 with acc = +0 at the start and no split of K (a
+ * product of two bf16 values is exact in f32, so multiply-then-add gives the same bits).  THIN MATRICES (P <= 4): only X X^T differs; its
+ * P (P + 1) / 2 entries are float64 sums of the exact products over the column index q = 0 .. Q - 1 in the chunk order of the OPTIMIZER section
+ * applied to q (chunks of 2048 columns, slots, butterfly, the chunks' sums ascending from +0.0), each rounded to f32 and then to bf16.
+ * REFERENCE QUIRK, not reproduced, as above: t is the caller's step number and the decay is applied although the optimizer is wrapped. */
+typedef struct {
+    uint32_t struct_size;         /* = sizeof(gaz_muon_config) */
+    int32_t n_tensors;            /* the optimizer's */
+    const int32_t* rows;          /* [n_tensors]; rows = cols = 0: an Adam tensor */
+    const int32_t* cols;          /* [n_tensors] */
+    const float* scale;           /* [n_tensors]; read for Muon tensors */
+    double muon_beta;             /* in [0, 1) */
+    int32_t nesterov;             /* 0 / 1 */
+    int32_t ns_steps;             /* 0 .. 16 */
+    double muon_a, muon_b, muon_c;/* finite */
+    double adam_lr_ratio;         /* finite, >= 0 */
+} gaz_muon_config;
+int gaz_muon_config_size(void);
+/* after gaz_optim_create and before the first step, once.  Allocates two X buffers of an arena's size and A, B (P x P) of every Muon tensor.
+ * Refused, each by its text: a stale struct_size, another n_tensors, rows * cols different from a tensor's size, ns_steps outside 0 .. 16,
+ * non-finite coefficients or scale, muon_beta outside [0, 1), a bad adam_lr_ratio or nesterov, a call after the first step, a second call.
+ * From then on gaz_optim_layout's launches entry is: the 1 or 3 above, and with at least one Muon tensor + 2 (k_muon_norm, k_muon_finish)
+ * + ns_steps * (k_muon_gram, k_muon_poly when a Muon tensor has P >= 5, k_muon_update) — whatever the number of tensors */
+int gaz_muon_set(gaz_optim* h, const gaz_muon_config* cfg);
+/* for tests: of Muon tensor `tensor` after the last step, what = 0 X0 [size, the tensor's flat layout], 1 n [1], 2 the final X [size, flat
+ * layout], 3 / 4 A / B of the last iteration [P * P, row-major] (zeros with ns_steps = 0).  A host synchronisation point */
+int gaz_muon_read(gaz_optim* h, int32_t tensor, int32_t what, float* out);
+
 #ifdef __cplusplus
 }
 #endif
