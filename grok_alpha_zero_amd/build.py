@@ -12,7 +12,7 @@ HEADER = os.path.join(os.path.dirname(_PKG), "include", "gaz_engine.h")
 # translation unit -> the headers it includes (rebuild trigger)
 UNITS = {
     "engine.hip": ["rt.hpp", "wave.hpp", "det.hpp", "games.hpp", "tree.hpp", "resign.hpp", "book.hpp", "book_start.hpp", "puct_core.hpp", "gumbel_core.hpp", "evaluator.hpp", "samples.hpp", "tree_export.hpp", "match.hpp", "det_probe.hpp", "replay.hpp", "score.hpp", "optim.hpp", "muon.hpp"],
-    "resnet.hip": ["rt.hpp", "wave.hpp", "evaluator.hpp", "netops.hpp", "conv3x3.hpp", "conv_wide.hpp", "resblock.hpp", "trunk.hpp", "tile_perm.hpp", "net_host.hpp",
+    "resnet.hip": ["rt.hpp", "wave.hpp", "evaluator.hpp", "netops.hpp", "conv_common.hpp", "conv_wide.hpp", "resblock.hpp", "trunk.hpp", "tile_perm.hpp", "net_host.hpp",
                    "det.hpp", "games.hpp", "tree.hpp", "resign.hpp", "puct_core.hpp", "gumbel_core.hpp"],          # the fused tree + trunk launch lives in resnet.hip
 }
 # -ffp-contract=off: the injected-noise samplers and PUCT scores must not be FMA-contracted (bit parity)

@@ -1,20 +1,29 @@
 // conv_wide.hpp — the trunk and head convolutions of networks whose residual width F is not 128 (F in {64, 192, 256}):
 // 3x3 F -> F and 128 | 256 -> F, the block-0 1x1 projection 128 | 256 -> F accumulated into conv2, and the heads' first
-// convolution F -> 32.  The 128-wide networks keep their own kernels (conv3x3.hpp, resblock.hpp, trunk.hpp); nothing here is
+// convolution F -> 32.  The 128-wide networks keep their own kernels (resblock.hpp, trunk.hpp); nothing here is
 // reached at F = 128.
 //
-// Implicit GEMM on v_mfma_f32_32x32x16_bf16 (bf16 operands, fp32 accumulate), the scheme of k_conv3x3: M = B*H*W board cells,
-// N = Cout, K = taps * Cin.  A 256-thread workgroup owns BM = 128 cells x BN output channels (blockIdx.y = the BN-wide column
-// tile of Cout):
-//   * the 128 rows plus a (W+1)-row halo of the activation come into LDS once by LDS-DMA and serve all nine taps; masked taps
-//     (board edges, rows past M) read a zero row;
-//   * the weights are arranged on the host as [column tile][tap][Cin/16][2][BN][8] (arrange_wide_weights), so each workgroup's
-//     stream is one contiguous array cut into 9 * KSPLIT slices; slice s+1 is DMA'd while slice s multiplies;
+// A 3x3 "same" convolution on NHWC bf16 board tensors as an implicit GEMM on the gfx950 matrix cores (v_mfma_f32_32x32x16_bf16,
+// bf16 operands, fp32 accumulate); it replaces the Conv2D layers of the reference network (Net/ResNet/ResNet_Block.py:12-20,
+// Connect4/Build_Model.py:41,62) as executed by ONNX Runtime.  GEMM view: M = B*H*W flattened board cells, N = Cout,
+// K = taps * Cin.  A 256-thread workgroup owns BM = 128 consecutive cells x BN output channels (blockIdx.y = the BN-wide
+// column tile of Cout):
+//   * the 128 rows plus a (W+1)-row halo of the activation are brought into LDS ONCE by LDS-DMA (global_load_lds_dwordx4) and
+//     serve all nine taps: the tap (dy,dx) operand of cell r is image row r + dy*W + dx; masked taps (board edges, rows past M)
+//     read a zero row instead of being zeroed in registers, so the rows of neighbouring boards that the halo drags in are never
+//     selected and nothing needs to be zero-filled;
+//   * the image is XOR-swizzled in 16-byte slots by permuting the per-lane SOURCE address of the DMA (the LDS side of a DMA is
+//     lane-linear), which makes every A-fragment ds_read_b128 conflict-free (LDS swizzle, below);
+//   * the weights are arranged on the host in fragment order [column tile][tap][Cin/16][2][BN][8] (arrange_wide_weights; k =
+//     k-step * 16 + half * 8 + j), so each workgroup's stream is one contiguous array cut into 9 * KSPLIT slices, its DMA is a
+//     straight copy and every fragment read is base + compile-time offset; the slices are double-buffered in LDS: slice s+1 is
+//     DMA'd while slice s multiplies, one barrier per slice; fragments are register double-buffered across k-steps;
 //   * an optional second operand (CIN2 > 0: the 1x1 projection of block 0) is staged after the first and accumulates into the
 //     SAME fp32 accumulators, so conv2 + projection take one bias (b2 + bp) and one rounding;
-//   * epilogue as k_conv3x3's: folded BN scale / shift, residual add, activation, and the second output relu(bn_next(x)) —
-//     here taken from the bf16-ROUNDED x, the value the next block reads (net.py forward_engine_numerics).  EPI_HEADS instead
-//     writes the Connect4 heads' fp32 features: channels 0-7 policy, 8-15 value, flat BN over (cell * 8 + c), ReLU.
+//   * epilogue: accumulators -> fp32 LDS tile -> per-thread 16-byte channel groups (dwordx4
+//     stores): folded BN scale / shift, residual add, activation, and (for the pre-activation blocks) the second output
+//     relu(bn_next(x)) — taken from the bf16-ROUNDED x, the value the next block reads (net.py forward_engine_numerics).  EPI_HEADS
+//     instead writes the Connect4 heads' fp32 features: channels 0-7 policy, 8-15 value, flat BN over (cell * 8 + c), ReLU.
 //
 // LDS swizzle.  ds_read_b128 serves a wave in four 16-lane groups (MI355X_MICROARCH.md §LDS); a group is conflict-free iff its
 // 16 lanes hit the 16 distinct 16-byte slots of one 256-byte bank row.  The A-fragment read of a group is 16 rows with distinct
@@ -27,7 +36,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "conv3x3.hpp"
+#include "conv_common.hpp"
 
 namespace gaz {
 

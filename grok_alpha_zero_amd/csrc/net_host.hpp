@@ -7,7 +7,7 @@
 #include <type_traits>
 #include <vector>
 #include "evaluator.hpp"
-#include "conv3x3.hpp"
+#include "conv_common.hpp"
 #include "conv_wide.hpp"
 #include "netops.hpp"
 #include "trunk.hpp"
@@ -18,7 +18,7 @@ inline bf16_t f2bf_host(float f) { unsigned u; memcpy(&u, &f, 4); return (bf16_t
 
 // ---- device tensors of one evaluator: every allocation (freed here), the host tensors of the load call by name, the uploaded fp32 tensors
 // and bf16 convolution operands by name, and the text of the first error.
-enum ConvOrder { CONV_MFMA, CONV_WIDE };            // arrange_conv_weights (conv3x3.hpp) | arrange_wide_weights (conv_wide.hpp)
+enum ConvOrder { CONV_MFMA, CONV_WIDE };            // arrange_conv_weights (conv_common.hpp) | arrange_wide_weights (conv_wide.hpp)
 struct DeviceStore {
     std::vector<void*> allocs; std::string err;
     std::map<std::string, const gaz_tensor*> by; std::map<std::string, float*> f32; std::map<std::string, bf16_t*> b16;

@@ -5,7 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include "conv3x3.hpp"
+#include "conv_common.hpp"
 
 namespace gaz {
 

@@ -20,7 +20,7 @@
 #include <vector>
 #include <algorithm>
 #include "evaluator.hpp"
-#include "conv3x3.hpp"
+#include "conv_common.hpp"
 #include "conv_wide.hpp"
 #include "netops.hpp"
 #include "resblock.hpp"
@@ -56,62 +56,6 @@ static void rb3_launch(hipStream_t s, ResBlockArgs r, const Rb3Plan& p, int ring
     else if (tm == 3 && ring == 4) hipLaunchKernelGGL((k_resblock3<3, 4>), dim3(nwg), dim3(RB3_THREADS), rb3_lds_bytes<3>(), s, r);
     else if (tm == 3) hipLaunchKernelGGL((k_resblock3<3, 8>), dim3(nwg), dim3(RB3_THREADS), rb3_lds_bytes<3>(), s, r);
     else hipLaunchKernelGGL((k_resblock3<4, 4>), dim3(nwg), dim3(RB3_THREADS), rb3_lds_bytes<4>(), s, r);
-}
-
-// ---- stem: Conv3x3(C_in = 4, int8 planes) -> 128, BN, exact GELU; second output relu(bn1_0(x))
-struct StemArgs {
-    const int8_t* in;        // [B][HW][4]
-    const float* w;          // [9][128][4]
-    const float* scale; const float* shift;
-    const float* scaleB; const float* shiftB;
-    bf16_t* out1; bf16_t* out2;
-    int M, H, W;
-};
-
-__global__ __launch_bounds__(256) void k_stem(StemArgs a) {
-    __shared__ float wl[36][128];
-    const int tid = threadIdx.x;
-    for (int i = tid; i < 36 * 128; i += 256) {
-        const int k = i / 128, ch = i % 128, tap = k / 4, c = k % 4;
-        wl[k][ch] = a.w[(tap * 128 + ch) * 4 + c];
-    }
-    __syncthreads();
-    const int chg = tid & 15, rsub = tid >> 4, HW = a.H * a.W;
-    const int ch0 = chg * 8;
-    float s[8], t[8], sb[8], tb[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { s[j] = a.scale[ch0 + j]; t[j] = a.shift[ch0 + j]; sb[j] = a.scaleB[ch0 + j]; tb[j] = a.shiftB[ch0 + j]; }
-    const int* in32 = reinterpret_cast<const int*>(a.in);
-    for (int pass = 0; pass < 4; ++pass) {
-        const long gr = (long)blockIdx.x * 64 + pass * 16 + rsub;
-        if (gr >= a.M) continue;
-        const int cell = (int)(gr % HW), y = cell / a.W, x = cell % a.W;
-        float acc[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = 0.0f;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int dy = tap / 3 - 1, dx = tap % 3 - 1;
-            if ((unsigned)(y + dy) >= (unsigned)a.H || (unsigned)(x + dx) >= (unsigned)a.W) continue;
-            const int packed = in32[gr + dy * a.W + dx];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float xv = (float)(int8_t)((packed >> (8 * c)) & 0xFF);
-                const float* wr = &wl[tap * 4 + c][ch0];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[j] += xv * wr[j];
-            }
-        }
-        bf16_t o1[8], o2[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float v = acc[j] * s[j] + t[j];
-            v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-            o1[j] = f2bf(v); o2[j] = f2bf(fmaxf(v * sb[j] + tb[j], 0.0f));
-        }
-        *reinterpret_cast<uint4*>(a.out1 + (size_t)gr * 128 + ch0) = *reinterpret_cast<uint4*>(o1);
-        if (a.out2) *reinterpret_cast<uint4*>(a.out2 + (size_t)gr * 128 + ch0) = *reinterpret_cast<uint4*>(o2);
-    }
 }
 
 // ---- stem on the matrix cores.  D[channel][cell] = W'[channel][k] * X[k][cell], k = tap * 4 + plane (36, padded to 48).
@@ -293,29 +237,6 @@ __global__ __launch_bounds__(256) void k_dense_mfma(DenseMArgs a) {
         const int row = (r & 3) + 8 * (r >> 2) + 4 * lhi;
         if (b0 + row < a.B) a.out[(size_t)(b0 + row) * N + n] = apply_act(acc[r] * s + t, a.act);
     }
-}
-
-// ---- heads: Dense(F -> 128) + folded BN + ReLU, fp32.  Block = 128 threads (one output each), 8 positions at a time.
-__global__ __launch_bounds__(128) void k_dense1(const float* feat, const float* w, const float* scale, const float* shift,
-                                                float* out, int B, int F) {
-    extern __shared__ float fl[];                  // [8][F]
-    const int j = threadIdx.x;
-    const int b0 = blockIdx.x * 8;
-    for (int i = threadIdx.x; i < 8 * F; i += 128) {
-        const int p = i / F, k = i % F;
-        fl[i] = (b0 + p < B) ? feat[(size_t)(b0 + p) * F + k] : 0.0f;
-    }
-    __syncthreads();
-    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int k = 0; k < F; ++k) {
-        const float wv = w[(size_t)k * 128 + j];
-#pragma unroll
-        for (int p = 0; p < 8; ++p) acc[p] += fl[p * F + k] * wv;
-    }
-    const float s = scale[j], t = shift[j];
-#pragma unroll
-    for (int p = 0; p < 8; ++p)
-        if (b0 + p < B) out[(size_t)(b0 + p) * 128 + j] = fmaxf(acc[p] * s + t, 0.0f);
 }
 
 // ---- heads: the same Dense(F -> 128) + folded BN + ReLU for BOTH heads on the matrix cores, exact fp32
@@ -634,8 +555,7 @@ static std::string net_width_error(int f) {
 struct ResNetEvaluator : Evaluator {
     int H, W, C, A, HW, blocks, filters, nmax, logits;
     DeviceStore st;                                 // device tensors by name (net_host.hpp)
-    bf16_t *X = nullptr, *Aa = nullptr, *Hh = nullptr, *X2 = nullptr;
-    bool fused = true;
+    bf16_t *X = nullptr, *Aa = nullptr, *Hh = nullptr, *X2 = nullptr;      // Aa / Hh: operands of the k_conv_wide trunk (filters != 128)
     int stamp_calls = 0, n_cus = 256;
     bf16_t* stem_frag = nullptr;
     bool trunk_m16 = true;                          // ... on v_mfma_f32_16x16x32_bf16 (higher clock held); GAZ_TRUNK_M16=0 -> 32x32x16 (bit-identical to k_resblock3)
@@ -652,7 +572,6 @@ struct ResNetEvaluator : Evaluator {
     float *pfeat = nullptr, *vfeat = nullptr, *pd1 = nullptr, *vd1 = nullptr;
     bool loaded = false;
     TrunkTimer timer;                               // brackets around the trunk conv chain
-    int64_t n_trunk_launches = 0;
 
     int load(const gaz_tensor* t, int n, hipStream_t s, std::string* err) override {
         st.set_tensors(t, n);
@@ -663,8 +582,8 @@ struct ResNetEvaluator : Evaluator {
     }
     bool load_tensors() {
         const int Fc = filters, F = HW * 8;
-        if (!st.up_f32("stem.w", 9 * 128 * C) || !st.up_f32("stem.scale", 128) || !st.up_f32("stem.shift", 128)) return false;
-        {   // MFMA stem operand, BN scale folded into the weights
+        if (!st.need("stem.w", 9 * 128 * C) || !st.need("stem.scale", 128) || !st.up_f32("stem.shift", 128)) return false;
+        {   // MFMA stem operand, BN scale folded into the weights on the host: stem.w and stem.scale have no device copy of their own
             if (C != 4) { st.err = "stem expects 4 input planes"; return false; }
             const std::vector<bf16_t> h = stem_fragments(st.by["stem.w"]->data, st.by["stem.scale"]->data, 4, 128);
             if (!(stem_frag = st.upload(h.data(), h.size()))) return false;
@@ -703,25 +622,9 @@ struct ResNetEvaluator : Evaluator {
         return true;
     }
 
-    void conv_trunk(hipStream_t s, const bf16_t* in, const bf16_t* w, const float* sA, const float* tA, const bf16_t* res,
-                    bf16_t* out1, int act1, const float* sB, const float* tB, bf16_t* out2, int M) {
-        ConvArgs a; memset(&a, 0, sizeof(a));
-        a.in = in; a.wgt = w; a.scaleA = sA; a.shiftA = tA; a.res = res; a.out1 = out1; a.act1 = act1;
-        a.scaleB = sB; a.shiftB = tB; a.out2 = out2; a.M = M; a.H = H; a.W = W;
-        static const int variant = env_int("GAZ_CONV_VARIANT", 0);
-        if (variant == 0) {          // 256 rows / 512 threads / whole-tap slices, one workgroup per CU
-            const size_t lds = conv_lds_bytes<128, 128, 256, 1>();
-            hipLaunchKernelGGL((k_conv3x3<128, 128, 256, 4, 2, 2, 2, 1, 1, 0>), dim3((M + 255) / 256), dim3(512), lds, s, a);
-        } else {                     // 128 rows / 256 threads / half-tap slices, two workgroups per CU overlap their phases
-            const size_t lds = conv_lds_bytes<128, 128, 128, 2>();
-            hipLaunchKernelGGL((k_conv3x3<128, 128, 128, 2, 2, 2, 2, 2, 2, 0>), dim3((M + 127) / 128), dim3(256), lds, s, a);
-        }
-        n_trunk_launches++;
-    }
-
     bool supports_row_base() const override { return true; }
     bool head_features(const float** p, const float** v, int* pr, int* vr) override { *p = pfeat; *v = vfeat; *pr = HW * 8; *vr = HW * 8; return true; }
-    bool supports_split() const override { return filters == 128 && fused && trunk && trunk_whole && blocks > 0 && HW <= 128; }
+    bool supports_split() const override { return filters == 128 && trunk && trunk_whole && blocks > 0 && HW <= 128; }
     // kernel arguments + grid of the k_trunk / k_trunk_mix launch for rows [p0, p0 + n): the ONE place that fills them.  The whole-trunk
     // variants (stem and heads inside) read every field; the blocks-only variant (GAZ_TRUNK_WHOLE=0) ignores planes ... v_feat and never mixes.
     void make_trunk_plan(const int8_t* in, int n, int p0, bool mix_allowed, bool fill_big, TrunkLaunchPlan& P) {
@@ -763,20 +666,13 @@ struct ResNetEvaluator : Evaluator {
         const int M = n * HW;
         // activation / feature buffers of rows [p0, p0 + n)
         bf16_t* const X = this->X + (size_t)p0 * HW * 128; bf16_t* const X2 = this->X2 + (size_t)p0 * HW * 128;
-        bf16_t* const Aa = this->Aa + (size_t)p0 * HW * 128; bf16_t* const Hh = this->Hh + (size_t)p0 * HW * 128;
         float* const pfeat = this->pfeat + (size_t)p0 * HW * 8; float* const vfeat = this->vfeat + (size_t)p0 * HW * 8;
-        StemArgs sa; sa.in = in; sa.w = st.g("stem.w"); sa.scale = st.g("stem.scale"); sa.shift = st.g("stem.shift");
-        sa.scaleB = blocks ? st.g("block0.bn1.scale") : st.g("stem.scale"); sa.shiftB = blocks ? st.g("block0.bn1.shift") : st.g("stem.shift");
-        sa.out1 = X; sa.out2 = fused ? nullptr : Aa; sa.M = M; sa.H = H; sa.W = W;    // the fused blocks pre-activate on load
-        const bool use_trunk = fused && trunk && blocks > 0 && HW <= 128;
+        const bool use_trunk = trunk && blocks > 0 && HW <= 128;
         const bool whole = use_trunk && trunk_whole;     // stem and heads' first convolution inside k_trunk as well
-        if (whole) {
-        } else if (fused) {
+        if (!whole) {                               // the stem writes the raw tensor only: the blocks pre-activate on load
             StemMArgs sm; memset(&sm, 0, sizeof(sm)); sm.in = in; sm.wfrag = reinterpret_cast<const uint4*>(stem_frag); sm.shift = st.g("stem.shift"); sm.out = X;
             sm.M = M; sm.H = H; sm.W = W;
             launch_stem_mfma<4, 128, true, false>(s, sm);
-        } else {
-            hipLaunchKernelGGL(k_stem, dim3((M + 63) / 64), dim3(256), 0, s, sa);
         }
         timer.begin(s, timing);
         bf16_t* cur = X;
@@ -797,34 +693,19 @@ struct ResNetEvaluator : Evaluator {
             stamps.finish();
             cur = X2;
         }
-        for (int i = 0; fused && !use_trunk && i < blocks; ++i) {             // one kernel per residual block (resblock.hpp)
+        for (int i = 0; !use_trunk && i < blocks; ++i) {                      // one kernel per residual block (resblock.hpp)
             const std::string b = "block" + std::to_string(i);
             ResBlockArgs r; r.xin = cur; r.xout = cur == X ? X2 : X; r.w1 = st.w(b + ".conv1.w"); r.w2 = st.w(b + ".conv2.w");
             r.s1 = st.g(b + ".bn1.scale"); r.t1 = st.g(b + ".bn1.shift"); r.s2 = st.g(b + ".conv1.scale"); r.t2 = st.g(b + ".conv1.shift");
             r.b2 = st.g(b + ".conv2.bias"); r.M = M; r.H = H; r.W = W; r.stamps = nullptr;
-            static const int rbv = env_int("GAZ_RB", 3);
-            static const int rb_tm = env_int("GAZ_RB_TM", 0);
-            static const int rb_ring = env_int("GAZ_RB_RING", 8);
-            Rb3Plan plan = rb3_plan(M, H, W, n_cus);
-            if (rb_tm) plan = Rb3Plan{rb_tm, W + 1, 64 * rb_tm - 2 * (W + 1)};
-            const int bmo = rbv == 3 ? plan.tile_rows : RB_ROWS - 2 * (W + 1);
-            const size_t lds = conv_lds_bytes<128, 128, 256, 1>();
-            const int nwg = (M + bmo - 1) / bmo;
+            const Rb3Plan plan = rb3_plan(M, H, W, n_cus);
+            const int nwg = (M + plan.tile_rows - 1) / plan.tile_rows;
             static const char* stamp_path = getenv("GAZ_RB_STAMPS");       // diagnostic: phase stamps of one launch -> file
             StampDump stamps(stamp_path && i == 1 && ++stamp_calls == 3 ? stamp_path : nullptr, (size_t)nwg * RB_STAMPS, s);
             r.stamps = stamps.dev;
-            if (rbv == 3) rb3_launch(s, r, plan, rb_ring);
-            else hipLaunchKernelGGL(k_resblock, dim3(nwg), dim3(RB_THREADS), lds, s, r);
+            rb3_launch(s, r, plan, 8);
             stamps.finish();
             cur = r.xout;
-        }
-        for (int i = 0; !fused && i < blocks; ++i) {
-            const std::string b = "block" + std::to_string(i), nb = "block" + std::to_string(i + 1);
-            conv_trunk(s, Aa, st.w(b + ".conv1.w"), st.g(b + ".conv1.scale"), st.g(b + ".conv1.shift"), nullptr, Hh, ACT_RELU,
-                       nullptr, nullptr, nullptr, M);
-            const bool last = i + 1 == blocks;
-            conv_trunk(s, Hh, st.w(b + ".conv2.w"), nullptr, st.g(b + ".conv2.bias"), X, X, ACT_NONE,
-                       last ? nullptr : st.g(nb + ".bn1.scale"), last ? nullptr : st.g(nb + ".bn1.shift"), last ? nullptr : Aa, M);
         }
         timer.end(s);
         if (!whole) {   // first conv of both heads + flat BN + ReLU (k_conv_heads)
@@ -886,13 +767,13 @@ struct ResNetEvaluator : Evaluator {
     }
 
     bool ready() const override { return loaded; }
-    void timing_reset() override { timer.reset(); n_trunk_launches = 0; }
+    void timing_reset() override { timer.reset(); }
     void timing_get(double* ms, int64_t* launches) override {
         *ms = timer.total_ms();
         // launches of the priced kernel per bracket: one where the bracket is priced as a whole (k_conv_wide per forward, k_trunk); otherwise
-        // one k_resblock3 per block, or two k_conv3x3 per block without the fused blocks
-        const bool per_forward = filters != 128 || (fused && trunk);
-        *launches = timer.brackets() * (per_forward ? 1 : (fused ? 1 : 2) * blocks);
+        // one k_resblock3 per block
+        const bool per_forward = filters != 128 || trunk;
+        *launches = timer.brackets() * (per_forward ? 1 : blocks);
     }
     const char* dominant_kernel(int n, double* flops) override {
         if (filters != 128) {                       // priced per forward: the bracket holds every trunk convolution (2 x blocks launches)
@@ -903,8 +784,8 @@ struct ResNetEvaluator : Evaluator {
             return dom_label.c_str();
         }
         const double conv = 2.0 * (double)n * HW * 128.0 * 1152.0;
-        *flops = fused ? 2 * conv : conv;
-        if (fused && trunk) {
+        *flops = 2 * conv;
+        if (trunk) {
             *flops = 2 * conv * blocks;
             if (trunk_whole && trunk_m16 && trunk_mix && perm_big && perm_small) {
                 // MFMA rows x taps actually issued / counted (n HW rows x 9 taps): 128-row tiles run 30 of 36 tile-taps per wave, 96-row tiles 45 of 54
@@ -924,22 +805,21 @@ struct ResNetEvaluator : Evaluator {
             return trunk_m16 ? "k_trunk (the whole residual trunk: blocks x two 3x3 convs 128->128, implicit GEMM on v_mfma_f32_16x16x32_bf16, activations resident in LDS)"
                              : "k_trunk (the whole residual trunk: blocks x two 3x3 convs 128->128, implicit GEMM on v_mfma_f32_32x32x16_bf16, activations resident in LDS)";
         }
-        return fused ? "k_resblock3 (whole residual block: two 3x3 convs 128->128, implicit GEMM on MFMA 32x32x16 bf16)"
-                     : "k_conv3x3<128,128> (trunk 3x3 conv, implicit GEMM on MFMA 32x32x16 bf16)";
+        return "k_resblock3 (whole residual block: two 3x3 convs 128->128, implicit GEMM on MFMA 32x32x16 bf16)";
     }
 };
 
 // ------------------------------------------------------------------------------------------ Gomoku / TicTacToe
-// Same trunk kernel (k_conv3x3) where the layer is 128-wide; the 256-channel first block of the Gomoku net uses the
-// CIN = 256 / 128-row instantiation (3x3 conv1 and the 1x1 residual projection); narrow layers go through netops.hpp.
+// Gomoku at 128 filters runs the same trunk kernels (k_trunk, k_resblock3) behind its 256-channel stem, with the 256 -> 128 first block and its
+// 1x1 projection inside k_trunk or as k_block0; other widths run k_conv_wide; TicTacToe's narrow layers go through netops.hpp.
 struct GenericEvaluator : Evaluator {
     int H, W, C, A, HW, blocks, F, nmax, logits; bool gomoku;
     DeviceStore st;                                 // device tensors by name (net_host.hpp)
     bool loaded = false;
     bf16_t *X0 = nullptr, *A0 = nullptr, *X = nullptr, *Aa = nullptr, *Hh = nullptr, *Va = nullptr, *PH = nullptr, *VH = nullptr;
     float *pfeat = nullptr, *vfeat = nullptr, *pd1 = nullptr, *vd1 = nullptr, *pd2 = nullptr, *vd2 = nullptr, *plog = nullptr;
-    TrunkTimer timer; int trunk_convs = 0; bool one_launch = false;   // one_launch: the bracket holds ONE kernel (the whole trunk, block 0 included)
-    bool fused = true, block0_fused = false, block0_inplace = false; int n_cus = 256, fused_blocks = 0;
+    TrunkTimer timer; bool one_launch = false;      // one_launch: the bracket holds ONE kernel (the whole trunk, block 0 included)
+    int n_cus = 256;
     hipStream_t side_stream = 0; hipEvent_t ev_fork = 0, ev_join = 0;     // value head next to the policy head (Gomoku)   // Gomoku: k_block0 + k_resblock3 (one kernel per block)
     bool trunk = true, trunk_m16 = true; bf16_t* trunk_w = nullptr; float* trunk_prm = nullptr;      // ... or k_block0 + ONE k_trunk launch for blocks 1.. (GAZ_TRUNK=0: per block)
     // ... or block 0 INSIDE that launch (trunk.hpp B0; GAZ_BLOCK0_IN_TRUNK=0: k_block0 ahead of it): block 0's 29 slices + the blocks' 18 each
@@ -993,7 +873,7 @@ struct GenericEvaluator : Evaluator {
     bool load_tensors() {
         auto up = [&](const std::string& name, int64_t numel) { return st.up_f32(name, numel); };
         const int SC = gomoku ? 256 : 128, K = gomoku ? 3 : 5;
-        const ConvOrder order = F == 128 ? CONV_MFMA : CONV_WIDE;      // Gomoku: k_conv3x3 / k_resblock3 / k_trunk operands, or k_conv_wide's at F != 128
+        const ConvOrder order = F == 128 ? CONV_MFMA : CONV_WIDE;      // Gomoku heads: k_conv_head32 operands, or k_conv_wide's at F != 128
         bool ok = up("stem.w", (int64_t)K * K * SC * C) && up("stem.scale", SC) && up("stem.shift", SC);
         if (ok && gomoku) {                         // MFMA stem operand (2 planes x 9 taps -> 256 channels), BN scale folded in
             const std::vector<bf16_t> h = stem_fragments(st.by["stem.w"]->data, st.by["stem.scale"]->data, 2, 256);
@@ -1005,10 +885,10 @@ struct GenericEvaluator : Evaluator {
             if (!ok) break;
             if (gomoku && F != 128) ok = st.up_conv(b + ".conv1.w", F, cin, 9, CONV_WIDE) && st.up_conv(b + ".conv2.w", F, F, 9, CONV_WIDE) && (cin == F || st.up_conv(b + ".proj.w", F, cin, 1, CONV_WIDE));
             else if (gomoku && cin == F) ok = st.up_conv_pair(b + ".conv1.w", b + ".conv2.w", F);
-            else if (gomoku) ok = st.up_conv(b + ".conv1.w", F, cin, 9, CONV_MFMA) && st.up_conv(b + ".conv2.w", F, F, 9, CONV_MFMA);
+            else if (gomoku) ok = st.need(b + ".conv1.w", 9LL * F * cin) && st.need(b + ".conv2.w", 9LL * F * F);      // block 0 at 128 filters: up_block0 reads the host tensors
             else ok = up(b + ".conv1.w", 9LL * F * cin) && up(b + ".conv2.w", 9LL * F * F);
             if (ok && cin != F && gomoku && F != 128) ok = up(b + ".proj.bias", F) && st.up_bias_sum(b + ".bias2p", b + ".conv2.bias", b + ".proj.bias");
-            else if (ok && cin != F) ok = (gomoku ? st.up_conv(b + ".proj.w", F, cin, 1, CONV_MFMA) : up(b + ".proj.w", (int64_t)F * cin)) && up(b + ".proj.bias", F);
+            else if (ok && cin != F) ok = (gomoku ? st.need(b + ".proj.w", (int64_t)F * cin) != nullptr : up(b + ".proj.w", (int64_t)F * cin)) && up(b + ".proj.bias", F);
             if (ok && gomoku && cin != F && F == 128 && cin == 256) ok = up_block0(b);
         }
         if (ok && gomoku) {
@@ -1030,25 +910,6 @@ struct GenericEvaluator : Evaluator {
         return ok;
     }
 
-    template <int CIN, int NT> void conv_mfma(hipStream_t s, const bf16_t* in, const bf16_t* w, const float* sA, const float* tA, const bf16_t* res,
-                                               bf16_t* out1, int act1, const float* sB, const float* tB, bf16_t* out2, int M) {
-        ConvArgs a; memset(&a, 0, sizeof(a));
-        a.in = in; a.wgt = w; a.scaleA = sA; a.shiftA = tA; a.res = res; a.out1 = out1; a.act1 = act1; a.scaleB = sB; a.shiftB = tB; a.out2 = out2;
-        a.M = M; a.H = H; a.W = W;
-        if (CIN == 128) {
-            const size_t lds = conv_lds_bytes<128, 128, 256, 1>();
-            hipLaunchKernelGGL((k_conv3x3<128, 128, 256, 4, 2, 2, 2, 1, 1, 0, NT>), dim3((M + 255) / 256), dim3(512), lds, s, a);
-        } else {
-            const size_t lds = conv_lds_bytes<256, 128, 128, 4>();
-            hipLaunchKernelGGL((k_conv3x3<256, 128, 128, 2, 2, 2, 2, 4, 1, 0, NT>), dim3((M + 127) / 128), dim3(256), lds, s, a);
-        }
-    }
-    void conv_mfma32(hipStream_t s, const bf16_t* in, const bf16_t* w, const float* sA, const float* tA, bf16_t* out1, int M) {
-        ConvArgs a; memset(&a, 0, sizeof(a));
-        a.in = in; a.wgt = w; a.scaleA = sA; a.shiftA = tA; a.out1 = out1; a.act1 = ACT_RELU; a.M = M; a.H = H; a.W = W;
-        const size_t lds = conv_lds_bytes<128, 32, 256, 1>();
-        hipLaunchKernelGGL((k_conv3x3<128, 32, 256, 8, 1, 1, 1, 1, 1, 0, 9>), dim3((M + 255) / 256), dim3(512), lds, s, a);
-    }
     void conv_direct(hipStream_t s, const bf16_t* in, const float* w, int cin, int cout, int K, const float* sA, const float* tA, const bf16_t* res,
                      bf16_t* out1, int act1, const float* sB, const float* tB, bf16_t* out2, float* flat, const float* fs, const float* ft,
                      int flat_act, int M) {
@@ -1071,7 +932,6 @@ struct GenericEvaluator : Evaluator {
 
     // ---- the forward pass in two parts (engine.hip: the fused tree + trunk launch replaces forward_trunk by its own launch of the same kernel)
     bf16_t* trunk_out = nullptr;                    // raw trunk activation the heads read (set by forward_trunk / the fused launch's plan)
-    bool fuse_heads = false;
     void forward(hipStream_t s, const int8_t* in, float* policy, float* value, int n, bool timing, int = 0) override {
         forward_trunk(s, in, n, timing, 0);
         forward_heads(s, policy, value, n, 0);
@@ -1083,7 +943,7 @@ struct GenericEvaluator : Evaluator {
         t.prm0 = trunk_prm0; t.xout = Hh; t.w = trunk_w0; t.prm = trunk_prm; t.M = n * HW; t.H = H; t.W = W; t.nblocks = blocks - 1; t.tile_rows = HW;
         t.planes = in; t.stem_frag = reinterpret_cast<const uint4*>(stem_frag); t.stem_shift = g("stem.shift");
     }
-    bool fusable() const { return gomoku && F == 128 && fused && blocks > 1 && one_launch_ok(); }
+    bool fusable() const { return gomoku && F == 128 && blocks > 1 && one_launch_ok(); }
     bool supports_split() const override { return loaded && fusable(); }
     TrunkLaunchPlan fused_plan;
     // the Gomoku trunk launch with the stem inside (trunk.hpp S0): it reads nothing but the int8 planes, so it can share a launch with the tree step
@@ -1093,55 +953,42 @@ struct GenericEvaluator : Evaluator {
         t.ready = h.ready; t.epoch = h.epoch; t.eval_done = h.eval_done; t.fuse_fault = h.fuse_fault; t.spin_ticks = h.spin_ticks; t.test_fault_mod = h.test_fault_mod;
         t.stamps = h.stamps; t.queue = h.queue;
         fused_plan.nwg = n; fused_plan.mix = 0; fused_plan.lds_bytes = (unsigned)trunk_lds_bytes_s0();
-        trunk_out = Hh; fuse_heads = true;
+        trunk_out = Hh;
         return &fused_plan;
     }
     bool plan_uses_queue(const void* plan) const override { return plan && static_cast<const TrunkLaunchPlan*>(plan)->args.queue != nullptr; }
     void forward_trunk(hipStream_t s, const int8_t* in, int n, bool timing, int) override {
         if (!loaded) return;
-        if (gomoku && F != 128) { forward_trunk_wide(s, in, n, timing); return; }
-        const int M = n * HW, SC = gomoku ? 256 : 128;
-        StemGenArgs sg; memset(&sg, 0, sizeof(sg));
-        sg.in = in; sg.w = g("stem.w"); sg.scale = g("stem.scale"); sg.shift = g("stem.shift"); sg.scaleB = g("block0.bn1.scale"); sg.shiftB = g("block0.bn1.shift");
-        sg.out1 = X0; sg.out2 = A0; sg.M = M; sg.H = H; sg.W = W; sg.CIN = C; sg.COUT = SC; sg.K = gomoku ? 3 : 5; sg.act = gomoku ? NACT_RELU : NACT_GELU;
-        // at every block count: a one-block net runs k_block0 straight into k_conv_head32 (trunk_w / trunk_w0 are null), so it rounds
-        // where the 2+ block launches round (GomokuNet.forward_engine_numerics)
-        const bool fuse = gomoku && fused;
+        if (!gomoku) { forward_trunk_direct(s, in, n, timing); return; }
+        if (F != 128) { forward_trunk_wide(s, in, n, timing); return; }
+        // Gomoku at 128 filters, at every block count: a one-block net runs k_block0 straight into k_conv_head32 (trunk_w / trunk_w0 are null),
+        // so it rounds where the 2+ block launches round (GomokuNet.forward_engine_numerics)
+        const int M = n * HW;
         // round 3: the stem inside the one trunk launch too (trunk.hpp S0; GAZ_STEM_IN_TRUNK=1): no stem kernel, no 256-channel stem tensor,
         // bit-identical outputs (tests/test_evaluator_gpu.py) — and measured SLOWER on its own: with one 512-thread workgroup per CU nothing
         // overlaps the four half-image stem passes (trunk launch 2298 -> 2444 us per 2048 positions against the 86 us of k_stem_mfma it
         // replaces: evaluator pass 2702 -> 2762 us, gpurun_out r03 gmk1 / gmk2).  Kept as an opt-in: it is what lets the launch depend on
         // nothing but the int8 planes, i.e. what a fused tree + trunk launch for Gomoku needs.
-        const bool stem_in_trunk = fuse && stem_in_trunk_ok && one_launch_ok();
-        if (stem_in_trunk) {
-        } else if (gomoku) {
+        const bool stem_in_trunk = stem_in_trunk_ok && one_launch_ok();
+        if (!stem_in_trunk) {
+            // round 2: the stem writes only the raw tensor — block 0 pre-activates its operand in LDS — which halves this HBM-bound kernel's
+            // writes (236 MB less per forward at 2048 positions)
             StemMArgs sm; memset(&sm, 0, sizeof(sm)); sm.in = in; sm.wfrag = reinterpret_cast<const uint4*>(stem_frag); sm.shift = g("stem.shift");
-            sm.out = X0; sm.scaleB = g("block0.bn1.scale"); sm.shiftB = g("block0.bn1.shift"); sm.out2 = A0; sm.M = M; sm.H = H; sm.W = W;
-            // round 2: with the fused first block (k_block0) the stem writes only the raw tensor — block 0 pre-activates its operand in
-            // LDS — which halves this HBM-bound kernel's writes (236 MB less per forward at 2048 positions).  GAZ_STEM_A0=1: the old way
-            static const bool stem_a0 = env_on("GAZ_STEM_A0", false);
-            block0_inplace = fuse && st.b16.count("block0.w29") && !stem_a0;
-            if (block0_inplace) launch_stem_mfma<2, 256, false, false>(s, sm);
-            else launch_stem_mfma<2, 256, false, true>(s, sm);
-        } else {
-            hipLaunchKernelGGL(k_stem_generic, dim3((unsigned)(((long)M * (SC / 8) + 255) / 256)), dim3(256), 0, s, sg);
+            sm.out = X0; sm.M = M; sm.H = H; sm.W = W;
+            launch_stem_mfma<2, 256, false, false>(s, sm);
         }
         timer.begin(s, timing);
-        trunk_convs = 0; fused_blocks = 0; one_launch = false;
-        bf16_t* cur = X;                            // raw trunk activation after the last block
-        for (int i = 0; i < blocks; ++i) {
-            const std::string b = "block" + std::to_string(i), nb = "block" + std::to_string(i + 1);
-            const bool first = i == 0, last = i + 1 == blocks;
-            if (fuse && first && one_launch_ok()) {      // the whole trunk, block 0 included, in one launch
-                TrunkArgs t; one_launch_args(t, in, n); t.x0 = X0;
-                if (stem_in_trunk) hipLaunchKernelGGL((k_trunk<2, 2, 8, 2, false, false, false, true, 8, true, 0, true>), dim3(n), dim3(512), trunk_lds_bytes_s0(), s, t);
-                else hipLaunchKernelGGL((k_trunk<2, 2, 8, 2, false, false, false, true, 8, true>), dim3(n), dim3(512), trunk_lds_bytes(256), s, t);
-                cur = Hh; fused_blocks += blocks; block0_fused = true; one_launch = true;
-                break;
-            }
-            if (fuse && first && st.b16.count(b + ".w29")) {          // the 256 -> 128 block with its projection, one kernel (k_block0)
+        bf16_t* cur = X;                            // raw trunk activation after the last block: the heads pre-activate it themselves (k_conv_head32)
+        if ((one_launch = one_launch_ok())) {       // the whole trunk, block 0 included, in one launch
+            TrunkArgs t; one_launch_args(t, in, n); t.x0 = X0;
+            if (stem_in_trunk) hipLaunchKernelGGL((k_trunk<2, 2, 8, 2, false, false, false, true, 8, true, 0, true>), dim3(n), dim3(512), trunk_lds_bytes_s0(), s, t);
+            else hipLaunchKernelGGL((k_trunk<2, 2, 8, 2, false, false, false, true, 8, true>), dim3(n), dim3(512), trunk_lds_bytes(256), s, t);
+            cur = Hh;
+        } else {
+            {   // the 256 -> 128 block with its projection, one kernel (k_block0)
+                const std::string b = "block0";
                 Block0Args r; memset(&r, 0, sizeof(r));
-                r.a0 = block0_inplace ? nullptr : A0; r.x0 = X0; r.xout = X; r.w = st.w(b + ".w29"); r.s2 = g(b + ".conv1.scale"); r.t2 = g(b + ".conv1.shift");
+                r.x0 = X0; r.xout = X; r.w = st.w(b + ".w29"); r.s2 = g(b + ".conv1.scale"); r.t2 = g(b + ".conv1.shift");
                 r.s1 = g(b + ".bn1.scale"); r.t1 = g(b + ".bn1.shift");
                 r.b2 = g(b + ".conv2.bias"); r.bp = g(b + ".proj.bias"); r.M = M; r.H = H; r.W = W;
                 const Rb3Plan plan = rb3_plan(M, H, W, n_cus);
@@ -1150,58 +997,57 @@ struct GenericEvaluator : Evaluator {
                 if (plan.tm == 2) hipLaunchKernelGGL((k_block0<2, 8>), dim3(nwg), dim3(RB3_THREADS), rb3_lds_bytes<2>(), s, r);
                 else if (plan.tm == 3) hipLaunchKernelGGL((k_block0<3, 8>), dim3(nwg), dim3(RB3_THREADS), rb3_lds_bytes<3>(), s, r);
                 else hipLaunchKernelGGL((k_block0<4, 4>), dim3(nwg), dim3(RB3_THREADS), rb3_lds_bytes<4>(), s, r);
-                cur = X; fused_blocks++; block0_fused = true;
-                if (trunk && trunk_w && HW <= 256) {   // blocks 1.. in one launch: one board per workgroup, residual stream through L2 (trunk.hpp, RESG)
-                    TrunkArgs t; memset(&t, 0, sizeof(t));
-                    t.xin = X; t.xout = Hh; t.w = trunk_w; t.prm = trunk_prm; t.M = M; t.H = H; t.W = W; t.nblocks = blocks - 1; t.tile_rows = HW;
-                    // default: 8 waves (WM = 4 x WN = 2, the Connect4 wave tile on 16x16x32), one workgroup per CU, x and operand images in
-                    // LDS; GAZ_TRUNK_M16=0: 4 waves of 128 cells x 64 channels on 32x32x16, two workgroups per CU, residual stream through L2
-                    if (trunk_m16) hipLaunchKernelGGL((k_trunk<2, 2, 8, 2, false, false, false, true, 8>), dim3(n), dim3(512), trunk_lds_bytes(256), s, t);
-                    else hipLaunchKernelGGL((k_trunk<4, 2, 4, 2, false, false, true>), dim3(n), dim3(TR_THREADS), trunk_lds_bytes(256, true), s, t);
-                    cur = Hh; fused_blocks += blocks - 1;
-                    break;
-                }
-                continue;
             }
-            if (fuse && !first) {                   // whole block in one kernel: raw x in, raw x out (pre-activation on load)
-                ResBlockArgs r; memset(&r, 0, sizeof(r));
-                r.xin = cur; r.xout = cur == X ? Hh : X; r.w1 = st.w(b + ".conv1.w"); r.w2 = st.w(b + ".conv2.w");
-                r.s1 = g(b + ".bn1.scale"); r.t1 = g(b + ".bn1.shift"); r.s2 = g(b + ".conv1.scale"); r.t2 = g(b + ".conv1.shift");
-                r.b2 = g(b + ".conv2.bias"); r.M = M; r.H = H; r.W = W;
-                const Rb3Plan plan = rb3_plan(M, H, W, n_cus);
-                rb3_launch(s, r, plan, plan.tm == 4 ? 4 : 8);
-                cur = r.xout; fused_blocks++;
-                continue;                           // the heads pre-activate the raw output themselves (k_conv_head32)
-            }
-            const bf16_t* ain = first ? A0 : Aa;
-            const float* sB = last ? (gomoku ? g("p.bn0.scale") : nullptr) : (fuse ? nullptr : g(nb + ".bn1.scale"));
-            const float* tB = last ? (gomoku ? g("p.bn0.shift") : nullptr) : (fuse ? nullptr : g(nb + ".bn1.shift"));
-            bf16_t* o2 = sB ? Aa : nullptr;
-            if (gomoku) {
-                if (first) {
-                    conv_mfma<256, 9>(s, ain, st.w(b + ".conv1.w"), g(b + ".conv1.scale"), g(b + ".conv1.shift"), nullptr, Hh, ACT_RELU, nullptr, nullptr, nullptr, M);
-                    conv_mfma<256, 1>(s, X0, st.w(b + ".proj.w"), nullptr, g(b + ".proj.bias"), nullptr, X, ACT_NONE, nullptr, nullptr, nullptr, M);
-                } else {
-                    conv_mfma<128, 9>(s, ain, st.w(b + ".conv1.w"), g(b + ".conv1.scale"), g(b + ".conv1.shift"), nullptr, Hh, ACT_RELU, nullptr, nullptr, nullptr, M);
-                    trunk_convs++;
-                }
-                conv_mfma<128, 9>(s, Hh, st.w(b + ".conv2.w"), nullptr, g(b + ".conv2.bias"), X, X, ACT_NONE, sB, tB, o2, M);
-                trunk_convs++;
+            if (trunk && trunk_w && HW <= 256) {   // blocks 1.. in one launch: one board per workgroup, residual stream through L2 (trunk.hpp, RESG)
+                TrunkArgs t; memset(&t, 0, sizeof(t));
+                t.xin = X; t.xout = Hh; t.w = trunk_w; t.prm = trunk_prm; t.M = M; t.H = H; t.W = W; t.nblocks = blocks - 1; t.tile_rows = HW;
+                // default: 8 waves (WM = 4 x WN = 2, the Connect4 wave tile on 16x16x32), one workgroup per CU, x and operand images in
+                // LDS; GAZ_TRUNK_M16=0: 4 waves of 128 cells x 64 channels on 32x32x16, two workgroups per CU, residual stream through L2
+                if (trunk_m16) hipLaunchKernelGGL((k_trunk<2, 2, 8, 2, false, false, false, true, 8>), dim3(n), dim3(512), trunk_lds_bytes(256), s, t);
+                else hipLaunchKernelGGL((k_trunk<4, 2, 4, 2, false, false, true>), dim3(n), dim3(TR_THREADS), trunk_lds_bytes(256, true), s, t);
+                cur = Hh;
             } else {
-                const int cin = first ? SC : F;
-                conv_direct(s, ain, g(b + ".conv1.w"), cin, F, 3, g(b + ".conv1.scale"), g(b + ".conv1.shift"), nullptr, Hh, NACT_RELU, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, nullptr, 0, M);
-                if (first) conv_direct(s, X0, g(b + ".proj.w"), cin, F, 1, nullptr, g(b + ".proj.bias"), nullptr, X, NACT_NONE, nullptr, nullptr, nullptr,
-                                       nullptr, nullptr, nullptr, 0, M);
-                conv_direct(s, Hh, g(b + ".conv2.w"), F, F, 3, nullptr, g(b + ".conv2.bias"), X, X, NACT_NONE, sB, tB, o2, nullptr, nullptr, nullptr, 0, M);
+                for (int i = 1; i < blocks; ++i) {  // whole block in one kernel: raw x in, raw x out (pre-activation on load)
+                    const std::string b = "block" + std::to_string(i);
+                    ResBlockArgs r; memset(&r, 0, sizeof(r));
+                    r.xin = cur; r.xout = cur == X ? Hh : X; r.w1 = st.w(b + ".conv1.w"); r.w2 = st.w(b + ".conv2.w");
+                    r.s1 = g(b + ".bn1.scale"); r.t1 = g(b + ".bn1.shift"); r.s2 = g(b + ".conv1.scale"); r.t2 = g(b + ".conv1.shift");
+                    r.b2 = g(b + ".conv2.bias"); r.M = M; r.H = H; r.W = W;
+                    const Rb3Plan plan = rb3_plan(M, H, W, n_cus);
+                    rb3_launch(s, r, plan, plan.tm == 4 ? 4 : 8);
+                    cur = r.xout;
+                }
             }
         }
         timer.end(s);
-        trunk_out = cur; fuse_heads = fuse;
+        trunk_out = cur;
+    }
+    // TicTacToe: the 5x5 stem and the 64-filter blocks through the direct kernels of netops.hpp, every block's conv2 writing the next block's
+    // operand relu(bn1(x)) as well; the heads read the raw stream in X
+    void forward_trunk_direct(hipStream_t s, const int8_t* in, int n, bool timing) {
+        const int M = n * HW, SC = 128;
+        StemGenArgs sg; memset(&sg, 0, sizeof(sg));
+        sg.in = in; sg.w = g("stem.w"); sg.scale = g("stem.scale"); sg.shift = g("stem.shift"); sg.scaleB = g("block0.bn1.scale"); sg.shiftB = g("block0.bn1.shift");
+        sg.out1 = X0; sg.out2 = A0; sg.M = M; sg.H = H; sg.W = W; sg.CIN = C; sg.COUT = SC; sg.K = 5; sg.act = NACT_GELU;
+        hipLaunchKernelGGL(k_stem_generic, dim3((unsigned)(((long)M * (SC / 8) + 255) / 256)), dim3(256), 0, s, sg);
+        timer.begin(s, timing);
+        for (int i = 0; i < blocks; ++i) {
+            const std::string b = "block" + std::to_string(i), nb = "block" + std::to_string(i + 1);
+            const bool first = i == 0, last = i + 1 == blocks;
+            const float* sB = last ? nullptr : g(nb + ".bn1.scale");
+            const float* tB = last ? nullptr : g(nb + ".bn1.shift");
+            const int cin = first ? SC : F;
+            conv_direct(s, first ? A0 : Aa, g(b + ".conv1.w"), cin, F, 3, g(b + ".conv1.scale"), g(b + ".conv1.shift"), nullptr, Hh, NACT_RELU, nullptr, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, 0, M);
+            if (first) conv_direct(s, X0, g(b + ".proj.w"), cin, F, 1, nullptr, g(b + ".proj.bias"), nullptr, X, NACT_NONE, nullptr, nullptr, nullptr,
+                                   nullptr, nullptr, nullptr, 0, M);
+            conv_direct(s, Hh, g(b + ".conv2.w"), F, F, 3, nullptr, g(b + ".conv2.bias"), X, X, NACT_NONE, sB, tB, last ? nullptr : Aa, nullptr, nullptr, nullptr, 0, M);
+        }
+        timer.end(s);
+        trunk_out = X;
     }
     // Gomoku at F != 128 (net_host.hpp forward_trunk_wide): stem -> X0 (256 channels), a0 -> A0, the residual stream in X, operands in Aa / Hh;
     // the last conv2 also writes relu(p.bn0(bf16 x)) -> Aa for the policy head.
-    bool wide_trunk = false;
     void forward_trunk_wide(hipStream_t s, const int8_t* in, int n, bool timing) {
         const int M = n * HW;
         StemMArgs sm; memset(&sm, 0, sizeof(sm)); sm.in = in; sm.wfrag = reinterpret_cast<const uint4*>(stem_frag); sm.shift = g("stem.shift");
@@ -1210,7 +1056,7 @@ struct GenericEvaluator : Evaluator {
         WideTrunk t; t.stem_c = 256; t.F = F; t.blocks = blocks; t.M = M; t.H = H; t.W = W;
         t.x0 = X0; t.a0 = A0; t.x = X; t.a = Aa; t.h = Hh; t.policy_preact = true;
         gaz::forward_trunk_wide(s, st, timer, timing, t);
-        trunk_out = X; fuse_heads = false; wide_trunk = true;
+        trunk_out = X;
     }
     // heads' first convolutions at F != 128: relu(p.bn0(x)) came with the last conv2 (Aa), relu(v.bn0(x)) -> Va; 3x3 F -> 32 + BN + ReLU
     void heads_conv_wide(hipStream_t s, int M) {
@@ -1229,30 +1075,22 @@ struct GenericEvaluator : Evaluator {
     void forward_heads(hipStream_t s, float* policy, float* value, int n, int) override {
         if (!loaded) return;
         const int M = n * HW;
-        bf16_t* const cur = trunk_out; const bool fuse = fuse_heads;
         if (gomoku) {
             if (F != 128) {
                 heads_conv_wide(s, M);
-            } else if (fuse) {                      // both heads' BN + ReLU + Conv3x3 128 -> 32 + BN + ReLU from the raw trunk output
+            } else {                                // both heads' BN + ReLU + Conv3x3 128 -> 32 + BN + ReLU from the raw trunk output
                 Head32Args hh; memset(&hh, 0, sizeof(hh));
-                hh.in = cur; hh.wgt[0] = st.w("p.c1.w"); hh.wgt[1] = st.w("v.c1.w");
+                hh.in = trunk_out; hh.wgt[0] = st.w("p.c1.w"); hh.wgt[1] = st.w("v.c1.w");
                 hh.s0[0] = g("p.bn0.scale"); hh.t0[0] = g("p.bn0.shift"); hh.s0[1] = g("v.bn0.scale"); hh.t0[1] = g("v.bn0.shift");
                 hh.s1[0] = g("p.c1.scale"); hh.t1[0] = g("p.c1.shift"); hh.s1[1] = g("v.c1.scale"); hh.t1[1] = g("v.c1.shift");
                 hh.out[0] = PH; hh.out[1] = VH; hh.M = M; hh.H = H; hh.W = W;
                 hipLaunchKernelGGL(k_conv_head32, dim3((M + HC_ROWS - 1) / HC_ROWS, 2), dim3(RB3_THREADS), hc_lds_bytes(), s, hh);
-            } else {
-                hipLaunchKernelGGL(k_affine_relu, dim3((unsigned)(((long)M * F / 8 + 255) / 256)), dim3(256), 0, s, cur, g("v.bn0.scale"), g("v.bn0.shift"), Va, (long)M * F / 8, F);
-                conv_mfma32(s, Aa, st.w("p.c1.w"), g("p.c1.scale"), g("p.c1.shift"), PH, M);
-                conv_mfma32(s, Va, st.w("v.c1.w"), g("v.c1.scale"), g("v.c1.shift"), VH, M);
             }
             // the two heads are independent chains of small kernels (policy ~0.22 ms, value ~0.08 ms per 2048 positions): the value head
-            // runs on a side stream next to the policy head and joins before the softmax (round 2; GAZ_HEADS_2STREAMS=0 -> one stream)
-            static const bool two = env_on("GAZ_HEADS_2STREAMS", true);
-            hipStream_t sv = s;
-            if (two) {
-                if (!side_stream) { hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking); hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming); hipEventCreateWithFlags(&ev_join, hipEventDisableTiming); }
-                hipEventRecord(ev_fork, s); hipStreamWaitEvent(side_stream, ev_fork, 0); sv = side_stream;
-            }
+            // runs on a side stream next to the policy head and joins before the softmax (round 2)
+            if (!side_stream) { hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking); hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming); hipEventCreateWithFlags(&ev_join, hipEventDisableTiming); }
+            hipEventRecord(ev_fork, s); hipStreamWaitEvent(side_stream, ev_fork, 0);
+            const hipStream_t sv = side_stream;
             {
                 ConvSmallArgs c; c.in = PH; c.w = g("p.c2.w"); c.bias = g("p.c2.bias"); c.flat = pfeat; c.fs = g("p.bn2.scale"); c.ft = g("p.bn2.shift");
                 c.act = NACT_RELU; c.M = M; c.H = H; c.W = W;
@@ -1263,10 +1101,10 @@ struct GenericEvaluator : Evaluator {
             dense(sv, vfeat, "v.d1.w", g("v.d1.scale"), g("v.d1.shift"), vd1, n, HW * 4, 256, NACT_RELU);
             dense(sv, vd1, "v.d2.w", g("v.d2.scale"), g("v.d2.shift"), vd2, n, 256, 128, NACT_RELU);
             dense(sv, vd2, "v.d3.w", nullptr, g("v.d3.bias"), value, n, 128, 1, NACT_TANH);
-            if (two) hipEventRecord(ev_join, side_stream);
+            hipEventRecord(ev_join, side_stream);
             dense(s, pfeat, "p.d1.w", g("p.d1.scale"), g("p.d1.shift"), pd1, n, HW * 8, 512, NACT_RELU);
             dense(s, pd1, "p.d2.w", nullptr, g("p.d2.bias"), plog, n, 512, A, NACT_NONE);
-            if (two) hipStreamWaitEvent(s, ev_join, 0);
+            hipStreamWaitEvent(s, ev_join, 0);
         } else {
             conv_direct(s, X, g("p.c.w"), F, 8, 1, g("p.c.scale"), g("p.c.shift"), nullptr, nullptr, 0, nullptr, nullptr, nullptr, pfeat, nullptr, nullptr, NACT_NONE, M);
             conv_direct(s, X, g("v.c.w"), F, 4, 1, g("v.c.scale"), g("v.c.shift"), nullptr, nullptr, 0, nullptr, nullptr, nullptr, vfeat, nullptr, nullptr, NACT_NONE, M);
@@ -1282,10 +1120,9 @@ struct GenericEvaluator : Evaluator {
     void timing_reset() override { timer.reset(); }
     void timing_get(double* ms, int64_t* launches) override {
         *ms = timer.total_ms();
-        // launches of the dominant kernel inside one bracket (counts of the last forward pass): one where the bracket is priced as a whole (the
-        // one-launch trunk, k_conv_wide per forward); else the fused blocks (k_resblock3), where an unfused block 0 (256 -> 128 + projection) rides
-        // in the same bracket as one more launch-equivalent; else the 128 -> 128 convolutions, at least one
-        const int per_bracket = one_launch || wide_trunk ? 1 : fused_blocks > 0 ? fused_blocks + (block0_fused ? 0 : 1) : std::max(trunk_convs, 1);
+        // launches of the dominant kernel inside one bracket: one where the bracket is priced as a whole (the one-launch trunk of the last forward
+        // pass, k_conv_wide per forward, TicTacToe); else Gomoku's residual blocks at 128 filters (k_block0 + k_trunk for blocks 1.. or k_resblock3)
+        const int per_bracket = gomoku && F == 128 && !one_launch ? blocks : 1;
         *launches = timer.brackets() * per_bracket;
     }
     const char* dominant_kernel(int n, double* flops) override {
@@ -1299,24 +1136,22 @@ struct GenericEvaluator : Evaluator {
         }
         const double conv = 2.0 * (double)n * HW * 128.0 * 1152.0;
         if (!gomoku) { *flops = 0; return ""; }
-        if (fused && blocks == 1) {                 // the bracket holds k_block0 alone, priced as block 0 of the one-launch trunk below
+        if (blocks == 1) {                          // the bracket holds k_block0 alone, priced as block 0 of the one-launch trunk below
             *flops = 3.0 * conv + 2.0 * (double)n * HW * 256.0 * 128.0;
             return "k_block0 (the one residual block of a one-block Gomoku network: 3x3 conv 256->128, 3x3 conv 128->128 and the 1x1 projection "
                    "256->128 in one launch, implicit GEMM on MFMA 32x32x16 bf16)";
         }
-        const bool fz = fused && blocks > 1;
-        *flops = fz ? 2 * conv : conv;
-        if (fz && trunk_w && one_launch_ok()) {
+        *flops = 2 * conv;
+        if (trunk_w && one_launch_ok()) {
             // priced per LAUNCH: the one kernel runs block 0 (3x3 256->128 = two 128-channel convolutions, 3x3 128->128, the 1x1
             // projection 256->128) and blocks - 1 regular blocks of two 3x3 convolutions each
             *flops = (2.0 * (blocks - 1) + 3.0) * conv + 2.0 * (double)n * HW * 256.0 * 128.0;
             return "k_trunk<8 waves, B0> (the whole Gomoku trunk in ONE launch per forward: block 0 with its 256-channel input and 1x1 projection + the other residual blocks, "
                    "every 3x3 / 1x1 convolution of them counted; implicit GEMM on v_mfma_f32_16x16x32_bf16, activations resident in LDS)";
         }
-        if (fz && trunk && trunk_w) return trunk_m16 ? "k_trunk<RESG, 8 waves> (blocks 1.. in one launch, priced per residual block: two 3x3 convs 128->128, implicit GEMM on v_mfma_f32_16x16x32_bf16)"
+        if (trunk && trunk_w) return trunk_m16 ? "k_trunk<RESG, 8 waves> (blocks 1.. in one launch, priced per residual block: two 3x3 convs 128->128, implicit GEMM on v_mfma_f32_16x16x32_bf16)"
                                                      : "k_trunk<4,2,RESG> (blocks 1.. in one launch, priced per residual block: two 3x3 convs 128->128, implicit GEMM on v_mfma_f32_32x32x16_bf16)";
-        return fz ? "k_resblock3 (whole residual block: two 3x3 convs 128->128, implicit GEMM on MFMA 32x32x16 bf16)"
-                  : "k_conv3x3<128,128> (trunk 3x3 conv, implicit GEMM on MFMA 32x32x16 bf16)";
+        return "k_resblock3 (whole residual block: two 3x3 convs 128->128, implicit GEMM on MFMA 32x32x16 bf16)";
     }
 };
 
@@ -1327,7 +1162,6 @@ static Evaluator* make_generic_evaluator(const gaz_engine_config& cfg, int H, in
     GenericEvaluator* e = new GenericEvaluator();
     e->H = H; e->W = W; e->C = C; e->A = A; e->HW = H * W; e->blocks = cfg.net_blocks; e->F = gomoku ? cfg.net_filters : 64; e->nmax = cfg.n_games;
     e->logits = cfg.policy_is_logits; e->gomoku = gomoku;
-    e->fused = env_on("GAZ_FUSED", true);
     e->trunk = env_on("GAZ_TRUNK", true);
     e->trunk_m16 = env_on("GAZ_TRUNK_M16", true);
     e->block0_in_trunk = env_on("GAZ_BLOCK0_IN_TRUNK", true);
@@ -1348,11 +1182,6 @@ static Evaluator* make_generic_evaluator(const gaz_engine_config& cfg, int H, in
     hipFuncSetAttribute((const void*)(k_trunk<2, 2, 8, 2, false, false, false, true, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes(256));
     hipFuncSetAttribute((const void*)(k_trunk<2, 2, 8, 2, false, false, false, true, 8, true, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes_s0());
     hipFuncSetAttribute((const void*)(k_resblock3<4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rb3_lds_bytes<4>());
-    hipFuncSetAttribute((const void*)(k_conv3x3<128, 128, 256, 4, 2, 2, 2, 1, 1, 0, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)(k_conv3x3<256, 128, 128, 2, 2, 2, 2, 4, 1, 0, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)(k_conv3x3<256, 128, 128, 2, 2, 2, 2, 4, 1, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)(k_conv3x3<128, 128, 256, 4, 2, 2, 2, 1, 1, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)(k_conv3x3<128, 32, 256, 8, 1, 1, 1, 1, 1, 0, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_dense, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
     return e;
 }
@@ -1367,7 +1196,7 @@ Evaluator* make_resnet_evaluator(const gaz_engine_config& cfg, int H, int W, int
     e->H = H; e->W = W; e->C = C; e->A = A; e->HW = H * W; e->blocks = cfg.net_blocks; e->filters = cfg.net_filters; e->nmax = cfg.n_games;
     e->logits = cfg.policy_is_logits;
     const size_t M = (size_t)cfg.n_games * e->HW, CW = std::max(cfg.net_filters, 128);     // activation buffers: the stem's 128 channels or F
-    e->X2 = e->st.dalloc<bf16_t>(M * CW + 1024); e->fused = env_on("GAZ_FUSED", true);
+    e->X2 = e->st.dalloc<bf16_t>(M * CW + 1024);
     e->trunk = env_on("GAZ_TRUNK", true);
     e->trunk_whole = env_on("GAZ_TRUNK_WHOLE", true);
     e->trunk_mix = env_on("GAZ_TRUNK_MIX", true);
@@ -1381,7 +1210,6 @@ Evaluator* make_resnet_evaluator(const gaz_engine_config& cfg, int H, int W, int
     e->pd1 = e->st.dalloc<float>((size_t)cfg.n_games * 128); e->vd1 = e->st.dalloc<float>((size_t)cfg.n_games * 128);
     if (!e->X || !e->Aa || !e->Hh || !e->pfeat || !e->vfeat || !e->pd1 || !e->vd1) { *err = "hipMalloc failed"; delete e; return nullptr; }
     // dynamic LDS above 64 KB needs the attribute
-    hipFuncSetAttribute((const void*)k_resblock, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)(k_resblock3<4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rb3_lds_bytes<4>());
     hipFuncSetAttribute((const void*)k_conv_heads, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hc_lds_bytes());
     hipFuncSetAttribute((const void*)k_heads_c4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)heads_c4_lds_bytes(384));
@@ -1391,8 +1219,6 @@ Evaluator* make_resnet_evaluator(const gaz_engine_config& cfg, int H, int W, int
     hipFuncSetAttribute((const void*)(k_trunk_mix<8, 2, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes(128));
     hipFuncSetAttribute((const void*)(k_trunk_mix<8, 2, true, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes(128));
     hipFuncSetAttribute((const void*)(k_trunk<2, 2, 8, 2, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trunk_lds_bytes(128));
-    hipFuncSetAttribute((const void*)(k_conv3x3<128, 128, 256, 4, 2, 2, 2, 1, 1, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)(k_conv3x3<128, 128, 128, 2, 2, 2, 2, 2, 2, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     return e;
 }
 

@@ -13,7 +13,7 @@ def avg(path, counter, needle):
     return sum(vals) / len(vals), len(vals)
 
 
-needle = sys.argv[3] if len(sys.argv) > 3 else "k_resblock"
+needle = sys.argv[3] if len(sys.argv) > 3 else "k_resblock3"
 f, nf = avg(sys.argv[1], "FETCH_SIZE", needle)
 w, nw = avg(sys.argv[2], "WRITE_SIZE", needle)
 out = dict(kernel=needle, kernel_tag=needle, launches=[nf, nw], fetch_size_kib=f, write_size_kib=w, fetch_bytes=f * 1024 * 2, write_bytes=w * 1024,

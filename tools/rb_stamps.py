@@ -1,4 +1,4 @@
-"""Summarise the phase stamps k_resblock writes under GAZ_RB_STAMPS=<file> (wall clock, 100 MHz ticks, wave 0 of each workgroup)."""
+"""Summarise the phase stamps k_resblock3 writes under GAZ_RB_STAMPS=<file> (wall clock, 100 MHz ticks, wave 0 of each workgroup)."""
 import sys
 import numpy as np
 raw = np.fromfile(sys.argv[1], dtype=np.uint64).reshape(-1, 64).astype(np.int64)
